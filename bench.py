@@ -23,6 +23,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
 "roofline" (dominant kernel against the 8 TB/s HBM peak, plus per_S: every dynamic range of
 the reference's sweep) and "cpu_baseline" (the CPU oracle timed on a bounded sample on this
 host's cores).
+
+--dump-outputs DIR writes what the last timed step computed (the encoded container and the decoded
+channels, a seeded sample of the large arrays) as DIR/<name>.npy, for comparing two builds output
+for output; the inputs depend on the arguments only (synth.generate, --seed).
 """
 import argparse
 import json
@@ -77,6 +81,9 @@ def parse(argv=None):
                          "(strong scaling, reported as the extra block \"configs3\")")
     ap.add_argument("--configs3-steps", type=int, default=3)
     ap.add_argument("--no-configs3", action="store_true", help="skip the configs[3] strong-scaling block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (encoded container and decoded "
+                         "channels) as DIR/<name>.npy, float32 / float64, 64 MB at most (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -255,6 +262,61 @@ def choose_buffers(plan, data, tries):
               "encode_plus_decode_ms_per_top_pair_and_output_candidate": joint,
               "chosen_encode_plus_decode_ms": best[0]}
     return inputs[best[1]], best[2], best[3], report
+
+
+DUMP_BYTES = 64 << 20
+
+
+def _sample_positions(starts, lengths, cap, seed):
+    """Positions of the elements of the runs [starts[i], starts[i] + lengths[i]), in order: all of them when there are
+    at most `cap`, else a sorted sample drawn by a generator seeded by `seed` and the element count (the same
+    arguments always give the same positions)."""
+    cum = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+    n = int(cum[-1])
+    if n <= cap:
+        j = np.arange(n, dtype=np.int64)
+    else:
+        j = np.unique(np.random.default_rng(list(seed) + [n]).integers(0, n, size=cap, dtype=np.int64))
+    r = np.searchsorted(cum, j, side="right") - 1
+    return np.asarray(starts, dtype=np.int64)[r] + (j - cum[r])
+
+
+def dump_outputs(d, plan, cs, enc, out, seed, rank, world):
+    """--dump-outputs: what the last timed step handed its caller -- the Encoded container of plan.encode and the
+    channel bytes plan.decode wrote -- as d/<name>.npy, so that two builds can be compared output for output.
+    Integers are stored as float64 (exact below 2^53), bytes as float32.  Each array has a fixed share of the
+    64 MB budget: it is written whole when it fits, else as a seeded sample (_sample_positions, seed = (--seed, rank)).
+    payload_words holds only the words the segments use (seg_words; the rest of a slot is never written), decoded
+    the bytes of the channels.  With several ranks each writes its own shard as <name>_rank<r>.npy, in a
+    1/world share.  -> {file name: shape}"""
+    os.makedirs(d, exist_ok=True)
+    share = (DUMP_BYTES - (64 << 10)) // world     # (64 KB left for the .npy headers)
+    seed = (seed, rank)
+    written = {}
+
+    def save(name, a):
+        fn = name if world == 1 else "%s_rank%d" % (name, rank)
+        np.save(os.path.join(d, fn + ".npy"), a)
+        written[fn] = list(a.shape)
+
+    n_seg = plan.n_segments
+    seg_words = enc.seg_words.cpu().numpy()[:n_seg]
+    for name, t, n, dt, frac in (("ch_bits", enc.ch_bits, plan.C, np.float64, 1 / 8),
+                                 ("peak", enc.peak, plan.C, np.float32, 1 / 24),
+                                 ("enc", enc.enc, plan.C, np.float32, 1 / 24),
+                                 ("skipped", enc.skipped, plan.C, np.float32, 1 / 24),
+                                 ("seg_words", enc.seg_words, n_seg, np.float64, 1 / 8)):
+        host = t.cpu().numpy()[:n]
+        save(name, host[_sample_positions([0], [n], int(share * frac) // np.dtype(dt).itemsize, seed)].astype(dt))
+    for name, buf, starts, lengths, dt, frac in (
+            ("payload_words", enc.payload, plan.segments()["off"], seg_words, np.float64, 3 / 8),
+            ("decoded", out, cs.ch_off, cs.ch_len, np.float32, 1 / 4)):
+        pos = _sample_positions(starts, lengths, int(share * frac) // np.dtype(dt).itemsize, seed)
+        if pos.size and not (0 <= int(pos.min()) and int(pos.max()) < buf.numel()):
+            raise RuntimeError("dump_outputs: %s positions outside the buffer" % name)
+        v = buf.index_select(0, torch.from_numpy(pos).to(buf.device)).cpu().numpy()
+        save(name, (v.view(np.uint32) if v.dtype == np.int32 else v).astype(dt))
+    return written
 
 
 def small_shape(S, h, mode, seg_chunks, reps=20):
@@ -536,6 +598,8 @@ def main(argv=None):
         t = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # before anything below reuses `out` (per_S_sweep decodes into it) or frees the buffers
+    dumped = dump_outputs(a.dump_outputs, plan, cs, enc, out, a.seed, rank, world) if a.dump_outputs else None
     devices, rank_words = None, None
     if dist is not None:
         devices = [None] * world
@@ -723,6 +787,8 @@ def main(argv=None):
             line["gather"] = gather
         if ok is not None:
             line["verified_roundtrip"] = ok
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": a.dump_outputs, "rank0_arrays": dumped}
         if not a.no_small_shape and world == 1:
             line["small_shape"] = small_shape(S, h, a.mode, a.seg_chunks)
         if c3 is not None:
