@@ -51,15 +51,25 @@ class ChannelSet:
     def matrix(self, buf=None):
         """[C, T] strided view of the channels (all of one length) in `buf` -- the set's own buffer, or another
         one laid out like it (a decoder's output).  Channel starts are padded (16 bytes; 128 for channels of >= 2^18
-        bins), so this is the set's buffer seen with a row pitch -- not a reshape of its first C * T bytes."""
+        bins), so this is the set's buffer seen with a row pitch -- not a reshape of its first C * T bytes.  The
+        offsets count from the start of `buf` (which may itself be a view into a larger storage) and must be equally
+        spaced; anything else raises ValueError rather than returning other bytes."""
         buf = self.data if buf is None else buf
         if self.C == 0:
             return buf[:0].view(0, 0)
         T = int(self.ch_len[0])
         if not (self.ch_len == self.ch_len[0]).all():
             raise ValueError("matrix(): channels of different lengths")
-        pitch = int(self.ch_off[1] - self.ch_off[0]) if self.C > 1 else T
-        return torch.as_strided(buf, (self.C, T), (pitch, 1), int(self.ch_off[0]))
+        if buf.dim() != 1 or (buf.numel() > 1 and buf.stride(0) != 1):
+            raise ValueError("matrix(): the buffer must be a 1-D contiguous byte tensor")
+        off = self.ch_off.astype(np.int64)
+        pitch = np.diff(off)
+        if self.C > 1 and not (pitch == pitch[0]).all():
+            raise ValueError("matrix(): channel offsets are not equally spaced")
+        pitch = int(pitch[0]) if self.C > 1 else T
+        if int(off[-1]) + T > buf.numel():
+            raise ValueError("matrix(): the buffer holds %d bytes, the last channel ends at %d" % (buf.numel(), int(off[-1]) + T))
+        return buf.as_strided((self.C, T), (pitch, 1), buf.storage_offset() + int(off[0]))
 
     @classmethod
     def from_channels(cls, channels, device="cuda"):

@@ -317,6 +317,73 @@ def test_full_size_properties(mh, S, h, K_rows):
     assert int(sums.sum()) == plan.window_samples
     bits_per_sample = float(e.ch_bits.sum()) / plan.window_samples
     assert 1.0 <= bits_per_sample <= float(tab.max())
+    del out, view_out, sums
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    # --- every field of the measure record, all 1024 channels, against torch counts of the input + host arithmetic
+    assert torch.equal(m.cutoff, torch.full_like(m.cutoff, c))
+    mat = cs.matrix()
+    cal = torch.stack([(torch.clamp(mat[:, :c], max=S - 1) == s).sum(1) for s in range(S)], 1).cpu().numpy()
+    post = torch.zeros((C, S), dtype=torch.int64, device="cuda")
+    for c0 in range(0, C, 64):
+        blk = torch.clamp(mat[c0:c0 + 64, c:], max=S - 1)
+        for s in range(S):
+            post[c0:c0 + 64, s] = (blk == s).sum(1)
+    del blk
+    post = post.cpu().numpy()                                        # [C, S] by symbol
+    peak = np.argmax(cal, 1)                                         # first maximum, as np.argmax in the reference
+    idx = np.stack([OC.approx_sort_rule(S, int(p)) for p in peak])   # rank -> symbol
+    for ch in range(C):                                              # the closed form == the literal statement sequence
+        assert np.array_equal(OC.approx_sort_literal(cal[ch]), idx[ch]), ch
+    cal_sorted = np.take_along_axis(cal, idx, 1)
+    post_sorted = np.take_along_axis(post, idx, 1)
+    tabi = tab.astype(np.int64)
+    enc = np.argmin(cal_sorted @ tabi.T, 1)                          # first minimum over the SCLV rows
+    bits = (tabi[enc] * post_sorted).sum(1)
+    assert np.array_equal(m.peak.cpu().numpy(), peak)
+    assert np.array_equal(m.cal_hist.cpu().numpy(), cal_sorted)
+    assert np.array_equal(m.enc.cpu().numpy(), enc)
+    assert np.array_equal(m.post_hist.cpu().numpy(), post_sorted)
+    assert np.array_equal(m.bits.cpu().numpy(), bits)
+    assert np.array_equal(e.ch_bits.cpu().numpy(), bits)
+    assert not m.skipped.any()
+    # --- whole channels 0, 511, 1023 through the CPU oracle: record, directory and every payload word
+    sel = (0, 511, 1023)
+    p = OC.Params(S, h, mh.MODE_APPROX, mh.WIN_AFTER_CAL, tab, seg_chunks=plan.seg_chunks)
+    data, off, ln = OC.flatten([cs.channel(ch).cpu().numpy() for ch in sel])
+    om = OC.measure(data, off, ln, p)
+    oe = OC.encode(data, off, ln, p)
+    seg = plan.segments()
+    n_seg = plan.n_segments
+    sw = e.seg_words[:n_seg].cpu().numpy()
+    got = dict(cutoff=m.cutoff, cal_sorted=m.cal_hist, peak=m.peak, enc=m.enc, post_mapped=m.post_hist, bits=m.bits,
+               skipped=m.skipped)
+    for k, v in got.items():
+        assert np.array_equal(v.cpu().numpy()[list(sel)], om[k]), k
+    for k, v in dict(ch_bits=e.ch_bits, peak=e.peak, enc=e.enc, skipped=e.skipped).items():
+        assert np.array_equal(v.cpu().numpy()[list(sel)], oe[k]), k
+    for i, ch in enumerate(sel):
+        gi, oi = np.nonzero(seg["ch"] == ch)[0], np.nonzero(oe["seg"]["ch"] == i)[0]
+        assert len(gi) == len(oi) > 0
+        assert np.array_equal(seg["first"][gi], oe["seg"]["first"][oi])
+        assert np.array_equal(seg["n"][gi], oe["seg"]["n"][oi])
+        assert np.array_equal(sw[gi], oe["seg_words"][oi].astype(np.int64)), ch
+        lo = int(seg["off"][gi[0]])
+        pay = e.payload[lo:int(seg["off"][gi[-1]]) + int(sw[gi[-1]])].cpu().numpy().view(np.uint32)
+        for g, o in zip(gi, oi):
+            a, n = int(seg["off"][g]) - lo, int(sw[g])
+            assert np.array_equal(pay[a:a + n], oe["payload"][int(oe["seg"]["off"][o]):int(oe["seg"]["off"][o]) + n]), (ch, g)
+    # --- dense compaction at full size
+    d, tot = plan.compact(e)
+    torch.cuda.synchronize()
+    swd = e.seg_words[:n_seg]
+    assert int(tot[0]) == int(swd.sum())
+    assert torch.equal(d.seg_off[:n_seg], torch.cumsum(swd, 0) - swd)
+    doff = d.seg_off[:n_seg].cpu().numpy()
+    for ch in sel:
+        gi = np.nonzero(seg["ch"] == ch)[0]
+        want = torch.cat([e.payload[int(seg["off"][g]):int(seg["off"][g]) + int(sw[g])] for g in gi])
+        assert torch.equal(d.payload[int(doff[gi[0]]):int(doff[gi[0]]) + want.numel()], want), ch
     plan.close()
 
 
@@ -859,27 +926,29 @@ def test_stream_blocks_through_the_packed_intermediate(mh, S):
     kernels), short ones (wave tasks), ragged lengths, counts up to 255."""
     from muahuff import stream
     rng = np.random.RandomState(100 + S)
-    C = 70
     tab = helpers.sclv_tables()[S]
-    rates = np.exp(rng.uniform(np.log(0.05), np.log(3.0), size=C))
-
-    def block(T):
-        x = np.minimum(rng.poisson(rates, size=(T, C)), 255).astype(np.uint8)
-        x[rng.random_sample((T, C)) < 0.01] = rng.randint(4, 256)
-        return x
-    se = stream.StreamEncoder(C, S, 6, tab)
-    peak, enc = se.calibrate(block(64))
-    peak, enc = peak.cpu().numpy(), enc.cpu().numpy()
     # MH_FUZZ_ITERS: one-off campaigns add that many random block lengths (log-uniform up to ~12 chunks)
     extra = [int(np.exp(rng.uniform(0, np.log(200_000)))) for _ in range(int(os.environ.get("MH_FUZZ_ITERS", "0")))]
-    for T in [16384 * 9 + 5, 16384 * 2, 16383, 100, 17, 16, 1] + extra:
-        x = block(T)
-        c = se.encode_block(x)
-        assert np.array_equal(stream.StreamEncoder.decode_block(c), np.minimum(x, S - 1)), T
-        for ch in range(0, C, 7):
-            rank_of = np.argsort(OC.approx_sort_rule(S, int(peak[ch])))
-            assert int(c.ch_bits[ch]) == int(tab[enc[ch]][rank_of[np.minimum(x[:, ch], S - 1)]].sum()), (T, ch)
-    se.close()
+    # C = 130: a partial second strip of 128 channels; block lengths at 16 chunks (262 144 steps) and either side
+    for C, lengths in ((70, [16384 * 9 + 5, 16384 * 2, 16383, 100, 17, 16, 1] + extra),
+                       (130, [16384 * 16 - 1, 16384 * 16, 16384 * 16 + 17])):
+        rates = np.exp(rng.uniform(np.log(0.05), np.log(3.0), size=C))
+
+        def block(T):
+            x = np.minimum(rng.poisson(rates, size=(T, C)), 255).astype(np.uint8)
+            x[rng.random_sample((T, C)) < 0.01] = rng.randint(4, 256)
+            return x
+        se = stream.StreamEncoder(C, S, 6, tab)
+        peak, enc = se.calibrate(block(64))
+        peak, enc = peak.cpu().numpy(), enc.cpu().numpy()
+        for T in lengths:
+            x = block(T)
+            c = se.encode_block(x)
+            assert np.array_equal(stream.StreamEncoder.decode_block(c), np.minimum(x, S - 1)), (C, T)
+            for ch in list(range(0, C, 7)) + [C - 1]:
+                rank_of = np.argsort(OC.approx_sort_rule(S, int(peak[ch])))
+                assert int(c.ch_bits[ch]) == int(tab[enc[ch]][rank_of[np.minimum(x[:, ch], S - 1)]].sum()), (C, T, ch)
+        se.close()
 
 
 def test_stream_slots_are_reused_and_follow_recalibration(mh):

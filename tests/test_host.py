@@ -380,3 +380,49 @@ def test_validate_stream_accepts_oracle_streams_and_names_corruption():
         assert _validate(*args, dense, e["seg_words"], pk, e["enc"]) == _lib.ERR_STREAM
         assert b"peak" in _lib.lib().mh_last_error()
         assert _validate(lens[:-1] + [101], S, h, 1, window, tab, sc, dense, e["seg_words"], e["peak"], e["enc"]) in (0, _lib.ERR_STREAM)
+
+
+def test_channel_set_matrix_views_exactly_the_channels():
+    """ChannelSet.matrix() on CPU tensors against plain slicing of the buffer: offsets count from the start of the
+    buffer even when it is a view at a non-zero storage offset, the pitch is the one spacing of all offsets, and
+    layouts it cannot show as one strided view (uneven spacing, a buffer that ends inside the last channel) raise."""
+    import torch
+
+    from muahuff.container import ChannelSet, layout
+
+    def rows(buf, off, T):
+        return torch.stack([buf[int(o):int(o) + T] for o in off])
+
+    base = torch.arange(100, dtype=torch.uint8)
+    # a view that does not start at its storage's first byte
+    cs = ChannelSet(base[3:], [0, 16], [10, 10])
+    assert torch.equal(cs.matrix(), rows(base[3:], [0, 16], 10))
+    assert int(cs.matrix()[0, 0]) == 3 and int(cs.matrix()[1, 0]) == 19
+    # the same view passed as a decoder's output buffer, at a first offset that is not 0
+    other = torch.arange(200, dtype=torch.uint8)[37:]
+    cs = ChannelSet(base, [5, 25, 45], [7, 7, 7])
+    assert torch.equal(cs.matrix(other), rows(other, [5, 25, 45], 7))
+    assert torch.equal(cs.matrix(), rows(base, [5, 25, 45], 7))
+    # offsets that are not equally spaced: no single pitch describes them
+    with pytest.raises(ValueError):
+        ChannelSet(base, [0, 16, 48], [10, 10, 10]).matrix()
+    # a buffer that ends inside the last channel
+    with pytest.raises(ValueError):
+        ChannelSet(base[:40], [0, 32], [10, 10]).matrix()
+    with pytest.raises(ValueError):
+        ChannelSet(base, [0, 16], [10, 10]).matrix(base[:25])
+    assert ChannelSet(base[:42], [0, 32], [10, 10]).matrix().shape == (2, 10)
+    # long channels: 128-byte line padding (T >= 2^18, T % 128 != 0) -- the layout ChannelSet.empty makes
+    T = (1 << 18) + 77
+    off, ln, total = layout([T] * 3)
+    assert int(off[1]) % 128 == 0 and int(off[1]) > T
+    buf = (torch.arange(total + 16, dtype=torch.int64) * 7 % 251).to(torch.uint8)
+    cs = ChannelSet(buf, off, ln)
+    assert torch.equal(cs.matrix(), rows(buf, off, T))
+    assert torch.equal(cs.matrix()[:, 1:].t().contiguous(), rows(buf, off, T)[:, 1:].t())
+    # one channel
+    cs = ChannelSet(base[10:], [4], [50])
+    assert torch.equal(cs.matrix(), base[14:64].view(1, 50))
+    assert ChannelSet(base, [60], [50]).C == 1
+    with pytest.raises(ValueError):
+        ChannelSet(base, [60], [50]).matrix()
