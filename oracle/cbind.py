@@ -170,6 +170,26 @@ def encode(data, ch_off, ch_len, params, nthreads=1):
     return out
 
 
+def encode_preset(data, ch_off, ch_len, params, peak, enc, nthreads=1):
+    """Encode every channel's window with the GIVEN per-channel (peak, enc) word instead of calibrating
+    (mh_encode_preset's contract: peak >= S or enc >= K count as 0).  The dict of encode(), whose
+    peak / enc are the words actually used."""
+    C = len(ch_off)
+    seg = plan_segments(ch_len, params)
+    pk = np.ascontiguousarray(np.broadcast_to(np.asarray(peak, np.uint8), (C,)))
+    en = np.ascontiguousarray(np.broadcast_to(np.asarray(enc, np.uint8), (C,)))
+    out = dict(seg=seg, payload=np.zeros(seg["cap_words"] + 4, np.uint32),
+               seg_words=np.zeros(len(seg["ch"]), np.uint64), ch_bits=np.zeros(C, np.uint64),
+               peak=np.where(pk < params.S, pk, 0).astype(np.uint8),
+               enc=np.where(en < params.K, en, 0).astype(np.uint8))
+    rc = lib().mho_encode_preset(_p(data), _p(ch_off), _p(ch_len), ct.c_uint32(C), params.ref, _p(pk), _p(en),
+                                 _p(out["payload"]), ct.c_uint64(seg["cap_words"]), _p(out["seg_words"]),
+                                 _p(out["ch_bits"]), int(nthreads))
+    if rc != 0:
+        raise RuntimeError("oracle encode_preset failed rc=%d" % rc)
+    return out
+
+
 def decode(payload, ch_off, ch_len, params, peak, enc, out_size, nthreads=1):
     out = np.zeros(out_size, np.uint8)
     payload = np.ascontiguousarray(payload, dtype=np.uint32)

@@ -499,17 +499,39 @@ uint64_t mho_decode_segment(const uint32_t *in, uint64_t n, const mho_params *p,
     return w;
 }
 
+/* encode every segment of the directory with the channels' words chs[] (calibrated or preset) */
+static void encode_segments(const uint8_t *data, const uint64_t *ch_off, const uint64_t *ch_len, uint32_t C,
+                            const mho_params *p, const mho_chan *chs, uint32_t *payload, uint64_t *seg_words,
+                            uint64_t *ch_bits, int nthreads)
+{
+    uint64_t cap = 0;
+    const uint64_t nseg = mho_plan_segments(ch_len, C, p, NULL, NULL, NULL, NULL, &cap);
+    uint32_t *seg_ch = (uint32_t *)malloc((nseg + 1) * sizeof(uint32_t));
+    uint64_t *seg_first = (uint64_t *)malloc((nseg + 1) * 3 * sizeof(uint64_t));
+    uint64_t *seg_n = seg_first + nseg + 1, *seg_off = seg_n + nseg + 1;
+    mho_plan_segments(ch_len, C, p, seg_ch, seg_first, seg_n, seg_off, &cap);
+    for (uint32_t c = 0; c < C; ++c) ch_bits[c] = 0;
+    (void)nthreads;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+    for (int64_t s = 0; s < (int64_t)nseg; ++s) {
+        const uint32_t c = seg_ch[s];
+        uint64_t bits = 0;
+        seg_words[s] = mho_encode_segment(data + ch_off[c] + chs[c].w0 + seg_first[s], seg_n[s], p, &chs[c],
+                                          payload + seg_off[s], &bits);
+#pragma omp atomic
+        ch_bits[c] += bits;
+    }
+    free(seg_first);
+    free(seg_ch);
+}
+
 int mho_encode(const uint8_t *data, const uint64_t *ch_off, const uint64_t *ch_len, uint32_t C,
                const mho_params *p, uint32_t *payload, uint64_t cap_words, uint64_t *seg_words,
                uint64_t *ch_bits, uint8_t *peak, uint8_t *enc, uint8_t *skipped, int nthreads)
 {
     uint64_t cap = 0;
-    const uint64_t nseg = mho_plan_segments(ch_len, C, p, NULL, NULL, NULL, NULL, &cap);
+    mho_plan_segments(ch_len, C, p, NULL, NULL, NULL, NULL, &cap);
     if (cap > cap_words) return -2;
-    uint32_t *seg_ch = (uint32_t *)malloc((nseg + 1) * sizeof(uint32_t));
-    uint64_t *seg_first = (uint64_t *)malloc((nseg + 1) * 3 * sizeof(uint64_t));
-    uint64_t *seg_n = seg_first + nseg + 1, *seg_off = seg_n + nseg + 1;
-    mho_plan_segments(ch_len, C, p, seg_ch, seg_first, seg_n, seg_off, &cap);
     mho_chan *chs = (mho_chan *)malloc((C + 1) * sizeof(mho_chan));
     int err = 0;
     (void)nthreads;
@@ -521,20 +543,38 @@ int mho_encode(const uint8_t *data, const uint64_t *ch_off, const uint64_t *ch_l
         skipped[c] = chs[c].skipped;
         ch_bits[c] = 0;
     }
-    if (!err) {
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-        for (int64_t s = 0; s < (int64_t)nseg; ++s) {
-            const uint32_t c = seg_ch[s];
-            uint64_t bits = 0;
-            seg_words[s] = mho_encode_segment(data + ch_off[c] + chs[c].w0 + seg_first[s],
-                                              seg_n[s], p, &chs[c], payload + seg_off[s], &bits);
-#pragma omp atomic
-            ch_bits[c] += bits;
-        }
-    }
+    if (!err) encode_segments(data, ch_off, ch_len, C, p, chs, payload, seg_words, ch_bits, nthreads);
     free(chs);
-    free(seg_first);
-    free(seg_ch);
+    return err;
+}
+
+int mho_encode_preset(const uint8_t *data, const uint64_t *ch_off, const uint64_t *ch_len, uint32_t C,
+                      const mho_params *p, const uint8_t *peak, const uint8_t *enc, uint32_t *payload,
+                      uint64_t cap_words, uint64_t *seg_words, uint64_t *ch_bits, int nthreads)
+{
+    const int S = (int)p->S;
+    uint64_t cap = 0;
+    mho_plan_segments(ch_len, C, p, NULL, NULL, NULL, NULL, &cap);
+    if (cap > cap_words) return -2;
+    mho_chan *chs = (mho_chan *)malloc((C + 1) * sizeof(mho_chan));
+    int err = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        mho_chan *ch = &chs[c];
+        memset(ch, 0, sizeof(*ch));
+        if (ch_len[c] == 0) err = -1;
+        int sk;
+        window_of(ch_len[c], p, &ch->w0, &ch->w1, &sk);
+        ch->skipped = (uint8_t)sk;
+        ch->peak = peak[c] < S ? peak[c] : 0;
+        ch->enc = enc[c] < p->K ? enc[c] : 0;
+        if (p->mode == MHO_MODE_APPROX)
+            mho_approx_sort_rule(S, ch->peak, ch->idx);
+        else
+            for (int s = 0; s < S; ++s) ch->idx[s] = (uint8_t)s;
+        for (int k = 0; k < S; ++k) ch->rank_of[ch->idx[k]] = (uint8_t)k;
+    }
+    if (!err) encode_segments(data, ch_off, ch_len, C, p, chs, payload, seg_words, ch_bits, nthreads);
+    free(chs);
     return err;
 }
 

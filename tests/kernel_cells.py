@@ -1,0 +1,158 @@
+"""The codec kernels the production library ships, one cell per instance (a plain module, not a conftest).
+
+libmuahuff.so compiles a fixed set of k_encode2 / k_encode2w / k_decode2 / k_decode2w template instances, and
+dispatch_encode, dispatch_encode_packed and dispatch_decode (csrc/muahuff.hip) choose among them from the plan:
+maxlen L (the longest codeword of the plan's SCLV rows), S <= 8 (3-bit pair packing) or not, input_bits (8, or
+packed 4 / 2), the planner's wave-task rule (csrc/mh_planner.hpp) and, for the decoder, the table width W and the
+staging registers dec_NR.  Every CELL names one instance and the plans that land on it:
+
+  cases    (S, SCLV rows) pairs -- each row Kraft-complete and non-decreasing -- with the maxlen they give; decoder
+           cells also give the planner's W, dec_K and dec_NR for that case
+  layouts  (channel lengths, seg_chunks): whole-channel windows (MH_WIN_FULL) that put the plan in the cell's task
+           form -- wave tasks when the workgroup tasks (<= 4 segments of one channel) would leave more than one
+           wave in 16 idle, workgroup tasks otherwise
+
+tests/test_host_kernel_cells.py checks without a GPU that the cells and the shipped symbols are the same set and
+that the host planner puts every case and layout where its cell says; tests/test_gpu_kernel_cells.py runs them
+against the CPU oracle.  UNREACHABLE lists the instances no production plan launches, each with its reason.
+"""
+from dataclasses import dataclass
+
+CHUNK = 16384
+
+
+@dataclass(frozen=True)
+class Case:
+    S: int
+    rows: tuple          # K rows of S code lengths
+    maxlen: int
+    W: int = 0           # decoder cells: index bits of the decode table ...
+    dec_K: int = 0       # ... symbols per lookup ...
+    dec_NR: int = 0      # ... and the planner's staging-register choice (31 only for the hybrid pair table)
+
+
+@dataclass(frozen=True)
+class Cell:
+    symbol: str          # demangled kernel name as the code object lists it, "mh::k_encode2<1, 4, 0, 0>"
+    wave: bool           # wave-task form (k_*2w) or workgroup-task form (k_*2)
+    input_bits: int      # 8 = byte input; 4 / 2 = packed pieces (mh_plan_create_packed)
+    mode: int            # mapper the placement is checked with (the GPU tests run both)
+    cases: tuple
+    layouts: tuple
+
+    @property
+    def decoder(self):
+        return "k_decode2" in self.symbol
+
+
+def _row(*lens):
+    return (tuple(lens),)
+
+
+# rows by (S, L)
+R = {
+    (2, 1): _row(1, 1),
+    (3, 2): _row(1, 2, 2),
+    (4, 2): _row(2, 2, 2, 2),
+    (4, 3): _row(1, 2, 3, 3),
+    (5, 4): _row(1, 2, 3, 4, 4),
+    (8, 3): _row(*[3] * 8),
+    (8, 4): _row(2, 2, 3, 3, 4, 4, 4, 4),
+    (9, 4): _row(2, 2, 3, 4, 4, 4, 4, 4, 4),
+    (10, 4): _row(2, 2, 4, 4, 4, 4, 4, 4, 4, 4),
+    (6, 5): _row(1, 2, 3, 4, 5, 5),
+    (8, 5): _row(2, 2, 2, 4, 4, 4, 5, 5),
+    (9, 5): _row(2, 2, 2, 4, 4, 5, 5, 5, 5),
+    (7, 6): _row(1, 2, 3, 4, 5, 6, 6),
+    (8, 7): _row(1, 2, 3, 4, 5, 6, 7, 7),
+    (9, 8): _row(1, 2, 3, 4, 5, 6, 7, 8, 8),
+    (10, 9): _row(1, 2, 3, 4, 5, 6, 7, 8, 9, 9),
+}
+# two candidate encoders, the longest code in the one a quiet calibration picks
+R2_10_9 = R[(10, 9)] + R[(10, 4)]
+
+
+def _c(S, L, rows=None, **dec):
+    return Case(S, rows or R[(S, L)], L, **dec)
+
+
+# Task forms.  Wave: every channel has at most 4 segments, so each workgroup task idles waves.  Workgroup: segment
+# counts are multiples of 4 -- a channel of 5 samples next to 44 full segments is exactly at the rule's edge
+# (48 padded waves * 15 == 45 segments * 16).  Lengths below 16, off multiples of 16, whole chunks and one past; the
+# equal-length layouts are also packed by the device de-interleaver.
+WAVE_LAYOUTS = (
+    ((7, 1000, CHUNK, CHUNK + 1, 40000, 3 * CHUNK), 1),
+    ((15, 16, 17, 2 * CHUNK + 1, 4 * CHUNK, 100000), 2),
+    ((1, 3 * CHUNK, 3 * CHUNK + 1, 120000), 3),
+    ((3, 4 * CHUNK + 1, 200000, 130000), 4),
+    ((CHUNK + 1,) * 6, 1),
+)
+WG_LAYOUTS = (
+    ((4 * CHUNK, 3 * CHUNK + 1, 8 * CHUNK - 5, 7 * CHUNK + 16), 1),
+    ((8 * CHUNK, 6 * CHUNK + 1, 115687), 2),
+    ((12 * CHUNK, 9 * CHUNK + 1), 3),
+    ((16 * CHUNK, 13 * CHUNK + 7), 4),
+    ((44 * CHUNK, 5), 1),
+    ((4 * CHUNK - 3,) * 3, 1),
+)
+
+
+def _pair(wg_symbol, wave_symbol, input_bits, cases, mode=1):
+    return [Cell(wg_symbol, False, input_bits, mode, tuple(cases), WG_LAYOUTS),
+            Cell(wave_symbol, True, input_bits, 1 - mode, tuple(cases), WAVE_LAYOUTS)]
+
+
+ENCODER_CELLS = tuple(
+    # byte input: LC = code class of L (<= 2, <= 4, <= 8, 9), PB = 3-bit pairs (S <= 8) or 4-bit pairs
+    _pair("mh::k_encode2<0, 3, 0, 0>", "mh::k_encode2w<0, 3, 0>", 8, [_c(3, 2), _c(2, 1), _c(4, 2)])
+    + _pair("mh::k_encode2<1, 3, 0, 0>", "mh::k_encode2w<1, 3, 0>", 8, [_c(8, 3), _c(4, 3), _c(8, 4)])
+    + _pair("mh::k_encode2<1, 4, 0, 0>", "mh::k_encode2w<1, 4, 0>", 8, [_c(9, 4), _c(10, 4)])
+    + _pair("mh::k_encode2<2, 3, 0, 0>", "mh::k_encode2w<2, 3, 0>", 8, [_c(8, 7), _c(6, 5), _c(8, 5)])
+    + _pair("mh::k_encode2<2, 4, 0, 0>", "mh::k_encode2w<2, 4, 0>", 8, [_c(9, 8), _c(9, 5)])
+    + _pair("mh::k_encode2<3, 4, 0, 0>", "mh::k_encode2w<3, 4, 0>", 8, [_c(10, 9), _c(10, 9, R2_10_9)])
+    # 2-bit pieces (S <= 4): the four-symbol table
+    + _pair("mh::k_encode2<0, 4, 0, 2>", "mh::k_encode2w<0, 4, 2>", 2, [_c(3, 2), _c(4, 2), _c(2, 1)])
+    + _pair("mh::k_encode2<1, 4, 0, 2>", "mh::k_encode2w<1, 4, 2>", 2, [_c(4, 3)])
+    # 4-bit pieces: a byte of the stream is the PB = 4 pair index
+    + _pair("mh::k_encode2<0, 4, 0, 4>", "mh::k_encode2w<0, 4, 4>", 4, [_c(3, 2), _c(4, 2)])
+    + _pair("mh::k_encode2<1, 4, 0, 4>", "mh::k_encode2w<1, 4, 4>", 4, [_c(4, 3), _c(5, 4), _c(9, 4), _c(10, 4)])
+    + _pair("mh::k_encode2<2, 4, 0, 4>", "mh::k_encode2w<2, 4, 4>", 4, [_c(6, 5), _c(8, 7), _c(9, 8)])
+    + _pair("mh::k_encode2<3, 4, 0, 4>", "mh::k_encode2w<3, 4, 4>", 4, [_c(10, 9)])
+)
+
+DECODER_CELLS = (
+    # workgroup form: shared tables of up to 10 index bits
+    Cell("mh::k_decode2<4, 4, 17, 1, false, false>", False, 8, 1,
+         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32)), WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 25, 2, false, false>", False, 8, 0,
+         (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 32, 0, false, false>", False, 8, 1,      # L = 5 is the last with W = 2L
+         (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32), _c(8, 5, W=10, dec_K=2, dec_NR=32)),
+         WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 31, 2, true, false>", False, 8, 0,       # L = 6 is the first hybrid one
+         (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31), _c(9, 8, W=10, dec_K=2, dec_NR=31)),
+         WG_LAYOUTS),
+    # wave form: per-wave tables of up to 8 index bits
+    Cell("mh::k_decode2w<4, 4, 17, 1, false, false>", True, 8, 0,
+         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 25, 2, false, false>", True, 8, 1,
+         (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 32, 0, false, false>", True, 8, 0,      # L = 4 is the last with W = 2L
+         (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(8, 4, W=8, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<1, 2, 36, 2, false, true>", True, 8, 1,       # L = 5 is the first one-symbol one
+         (_c(6, 5, W=8, dec_K=2, dec_NR=31), _c(9, 5, W=8, dec_K=2, dec_NR=31),
+          _c(10, 9, W=9, dec_K=2, dec_NR=31)),                          # (W >= L: an entry holds its first code)
+         WAVE_LAYOUTS),
+)
+
+CELLS = ENCODER_CELLS + DECODER_CELLS
+
+# Compiled instances that no production plan launches (removing them is a kernel change of its own).
+UNREACHABLE = {
+    "mh::k_encode2<0, 4, 0, 0>": "byte input with 4-bit pairs means S >= 9, and S >= 9 symbols cannot have L <= 2",
+    "mh::k_encode2w<0, 4, 0>": "byte input with 4-bit pairs means S >= 9, and S >= 9 symbols cannot have L <= 2",
+    "mh::k_decode2<1, 2, 36, 2, false, true>": "the one-symbol decoder is chosen for wave-task plans only (MH_DEC_K1 = 1)",
+    "mh::k_decode2<2, 2, 32, 0, true, false>": "dec_NR is 31 for every hybrid table outside MH_TUNING builds",
+    "mh::k_decode2w<2, 2, 32, 0, true, false>": "dec_NR is 31 for every hybrid table outside MH_TUNING builds",
+    "mh::k_decode2w<2, 2, 31, 2, true, false>": "wave-task plans take the one-symbol decoder before the hybrid one",
+}

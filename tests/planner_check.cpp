@@ -4,8 +4,12 @@
 //     C S h mode window K seg_chunks  len[0..C)  sclv[0..K*S)
 // checks the planner's internal invariants and prints, per case, the directory for the test to
 // compare with the CPU oracle's:  "nseg cap seg_chunks wave_tasks" then four lines ch / first / n / off.
+// With --cells (tests/kernel_cells.py) each case carries input_bits after seg_chunks,
+//     C S h mode window K seg_chunks input_bits  len[0..C)  sclv[0..K*S)
+// and the program prints only where the kernel dispatch lands:  "maxlen wave_tasks W dec_K dec_NR".
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "mh_planner.hpp"
@@ -18,8 +22,45 @@
         }                                                              \
     } while (0)
 
-int main()
+static int cells()
 {
+    unsigned C, S, h, mode, window, K, sc, bits;
+    while (scanf("%u %u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc, &bits) == 8) {
+        std::vector<uint64_t> len(C), off(C);
+        std::vector<uint8_t> sclv((size_t)K * S);
+        uint64_t o = 0;
+        for (unsigned c = 0; c < C; ++c) {
+            unsigned long long v;
+            if (scanf("%llu", &v) != 1) return 1;
+            len[c] = v;
+            off[c] = o;
+            o += (v + 15) & ~15ull;
+        }
+        for (auto &b : sclv) {
+            unsigned v;
+            if (scanf("%u", &v) != 1) return 1;
+            b = (uint8_t)v;
+        }
+        const char *msg = "";
+        uint32_t arg = 0, maxlen = 0;
+        const int rc = mh::plan_check_args(len.data(), C, S, h, mode, window, sclv.data(), K, &maxlen, &msg, &arg);
+        if (rc != MH_OK) {
+            printf("error %d\n", rc);
+            continue;
+        }
+        mh::PlanHost p;
+        p.info.C = C; p.info.S = S; p.info.h = h; p.info.mode = mode; p.info.window = window;
+        p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
+        p.input_bits = bits;
+        mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+        printf("%u %d %u %u %u\n", p.info.maxlen, (int)p.use_wave_tasks, p.W, p.dec_K, p.dec_NR);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && !strcmp(argv[1], "--cells")) return cells();
     unsigned C, S, h, mode, window, K, sc;
     while (scanf("%u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc) == 7) {
         std::vector<uint64_t> len(C), off(C);

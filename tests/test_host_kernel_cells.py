@@ -1,0 +1,91 @@
+"""The table of codec kernel cells (tests/kernel_cells.py) against the shipped code object and the host planner.
+Runs without a GPU: a kernel instance added to libmuahuff.so fails here until it gets a cell (or an UNREACHABLE
+entry with its reason), and a cell whose plans no longer land on its kernel fails before any GPU run."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from tests import kernel_cells as kc
+from tests.test_planner_sanitized import exe  # noqa: F401  (fixture: planner_check built under the sanitizers)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
+
+
+def _shipped_codec_kernels(tmp_path):
+    """demangled names of every k_encode2* / k_decode2* kernel in the gfx950 code object of libmuahuff.so"""
+    from muahuff import _lib
+    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump")]
+    if not all(os.path.exists(t) for t in tools):
+        pytest.skip("no ROCm LLVM tools here")
+    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "gfx950.co")
+    subprocess.run([tools[0], "--dump-section", ".hip_fatbin=" + fat, _lib.SO], check=True)
+    subprocess.run([tools[1], "--unbundle", "--type=o", "--input=" + fat, "--output=" + co,
+                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
+    table = subprocess.run([tools[2], "-t", co], check=True, capture_output=True, text=True).stdout
+    # kernel entry points are the function symbols (their descriptors are the ".kd" objects)
+    mangled = sorted({ln.split()[-1] for ln in table.splitlines()
+                      if " F " in ln and re.search(r"k_(en|de)code2", ln)})
+    assert mangled, "no codec kernels in the code object"
+    names = subprocess.run(["c++filt"], input="\n".join(mangled) + "\n", check=True, capture_output=True,
+                           text=True).stdout.split("\n")[:len(mangled)]
+    out = set()
+    for n in names:
+        m = re.fullmatch(r"void (mh::k_(?:en|de)code2w?<[^>]*>)\(mh::(?:Enc|Dec)2Args\)", n.strip())
+        assert m, n
+        out.add(m.group(1))
+    return out
+
+
+def test_every_shipped_codec_kernel_has_a_cell(tmp_path):
+    shipped = _shipped_codec_kernels(tmp_path)
+    cells = [c.symbol for c in kc.CELLS]
+    assert len(cells) == len(set(cells)), "one cell per kernel instance"
+    assert len(kc.ENCODER_CELLS) == 24 and len(kc.DECODER_CELLS) == 8
+    assert not set(cells) & set(kc.UNREACHABLE)
+    assert set(cells) | set(kc.UNREACHABLE) == shipped, dict(
+        without_cell=sorted(shipped - set(cells) - set(kc.UNREACHABLE)),
+        not_shipped=sorted((set(cells) | set(kc.UNREACHABLE)) - shipped))
+    assert all(len(why) > 20 for why in kc.UNREACHABLE.values())
+
+
+def test_cell_symbols_name_their_task_form_and_input():
+    for c in kc.CELLS:
+        assert ("2w<" in c.symbol) == c.wave, c.symbol
+        if not c.decoder:
+            pk = int(c.symbol.rstrip(">").split(",")[-1])
+            assert pk == (0 if c.input_bits == 8 else c.input_bits), c.symbol
+            pb = int(c.symbol.split("<")[1].split(",")[1])
+            for k in c.cases:
+                if c.input_bits == 8:
+                    assert pb == (3 if k.S <= 8 else 4), (c.symbol, k.S)
+                if c.input_bits == 2:
+                    assert k.S <= 4
+        else:
+            assert c.input_bits == 8
+
+
+def test_every_cell_lands_where_the_table_says(exe):  # noqa: F811
+    """Each case x layout of each cell through the host planner (--cells): maxlen and the task form; decoder cells
+    also W, dec_K and dec_NR."""
+    lines, want = [], []
+    for c in kc.CELLS:
+        for k in c.cases:
+            for lens, sc in c.layouts:
+                rows = " ".join(str(v) for r in k.rows for v in r)
+                lines.append("%d %d 6 %d 3 %d %d %d  %s  %s" % (len(lens), k.S, c.mode, len(k.rows), sc, c.input_bits,
+                                                               " ".join(map(str, lens)), rows))
+                want.append((c, k, lens, sc))
+    r = subprocess.run([exe, "--cells"], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = r.stdout.splitlines()
+    assert len(got) == len(want)
+    for g, (c, k, lens, sc) in zip(got, want):
+        maxlen, wave, W, dec_K, dec_NR = (int(v) for v in g.split())
+        tag = (c.symbol, k.S, k.rows, lens, sc)
+        assert maxlen == k.maxlen, tag
+        assert wave == int(c.wave), tag
+        if c.decoder:
+            assert (W, dec_K, dec_NR) == (k.W, k.dec_K, k.dec_NR), tag

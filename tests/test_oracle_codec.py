@@ -172,3 +172,45 @@ def test_container_validation_accepts_good_and_rejects_corrupt_streams():
             cio.validate(rep(enc=np.full_like(c.enc, 200)))
         with pytest.raises(ValueError):
             cio.validate(rep(ch_len=c.ch_len[:-1]))
+
+
+@pytest.mark.parametrize("S,h,mode,window", [
+    (3, 6, 1, OC.WIN_REF_HALF), (5, 2, 1, OC.WIN_AFTER_CAL), (10, 10, 1, OC.WIN_AFTER_CAL),
+    (7, 3, 0, OC.WIN_REF_HALF_TRUNC), (9, 4, 0, OC.WIN_FULL), (4, 6, 1, OC.WIN_FULL | OC.WIN_REV2_SEGMENTS),
+])
+def test_encode_preset_equals_encode_under_the_calibrated_word(S, h, mode, window):
+    """encode_preset (the oracle of mh_encode_preset) with the word encode() calibrated is encode() byte for byte;
+    a word out of range (peak >= S, enc >= K) is the word (0, 0)."""
+    rng = np.random.RandomState(S * 11 + h)
+    chans = _channels(rng, [1, 15, 16, 17, 1000, 16384, 16385, 40000, 300_000 + 3])
+    data, off, ln = OC.flatten(chans)
+    tab = helpers.sclv_tables()[S]
+    p = OC.Params(S, h, mode, window, tab, seg_chunks=2)
+    oe = OC.encode(data, off, ln, p)
+    pe = OC.encode_preset(data, off, ln, p, oe["peak"], oe["enc"])
+    for k in ("payload", "seg_words", "ch_bits", "peak", "enc"):
+        assert np.array_equal(pe[k], oe[k]), k
+    C = len(chans)
+    zero = OC.encode_preset(data, off, ln, p, np.zeros(C, np.uint8), np.zeros(C, np.uint8))
+    bad_peak = np.array([S, S + 1, 255] * C, np.uint8)[:C]
+    bad_enc = np.array([len(tab), 255, len(tab) + 7] * C, np.uint8)[:C]
+    for pk, en in ((bad_peak, 0), (0, bad_enc), (bad_peak, bad_enc)):
+        got = OC.encode_preset(data, off, ln, p, pk, en)
+        for k in ("payload", "seg_words", "ch_bits", "peak", "enc"):
+            assert np.array_equal(got[k], zero[k]), k
+    # and the word is really used: the bits are the code lengths of the clipped samples under it
+    pk = rng.randint(0, S, size=C).astype(np.uint8)
+    en = rng.randint(0, len(tab), size=C).astype(np.uint8)
+    got = OC.encode_preset(data, off, ln, p, pk, en)
+    seg = OC.plan_segments(ln, p)
+    for c, x in enumerate(chans):
+        idx = OC.approx_sort_rule(S, int(pk[c])) if mode == OC.MODE_APPROX else np.arange(S)
+        rank_of = np.argsort(idx)
+        c0 = min(2 ** h, len(x))
+        lo, hi = {OC.WIN_REF_HALF: (c0, c0 + len(x) // 2), OC.WIN_REF_HALF_TRUNC: (c0, min(c0 + len(x) // 2, len(x))),
+                  OC.WIN_AFTER_CAL: (c0, len(x)), OC.WIN_FULL: (0, len(x))}[window & 0xFF]
+        if window & 0xFF == OC.WIN_REF_HALF and hi > len(x):
+            assert got["ch_bits"][c] == 0 and not (seg["ch"] == c).any()
+            continue
+        want = int(tab[en[c]][rank_of[np.minimum(x[lo:hi], S - 1)]].sum())
+        assert int(got["ch_bits"][c]) == want, c
