@@ -12,7 +12,6 @@ SO = os.path.join(HERE, "libmuahuff.so")
 SOURCES = ["csrc/muahuff.hip"]
 HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csrc/mh_codec2.hpp", "csrc/mh_layout.hpp",
            "csrc/mh_planner.hpp", "csrc/mh_analysis.hpp", "../include/muahuff.h"]
-TUNING_SO = os.path.join(HERE, "libmuahuff_tuning.so")  # -DMH_TUNING: env knobs + ablation hook, tools/ only
 
 
 def stale():
@@ -22,29 +21,19 @@ def stale():
     return any(os.path.getmtime(os.path.join(HERE, f)) > t for f in SOURCES + HEADERS)
 
 
-def build(force=False, verbose=False, tuning=False):
-    """libmuahuff.so -- or, with tuning=True, libmuahuff_tuning.so: the same kernels plus the
-    A/B knobs (MH_DEC_W, MH_DEC_NR, MH_WAVE_TASKS, mhdbg_set_ablation) that the production
-    library does not contain; tools/ load it through _lib.use_library()."""
-    so = TUNING_SO if tuning else SO
-    if tuning:
-        if not force and os.path.exists(so) and not any(
-                os.path.getmtime(os.path.join(HERE, f)) > os.path.getmtime(so) for f in SOURCES + HEADERS):
-            return so
-    elif not force and not stale():
+def build(force=False, verbose=False):
+    """libmuahuff.so, exporting the C ABI of include/muahuff.h and nothing else (csrc/exports.map)."""
+    if not force and not stale():
         return SO
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc")]
-    if tuning:
-        cmd.append("-DMH_TUNING")   # (exports mhdbg_* besides the ABI)
-    else:
-        cmd.append("-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports.map"))
-    cmd += [os.path.join(HERE, s) for s in SOURCES] + ["-o", so]
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports.map")]
+    cmd += [os.path.join(HERE, s) for s in SOURCES] + ["-o", SO]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=HERE)
-    return so
+    return SO
 
 
 def build_example(force=False):

@@ -51,7 +51,7 @@ __host__ __device__ inline uint32_t enc2_wave_dwords(uint32_t stage_dw)
 // atomics.  Correct for any data; only adversarial inputs ever get here.
 // Returns {words written, code bits}.
 // Input packing PK of the encoder (template parameter throughout): 0 = one byte per sample (the
-// channel-major container), 4 / 2 = packed pieces written by k_deinterleave2<PK> for the time-major path.
+// channel-major container), 4 / 2 = packed pieces written by k_deinterleave_p<PK> for the time-major path.
 template <int PK>
 struct RawPiece { typedef u32x4 type; };
 template <>
@@ -187,7 +187,7 @@ __device__ __forceinline__ void pair_entries(uint32_t x, const uint2 *lut2, uint
 // One 16-sample piece per lane (x = 4 dwords of counts) appended to the lane's 64-bit accumulator.  It exists
 // as MACROS because two functions need the same statements -- encode_full_chunk's unrolled row loop and
 // encode_row for partial chunks -- and routing the hot loop through a function cost the S = 10 kernel 6 %:
-// one source text, two expansions.  The expansion site provides LC, PB, ABL, lut2, acc, nb, sp, st, cap.
+// one source text, two expansions.  The expansion site provides LC, PB, lut2, acc, nb, sp, st, cap.
 __host__ __device__ constexpr int stage_ne(int LC) { return LC == 0 ? 4 : 8; }  // cap / 4 for the largest cap of the class
 
 // Where a lane keeps its j-th spilled dword: staging ROW (j % NE) * 4 + j / NE of its column (NE = dwords one lane of
@@ -197,7 +197,7 @@ __host__ __device__ constexpr int stage_ne(int LC) { return LC == 0 ? 4 : 8; }  
 #define MH_STAGE_AT(j) ((((j) & (uint32_t)(MH_NE_ - 1)) << 2 | ((j) >> (MH_NE_ == 4 ? 2 : 3))) * 16)
 #define MH_FLUSH()                                                                                  \
     if (nb >= 32) {                                                                                 \
-        if ((ABL < 3 || ABL >= 5) && (LC <= 1 || sp < cap)) st[MH_STAGE_AT(sp)] = (uint32_t)acc;    \
+        if (LC <= 1 || sp < cap) st[MH_STAGE_AT(sp)] = (uint32_t)acc;                               \
         acc >>= 32;                                                                                 \
         nb -= 32;                                                                                   \
         ++sp;                                                                                       \
@@ -294,9 +294,6 @@ template <int PK>
 __device__ __forceinline__ typename RawPiece<PK>::type load_row(const uint8_t *p)
 {
     if constexpr (PK == 0) {
-#ifdef MH_ROW_PLAIN  // A/B builds: plain instead of non-temporal row loads
-        return *reinterpret_cast<const u32x4_u *>(p);
-#endif
         return __builtin_nontemporal_load(reinterpret_cast<const u32x4_u *>(p));
     } else if constexpr (PK == 4) {
         typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
@@ -365,7 +362,7 @@ __device__ __forceinline__ uint32_t *stage_lane_base(uint32_t *buf, uint32_t cap
 // zero-fill of the image).  Partial chunks (sub-streams of any length, several to a word) keep the OR for every dword.
 // DPP: the wave-wide scan / min / max of the sub-stream lengths as DPP ladders instead of ds_bpermute chains (mh_device.hpp,
 // wave_scan_incl_dpp: for launches that wait on latency -- wave-task encoders, partial chunks).
-template <int NE, int ABL, bool FULL, bool DPP = false>
+template <int NE, bool FULL, bool DPP = false>
 __device__ __forceinline__ void merge_and_flush(uint32_t *buf, uint32_t cap, uint32_t tot, uint32_t sp,
                                                 uint32_t *__restrict__ &dst, uint32_t &pend, int lane,
                                                 uint32_t &words, uint32_t &bits)
@@ -445,31 +442,8 @@ __device__ __forceinline__ void merge_and_flush(uint32_t *buf, uint32_t cap, uin
     // only whole, 256-byte-aligned blocks go to HBM (16 B per lane, non-temporal); the rest waits
     const uint32_t total = pend + hw + nw;
     const uint32_t nflush = total & ~63u;
-    // (ABL 8 only; an offset, not a rebuilt pointer -- that would turn the store into a FLAT access)
-    const ptrdiff_t back_abl = (ptrdiff_t)((reinterpret_cast<uintptr_t>(dst) & (uintptr_t)32767) >> 2);
-    if (ABL < 1 || ABL >= 5) {
-        for (uint32_t i = lane * 4; i < nflush; i += 256) {
-            u32x4 blk = {0u, 0u, 0u, 0u};
-            if (ABL != 13) blk = *reinterpret_cast<const u32x4 *>(buf + i);
-            u32x4_u *to = reinterpret_cast<u32x4_u *>(dst + i);
-            // (tuning builds: ABL 5..7 time other flavours of this store -- plain, nt + sc1, sc0 sc1; 8 issues
-            // the same stores but keeps them inside one L2-resident 4 KiB per wave: no DRAM writes)
-            if (ABL == 8) to = reinterpret_cast<u32x4_u *>(dst - back_abl + (i & 1023u));
-            if (ABL == 13) {  // image merged as usual, but the stores take register data: no ds_read -> store chain
-                const u32x4 junk = {tot, sp, P, (uint32_t)lane};
-                __builtin_nontemporal_store(junk, to);
-                continue;
-            }
-            if (ABL == 5 || ABL == 8)
-                *to = blk;
-            else if (ABL == 6)
-                asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(to), "v"(blk) : "memory");
-            else if (ABL == 7)
-                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(to), "v"(blk) : "memory");
-            else
-                __builtin_nontemporal_store(blk, to);
-        }
-    }
+    for (uint32_t i = lane * 4; i < nflush; i += 256)
+        __builtin_nontemporal_store(*reinterpret_cast<const u32x4 *>(buf + i), reinterpret_cast<u32x4_u *>(dst + i));
     const uint32_t tail = total - nflush;
     uint32_t t = 0;
     if ((uint32_t)lane < tail) t = buf[nflush + lane];
@@ -480,20 +454,6 @@ __device__ __forceinline__ void merge_and_flush(uint32_t *buf, uint32_t cap, uin
     pend = tail;
     words = hw + nw;
     bits = B;
-}
-
-// Ablation only (tuning builds): the flush of a typical chunk image (736 words = 1.44 bits/sample) with register data
-// instead of the merged image -- same addresses, same block rule as merge_and_flush.
-__device__ __forceinline__ void abl_flush_fixed(uint32_t seed, uint32_t *__restrict__ &dst, uint32_t &pend, int lane,
-                                                uint32_t &words, uint32_t &bits)
-{
-    const uint32_t total = pend + 736u, nflush = total & ~63u;
-    const u32x4 blk = {seed, seed ^ 1u, seed ^ 2u, (uint32_t)lane};
-    for (uint32_t i = lane * 4; i < nflush; i += 256) __builtin_nontemporal_store(blk, reinterpret_cast<u32x4_u *>(dst + i));
-    dst += nflush;
-    pend = total - nflush;
-    words = 736u;
-    bits = 736u * 32u;
 }
 
 // chunk whose sub-streams outgrew the staging: flush the carried tail, then the global slow path
@@ -512,8 +472,8 @@ __device__ __forceinline__ void overflow_chunk(const uint8_t *src, uint32_t m, c
     dst += words;
 }
 
-// The row body as a function, for the partial-chunk encoder (ABL: see encode_full_chunk).
-template <int LC, int PB, int ABL>
+// The row body as a function, for the partial-chunk encoder.
+template <int LC, int PB>
 __device__ __forceinline__ void encode_row(u32x4 x, const uint2 *lut2, uint64_t &acc, uint32_t &nb, uint32_t &sp,
                                            uint32_t *st, uint32_t cap)
 {
@@ -525,7 +485,7 @@ __device__ __forceinline__ void encode_row(u32x4 x, const uint2 *lut2, uint64_t 
 // The same for a piece of packed input (r = 2 dwords of 4-bit or 1 dword of 2-bit samples): every byte of
 // the piece is a table index as it stands -- nothing is spread back to one byte per sample.  Used by the
 // full-chunk and the partial-chunk encoder alike.
-template <int LC, int PK, int ABL>
+template <int LC, int PK>
 __device__ __forceinline__ void encode_row_packed(typename RawPiece<PK>::type r, const uint2 *lut2, uint64_t &acc,
                                                   uint32_t &nb, uint32_t &sp, uint32_t *st, uint32_t cap)
 {
@@ -571,14 +531,12 @@ __device__ __forceinline__ void encode_row_packed(typename RawPiece<PK>::type r,
 
 // One full chunk.  v[] is a rolling window: row k of this chunk sits in v[k & 7]; after it is
 // consumed the slot is refilled with the row 8 KiB further on (this chunk, then the next one).
-// ABL (debug ablation, 0 in production): 1 no global stores, 2 also no merge, 3 also no staging
-// writes, 4 loads only
 // HAS_NEXT is a template constant on purpose: with a run-time flag the refill loads of the second half
 // sit in a branch, the compiler's wait-count pass cannot count them, and every vmcnt in that half
 // tightens by one per row down to vmcnt(0) -- the wave then drains its whole window at each chunk end.
 // nxt = first byte of the chunk that follows `cur` in the stream (cur + one chunk in the plain layouts,
 // elsewhere in the chunk-blocked intermediate of the time-major path); only read when HAS_NEXT
-template <int LC, int PB, int ABL, bool HAS_NEXT, int PK, bool DPP = false>
+template <int LC, int PB, bool HAS_NEXT, int PK, bool DPP = false>
 __device__ __forceinline__ void encode_full_chunk(typename RawPiece<PK>::type (&v)[kWin], const uint8_t *__restrict__ cur,
                                                   const uint8_t *__restrict__ nxt, const uint2 *lut2, const uint2 *lut1,
                                                   uint32_t *buf, uint32_t cap, uint32_t *__restrict__ &dst,
@@ -589,7 +547,6 @@ __device__ __forceinline__ void encode_full_chunk(typename RawPiece<PK>::type (&
     uint64_t acc = 0;
     uint32_t nb = 0, sp = 0;
     uint32_t *st = stage_lane_base(buf, cap, lane);
-    // (A/B builds: -DMH_ROW_GLOBAL = global loads for every encoder's rows, as before)
     // The rows of a chunk through a buffer resource on the chunk's first byte (wave-uniform: four scalar
     // registers) -- the row is an immediate / scalar offset and the lane's 16 bytes one vector register, where a
     // global load needs a 64-bit vector address per row (two VALU adds); and the cache policy is an operand of the
@@ -617,12 +574,7 @@ __device__ __forceinline__ void encode_full_chunk(typename RawPiece<PK>::type (&
         // (NOT the byte-input encoder of S <= 3: in the headline's alternation -- encode, decode, encode, ... -- the
         // decode that FOLLOWS that encoder runs 4 % slower when every row was read nt through the buffer form
         // (2.03 instead of 1.94-1.99 ms, tools/bench_with_lib.py; the encoder itself gains nothing at S = 3))
-        constexpr bool kRowsByBuffer =
-#ifndef MH_ROW_GLOBAL
-            !(PK == 0 && LC == 0);
-#else
-            false;
-#endif
+        constexpr bool kRowsByBuffer = !(PK == 0 && LC == 0);
         if constexpr (kRowsByBuffer) {
             if (k < kRows - kWin)
                 v[k & (kWin - 1)] = row_load(rs_cur, k + kWin);
@@ -635,25 +587,12 @@ __device__ __forceinline__ void encode_full_chunk(typename RawPiece<PK>::type (&
                 v[k & (kWin - 1)] = load_row<PK>(nxt + ((uint32_t)(k + kWin - kRows) * kLanes + lane) * piece_bytes<PK>());
         }
         if constexpr (PK != 0) {
-            encode_row_packed<LC, PK, ABL>(raw, lut2, acc, nb, sp, st, cap);
+            encode_row_packed<LC, PK>(raw, lut2, acc, nb, sp, st, cap);
             continue;
         }
         u32x4 x;
         if constexpr (PK == 0) x = raw;
-        if (ABL == 4 || ABL == 11) {
-            acc += x.x ^ x.y ^ x.z ^ x.w;
-            continue;
-        }
         MH_ENCODE_ROW(x)
-    }
-    if (ABL == 11 || ABL == 12) {  // 11: loads + a typical chunk's stores (the probe inside the real kernel);
-        abl_flush_fixed((uint32_t)acc + nb + sp, dst, pend, lane, words, bits);  // 12: + the row arithmetic and staging
-        return;
-    }
-    if (ABL >= 2 && ABL < 5) {  // keep the work alive, skip the rest
-        words = 0;
-        bits = (uint32_t)acc + nb + sp;
-        return;
     }
     const uint32_t tot = sp * 32 + nb;
     if (nb > 0) {
@@ -665,7 +604,7 @@ __device__ __forceinline__ void encode_full_chunk(typename RawPiece<PK>::type (&
         overflow_chunk<false, PK>(cur, kChunk, lut1, buf, dst, pend, lane, words, bits);
         return;
     }
-    merge_and_flush<stage_ne(LC), ABL, true, DPP>(buf, cap, tot, sp, dst, pend, lane, words, bits);
+    merge_and_flush<stage_ne(LC), true, DPP>(buf, cap, tot, sp, dst, pend, lane, words, bits);
 }
 
 // Last, partial chunk of a channel (m < 16384 samples).  Its full pieces (16 samples) take the same
@@ -710,9 +649,9 @@ __device__ __noinline__ uint4 encode_partial_chunk(const MH_AS_GLOBAL uint8_t *s
             const uint32_t k = (uint32_t)(half * 8 + r);
             if (k < nrows && k * kLanes + lane < nfp) {  // the escapes inside ballot the active lanes only
                 if constexpr (PK == 0)
-                    encode_row<LC, PB, 0>(v[r], lut2, acc, nb, sp, st, cap);
+                    encode_row<LC, PB>(v[r], lut2, acc, nb, sp, st, cap);
                 else
-                    encode_row_packed<LC, PK, 0>(v[r], lut2, acc, nb, sp, st, cap);
+                    encode_row_packed<LC, PK>(v[r], lut2, acc, nb, sp, st, cap);
             }
         }
     }
@@ -741,7 +680,7 @@ __device__ __noinline__ uint4 encode_partial_chunk(const MH_AS_GLOBAL uint8_t *s
     if (LC >= 2 && __any(sp > cap))
         overflow_chunk<true, PK>(src, m, lut1, buf, dst, pend, lane, words, bits);
     else
-        merge_and_flush<NE, 0, false, true>(buf, cap, tot, sp, dst, pend, lane, words, bits);
+        merge_and_flush<NE, false, true>(buf, cap, tot, sp, dst, pend, lane, words, bits);
     return make_uint4(words, bits, pend, (uint32_t)(dst - dst0));
 }
 
@@ -764,9 +703,9 @@ __device__ __forceinline__ void load_first_rows(typename RawPiece<PK>::type (&v)
 // PUBLISH: the wave stores the segment's word count and adds its bits to the channel's total itself (wave tasks);
 // otherwise the caller does (the shared-table kernel publishes a whole task at once: one 32-byte store and one
 // atomic per workgroup instead of four scattered 8-byte stores and four atomics -- 313 000 of each per launch on
-// the 1024 x 1e7 set cost 0.06 ms, tools/ablate_encode.py level 15).
+// the 1024 x 1e7 set cost 0.06 ms, profiles/r03_encode_ablation.txt).
 // PUBLISH (the wave-task kernels: a wave is a task of its own) also selects the DPP reductions in the chunks' merge.
-template <int LC, int PB, int ABL, bool PRE, int PK, bool PUBLISH = true>
+template <int LC, int PB, bool PRE, int PK, bool PUBLISH = true>
 __device__ __forceinline__ void encode_segment(const EncArgs &e, uint32_t seg, uint32_t ch, const uint8_t *src, uint64_t n,
                                                uint32_t *__restrict__ out, typename RawPiece<PK>::type (&v)[kWin], const uint2 *lut2,
                                                const uint2 *lut1, uint32_t *buf, uint32_t cap, int lane,
@@ -782,13 +721,13 @@ __device__ __forceinline__ void encode_segment(const EncArgs &e, uint32_t seg, u
         if (!PRE) load_first_rows<PK>(v, src, lane);
         uint32_t w, b;
         for (uint32_t c = 0; c + 1 < nfull; ++c) {
-            encode_full_chunk<LC, PB, ABL, true, PK, PUBLISH>(v, src + (size_t)c * cstride, src + (size_t)(c + 1) * cstride, lut2, lut1, buf,
-                                                     cap, out, pend, lane, w, b);
+            encode_full_chunk<LC, PB, true, PK, PUBLISH>(v, src + (size_t)c * cstride, src + (size_t)(c + 1) * cstride, lut2, lut1, buf,
+                                                cap, out, pend, lane, w, b);
             words += w;
             bits += b;
         }
-        encode_full_chunk<LC, PB, ABL, false, PK, PUBLISH>(v, src + (size_t)(nfull - 1) * cstride, src, lut2, lut1, buf, cap, out, pend,
-                                                  lane, w, b);
+        encode_full_chunk<LC, PB, false, PK, PUBLISH>(v, src + (size_t)(nfull - 1) * cstride, src, lut2, lut1, buf, cap, out, pend,
+                                             lane, w, b);
         words += w;
         bits += b;
     }
@@ -801,9 +740,8 @@ __device__ __forceinline__ void encode_segment(const EncArgs &e, uint32_t seg, u
         pend = r.z;
         out += r.w;
     }
-    // (tuning builds: ABL 14 = everything but this partial-block store, 15 = also without seg_words / ch_bits)
-    if ((ABL < 1 || ABL >= 5) && ABL != 14 && ABL != 15 && (uint32_t)lane < pend) out[lane] = buf[lane];  // segment tail (partial block)
-    if (PUBLISH && lane == 0 && ABL != 15) {
+    if ((uint32_t)lane < pend) out[lane] = buf[lane];  // segment tail (partial block)
+    if (PUBLISH && lane == 0) {
         e.seg_words[seg] = words;
         if (!PRE || e.cal_mode == 0) atomicAdd(&e.ch_bits[ch], (unsigned long long)bits);  // zeroed by k_calibrate
     }
@@ -816,7 +754,7 @@ __device__ __forceinline__ void encode_segment(const EncArgs &e, uint32_t seg, u
 template <int PK>
 __device__ __forceinline__ uint64_t stream_bytes(uint64_t t) { return PK == 0 ? t : (t >> 4) * piece_bytes<PK>(); }
 
-template <int LC, int PB, int ABL = 0, int PK = 0>
+template <int LC, int PB, int PK = 0>
 __global__ __launch_bounds__(256, 4) void k_encode2(Enc2Args a)
 {
     // the workgroup's tables are STATIC shared memory: their addresses are compile-time constants that go into
@@ -876,16 +814,15 @@ __global__ __launch_bounds__(256, 4) void k_encode2(Enc2Args a)
     uint64_t bits = 0, words = 0;
     // (packed input exists for whole-channel windows only: w0 = 0 and segments start at chunk boundaries)
     if (n)
-        encode_segment<LC, PB, ABL, true, PK, false>(a.e, t.seg0 + (uint32_t)wave, ch, src, n,
-                                                     a.e.payload + t.dst_off + (uint64_t)wave * a.t.slot_full, v, lut2, lut1, buf,
-                                                     cap, lane, bits, &words);
+        encode_segment<LC, PB, true, PK, false>(a.e, t.seg0 + (uint32_t)wave, ch, src, n,
+                                                a.e.payload + t.dst_off + (uint64_t)wave * a.t.slot_full, v, lut2, lut1, buf,
+                                                cap, lane, bits, &words);
     // the task's results leave together: word counts of its <= 4 segments in one store, ONE atomic for the channel
     if (lane == 0) {
         s_pub[wave] = words;
         s_pub[4 + wave] = bits;
     }
     __syncthreads();
-    if (ABL == 15) return;
     if (threadIdx.x < nseg) a.e.seg_words[t.seg0 + threadIdx.x] = s_pub[threadIdx.x];
     if (threadIdx.x == 0)
         atomicAdd(&a.e.ch_bits[ch], (unsigned long long)(s_pub[4] + s_pub[5] + s_pub[6] + s_pub[7]));  // zeroed by k_calibrate / k_lut_preset
@@ -1001,8 +938,8 @@ __global__ __launch_bounds__(256, 4) void k_encode2w(Enc2Args a)
     MH_WAVE_SYNC();
     uint64_t bits = 0;
     if (t.n)
-        encode_segment<LC, PB, 0, true, PK>(a.e, t.seg, t.ch, src, t.n, a.e.payload + t.dst_off, v, lut2, lut1,
-                                            wbase + kTabDw, cap, lane, bits);
+        encode_segment<LC, PB, true, PK>(a.e, t.seg, t.ch, src, t.n, a.e.payload + t.dst_off, v, lut2, lut1,
+                                         wbase + kTabDw, cap, lane, bits);
     if (a.e.cal_mode != 0 && lane == 0) {
         // Bit total of the channel without a zeroing launch: every record adds {bits << 24 | 1} to the
         // channel's word in plan scratch with ONE returning device-scope atomic.  The record that sees
@@ -1025,10 +962,6 @@ __global__ __launch_bounds__(256, 4) void k_encode2w(Enc2Args a)
 // ------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------
-#ifdef MH_TUNING
-__device__ int d_dec_abl;  // see decode_staged_chunk
-#endif
-
 struct Dec2Args {
     DecArgs d;
     TaskArgs t;
@@ -1088,9 +1021,9 @@ __device__ __forceinline__ ChunkHdr scan_header(uint32_t hw32, int lane)
 // PARTIAL: the chunk holds m < 16384 samples.  Rows past the last sample are skipped (wave-uniform),
 // lanes whose piece is not complete skip the row, and the one cut piece (m % 16 samples) is decoded
 // symbol by symbol from the same window.
-// ST: how a decoded row leaves.  0 = global store (the long-channel kernels and the one-symbol decoder); 1 / 2 =
-// through a buffer resource on the chunk's first output byte with the default / the nt cache policy (no 64-bit vector
-// address per row).  The wave-task decoders of S <= 6 use 1: 2400 x 72 000 decode S = 3 41 -> 35.5 us, S = 5 47.7 -> 45 us;
+// ST: how a decoded row leaves.  0 = global store (the long-channel kernels and the one-symbol decoder); 1 = through
+// a buffer resource on the chunk's first output byte with the default cache policy (no 64-bit vector address per row).
+// The wave-task decoders of S <= 6 use 1: 2400 x 72 000 decode S = 3 41 -> 35.5 us, S = 5 47.7 -> 45 us;
 // 10 000 x 20 000 S = 3 55 -> 40.6 us, S = 5 60 -> 53.5 us.  The long-channel kernels LOSE with either buffer form (S = 3:
 // 1.95 -> 2.25 ms with the default policy, 2.0-2.1 with nt): a decoder that gets its rows out faster writes worse on
 // this part (cf. the occupancy cap); the one-symbol decoder loses 4 % (profiles/r03_dpp_reductions.txt).
@@ -1133,9 +1066,6 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
     uint32_t nxt = kReload ? 0u : stage[wi + 2];
     const uint32_t nfp = m >> 4;                   // complete pieces (PARTIAL)
     const uint32_t nrows_any = (m + 1023u) >> 10;  // rows holding any sample (PARTIAL)
-#ifdef MH_TUNING
-    const int dec_abl = __builtin_amdgcn_readfirstlane(d_dec_abl);  // once per chunk: the row stores below may alias it
-#endif
     const auto rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0x7FFFFFFF, 0x00020000);  // (ST != 0)
     auto row = [&](int k) {
         const uint32_t piece = (uint32_t)k * kLanes + lane;
@@ -1181,11 +1111,7 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
                     const uint32_t e = *reinterpret_cast<lds_u1 *>(off + tbase);
                     w |= (e & 0xFFFFu) << (8 * K * i);
                     adv = HY ? (e >> 16) & 0x7FFFu : e >> 16;
-#ifdef MH_HY_NEVER  // timing-only A/B build: what the decoders would cost if no entry were ever flagged (wrong output)
-                    if (false) {
-#else
                     if (HY && (int32_t)e < 0) {  // rare: second codeword reaches past the index bits
-#endif
                         bp += adv;
                         if (bp >= 32) {
                             buf = (buf >> 32) | ((uint64_t)nxt << 32);
@@ -1223,27 +1149,13 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
             }
             o[d] = w;
         }
-#ifdef MH_TUNING  // timing-only ablation (tools/ablate_decode.py): 1 = every row of a chunk lands on its first KiB
-        const uint32_t krow = dec_abl == 1 ? 0u : (uint32_t)k;  // (1/16 of the DRAM writes), 2 = no row stores
-        if (dec_abl == 2) {
-            if ((o.x ^ o.y) == 0x12345678u && o.z == 77u) out[0] = 1;
-            return;
-        }
-#else
         const uint32_t krow = (uint32_t)k;
-#endif
-#ifdef MH_TUNING
-        if (dec_abl == 3) {  // plain instead of non-temporal row stores
-            *reinterpret_cast<u32x4_u *>(out + (krow * kLanes + lane) * MH_PIECE) = o;
-            return;
-        }
-#endif
         if (!PARTIAL && ST != 0) {
             // (the row offset is part of the VECTOR offset -- the compiler folds what fits into the immediate: with a scalar-
             // register offset hipcc 7.2 leaves no wait state between this store and a VALU write of its data
             // registers -- GCNHazardRecognizer assumes that form has no such hazard -- and gfx950 then stores the
             // new value in lanes 12..15 of every 16: seen as wrong symbols in row 14 of a chunk)
-            __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, lane * MH_PIECE + (int)krow * kLanes * MH_PIECE, 0, ST == 2 ? 2 : 0);
+            __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, lane * MH_PIECE + (int)krow * kLanes * MH_PIECE, 0, 0);
             return;
         }
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4_u *>(out + (krow * kLanes + lane) * MH_PIECE));
@@ -1265,7 +1177,7 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
 // independent chains -- the same lane's sub-streams in two chunks -- interleave perfectly: their lookups are issued back
 // to back and each LDS round trip serves both.  (The same pairing around the hybrid loop was slower: its branches cut
 // the two chains into separate basic blocks, r03_pair_decoding_ab.txt.)
-template <int M, int RL, int ST = 0>
+template <int M, int RL>
 __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, const uint8_t *tab1, uint32_t mask1,
                                                     const uint32_t *stageA, const uint32_t *stageB,
                                                     uint8_t *__restrict__ outA, uint8_t *__restrict__ outB, int lane)
@@ -1286,8 +1198,6 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
     };
     start(A, stageA, hA.P);
     start(B, stageB, hB.P);
-    const auto rs_A = __builtin_amdgcn_make_buffer_rsrc(outA, 0, 0x7FFFFFFF, 0x00020000);  // (ST != 0: see decode_staged_chunk)
-    const auto rs_B = __builtin_amdgcn_make_buffer_rsrc(outB, 0, 0x7FFFFFFF, 0x00020000);
     auto top_up = [&](Chain &c) {
         if (RL == 2) {
             const bool t = c.bp >= 32;
@@ -1326,13 +1236,8 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
             oA[d] = wA;
             oB[d] = wB;
         }
-        if (ST != 0) {
-            __builtin_amdgcn_raw_buffer_store_b128(oA, rs_A, lane * MH_PIECE + k * kLanes * MH_PIECE, 0, ST == 2 ? 2 : 0);
-            __builtin_amdgcn_raw_buffer_store_b128(oB, rs_B, lane * MH_PIECE + k * kLanes * MH_PIECE, 0, ST == 2 ? 2 : 0);
-        } else {
-            __builtin_nontemporal_store(oA, reinterpret_cast<u32x4_u *>(outA + ((uint32_t)k * kLanes + lane) * MH_PIECE));
-            __builtin_nontemporal_store(oB, reinterpret_cast<u32x4_u *>(outB + ((uint32_t)k * kLanes + lane) * MH_PIECE));
-        }
+        __builtin_nontemporal_store(oA, reinterpret_cast<u32x4_u *>(outA + ((uint32_t)k * kLanes + lane) * MH_PIECE));
+        __builtin_nontemporal_store(oB, reinterpret_cast<u32x4_u *>(outB + ((uint32_t)k * kLanes + lane) * MH_PIECE));
     }
 }
 
@@ -1422,15 +1327,11 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
     const uint32_t *in = d.payload + pos;
     const uint32_t nfull = (uint32_t)(n / kChunk);
     const uint32_t rem = (uint32_t)(n % kChunk);
-#ifdef MH_DEC_NOCHECK  // A/B builds only: what the bounds checks cost
-#define MH_DEC_BAIL() do { } while (0)
-#else
 #define MH_DEC_BAIL()                              \
     do {                                           \
         if (lane == 0) atomicMax(d.err, d.epoch);  \
         return;                                    \
     } while (0)
-#endif
     // `need` words readable from word `at` on?  Subtractive, so that a wild 64-bit offset cannot wrap the sum.
     auto room = [&](uint64_t at, uint64_t need) { return at <= lim && lim - at >= need; };
     // A full chunk holds 16384 codewords of >= 1 bit: a header that announces fewer than 512 payload words is
@@ -1545,7 +1446,8 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
 // payload B -- contiguous in the stream -- into the wave's staging area, and the two chunks decode side by side.
 // Whatever does not fit that scheme goes through decode_segment: a pair too large for the staging area, the odd full
 // chunk, the partial chunk.  Same bounds rules: every header-steered read is checked against lim first.
-template <int K, int M, int NR, int RL, bool HY, bool WT = false>
+// (Wave-task plans only: on long channels the one-symbol decoder loses, see dispatch_decode.)
+template <int K, int M, int NR, int RL, bool HY>
 __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                     const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,
                                                     uint32_t mask1, uint32_t *stage, int lane)
@@ -1595,7 +1497,7 @@ __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t p
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        decode_staged_pair1<M, RL, 0>(hA, hB, tab1, mask1, stage, stage + hA.nw + hB.hw, out + (size_t)c * kChunk,
+        decode_staged_pair1<M, RL>(hA, hB, tab1, mask1, stage, stage + hA.nw + hB.hw, out + (size_t)c * kChunk,
                                    out + (size_t)(c + 1) * kChunk, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1603,8 +1505,8 @@ __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t p
         c += 2;
     }
     if ((uint64_t)c * kChunk < n)
-        decode_segment<K, M, NR, RL, HY, WT>(d, pos, out + (size_t)c * kChunk, n - (uint64_t)c * kChunk, tab, tbase, maskW, tab1, mask1,
-                                         stage, lane);
+        decode_segment<K, M, NR, RL, HY, true>(d, pos, out + (size_t)c * kChunk, n - (uint64_t)c * kChunk, tab, tbase, maskW, tab1, mask1,
+                                           stage, lane);
 }
 
 // NR payload registers per lane: the next chunk's payload (up to NR*64 words) is fetched into
@@ -1613,9 +1515,7 @@ __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t p
 // (in-order vmcnt) never waits for a store.  A chunk whose payload exceeds NR*64 words (more
 // than 3 bits/sample when NR = 24; impossible when NR = 17 and maxlen <= 2) takes the
 // per-symbol routine that reads the stream straight from global memory.
-#ifndef MH_DEC_MIN_WAVES
-#define MH_DEC_MIN_WAVES 1
-#endif
+constexpr int kDecMinBlocks = 1;  // launch-bounds minimum of the decoders
 // Long channels: up to 4 consecutive segments of ONE channel per workgroup, tables shared at LDS
 // address 0 (the kernel has no static LDS; mh_plan_create verifies that from the code object).
 // The decode tables of channel `ch` built in LDS from its (peak, encoder) word by NT cooperating threads (64: one
@@ -1698,8 +1598,8 @@ __device__ __forceinline__ uint32_t build_decode_tables(const Dec2Args &a, uint3
     return mask1;
 }
 
-template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
-__global__ __launch_bounds__(256, MH_DEC_MIN_WAVES) void k_decode2(Dec2Args a)
+template <int K, int M, int NR, int RL, bool HY>
+__global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2(Dec2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -1720,19 +1620,15 @@ __global__ __launch_bounds__(256, MH_DEC_MIN_WAVES) void k_decode2(Dec2Args a)
     if ((uint32_t)wave >= nseg) return;
     uint32_t *stage = smem + dec2_shared_dwords(W, K) + (size_t)wave * dec2_stage_dwords(NR);
     const uint32_t seg = seg0 + (uint32_t)wave;
-    if constexpr (DUAL)
-        decode_segment_dual<K, M, NR, RL, HY>(a.d, a.d.seg_off[seg], a.d.out + a.d.ch_off[ch] + a.d.w0[ch] + a.d.seg_first[seg],
-                                              a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane);
-    else
-        decode_segment<K, M, NR, RL, HY>(a.d, a.d.seg_off[seg], a.d.out + a.d.ch_off[ch] + a.d.w0[ch] + a.d.seg_first[seg],
-                                         a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane);
+    decode_segment<K, M, NR, RL, HY>(a.d, a.d.seg_off[seg], a.d.out + a.d.ch_off[ch] + a.d.w0[ch] + a.d.seg_first[seg],
+                                     a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane);
 }
 
 // Short channels: one WAVE per segment of any channel, tables per wave (see k_encode2w).  The wave
 // derives its tables from the channel's (peak, encoder) word and the plan's codebooks itself, so
 // this decode is ONE launch: no table kernel in front of it.
 template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
-__global__ __launch_bounds__(256, MH_DEC_MIN_WAVES) void k_decode2w(Dec2Args a)
+__global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2w(Dec2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -1749,8 +1645,8 @@ __global__ __launch_bounds__(256, MH_DEC_MIN_WAVES) void k_decode2w(Dec2Args a)
     const uint32_t mask1 = build_decode_tables<K, 64>(a, t.ch, tab, tab1, lane, lane);
     const uint32_t tbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)tab;
     if constexpr (DUAL)
-        decode_segment_dual<K, M, NR, RL, HY, true>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
-                                              tab + dec2_shared_dwords(W, K), lane);
+        decode_segment_dual<K, M, NR, RL, HY>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
+                                        tab + dec2_shared_dwords(W, K), lane);
     else
         decode_segment<K, M, NR, RL, HY, true>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
                                          tab + dec2_shared_dwords(W, K), lane);

@@ -663,10 +663,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const uint64_t *seg_words, u
 // segment is dispatch-bound; more than one segment per WAVE serialises their round trips -- 16 / 8 / 4 per
 // workgroup: 0.82 / 0.78 / 0.72 ms for 1.85 GB).  The destination is word-aligned only, so up to 3
 // head words are peeled off to make the 16-byte stores aligned; the loads take the misalignment.
-#ifndef MH_COMPACT_SEGS
-#define MH_COMPACT_SEGS 4
-#endif
-constexpr uint32_t kCompactSegs = MH_COMPACT_SEGS;
+constexpr uint32_t kCompactSegs = 4;
 
 // SELF_SCAN (<= kScanBlock segments: small recordings, stream blocks): no scan kernels in front -- every wave
 // sums the word counts of the segments before its own (<= 32 loads per lane), writes its dense offset, and the

@@ -216,8 +216,8 @@ constexpr int kTr2T = 256, kTr2C = 128;
 // S <= 4 -- and halve / quarter the intermediate's trip through HBM.  Layout: plain little-endian bit
 // packing, sample i of a channel's stream in bits [i * bits, (i + 1) * bits) -- so a byte of the 4-bit
 // stream IS the encoder's pair-table index (s[2j] | s[2j+1] << 4) and a byte of the 2-bit stream indexes a
-// four-symbol table directly; the encoder never spreads the samples back to bytes.  The de-interleaver
-// gets this order for free by choosing which time rows feed which dword of its byte transposition.
+// four-symbol table directly; the encoder never spreads the samples back to bytes.  k_deinterleave_p gets this
+// order by OR-ing shifted time rows together before its byte transposition.
 __device__ __forceinline__ uint32_t clip_bytes(uint32_t d, uint32_t lim)
 {
     uint32_t r = 0;
@@ -228,28 +228,6 @@ __device__ __forceinline__ uint32_t clip_bytes(uint32_t d, uint32_t lim)
         r |= b << (8 * i);
     }
     return r;
-}
-
-// o = one byte per sample in TURNED order (see tr2_row): PK = 4: o.x / o.y = even / odd samples of the
-// piece's first 8, o.z / o.w of its last 8; PK = 2: o[f] byte j = sample 4j + f
-template <int PK>
-__device__ __forceinline__ void pack_piece(u32x4 o, uint32_t &p0, uint32_t &p1)
-{
-    constexpr uint32_t lim = (1u << PK) - 1u;
-    constexpr uint32_t hi = 0x01010101u * (0xFFu & ~lim);
-    if ((o.x | o.y | o.z | o.w) & hi) {  // rare: a count above the field's range
-        o.x = clip_bytes(o.x, lim);
-        o.y = clip_bytes(o.y, lim);
-        o.z = clip_bytes(o.z, lim);
-        o.w = clip_bytes(o.w, lim);
-    }
-    if (PK == 4) {
-        p0 = o.x | (o.y << 4);
-        p1 = o.z | (o.w << 4);
-    } else {
-        p0 = o.x | (o.y << 2) | (o.z << 4) | (o.w << 6);
-        p1 = 0;
-    }
 }
 
 // ragged-edge helpers of k_deinterleave2, kept out of line so the hot path's register
@@ -270,23 +248,9 @@ __device__ __noinline__ void tr2_store_partial(uint8_t *dst, u32x4 o, uint32_t n
 
 __device__ __forceinline__ uint32_t tr2_swz(uint32_t row) { return (((row >> 4) & 15u) << 1) ^ (row & 3u); }
 
-// time row (of a 16-step block) whose byte becomes byte j of dword m of a channel's turned piece: bytes in
-// time order for byte output; for the packed outputs the order that makes pack_piece's shifts-and-ors
-// produce plain little-endian bit packing
-template <int PK>
-__device__ __forceinline__ constexpr int tr2_row(int m, int j)
-{
-    return PK == 0 ? 4 * m + j : PK == 2 ? 4 * j + m : (m >> 1) * 8 + 2 * j + (m & 1);
-}
-
-// PK = 0: bytes out (channel c = T bytes at out + out_off[c]); PK = 4 / 2: packed pieces out
-// (channel c = ceil(T / 16) pieces of 8 / 4 bytes at out + out_off[c]; a cut last piece is zero-padded)
-// abl (tuning builds pass it; 0 in production): 1 = no global stores, 2 = also no turn (loads + LDS writes only),
-// 3 = loads only
-template <int PK>
+// channel c = T bytes at out + out_off[c]
 __global__ __launch_bounds__(256) void k_deinterleave2(const uint8_t *__restrict__ in, uint64_t T, uint32_t C,
-                                                       uint32_t tpw, uint8_t *__restrict__ out,
-                                                       const uint64_t *out_off, uint32_t abl = 0, uint64_t blk_stride = 0)
+                                                       uint32_t tpw, uint8_t *__restrict__ out, const uint64_t *out_off)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[kTr2T * (kTr2C / 4)];
     // 1-D grid, channel strip fastest: consecutive workgroups -- dealt round-robin over the XCDs, running at
@@ -298,24 +262,12 @@ __global__ __launch_bounds__(256) void k_deinterleave2(const uint8_t *__restrict
     const uint32_t cw = C - c0 < (uint32_t)kTr2C ? C - c0 : (uint32_t)kTr2C;
     const uint64_t ntiles = (T + kTr2T - 1) / kTr2T;
     const uint64_t gx = gridDim.x / nstrip;
-    // channel bases of this thread's work items, loaded once: a global load inside the turn would sit
-    // behind the prefetched tile in the in-order memory counter and drain it
-    constexpr int kG = PK == 0 ? 1 : PK == 4 ? 2 : 4;
-    constexpr int kUU = kG == 4 ? 1 : 2 / kG;
-    uint64_t obase[4] = {0, 0, 0, 0};  // (packed modes: one work item per thread and tile)
-    if (PK != 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t c = (threadIdx.x / (16u / kG)) * 4 + k;
-            obase[k] = c < cw ? out_off[c0 + c] : 0;
-        }
-    }
     for (uint64_t tile0 = (uint64_t)(blockIdx.x / nstrip) * tpw; tile0 < ntiles; tile0 += gx * tpw) {
         const uint64_t tend = tile0 + tpw < ntiles ? tile0 + tpw : ntiles;
-        u32x4 V[8];
-        auto fetch = [&](uint64_t tl) {
+        for (uint64_t tl = tile0; tl < tend; ++tl) {
             const uint64_t t0 = tl * kTr2T;
             const uint32_t th = T - t0 < (uint64_t)kTr2T ? (uint32_t)(T - t0) : (uint32_t)kTr2T;
+            u32x4 V[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const uint32_t i = (uint32_t)j * 256 + threadIdx.x, row = i >> 3, q = (i & 7) * 16;
@@ -330,23 +282,6 @@ __global__ __launch_bounds__(256) void k_deinterleave2(const uint8_t *__restrict
                 }
                 V[j] = v;
             }
-        };
-        // PIPE: the next tile's loads are issued before this tile is turned (its registers stay live across
-        // the turn); measured per variant
-        constexpr bool PIPE = PK != 0;
-        if (PIPE) fetch(tile0);
-        for (uint64_t tl = tile0; tl < tend; ++tl) {
-            const uint64_t t0 = tl * kTr2T;
-            const uint32_t th = T - t0 < (uint64_t)kTr2T ? (uint32_t)(T - t0) : (uint32_t)kTr2T;
-            if (!PIPE) fetch(tl);
-            if (abl == 3) {  // ablation: consume the loads, nothing else
-                uint32_t z = 0;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) z ^= V[j].x ^ V[j].y ^ V[j].z ^ V[j].w;
-                if (z == 0x12345678u) out[0] = 1;
-                if (PIPE && tl + 1 < tend) fetch(tl + 1);
-                continue;
-            }
             __syncthreads();  // previous tile fully turned
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -359,102 +294,45 @@ __global__ __launch_bounds__(256) void k_deinterleave2(const uint8_t *__restrict
                 r[(q4 + 3) ^ sw] = V[j].w;
             }
             __syncthreads();
-            if (PIPE && tl + 1 < tend) fetch(tl + 1);
-            if (abl == 2) continue;
-            // turn: a work item = 4 channels x G blocks of 16 time steps; G = 1 (bytes out), 2 (4-bit) or
-            // 4 (2-bit), so that an item always emits 16 bytes per channel (narrow stores cost several
+            // turn: a work item = 4 channels x 16 time steps, 16 bytes per channel (narrow stores cost several
             // times a 16-byte store per byte on this part)
-            constexpr int G = PK == 0 ? 1 : PK == 4 ? 2 : 4;
-            constexpr uint32_t NTB = 16 / G;  // items along the tile's 256 time steps
 #pragma unroll 1
-            for (int uu = 0; uu < kUU; ++uu) {
-                const uint32_t id = threadIdx.x + 256u * uu, tb = id % NTB, cg = id / NTB;
-                if (cg >= (uint32_t)(kTr2C / 4) || cg * 4 >= cw || tb * G * 16 >= th) continue;
-                u32x4 pk[4] = {};  // packed output of the item's 4 channels, filled by shifting pieces in
-#pragma unroll 1
-                for (int g = 0; g < G; ++g) {  // (rolled: the transposition's registers are reused per block)
-                    const uint32_t tbb = tb * G + g;  // 16-step block inside the tile; rows past th hold zeros
-                    uint32_t d[16];
+            for (int uu = 0; uu < 2; ++uu) {
+                const uint32_t id = threadIdx.x + 256u * uu, tb = id % 16u, cg = id / 16u;
+                if (cg >= (uint32_t)(kTr2C / 4) || cg * 4 >= cw || tb * 16 >= th) continue;
+                uint32_t d[16];  // rows past th hold zeros
 #pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        d[i] = tile[(tbb * 16 + i) * (kTr2C / 4) + (cg ^ (tbb << 1) ^ (uint32_t)(i & 3))];
-                    u32x4 o[4];
+                for (int i = 0; i < 16; ++i) d[i] = tile[(tb * 16 + i) * (kTr2C / 4) + (cg ^ (tb << 1) ^ (uint32_t)(i & 3))];
+                u32x4 o[4];
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) {  // four rows -> dword m of each channel's 16 bytes
-                        const uint32_t a = d[tr2_row<PK>(m, 0)], b = d[tr2_row<PK>(m, 1)], c = d[tr2_row<PK>(m, 2)],
-                                       e = d[tr2_row<PK>(m, 3)];
-                        const uint32_t t0_ = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
-                        const uint32_t t1_ = __builtin_amdgcn_perm(e, c, 0x05010400u);  // c0 e0 c1 e1
-                        const uint32_t t2_ = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
-                        const uint32_t t3_ = __builtin_amdgcn_perm(e, c, 0x07030602u);
-                        o[0][m] = __builtin_amdgcn_perm(t1_, t0_, 0x05040100u);
-                        o[1][m] = __builtin_amdgcn_perm(t1_, t0_, 0x07060302u);
-                        o[2][m] = __builtin_amdgcn_perm(t3_, t2_, 0x05040100u);
-                        o[3][m] = __builtin_amdgcn_perm(t3_, t2_, 0x07060302u);
-                    }
-                    if (PK == 0) {
-                        const bool whole = tbb * 16 + 16 <= th;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const uint32_t c = cg * 4 + k;
-                            if (c >= cw) break;
-                            uint8_t *dst = out + out_off[c0 + c] + t0 + tbb * 16;
-                            if (abl == 1) {
-                                if ((o[k].x ^ o[k].y) == 0x12345678u && o[k].z == 77u) dst[0] = 1;
-                            } else if (whole) {
-                                __builtin_nontemporal_store(o[k], reinterpret_cast<u32x4_u *>(dst));
-                            } else {
-                                tr2_store_partial(dst, o[k], th - tbb * 16);
-                            }
-                        }
-                    } else {  // rows past th were loaded as zeros: a cut piece is zero-padded
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            uint32_t p0, p1;
-                            pack_piece<(PK ? PK : 4)>(o[k], p0, p1);
-                            const u32x4 q = pk[k];
-                            if (PK == 4) {
-                                const u32x4 r = {q.z, q.w, p0, p1};
-                                pk[k] = r;
-                            } else {
-                                const u32x4 r = {q.y, q.z, q.w, p0};
-                                pk[k] = r;
-                            }
-                        }
-                    }
+                for (int m = 0; m < 4; ++m) {  // four rows -> dword m of each channel's 16 bytes
+                    const uint32_t a = d[4 * m], b = d[4 * m + 1], c = d[4 * m + 2], e = d[4 * m + 3];
+                    const uint32_t t0_ = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
+                    const uint32_t t1_ = __builtin_amdgcn_perm(e, c, 0x05010400u);  // c0 e0 c1 e1
+                    const uint32_t t2_ = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
+                    const uint32_t t3_ = __builtin_amdgcn_perm(e, c, 0x07030602u);
+                    o[0][m] = __builtin_amdgcn_perm(t1_, t0_, 0x05040100u);
+                    o[1][m] = __builtin_amdgcn_perm(t1_, t0_, 0x07060302u);
+                    o[2][m] = __builtin_amdgcn_perm(t3_, t2_, 0x05040100u);
+                    o[3][m] = __builtin_amdgcn_perm(t3_, t2_, 0x07060302u);
                 }
-                if (PK != 0) {  // 16 bytes per channel: G pieces; channel regions are padded to 16 bytes
+                const bool whole = tb * 16 + 16 <= th;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t c = cg * 4 + k;
-                        if (c >= cw) break;
-                        const u32x4 pv = pk[k];
-                        // blk_stride != 0: CHUNK-BLOCKED layout -- the 16384-sample chunk j of a channel sits at
-                        // out_off[c] + j * blk_stride, so that one tile's stores stay inside one small region
-                        const uint64_t piece = (t0 >> 4) + (uint64_t)tb * G;  // piece index in the channel
-                        uint8_t *dst = out + obase[k] +
-                                       (blk_stride ? (piece >> 10) * blk_stride + (piece & 1023u) * (PK == 4 ? 8 : 4)
-                                                   : piece * (PK == 4 ? 8 : 4));
-                        if (abl == 1) {
-                            if ((pv.x ^ pv.y) == 0x12345678u && pv.z == 77u) dst[0] = 1;
-                        } else {
-                            // plain, not non-temporal: the workgroup's consecutive tiles extend the same lines of
-                            // this channel, and the XCD's L2 merges them into whole lines before they go out --
-                            // each visit of a channel's stream costs a DRAM row activation whatever it carries
-                            if (abl == 4)
-                                __builtin_nontemporal_store(pv, reinterpret_cast<u32x4_u *>(dst));
-                            else
-                                *reinterpret_cast<u32x4_u *>(dst) = pv;
-                        }
-                    }
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t c = cg * 4 + k;
+                    if (c >= cw) break;
+                    uint8_t *dst = out + out_off[c0 + c] + t0 + tb * 16;
+                    if (whole)
+                        __builtin_nontemporal_store(o[k], reinterpret_cast<u32x4_u *>(dst));
+                    else
+                        tr2_store_partial(dst, o[k], th - tb * 16);
                 }
             }
         }
     }
 }
 
-// k_deinterleave_p<2>: time-major bytes -> 2-bit packed pieces (what k_deinterleave2<2> produced, byte for byte), with
-// the PACKING DONE BEFORE THE TURN.  A piece is 16 consecutive time steps of one channel, 2 bits each, little-endian:
+// k_deinterleave_p<2>: time-major bytes -> 2-bit packed pieces, with the PACKING DONE BEFORE THE TURN.  A piece is 16 consecutive time steps of one channel, 2 bits each, little-endian:
 // its byte r holds steps 4r .. 4r+3.  In the time-major matrix those four steps are the same byte column of four
 // consecutive rows, so `V0 | V1 << 2 | V2 << 4 | V3 << 6` of four rows' 16-byte vectors IS byte r of the pieces of 16
 // channels -- three VALU instructions per dword for 16 samples, before anything is transposed.  What remains to be
@@ -462,7 +340,9 @@ __global__ __launch_bounds__(256) void k_deinterleave2(const uint8_t *__restrict
 // `tpw` (4) tiles = 1024 time steps x 128 channels is packed into 32 KiB and turned at once, and every channel then
 // receives its 256 output bytes of the visit in ONE run -- 16 lanes x 16 bytes, two whole lines -- where the byte-wise
 // turn wrote 64-byte runs four times over and left the merging to the L2.
-// Same grid, tiles, output addressing (plain and chunk-blocked) and zero padding as k_deinterleave2.
+// Same grid and tiles as k_deinterleave2.  Channel c = ceil(T / 16) pieces of 4 (2-bit) / 8 (4-bit) bytes at
+// out + out_off[c], a cut last piece zero-padded; blk_stride != 0: CHUNK-BLOCKED layout -- the 16384-sample chunk j of
+// a channel sits at out_off[c] + j * blk_stride.
 // LDS rows are 32 dwords (128 channels of one packed row); 4 more are skipped after every 16 rows, so that the 16 time
 // quarters x 4 channel groups a wave reads at once sit in 64 different banks.
 // (4-bit pieces -- S = 5..16 -- the same way: two rows per packed byte, `V0 | V1 << 4`, so a visit is 512 time steps;
@@ -476,13 +356,12 @@ struct P2 {
     static constexpr int kItemSteps = 16 * kRowsPerByte;               // time steps of a work item: 64 / 32
     static constexpr int kGroups = kTr2T / kRowsPerByte / 32;          // packed rows per thread and tile: 2 / 4
 };
-constexpr int kP2Tpw = P2<2>::kTpw;
 __device__ __forceinline__ uint32_t p2_row_dw(uint32_t rg) { return rg * 32u + (rg >> 4) * 4u; }
 
 template <int PK>
 __global__ __launch_bounds__(256) void k_deinterleave_p(const uint8_t *__restrict__ in, uint64_t T, uint32_t C, uint32_t tpw,
                                                         uint8_t *__restrict__ out, const uint64_t *out_off,
-                                                        uint32_t abl = 0, uint64_t blk_stride = 0, uint32_t cached_stores = 0)
+                                                        uint64_t blk_stride, uint32_t cached_stores)
 {
     typedef P2<PK> G;
     constexpr int RP = G::kRowsPerByte, NG = G::kGroups;
@@ -492,7 +371,7 @@ __global__ __launch_bounds__(256) void k_deinterleave_p(const uint8_t *__restric
     const uint32_t cw = C - c0 < (uint32_t)kTr2C ? C - c0 : (uint32_t)kTr2C;
     const uint64_t ntiles = (T + kTr2T - 1) / kTr2T;
     const uint64_t gx = gridDim.x / nstrip;
-    tpw = tpw < (uint32_t)G::kTpw ? tpw : (uint32_t)G::kTpw;  // (the host passes kTpw; the tuning knob may pass less)
+    tpw = tpw < (uint32_t)G::kTpw ? tpw : (uint32_t)G::kTpw;  // (the LDS tile holds kTpw tiles: what the host passes)
     // turn: two items per thread, item = (4 channels cg, 16 packed rows tq of the visit); lanes = tq fastest
     const uint32_t tq = threadIdx.x & 15u;
     uint64_t obase[2][4];
@@ -561,7 +440,6 @@ __global__ __launch_bounds__(256) void k_deinterleave_p(const uint8_t *__restric
                 fetch(tile0 + gx * tpw);
         }
         __syncthreads();
-        if (abl == 2 || abl == 3) continue;
 #pragma unroll  // (unrolled: obase[u] must stay in registers -- a scratch reload here waits with vmcnt(0), i.e. for the
         // next tile's loads as well)
         for (int u = 0; u < 2; ++u) {
@@ -591,11 +469,9 @@ __global__ __launch_bounds__(256) void k_deinterleave_p(const uint8_t *__restric
                 const uint64_t piece = (t0v >> 4) + (uint64_t)tq * kItemPieces;  // first of the item's pieces
                 uint8_t *dst = out + obase[u][k] +
                                (blk_stride ? (piece >> 10) * blk_stride + (piece & 1023u) * kPieceBytes : piece * kPieceBytes);
-                if (abl == 1) {
-                    if ((pk[k].x ^ pk[k].y) == 0x12345678u && pk[k].z == 77u) dst[0] = 1;
-                } else if (abl == 4 || cached_stores) {
+                if (cached_stores) {
                     // plain: an intermediate that fits the Infinity Cache is re-read from there by the encoder
-                    // (cached_stores, set by the host for blocks up to 192 MiB of pieces); also the A/B knob
+                    // (cached_stores, set by the host for blocks up to 192 MiB of pieces)
                     *reinterpret_cast<u32x4_u *>(dst) = pk[k];
                 } else {
                     // non-temporal: a wave instruction writes whole lines here (16 lanes x 16 bytes per channel), nothing

@@ -133,12 +133,6 @@ struct PlanHost {
     uint32_t W = 0, dec_K = 4, dec_NR = 32;
 };
 
-struct PlanTuning {  // MH_TUNING builds only; the defaults are the measured best (profiles/README.md)
-    int dec_w_cap = 0;    // index bits of the hybrid pair table (0: 10, and 8 for wave-task plans)
-    int dec_nr = 31;      // staging registers per lane of the hybrid decoder
-    int wave_tasks = -1;  // -1 = planner's rule, 0 / 1 = force
-};
-
 // Head segment of a window [w0, w1) (container format revision 3, include/muahuff.h): samples up to the next
 // multiple of MH_HEAD_ALIGN when the window is long enough for the alignment of its rows to matter.
 inline uint64_t head_samples(uint64_t w0, uint64_t w1, uint32_t window)
@@ -205,8 +199,7 @@ inline int plan_check_args(const uint64_t *ch_len, uint32_t C, uint32_t S, uint3
 
 // Everything mh_plan_create uploads, computed on the host.  `info` must hold C, S, h, mode, window,
 // K, seg_chunks (0 = choose) and maxlen; arguments are already checked.
-inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t *ch_len, const uint8_t *sclv,
-                            const PlanTuning &tune = PlanTuning())
+inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t *ch_len, const uint8_t *sclv)
 {
     mh_plan_info_t &I = p.info;
     const uint32_t C = I.C, S = I.S, K = I.K;
@@ -304,7 +297,6 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
     // per-wave-table kernels when the shared-table tasks would leave more than 1 wave in 16 idle
     // (channels of a few segments); their wave tasks run longest first
     p.use_wave_tasks = padded_waves * 15 > (uint64_t)I.n_segments * 16;
-    if (tune.wave_tasks >= 0) p.use_wave_tasks = tune.wave_tasks != 0;
     const uint64_t lim = (uint64_t)1 << I.h;
     p.fused_calibration = p.use_wave_tasks && lim <= kCalDirect;
     if (p.use_wave_tasks) {
@@ -364,10 +356,10 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
     if (p.dec_K == 2) {
         // (wave-task plans build the table once per WAVE: 256 entries instead of 1024 cost a few more flagged
         // entries but a quarter of the build and 3 KiB less LDS per wave -- 2400 x 72 000, S = 8: 66 -> 58 us)
-        uint32_t cap = tune.dec_w_cap >= 8 && tune.dec_w_cap <= 12 ? (uint32_t)tune.dec_w_cap : p.use_wave_tasks ? 8u : 10u;
+        uint32_t cap = p.use_wave_tasks ? 8u : 10u;
         if (cap < I.maxlen) cap = I.maxlen;  // a flagged entry still holds its first codeword
         if (p.W > cap) p.W = cap;
-        if (p.W < 2 * I.maxlen) p.dec_NR = tune.dec_nr == 32 ? 32 : 31;
+        if (p.W < 2 * I.maxlen) p.dec_NR = 31;
     }
     // codebooks by rank: bit-reversed code (first code bit at bit 0) | len << 16
     p.codes.assign((size_t)K * 16, 0);

@@ -57,19 +57,6 @@ int alloc(T **dst, size_t n)
     return MH_OK;
 }
 
-// Tuning knobs exist only in -DMH_TUNING builds (A/B runs, tools/); the production library reads
-// no environment variable and exports no debug hook.
-mh::PlanTuning plan_tuning()
-{
-    mh::PlanTuning t;
-#ifdef MH_TUNING
-    if (const char *e = getenv("MH_DEC_W")) t.dec_w_cap = atoi(e);
-    if (const char *e = getenv("MH_DEC_NR")) t.dec_nr = atoi(e);
-    if (const char *e = getenv("MH_WAVE_TASKS")) t.wave_tasks = atoi(e);
-#endif
-    return t;
-}
-
 }  // namespace
 
 struct mh_plan {
@@ -186,10 +173,6 @@ static void launch_hist(const mh::HistArgs &a, uint64_t n_tiles, hipStream_t st)
     hipLaunchKernelGGL(mh::k_hist<NS>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
 }
 
-#ifdef MH_TUNING
-static int g_ablate = 0;  // timing-only ablations of the S <= 3 encoder (mhdbg_set_ablation)
-#endif
-
 // The launch helpers double as "prepare" helpers: with this thread-local flag set they only
 // raise the kernel's dynamic-LDS limit (hipFuncSetAttribute), check that the kernel has no static
 // LDS (the decoders address their table by raw LDS offset) and do not launch.  mh_plan_create
@@ -211,12 +194,9 @@ static int prepare_kernel(const void *kern, size_t lds, bool needs_lds_base_0)
     return MH_OK;
 }
 
-#ifndef MH_DEC_K4_LDS_FLOOR
-#define MH_DEC_K4_LDS_FLOOR (41 * 1024)
-#endif
-constexpr size_t kDecK4LdsFloor = MH_DEC_K4_LDS_FLOOR;  // 3 workgroups per CU (see launch_decode2, launch_encode2)
+constexpr size_t kDecK4LdsFloor = 41 * 1024;  // 3 workgroups per CU (see launch_decode2, launch_encode2)
 
-template <int LC, int PB, int ABL = 0, int PK = 0>
+template <int LC, int PB, int PK = 0>
 static int launch_encode2(const mh::Enc2Args &a, hipStream_t st)
 {
     size_t lds = 4 * (size_t)mh::enc2_wave_dwords(a.e.stage_dw) * sizeof(uint32_t);  // + the static tables
@@ -227,14 +207,8 @@ static int launch_encode2(const mh::Enc2Args &a, hipStream_t st)
     // (S = 8: +4 %), S = 4..6 are indifferent (-0.8 %): only LC = 0 is capped, through the LDS request.
     // Only where the launch has many rounds of workgroups: with 2640 tasks (96 ch x 3.6e6 bins) a quarter fewer slots cost
     // a whole extra round (77.7 -> 80.2 us).
-    if (LC == 0 && PK == 0 && ABL == 0 && a.t.ntask >= 16384 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
-#ifdef MH_TUNING  // occupancy cap through the LDS request (A/B runs)
-    if (const char *e = getenv("MH_ENC_LDS_MIN")) {  // replaces the floor above
-        const size_t need = 4 * (size_t)mh::enc2_wave_dwords(a.e.stage_dw) * sizeof(uint32_t);
-        lds = (size_t)atoi(e) > need ? (size_t)atoi(e) : need;
-    }
-#endif
-    auto kern = mh::k_encode2<LC, PB, ABL, PK>;
+    if (LC == 0 && PK == 0 && a.t.ntask >= 16384 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
+    auto kern = mh::k_encode2<LC, PB, PK>;
     if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
     hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
     MH_HIP(hipGetLastError());
@@ -252,32 +226,32 @@ static int launch_encode2w(const mh::Enc2Args &a, hipStream_t st)
     return MH_OK;
 }
 
-
-
-template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
-static int launch_decode2(const mh::Dec2Args &a, bool wave_tasks, hipStream_t st)
+// workgroup tasks (long channels)
+template <int K, int M, int NR, int RL, bool HY>
+static int launch_decode2(const mh::Dec2Args &a, hipStream_t st)
 {
-    if (wave_tasks) {
-        const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-        auto kern = mh::k_decode2w<K, M, NR, RL, HY, DUAL>;
-        if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
-        hipLaunchKernelGGL(kern, dim3((a.t.ntask + 3) / 4), dim3(256), lds, st, a);
-    } else {
-        const size_t lds_need = ((size_t)mh::dec2_shared_dwords(a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-        size_t lds = lds_need;
-        // The four-symbol decoder (S <= 3) is bound by its 1-KiB row stores, not by its arithmetic, and the part
-        // writes FASTER with fewer waves streaming at once: 3 workgroups per CU instead of the 4 its registers
-        // allow, enforced through the LDS request (160 KiB / 41 KiB = 3): 1024 ch x 1e7 bins decode 2.25 -> 2.04 ms
-        // on one box; 2 per CU: 2.40 ms (profiles/r03_occupancy_ab.txt).  The pair-table decoders (S >= 4) are
-        // bound by their dependent lookup chain and lose with fewer waves (S = 5: 2.27 -> 2.38 ms).
-        if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
-#ifdef MH_TUNING
-        if (const char *e = getenv("MH_DEC_LDS_MIN")) lds = (size_t)atoi(e) > lds_need ? (size_t)atoi(e) : lds_need;
-#endif
-        auto kern = mh::k_decode2<K, M, NR, RL, HY, DUAL>;
-        if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
-        hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
-    }
+    size_t lds = ((size_t)mh::dec2_shared_dwords(a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
+    // The four-symbol decoder (S <= 3) is bound by its 1-KiB row stores, not by its arithmetic, and the part
+    // writes FASTER with fewer waves streaming at once: 3 workgroups per CU instead of the 4 its registers
+    // allow, enforced through the LDS request (160 KiB / 41 KiB = 3): 1024 ch x 1e7 bins decode 2.25 -> 2.04 ms
+    // on one box; 2 per CU: 2.40 ms (profiles/r03_occupancy_ab.txt).  The pair-table decoders (S >= 4) are
+    // bound by their dependent lookup chain and lose with fewer waves (S = 5: 2.27 -> 2.38 ms).
+    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
+    auto kern = mh::k_decode2<K, M, NR, RL, HY>;
+    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
+    hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
+// wave tasks (short channels)
+template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
+static int launch_decode2w(const mh::Dec2Args &a, hipStream_t st)
+{
+    const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
+    auto kern = mh::k_decode2w<K, M, NR, RL, HY, DUAL>;
+    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
+    hipLaunchKernelGGL(kern, dim3((a.t.ntask + 3) / 4), dim3(256), lds, st, a);
     MH_HIP(hipGetLastError());
     return MH_OK;
 }
@@ -296,7 +270,7 @@ static int dispatch_encode_packed(const mh_plan *p, const mh::Enc2Args &a2, hipS
     const uint32_t L = p->h.info.maxlen;
     if (PK == 2) {  // S <= 4 only: maxlen <= 3; the table is the four-symbol one (PB unused)
         if (p->h.use_wave_tasks) return L <= 2 ? launch_encode2w<0, 4, 2>(a2, st) : launch_encode2w<1, 4, 2>(a2, st);
-        return L <= 2 ? launch_encode2<0, 4, 0, 2>(a2, st) : launch_encode2<1, 4, 0, 2>(a2, st);
+        return L <= 2 ? launch_encode2<0, 4, 2>(a2, st) : launch_encode2<1, 4, 2>(a2, st);
     }
     // 4-bit pieces: a byte of the stream is the PB = 4 pair index
     if (p->h.use_wave_tasks) {
@@ -305,10 +279,10 @@ static int dispatch_encode_packed(const mh_plan *p, const mh::Enc2Args &a2, hipS
         if (L <= 8) return launch_encode2w<2, 4, 4>(a2, st);
         return launch_encode2w<3, 4, 4>(a2, st);
     }
-    if (L <= 2) return launch_encode2<0, 4, 0, 4>(a2, st);
-    if (L <= 4) return launch_encode2<1, 4, 0, 4>(a2, st);
-    if (L <= 8) return launch_encode2<2, 4, 0, 4>(a2, st);
-    return launch_encode2<3, 4, 0, 4>(a2, st);
+    if (L <= 2) return launch_encode2<0, 4, 4>(a2, st);
+    if (L <= 4) return launch_encode2<1, 4, 4>(a2, st);
+    if (L <= 8) return launch_encode2<2, 4, 4>(a2, st);
+    return launch_encode2<3, 4, 4>(a2, st);
 }
 
 static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a2, hipStream_t st)
@@ -317,61 +291,14 @@ static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a2, hipStream_t
     const bool pb3 = p->h.info.S <= 8;  // 3-bit pair packing when every symbol fits 3 bits
     if (p->h.input_bits == 4) return dispatch_encode_packed<4>(p, a2, st);
     if (p->h.input_bits == 2) return dispatch_encode_packed<2>(p, a2, st);
+    // (maxlen <= 2 means S <= 4: always 3-bit pairs)
     if (p->h.use_wave_tasks) {
-        if (L <= 2) return pb3 ? launch_encode2w<0, 3>(a2, st) : launch_encode2w<0, 4>(a2, st);
+        if (L <= 2) return launch_encode2w<0, 3>(a2, st);
         if (L <= 4) return pb3 ? launch_encode2w<1, 3>(a2, st) : launch_encode2w<1, 4>(a2, st);
         if (L <= 8) return pb3 ? launch_encode2w<2, 3>(a2, st) : launch_encode2w<2, 4>(a2, st);
         return launch_encode2w<3, 4>(a2, st);
     }
-#ifdef MH_TUNING
-    if (L <= 2 && pb3 && g_ablate) {
-        switch (g_ablate) {
-        case 1: return launch_encode2<0, 3, 1>(a2, st);
-        case 2: return launch_encode2<0, 3, 2>(a2, st);
-        case 3: return launch_encode2<0, 3, 3>(a2, st);
-        case 4: return launch_encode2<0, 3, 4>(a2, st);
-        case 5: return launch_encode2<0, 3, 5>(a2, st);
-        case 6: return launch_encode2<0, 3, 6>(a2, st);
-        case 7: return launch_encode2<0, 3, 7>(a2, st);
-        case 11: return launch_encode2<0, 3, 11>(a2, st);
-        case 12: return launch_encode2<0, 3, 12>(a2, st);
-        case 13: return launch_encode2<0, 3, 13>(a2, st);
-        case 14: return launch_encode2<0, 3, 14>(a2, st);
-        case 15: return launch_encode2<0, 3, 15>(a2, st);
-        default: return launch_encode2<0, 3, 8>(a2, st);
-        }
-    }
-    if (L > 2 && L <= 4 && pb3 && g_ablate) {  // the same for the S = 4..6 kernel (levels 1, 2, 4, 8)
-        switch (g_ablate) {
-        case 1: return launch_encode2<1, 3, 1>(a2, st);
-        case 2: return launch_encode2<1, 3, 2>(a2, st);
-        case 4: return launch_encode2<1, 3, 4>(a2, st);
-        default: return launch_encode2<1, 3, 8>(a2, st);
-        }
-    }
-    if (L > 4 && L <= 8 && g_ablate) {  // S = 7, 8 (3-bit pairs) and S = 9 (4-bit pairs): levels 1, 2, 4
-        if (pb3) {
-            switch (g_ablate) {
-            case 1: return launch_encode2<2, 3, 1>(a2, st);
-            case 2: return launch_encode2<2, 3, 2>(a2, st);
-            default: return launch_encode2<2, 3, 4>(a2, st);
-            }
-        }
-        switch (g_ablate) {
-        case 1: return launch_encode2<2, 4, 1>(a2, st);
-        case 2: return launch_encode2<2, 4, 2>(a2, st);
-        default: return launch_encode2<2, 4, 4>(a2, st);
-        }
-    }
-    if (L > 8 && g_ablate) {  // and for the S = 10 kernel (levels 1, 2, 4)
-        switch (g_ablate) {
-        case 1: return launch_encode2<3, 4, 1>(a2, st);
-        case 2: return launch_encode2<3, 4, 2>(a2, st);
-        default: return launch_encode2<3, 4, 4>(a2, st);
-        }
-    }
-#endif
-    if (L <= 2) return pb3 ? launch_encode2<0, 3>(a2, st) : launch_encode2<0, 4>(a2, st);
+    if (L <= 2) return launch_encode2<0, 3>(a2, st);
     if (L <= 4) return pb3 ? launch_encode2<1, 3>(a2, st) : launch_encode2<1, 4>(a2, st);
     if (L <= 8) return pb3 ? launch_encode2<2, 3>(a2, st) : launch_encode2<2, 4>(a2, st);
     return launch_encode2<3, 4>(a2, st);
@@ -379,40 +306,26 @@ static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a2, hipStream_t
 
 static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a2, hipStream_t st)
 {
-#ifdef MH_TUNING
-    {
-        static int last = -1;
-        const char *e = getenv("MH_DEC_ABL");
-        const int want = e ? atoi(e) : 0;
-        if (want != last) {
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(mh::d_dec_abl), &want, sizeof(int));
-            last = want;
-        }
-    }
-#endif
     const uint32_t L = p->h.info.maxlen;
-    const bool wt = p->h.use_wave_tasks;
     // window maintenance (decode_staged_chunk): 1 = reload, 0 = branchy top-up, 2 = select top-up;
     // the choices are the measured best per variant (profiles/README.md)
-    if (L <= 2) return launch_decode2<4, 4, 17, 1, false>(a2, wt, st);  // worst-case chunk = 1027 words: never oversize
-    if (L == 3) return launch_decode2<2, 2, 25, 2, false>(a2, wt, st);
-    if (a2.W >= 2 * L) return launch_decode2<2, 2, 32, 0, false>(a2, wt, st);
-#ifndef MH_DEC_K1
-#define MH_DEC_K1 1  // A/B builds: 0 = never, 1 = wave-task plans, 2 = every plan whose pair table would be hybrid
-#endif
-#ifndef MH_DEC_K1_NR
-#define MH_DEC_K1_NR 36
-#endif
-    // Long codes on SHORT channels (wave tasks, where every wave builds its own tables): the one-symbol decoder -- a
-    // 2^maxlen-byte table instead of a 256-entry hybrid pair table whose flagged entries make almost every lookup of
-    // the wave take the slow path (8 index bits) -- with the two chunks of a segment side by side (decode_staged_pair1).
-    // 10 000 x 20 000: decode S=8 82 -> 74 us, S=10 92 -> 77 us; 2400 x 72 000: 70 -> 68 us.  On long channels (shared
-    // 1024-entry tables) it loses: S=8 2.35 -> 2.82 ms -- twice the LDS lookups, and those decoders are bound by LDS
-    // bank-conflict throughput, not by the latency of the chain (profiles/r03_k1_pair_decoding_ab.txt).
-    if ((MH_DEC_K1 >= 2 || (MH_DEC_K1 == 1 && wt)) && a2.W < 2 * L) return launch_decode2<1, 2, MH_DEC_K1_NR, 2, false, true>(a2, wt, st);
-    // hybrid pair table: W < 2 * maxlen index bits, one-symbol entries flagged
-    if (p->h.dec_NR == 31) return launch_decode2<2, 2, 31, 2, true>(a2, wt, st);
-    return launch_decode2<2, 2, 32, 0, true>(a2, wt, st);
+    if (p->h.use_wave_tasks) {
+        if (L <= 2) return launch_decode2w<4, 4, 17, 1, false>(a2, st);
+        if (L == 3) return launch_decode2w<2, 2, 25, 2, false>(a2, st);
+        if (a2.W >= 2 * L) return launch_decode2w<2, 2, 32, 0, false>(a2, st);
+        // Long codes on SHORT channels (wave tasks, where every wave builds its own tables): the one-symbol decoder -- a
+        // 2^maxlen-byte table instead of a 256-entry hybrid pair table whose flagged entries make almost every lookup of
+        // the wave take the slow path (8 index bits) -- with the two chunks of a segment side by side (decode_staged_pair1).
+        // 10 000 x 20 000: decode S=8 82 -> 74 us, S=10 92 -> 77 us; 2400 x 72 000: 70 -> 68 us.  On long channels (shared
+        // 1024-entry tables) it loses: S=8 2.35 -> 2.82 ms -- twice the LDS lookups, and those decoders are bound by LDS
+        // bank-conflict throughput, not by the latency of the chain (profiles/r03_k1_pair_decoding_ab.txt).
+        return launch_decode2w<1, 2, 36, 2, false, true>(a2, st);
+    }
+    if (L <= 2) return launch_decode2<4, 4, 17, 1, false>(a2, st);  // worst-case chunk = 1027 words: never oversize
+    if (L == 3) return launch_decode2<2, 2, 25, 2, false>(a2, st);
+    if (a2.W >= 2 * L) return launch_decode2<2, 2, 32, 0, false>(a2, st);
+    // hybrid pair table: W < 2 * maxlen index bits, one-symbol entries flagged (31 staging registers: PlanHost::dec_NR)
+    return launch_decode2<2, 2, 31, 2, true>(a2, st);
 }
 
 // raise the dynamic-LDS limits of the kernels this plan will launch (once, at plan creation)
@@ -433,11 +346,6 @@ static int prepare_kernels(const mh_plan *p)
 extern "C" {
 
 int mh_version(void) { return MH_VERSION; }
-
-#ifdef MH_TUNING
-/* tuning builds only: selects a timing-only ablation of k_encode2 */
-void mhdbg_set_ablation(int level) { g_ablate = level; }
-#endif
 
 const char *mh_last_error(void) { return g_err; }
 
@@ -551,7 +459,7 @@ int mh_plan_query(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, ui
     mh::PlanHost H;
     if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &H.info)) return rc;
     std::vector<uint64_t> off(C, 0);  // offsets do not enter the directory
-    mh::plan_host_build(H, off.data(), ch_len, sclv, plan_tuning());
+    mh::plan_host_build(H, off.data(), ch_len, sclv);
     *info = H.info;
     const size_t n = H.seg_ch.size() < seg_cap ? H.seg_ch.size() : (size_t)seg_cap;
     if (seg_ch && n) memcpy(seg_ch, H.seg_ch.data(), n * sizeof(uint32_t));
@@ -594,7 +502,7 @@ int mh_plan_create_packed(mh_plan **plan, const uint64_t *ch_off, const uint64_t
     p->h.info = I;
     p->h.input_bits = input_bits;
     p->h.chunk_stride = chunk_stride;
-    mh::plan_host_build(p->h, ch_off, ch_len, sclv, plan_tuning());
+    mh::plan_host_build(p->h, ch_off, ch_len, sclv);
     if (p->h.seg_ch.size() > 0xFFFFFFF0ull) {  // segment and task indices are 32-bit on the device
         const size_t nseg = p->h.seg_ch.size();
         mh_plan_destroy(p);
@@ -1011,14 +919,6 @@ int mh_rebin(const uint8_t *data, const uint64_t *in_off, const uint64_t *in_len
     return MH_OK;
 }
 
-static uint32_t layout_ablation()
-{
-#ifdef MH_TUNING
-    if (const char *e = getenv("MH_LAYOUT_ABL")) return (uint32_t)atoi(e);
-#endif
-    return 0;
-}
-
 int mh_deinterleave(const uint8_t *in, uint64_t T, uint32_t C, uint8_t *out, const uint64_t *out_off,
                     void *stream)
 {
@@ -1029,8 +929,8 @@ int mh_deinterleave(const uint8_t *in, uint64_t T, uint32_t C, uint8_t *out, con
     const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
     if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
     if (by > 65535) return fail(MH_ERR_ARG, "mh_deinterleave: C=%u too large", C);
-    hipLaunchKernelGGL(mh::k_deinterleave2<0>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
-                       out, out_off, layout_ablation());
+    hipLaunchKernelGGL(mh::k_deinterleave2, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
+                       out, out_off);
     MH_HIP(hipGetLastError());
     return MH_OK;
 }
@@ -1043,27 +943,19 @@ int mh_deinterleave_packed(const uint8_t *in, uint64_t T, uint32_t C, uint32_t b
     if (chunk_stride && (chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * bits / 8))
         return fail(MH_ERR_ARG, "mh_deinterleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
     if (T == 0) return MH_OK;
-    const uint32_t tpw_max = bits == 2 ? (uint32_t)mh::P2<2>::kTpw : (uint32_t)mh::P2<4>::kTpw;  // tiles of a visit held in LDS
-    uint32_t tpw = tpw_max;
-#ifdef MH_TUNING
-    if (const char *e = getenv("MH_LAYOUT_TPW")) tpw = (uint32_t)atoi(e);
-    if (tpw < 1 || tpw > tpw_max) tpw = tpw_max;
-#endif
+    const uint32_t tpw = bits == 2 ? (uint32_t)mh::P2<2>::kTpw : (uint32_t)mh::P2<4>::kTpw;  // tiles of a visit held in LDS
     uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
     const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
     if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
     if (by > 65535) return fail(MH_ERR_ARG, "mh_deinterleave_packed: C=%u too large", C);
     // pieces that fit the Infinity Cache (256 MiB) stay cacheable for the encoder that reads them next
-    uint32_t cached = (double)T * C * bits / 8.0 <= 192.0 * 1048576.0 ? 1u : 0u;
-#ifdef MH_TUNING
-    if (const char *e = getenv("MH_LAYOUT_CACHED")) cached = (uint32_t)atoi(e);
-#endif
+    const uint32_t cached = (double)T * C * bits / 8.0 <= 192.0 * 1048576.0 ? 1u : 0u;
     if (bits == 4)
         hipLaunchKernelGGL(mh::k_deinterleave_p<4>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
-                           out, out_off, layout_ablation(), chunk_stride, cached);
+                           out, out_off, chunk_stride, cached);
     else
         hipLaunchKernelGGL(mh::k_deinterleave_p<2>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
-                           out, out_off, layout_ablation(), chunk_stride, cached);
+                           out, out_off, chunk_stride, cached);
     MH_HIP(hipGetLastError());
     return MH_OK;
 }

@@ -14,7 +14,7 @@ staging registers dec_NR.  Every CELL names one instance and the plans that land
 
 tests/test_host_kernel_cells.py checks without a GPU that the cells and the shipped symbols are the same set and
 that the host planner puts every case and layout where its cell says; tests/test_gpu_kernel_cells.py runs them
-against the CPU oracle.  UNREACHABLE lists the instances no production plan launches, each with its reason.
+against the CPU oracle.
 """
 from dataclasses import dataclass
 
@@ -33,7 +33,7 @@ class Case:
 
 @dataclass(frozen=True)
 class Cell:
-    symbol: str          # demangled kernel name as the code object lists it, "mh::k_encode2<1, 4, 0, 0>"
+    symbol: str          # demangled kernel name as the code object lists it, "mh::k_encode2<1, 4, 0>"
     wave: bool           # wave-task form (k_*2w) or workgroup-task form (k_*2)
     input_bits: int      # 8 = byte input; 4 / 2 = packed pieces (mh_plan_create_packed)
     mode: int            # mapper the placement is checked with (the GPU tests run both)
@@ -43,6 +43,19 @@ class Cell:
     @property
     def decoder(self):
         return "k_decode2" in self.symbol
+
+    @property
+    def key(self):
+        """Name of the cell's GPU tests and seed of their data.  It keeps the symbol's form from when the table was
+        written, before k_encode2 lost its ablation level (always 0, before PK) and k_decode2 its DUAL flag (always
+        false), so that every cell keeps its test ids and its data across that rename."""
+        head, args = self.symbol[:-1].split("<")
+        if head == "mh::k_encode2":
+            lc, pb, pk = args.split(", ")
+            return "%s<%s, %s, 0, %s>" % (head, lc, pb, pk)
+        if head == "mh::k_decode2":
+            return "%s<%s, false>" % (head, args)
+        return self.symbol
 
 
 def _row(*lens):
@@ -104,32 +117,32 @@ def _pair(wg_symbol, wave_symbol, input_bits, cases, mode=1):
 
 ENCODER_CELLS = tuple(
     # byte input: LC = code class of L (<= 2, <= 4, <= 8, 9), PB = 3-bit pairs (S <= 8) or 4-bit pairs
-    _pair("mh::k_encode2<0, 3, 0, 0>", "mh::k_encode2w<0, 3, 0>", 8, [_c(3, 2), _c(2, 1), _c(4, 2)])
-    + _pair("mh::k_encode2<1, 3, 0, 0>", "mh::k_encode2w<1, 3, 0>", 8, [_c(8, 3), _c(4, 3), _c(8, 4)])
-    + _pair("mh::k_encode2<1, 4, 0, 0>", "mh::k_encode2w<1, 4, 0>", 8, [_c(9, 4), _c(10, 4)])
-    + _pair("mh::k_encode2<2, 3, 0, 0>", "mh::k_encode2w<2, 3, 0>", 8, [_c(8, 7), _c(6, 5), _c(8, 5)])
-    + _pair("mh::k_encode2<2, 4, 0, 0>", "mh::k_encode2w<2, 4, 0>", 8, [_c(9, 8), _c(9, 5)])
-    + _pair("mh::k_encode2<3, 4, 0, 0>", "mh::k_encode2w<3, 4, 0>", 8, [_c(10, 9), _c(10, 9, R2_10_9)])
+    _pair("mh::k_encode2<0, 3, 0>", "mh::k_encode2w<0, 3, 0>", 8, [_c(3, 2), _c(2, 1), _c(4, 2)])
+    + _pair("mh::k_encode2<1, 3, 0>", "mh::k_encode2w<1, 3, 0>", 8, [_c(8, 3), _c(4, 3), _c(8, 4)])
+    + _pair("mh::k_encode2<1, 4, 0>", "mh::k_encode2w<1, 4, 0>", 8, [_c(9, 4), _c(10, 4)])
+    + _pair("mh::k_encode2<2, 3, 0>", "mh::k_encode2w<2, 3, 0>", 8, [_c(8, 7), _c(6, 5), _c(8, 5)])
+    + _pair("mh::k_encode2<2, 4, 0>", "mh::k_encode2w<2, 4, 0>", 8, [_c(9, 8), _c(9, 5)])
+    + _pair("mh::k_encode2<3, 4, 0>", "mh::k_encode2w<3, 4, 0>", 8, [_c(10, 9), _c(10, 9, R2_10_9)])
     # 2-bit pieces (S <= 4): the four-symbol table
-    + _pair("mh::k_encode2<0, 4, 0, 2>", "mh::k_encode2w<0, 4, 2>", 2, [_c(3, 2), _c(4, 2), _c(2, 1)])
-    + _pair("mh::k_encode2<1, 4, 0, 2>", "mh::k_encode2w<1, 4, 2>", 2, [_c(4, 3)])
+    + _pair("mh::k_encode2<0, 4, 2>", "mh::k_encode2w<0, 4, 2>", 2, [_c(3, 2), _c(4, 2), _c(2, 1)])
+    + _pair("mh::k_encode2<1, 4, 2>", "mh::k_encode2w<1, 4, 2>", 2, [_c(4, 3)])
     # 4-bit pieces: a byte of the stream is the PB = 4 pair index
-    + _pair("mh::k_encode2<0, 4, 0, 4>", "mh::k_encode2w<0, 4, 4>", 4, [_c(3, 2), _c(4, 2)])
-    + _pair("mh::k_encode2<1, 4, 0, 4>", "mh::k_encode2w<1, 4, 4>", 4, [_c(4, 3), _c(5, 4), _c(9, 4), _c(10, 4)])
-    + _pair("mh::k_encode2<2, 4, 0, 4>", "mh::k_encode2w<2, 4, 4>", 4, [_c(6, 5), _c(8, 7), _c(9, 8)])
-    + _pair("mh::k_encode2<3, 4, 0, 4>", "mh::k_encode2w<3, 4, 4>", 4, [_c(10, 9)])
+    + _pair("mh::k_encode2<0, 4, 4>", "mh::k_encode2w<0, 4, 4>", 4, [_c(3, 2), _c(4, 2)])
+    + _pair("mh::k_encode2<1, 4, 4>", "mh::k_encode2w<1, 4, 4>", 4, [_c(4, 3), _c(5, 4), _c(9, 4), _c(10, 4)])
+    + _pair("mh::k_encode2<2, 4, 4>", "mh::k_encode2w<2, 4, 4>", 4, [_c(6, 5), _c(8, 7), _c(9, 8)])
+    + _pair("mh::k_encode2<3, 4, 4>", "mh::k_encode2w<3, 4, 4>", 4, [_c(10, 9)])
 )
 
 DECODER_CELLS = (
     # workgroup form: shared tables of up to 10 index bits
-    Cell("mh::k_decode2<4, 4, 17, 1, false, false>", False, 8, 1,
+    Cell("mh::k_decode2<4, 4, 17, 1, false>", False, 8, 1,
          (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32)), WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 25, 2, false, false>", False, 8, 0,
+    Cell("mh::k_decode2<2, 2, 25, 2, false>", False, 8, 0,
          (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 32, 0, false, false>", False, 8, 1,      # L = 5 is the last with W = 2L
+    Cell("mh::k_decode2<2, 2, 32, 0, false>", False, 8, 1,      # L = 5 is the last with W = 2L
          (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32), _c(8, 5, W=10, dec_K=2, dec_NR=32)),
          WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 31, 2, true, false>", False, 8, 0,       # L = 6 is the first hybrid one
+    Cell("mh::k_decode2<2, 2, 31, 2, true>", False, 8, 0,       # L = 6 is the first hybrid one
          (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31), _c(9, 8, W=10, dec_K=2, dec_NR=31)),
          WG_LAYOUTS),
     # wave form: per-wave tables of up to 8 index bits
@@ -146,13 +159,3 @@ DECODER_CELLS = (
 )
 
 CELLS = ENCODER_CELLS + DECODER_CELLS
-
-# Compiled instances that no production plan launches (removing them is a kernel change of its own).
-UNREACHABLE = {
-    "mh::k_encode2<0, 4, 0, 0>": "byte input with 4-bit pairs means S >= 9, and S >= 9 symbols cannot have L <= 2",
-    "mh::k_encode2w<0, 4, 0>": "byte input with 4-bit pairs means S >= 9, and S >= 9 symbols cannot have L <= 2",
-    "mh::k_decode2<1, 2, 36, 2, false, true>": "the one-symbol decoder is chosen for wave-task plans only (MH_DEC_K1 = 1)",
-    "mh::k_decode2<2, 2, 32, 0, true, false>": "dec_NR is 31 for every hybrid table outside MH_TUNING builds",
-    "mh::k_decode2w<2, 2, 32, 0, true, false>": "dec_NR is 31 for every hybrid table outside MH_TUNING builds",
-    "mh::k_decode2w<2, 2, 31, 2, true, false>": "wave-task plans take the one-symbol decoder before the hybrid one",
-}

@@ -47,7 +47,7 @@ def mh():
 
 
 def _ident(c):
-    return c.symbol.replace("mh::", "").replace(" ", "")
+    return c.key.replace("mh::", "").replace(" ", "")
 
 
 def _order(S, mode, peak):
@@ -217,7 +217,7 @@ def _layouts(cell, pattern):
 @pytest.mark.parametrize("pattern", PATTERNS)
 @pytest.mark.parametrize("cell", kc.ENCODER_CELLS, ids=_ident)
 def test_encoder_cell_vs_oracle(mh, cell, pattern):
-    rng = np.random.RandomState(zlib.crc32((cell.symbol + pattern).encode()))
+    rng = np.random.RandomState(zlib.crc32((cell.key + pattern).encode()))
     for case, lens, sc, mode, w255, blocked in _layouts(cell, pattern):
         _run(mh, cell, case, lens, sc, mode, pattern, rng, word255=w255, blocked=blocked)
 
@@ -226,7 +226,7 @@ def test_encoder_cell_vs_oracle(mh, cell, pattern):
 @pytest.mark.parametrize("cell", kc.DECODER_CELLS, ids=_ident)
 def test_decoder_cell_vs_oracle(mh, cell, pattern):
     """Every case of the cell (both sides of the W caps), the oracle's stream and the GPU's decoded by the cell."""
-    rng = np.random.RandomState(zlib.crc32((pattern + cell.symbol).encode()))
+    rng = np.random.RandomState(zlib.crc32((pattern + cell.key).encode()))
     for j, case in enumerate(cell.cases):
         lens, sc = cell.layouts[(j + PATTERNS.index(pattern)) % len(cell.layouts)]
         _run(mh, cell, case, lens, sc, j % 2, pattern, rng, word255=pattern == "drift" and j == 0)

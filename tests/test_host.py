@@ -216,7 +216,7 @@ def test_plain_c_client_builds_and_fails_loudly_without_gpu():
 
 
 def test_production_library_has_no_debug_surface():
-    """No ablation hook, no environment knobs in the shipped .so (they exist only in -DMH_TUNING builds)."""
+    """No ablation hook, no environment knobs in the shipped .so."""
     raw = ct.CDLL(_lib.SO)
     assert not hasattr(raw, "mhdbg_set_ablation")
     # the dynamic symbol table IS the header: no exported globals (g_prepare_only once was one), no

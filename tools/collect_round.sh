@@ -15,8 +15,6 @@ cut -c1-300 $O/${TAG}_bench.json
 timeout -k 10 300 python tools/bench_small.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_bench_small.txt
 timeout -k 10 300 python tools/small_shape_probe.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_small_shape_probe.txt
 timeout -k 10 300 python tools/bench_stream.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_bench_stream.txt
-timeout -k 10 300 python tools/ablate_deinterleave.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_ablate_deinterleave.txt
-timeout -k 10 300 python tools/ablate_encode.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_ablate_encode.txt
 cat $O/${TAG}_bench_small.txt $O/${TAG}_bench_stream.txt
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/${TAG}_prof $O/${TAG}_prof_stream
