@@ -48,6 +48,7 @@ PROTOTYPES = {
     "mh_encode_preset": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "mh_plan_query": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, ct.POINTER(PlanInfo), _vp, _vp, _vp, _vp, _u64]),
     "mh_decode": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mh_decode_packed": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mh_decode_status": (_int, [_vp, ct.POINTER(_u32), _vp]),
     "mh_validate_stream": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
     "mh_power_draws": (_int, [_vp, _u32, _vp, _u32, _u64, ct.c_double, ct.c_double, ct.c_double, _vp, _u64, _vp]),
@@ -58,6 +59,7 @@ PROTOTYPES = {
     "mh_deinterleave": (_int, [_vp, _u64, _u32, _vp, _vp, _vp]),
     "mh_deinterleave_packed": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _u64, _vp]),
     "mh_interleave": (_int, [_vp, _vp, _u64, _u32, _vp, _vp]),
+    "mh_interleave_packed": (_int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp]),
     "mh_sweep_create": (_int, [ct.POINTER(_vp), _vp, _vp, _u32, _vp, _u32]),
     "mh_sweep_destroy": (_int, [_vp]),
     "mh_sweep_info": (_int, [_vp, ct.POINTER(_u32), _vp]),

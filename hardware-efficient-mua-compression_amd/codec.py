@@ -180,6 +180,14 @@ class Plan:
                                         _ptr(enc.peak), _ptr(enc.enc), _ptr(out), _stream()))
         return out
 
+    def decode_packed(self, enc, out):
+        """Packed plans (input_bits 2 for S <= 4, 4 for S >= 5): decode into the plan's packed pieces -- min(x, S-1) in the
+        bit layout mh_deinterleave_packed writes (include/muahuff.h, mh_decode_packed).  out: uint8 tensor holding the
+        plan's pieces; nothing outside them is written.  Same safety contract and status word as decode()."""
+        _lib.check(_lib.lib().mh_decode_packed(self._h, _ptr(enc.payload), enc.payload.numel(), _ptr(enc.seg_off),
+                                               _ptr(enc.peak), _ptr(enc.enc), _ptr(out), _stream()))
+        return out
+
     def decode_ok(self):
         """True when every decode() on this plan since the previous decode_ok() (direct calls and graph
         replays alike) stayed inside its payload; reading clears the flag (synchronises)."""

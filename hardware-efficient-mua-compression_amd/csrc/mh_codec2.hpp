@@ -1029,7 +1029,10 @@ __device__ __forceinline__ ChunkHdr scan_header(uint32_t hw32, int lane)
 // this part (cf. the occupancy cap); the one-symbol decoder loses 4 % (profiles/r03_dpp_reductions.txt).
 // (The source asks for non-temporal global stores; all but one of a kernel's 33 lose that metadata in an IR pass --
 // seen in the ISA -- so "global store" means the default policy.)
-template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0>
+// PO: output packing.  0 = one byte per symbol (mh_decode); 2 / 4 = packed pieces (mh_decode_packed): the tables hold
+// their symbols already packed (build_decode_tables), a row is assembled with shifts and ORs into the lane's 4- / 8-byte
+// piece and leaves in one global store (ST is not used); the cut piece of a partial chunk is written whole, zero-padded.
+template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0, int PO = 0>
 __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *tabw, uint32_t tbase, uint32_t maskW,
                                                     const uint8_t *tab1, uint32_t mask1,
                                                     const uint32_t *stage, uint8_t *__restrict__ out,
@@ -1072,9 +1075,16 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
         if (PARTIAL && piece >= nfp) {
             if (piece == nfp && (m & 15u)) {  // the cut piece: m % 16 symbols, one lane of the chunk
                 uint8_t *q = out + piece * MH_PIECE;
+                uint2 pw = make_uint2(0u, 0u);  // (PO != 0) the piece, zero-padded
                 for (uint32_t i = 0; i < (m & 15u); ++i) {
                     const uint32_t e1 = tab1[(uint32_t)(buf >> (bp + SH)) & mask1];
-                    q[i] = (uint8_t)(e1 & 15u);
+                    if constexpr (PO != 0) {
+                        const uint32_t b = (uint32_t)PO * i;
+                        if (b < 32) pw.x |= (e1 & 15u) << b;
+                        else pw.y |= (e1 & 15u) << (b - 32);
+                    } else {
+                        q[i] = (uint8_t)(e1 & 15u);
+                    }
                     bp += e1 >> 4;
                     if (kReload) {
                         pos += e1 >> 4;
@@ -1088,10 +1098,14 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
                         nxt = stage[wi + 2];
                     }
                 }
+                if constexpr (PO != 0) store_piece<PO>(out, piece, pw);
             }
             return;
         }
         u32x4 o;
+        uint32_t pw[2] = {0u, 0u};  // (PO != 0) the lane's piece
+        // symbol `s` of the piece (s < 16, a constant once unrolled) goes to bits [PO * s, PO * (s + 1)) of pw
+        auto put = [&](int s_, uint32_t v) { pw[(PO * s_) >> 5] |= v << ((PO * s_) & 31); };
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             uint32_t w = 0;
@@ -1101,15 +1115,18 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
                 uint32_t adv;
                 if (K == 1) {  // one symbol per lookup from the 2^maxlen-entry byte table: no flagged entries, no branch
                     const uint32_t e1 = tab1[(uint32_t)(buf >> bp) & mask1];
-                    w |= (e1 & 15u) << (8 * i);
+                    if constexpr (PO != 0) put(4 * d + i, e1 & 15u);
+                    else w |= (e1 & 15u) << (8 * i);
                     adv = e1 >> 4;
                 } else if (K == 4) {
                     const uint2 e = reinterpret_cast<const uint2 *>(tabw)[off];
-                    w = e.x;
+                    if constexpr (PO != 0) put(4 * d, e.x);
+                    else w = e.x;
                     adv = e.y;
                 } else {
                     const uint32_t e = *reinterpret_cast<lds_u1 *>(off + tbase);
-                    w |= (e & 0xFFFFu) << (8 * K * i);
+                    if constexpr (PO != 0) put(4 * d + K * i, e & 0xFFFFu);
+                    else w |= (e & 0xFFFFu) << (8 * K * i);
                     adv = HY ? (e >> 16) & 0x7FFFu : e >> 16;
                     if (HY && (int32_t)e < 0) {  // rare: second codeword reaches past the index bits
                         bp += adv;
@@ -1120,7 +1137,8 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
                             nxt = stage[wi + 2];
                         }
                         const uint32_t e1 = tab1[(uint32_t)(buf >> (bp + SH)) & mask1];
-                        w |= (e1 & 15u) << (8 * K * i + 8);
+                        if constexpr (PO != 0) put(4 * d + K * i + 1, e1 & 15u);
+                        else w |= (e1 & 15u) << (8 * K * i + 8);
                         adv = e1 >> 4;
                     }
                 }
@@ -1150,6 +1168,10 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
             o[d] = w;
         }
         const uint32_t krow = (uint32_t)k;
+        if constexpr (PO != 0) {
+            store_piece<PO>(out, krow * kLanes + lane, make_uint2(pw[0], pw[1]));
+            return;
+        }
         if (!PARTIAL && ST != 0) {
             // (the row offset is part of the VECTOR offset -- the compiler folds what fits into the immediate: with a scalar-
             // register offset hipcc 7.2 leaves no wait state between this store and a VALU write of its data
@@ -1177,7 +1199,7 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
 // independent chains -- the same lane's sub-streams in two chunks -- interleave perfectly: their lookups are issued back
 // to back and each LDS round trip serves both.  (The same pairing around the hybrid loop was slower: its branches cut
 // the two chains into separate basic blocks, r03_pair_decoding_ab.txt.)
-template <int M, int RL>
+template <int M, int RL, int PO = 0>
 __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, const uint8_t *tab1, uint32_t mask1,
                                                     const uint32_t *stageA, const uint32_t *stageB,
                                                     uint8_t *__restrict__ outA, uint8_t *__restrict__ outB, int lane)
@@ -1217,6 +1239,7 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
 #pragma unroll
     for (int k = 0; k < kRows; ++k) {
         u32x4 oA, oB;
+        uint32_t pA[2] = {0u, 0u}, pB[2] = {0u, 0u};  // (PO != 0) the lane's pieces, see decode_staged_chunk
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             uint32_t wA = 0, wB = 0;
@@ -1224,8 +1247,14 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
             for (int i = 0; i < 4; ++i) {
                 const uint32_t eA = tab1[(uint32_t)(A.buf >> A.bp) & mask1];  // both lookups in flight together
                 const uint32_t eB = tab1[(uint32_t)(B.buf >> B.bp) & mask1];
-                wA |= (eA & 15u) << (8 * i);
-                wB |= (eB & 15u) << (8 * i);
+                if constexpr (PO != 0) {
+                    const int b = PO * (4 * d + i);
+                    pA[b >> 5] |= (eA & 15u) << (b & 31);
+                    pB[b >> 5] |= (eB & 15u) << (b & 31);
+                } else {
+                    wA |= (eA & 15u) << (8 * i);
+                    wB |= (eB & 15u) << (8 * i);
+                }
                 A.bp += eA >> 4;
                 B.bp += eB >> 4;
                 if ((d * 4 + i + 1) % M == 0) {
@@ -1236,6 +1265,11 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
             oA[d] = wA;
             oB[d] = wB;
         }
+        if constexpr (PO != 0) {
+            store_piece<PO>(outA, (uint32_t)k * kLanes + lane, make_uint2(pA[0], pA[1]));
+            store_piece<PO>(outB, (uint32_t)k * kLanes + lane, make_uint2(pB[0], pB[1]));
+            continue;
+        }
         __builtin_nontemporal_store(oA, reinterpret_cast<u32x4_u *>(outA + ((uint32_t)k * kLanes + lane) * MH_PIECE));
         __builtin_nontemporal_store(oB, reinterpret_cast<u32x4_u *>(outB + ((uint32_t)k * kLanes + lane) * MH_PIECE));
     }
@@ -1245,7 +1279,7 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
 // reads of this chunk's own words), the whole payload copied to LDS in one batch of loads, then
 // decode_staged_chunk<PARTIAL>.  A chunk too large for the staging area takes the per-symbol
 // routine on global memory.
-template <int K, int M, int RL, bool HY>
+template <int K, int M, int RL, bool HY, int PO = 0>
 __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict__ in, uint32_t m, const uint32_t *tabw,
                                                   uint32_t tbase, uint32_t maskW, const uint8_t *tab1, uint32_t mask1,
                                                   uint32_t *stage, uint32_t cap_words, uint8_t *__restrict__ out,
@@ -1272,7 +1306,7 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
     const uint32_t ns = h.nw + 3;
     if (avail < (uint64_t)h.hw + ns) { if (lane == 0) atomicMax(err, epoch); return; }
     if (ns > cap_words) {
-        decode_chunk<3, false>(in, m, tab1, mask1, out, lane);
+        decode_chunk<3, false, PO>(in, m, tab1, mask1, out, lane);
         return;
     }
     const uint32_t *pay = in + h.hw;
@@ -1289,7 +1323,7 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    decode_staged_chunk<K, M, RL, HY, true>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m);
+    decode_staged_chunk<K, M, RL, HY, true, 0, PO>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m);
 }
 
 // One segment, one wave: the chunks of segment `seg` through the wave's tables (`tab` multi-symbol
@@ -1309,11 +1343,14 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
 // The oversize-chunk slow path has loads of its own and therefore sits OUTSIDE the loop: the
 // first chunk that does not fit the staging area ends it and the rest of the segment goes chunk
 // by chunk through decode_chunk (adversarial data only).
-template <int K, int M, int NR, int RL, bool HY, bool WT = false>
+// PO != 0 (packed output): `out` is the segment's first piece and chunk c starts at out + c * cstride (the plan's
+// chunk_stride, or 1024 pieces when they are contiguous); PO = 0 ignores cstride (chunks are kChunk bytes apart).
+template <int K, int M, int NR, int RL, bool HY, bool WT = false, int PO = 0>
 __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,
-                                               uint32_t mask1, uint32_t *stage, int lane)
+                                               uint32_t mask1, uint32_t *stage, int lane, size_t cstride = 0)
 {
+    const size_t cs = PO != 0 ? cstride : (size_t)kChunk;  // bytes from one chunk's output to the next
     constexpr bool kHdrDpp = WT || HY;  // see scan_header
     constexpr int kSt = WT && K != 1 ? 1 : 0;  // see decode_staged_chunk
     constexpr uint32_t kCap = NR * 64;         // words of payload (+3 read-ahead) a staged chunk may have
@@ -1395,7 +1432,7 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
                 // flight before this chunk's stores
                 fetch(pay_n, avail_n);
                 hw_next = peek(pay_n, nx.nw, peek_n);
-                decode_staged_chunk<K, M, RL, HY, false, kSt>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * kChunk, lane);
+                decode_staged_chunk<K, M, RL, HY, false, kSt, PO>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * cs, lane);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 ++c;
@@ -1431,12 +1468,12 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
         if (!room(pos, 32)) MH_DEC_BAIL();
         const ChunkHdr h = scan_header<kHdrDpp>(in[lane & 31], lane);
         if (h.nw < kMinFull || !room(pos, (uint64_t)h.hw + h.nw + 3)) MH_DEC_BAIL();
-        decode_chunk<3, true>(in, kChunk, tab1, mask1, out + (size_t)c * kChunk, lane);
+        decode_chunk<3, true, PO>(in, kChunk, tab1, mask1, out + (size_t)c * cs, lane);
         in += h.hw + h.nw;
         pos += h.hw + h.nw;
     }
     if (rem)
-        decode_partial_chunk<K, M, RL, HY>(in, rem, tab, tbase, maskW, tab1, mask1, stage, kCap, out + (size_t)nfull * kChunk,
+        decode_partial_chunk<K, M, RL, HY, PO>(in, rem, tab, tbase, maskW, tab1, mask1, stage, kCap, out + (size_t)nfull * cs,
                                             lane, pos < lim ? lim - pos : 0, d.err, d.epoch);
 #undef MH_DEC_BAIL
 }
@@ -1447,11 +1484,12 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
 // Whatever does not fit that scheme goes through decode_segment: a pair too large for the staging area, the odd full
 // chunk, the partial chunk.  Same bounds rules: every header-steered read is checked against lim first.
 // (Wave-task plans only: on long channels the one-symbol decoder loses, see dispatch_decode.)
-template <int K, int M, int NR, int RL, bool HY>
+template <int K, int M, int NR, int RL, bool HY, int PO = 0>
 __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                     const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,
-                                                    uint32_t mask1, uint32_t *stage, int lane)
+                                                    uint32_t mask1, uint32_t *stage, int lane, size_t cstride = 0)
 {
+    const size_t cs = PO != 0 ? cstride : (size_t)kChunk;  // see decode_segment
     static_assert(K == 1 && !HY, "pairing is for the branch-free one-symbol loop");
     constexpr bool kHdrDpp = true;
     constexpr uint32_t kCap = NR * 64;
@@ -1497,16 +1535,16 @@ __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t p
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        decode_staged_pair1<M, RL>(hA, hB, tab1, mask1, stage, stage + hA.nw + hB.hw, out + (size_t)c * kChunk,
-                                   out + (size_t)(c + 1) * kChunk, lane);
+        decode_staged_pair1<M, RL, PO>(hA, hB, tab1, mask1, stage, stage + hA.nw + hB.hw, out + (size_t)c * cs,
+                                       out + (size_t)(c + 1) * cs, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         pos = posB + hB.hw + hB.nw;
         c += 2;
     }
     if ((uint64_t)c * kChunk < n)
-        decode_segment<K, M, NR, RL, HY, true>(d, pos, out + (size_t)c * kChunk, n - (uint64_t)c * kChunk, tab, tbase, maskW, tab1, mask1,
-                                           stage, lane);
+        decode_segment<K, M, NR, RL, HY, true, PO>(d, pos, out + (size_t)c * cs, n - (uint64_t)c * kChunk, tab, tbase, maskW, tab1,
+                                               mask1, stage, lane, cstride);
 }
 
 // NR payload registers per lane: the next chunk's payload (up to NR*64 words) is fetched into
@@ -1533,7 +1571,8 @@ __device__ __forceinline__ void table_sync()
     }
 }
 
-template <int K, int NT>
+// PO != 0 (packed output): the multi-symbol entries hold their symbols packed, PO bits each, instead of one per byte.
+template <int K, int NT, int PO = 0>
 __device__ __forceinline__ uint32_t build_decode_tables(const Dec2Args &a, uint32_t ch, uint32_t *tab, uint8_t *tab1, int t,
                                                         int lane)
 {
@@ -1578,7 +1617,7 @@ __device__ __forceinline__ uint32_t build_decode_tables(const Dec2Args &a, uint3
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t e = tab1[(idx >> bpos) & mask1];
-                bytes |= (e & 15u) << (8 * j);
+                bytes |= (e & 15u) << ((PO != 0 ? PO : 8) * j);
                 bpos += e >> 4;
             }
             reinterpret_cast<uint2 *>(tab)[idx] = make_uint2(bytes, bpos);
@@ -1590,7 +1629,7 @@ __device__ __forceinline__ uint32_t build_decode_tables(const Dec2Args &a, uint3
             const uint32_t l1 = e1 >> 4;
             const uint32_t e2 = tab1[(idx >> l1) & mask1];
             const uint32_t l2 = e2 >> 4;
-            tab[idx] = l1 + l2 <= W ? (e1 & 15u) | ((e2 & 15u) << 8) | ((l1 + l2) << 16)
+            tab[idx] = l1 + l2 <= W ? (e1 & 15u) | ((e2 & 15u) << (PO != 0 ? PO : 8)) | ((l1 + l2) << 16)
                                     : (e1 & 15u) | (l1 << 16) | 0x80000000u;
         }
     }
@@ -1650,6 +1689,65 @@ __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2w(Dec2Args a)
     else
         decode_segment<K, M, NR, RL, HY, true>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
                                          tab + dec2_shared_dwords(W, K), lane);
+}
+
+// Packed-output decoders (mh_decode_packed): the same tables, pipeline and bounds checks as k_decode2 / k_decode2w,
+// with every piece written as PO = 2 / 4 bits per symbol into the layout of a PACKED plan (mh_plan_create_packed) --
+// the pieces mh_deinterleave_packed writes and the preset encoder reads.  A segment's output starts at the planner's
+// packed source offset (the task record's src_off, as the packed encoder reads it), chunk c of it cstride bytes further.
+// (Own names: the byte-output kernels k_decode2* keep their symbols and their code.)
+struct DecPkArgs {
+    Dec2Args a;
+    uint64_t cstride;  // bytes from one chunk of a channel's pieces to the next: the plan's chunk_stride or 1024 pieces
+};
+
+template <int K, int M, int NR, int RL, bool HY, int PO>
+__global__ __launch_bounds__(256, kDecMinBlocks) void k_decpk(DecPkArgs p)
+{
+    static_assert(PO == 2 || PO == 4, "packed output: 2 or 4 bits per symbol");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const Dec2Args &a = p.a;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const WgTask t = a.t.wg[blockIdx.x];
+    const uint32_t seg0 = t.seg0, nseg = t.nseg, ch = t.ch;
+    const uint32_t W = a.W;
+    constexpr uint32_t kEntDw = K == 4 ? 2 : 1;
+    uint32_t *tab = smem;
+    uint8_t *tab1 = reinterpret_cast<uint8_t *>(smem + (K == 1 ? 0u : kEntDw << W));
+    const uint32_t mask1 = build_decode_tables<K, 256, PO>(a, ch, tab, tab1, (int)threadIdx.x, lane);
+    if ((uint32_t)wave >= nseg) return;
+    uint32_t *stage = smem + dec2_shared_dwords(W, K) + (size_t)wave * dec2_stage_dwords(NR);
+    const uint32_t seg = seg0 + (uint32_t)wave;
+    // all but a task's last segment hold seg_chunks whole chunks: the wave's pieces by arithmetic, as the encoder reads
+    decode_segment<K, M, NR, RL, HY, false, PO>(a.d, a.d.seg_off[seg], a.d.out + t.src_off + (uint64_t)wave * a.t.seg_src_stride,
+                                                a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane,
+                                                (size_t)p.cstride);
+}
+
+template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
+__global__ __launch_bounds__(256, kDecMinBlocks) void k_decpkw(DecPkArgs p)
+{
+    static_assert(PO == 2 || PO == 4, "packed output: 2 or 4 bits per symbol");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const Dec2Args &a = p.a;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const uint32_t slot = blockIdx.x * 4 + (uint32_t)wave;
+    if (slot >= a.t.ntask) return;
+    const WaveTask t = a.t.wt[slot];
+    const uint32_t W = a.W;
+    constexpr uint32_t kEntDw = K == 4 ? 2 : 1;
+    const uint32_t wdw = dec2_shared_dwords(W, K) + dec2_stage_dwords(NR);
+    uint32_t *tab = smem + (size_t)wave * wdw;
+    uint8_t *tab1 = reinterpret_cast<uint8_t *>(tab + (K == 1 ? 0u : kEntDw << W));
+    const uint64_t pos = a.plan_slots ? t.dst_off : a.d.seg_off[t.seg];
+    const uint32_t mask1 = build_decode_tables<K, 64, PO>(a, t.ch, tab, tab1, lane, lane);
+    const uint32_t tbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)tab;
+    if constexpr (DUAL)
+        decode_segment_dual<K, M, NR, RL, HY, PO>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
+                                                  tab + dec2_shared_dwords(W, K), lane, (size_t)p.cstride);
+    else
+        decode_segment<K, M, NR, RL, HY, true, PO>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
+                                                   tab + dec2_shared_dwords(W, K), lane, (size_t)p.cstride);
 }
 
 // ------------------------------------------------------------------------------------------

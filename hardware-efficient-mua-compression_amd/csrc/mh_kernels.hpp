@@ -519,7 +519,43 @@ struct DecArgs {
     uint32_t epoch;
 };
 
-template <int FI, bool FULL>
+// Packed decoder output (mh_decode_packed): a piece of 16 symbols in PO * 16 bits, little-endian (the layout of
+// mh_deinterleave_packed, include/muahuff.h): 2 bits -> one dword, 4 bits -> two.  o = the 16 symbols one per byte,
+// each below 2^PO, so the shifted copies OR-ed together below never overlap in the bits that are kept.
+template <int PO>
+__device__ __forceinline__ uint2 pack_piece(u32x4 o)
+{
+    uint2 r;
+    if (PO == 2) {
+        uint32_t p = 0;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) p |= ((o[d] | (o[d] >> 6) | (o[d] >> 12) | (o[d] >> 18)) & 0xFFu) << (8 * d);
+        r = make_uint2(p, 0u);
+    } else {
+        uint32_t h[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t t = o[d] | (o[d] >> 4);
+            h[d] = (t & 0xFFu) | ((t >> 8) & 0xFF00u);
+        }
+        r = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+    }
+    return r;
+}
+
+// stores piece `piece` of a packed chunk that starts at `out` (4 / 8 bytes, one store)
+template <int PO>
+__device__ __forceinline__ void store_piece(uint8_t *out, uint32_t piece, uint2 v)
+{
+    if (PO == 2)
+        *reinterpret_cast<uint32_t *>(out + (size_t)piece * 4u) = v.x;
+    else
+        *reinterpret_cast<uint2 *>(out + (size_t)piece * 8u) = v;
+}
+
+// PO = 0: one byte per symbol (mh_decode); 2 / 4: packed pieces (mh_decode_packed), `out` = the chunk's first piece,
+// a cut last piece written whole and zero-padded
+template <int FI, bool FULL, int PO = 0>
 __device__ __forceinline__ uint32_t decode_chunk(const uint32_t *__restrict__ in, uint32_t m,
                                                  const uint8_t *dtab, uint32_t mask,
                                                  uint8_t *__restrict__ out, int lane)
@@ -570,7 +606,9 @@ __device__ __forceinline__ uint32_t decode_chunk(const uint32_t *__restrict__ in
                 }
             }
         }
-        if (FULL || cnt == MH_PIECE) {
+        if constexpr (PO != 0) {
+            if (cnt > 0) store_piece<PO>(out, (uint32_t)k * kLanes + lane, pack_piece<PO>(o));
+        } else if (FULL || cnt == MH_PIECE) {
             *reinterpret_cast<u32x4_u *>(out + base) = o;
         } else {
 #pragma unroll

@@ -10,6 +10,8 @@
 //                    the channel-major layout the codec reads: 256(t) x 128(c) byte tiles,
 //                    dword-only LDS traffic, 4x4 byte transposes with v_perm_b32.
 //   k_interleave     channel-major -> time-major, the inverse
+//   k_deinterleave_p / k_interleave_p   the same two directions with the channel-major side in packed
+//                    2- / 4-bit pieces (the intermediate of the stream path)
 #pragma once
 #include "mh_device.hpp"
 
@@ -556,6 +558,113 @@ __global__ __launch_bounds__(256) void k_interleave(const uint8_t *__restrict__ 
                     __builtin_nontemporal_store(v, reinterpret_cast<u32x4_u *>(dst));
                 else
                     tr2_store_partial(dst, v, cw - q);
+            }
+        }
+    }
+}
+
+// k_interleave_p<PK>: the inverse of k_deinterleave_p -- packed pieces (2 / 4 bits per sample, contiguous or chunk-blocked)
+// -> time-major bytes out[t * C + c].  k_interleave's tile, swizzle and byte transposes, with the pieces expanded to bytes
+// in registers first: a work item (4 channels x 16 time steps) reads ONE piece of 4 / 8 bytes per channel instead of
+// 16 bytes, spreads it to the 16 bytes k_interleave would have loaded (shifts and masks, no table), turns through LDS
+// and leaves as whole rows of C bytes.  A cut last piece is read whole (it is part of the channel's pieces); its time
+// steps past T are never stored.  nt_stores: the rows leave with non-temporal stores (what k_interleave does) or plain
+// ones; the host decides (mh_interleave_packed).
+template <int PK>
+__device__ __forceinline__ u32x4 expand_piece(uint2 p)
+{
+    u32x4 x;
+    if (PK == 2) {  // byte d of the piece = samples 4d .. 4d+3, 2 bits each -> one per byte
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t b = (p.x >> (8 * d)) & 0xFFu;
+            x[d] = (b | (b << 6) | (b << 12) | (b << 18)) & 0x03030303u;
+        }
+    } else {        // 16 bits = samples 4d .. 4d+3, 4 bits each -> one per byte
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t h = ((d < 2 ? p.x : p.y) >> (16 * (d & 1))) & 0xFFFFu;
+            const uint32_t t = (h & 0xFFu) | ((h & 0xFF00u) << 8);
+            x[d] = (t | (t << 4)) & 0x0F0F0F0Fu;
+        }
+    }
+    return x;
+}
+
+template <int PK>
+__global__ __launch_bounds__(256) void k_interleave_p(const uint8_t *__restrict__ in, const uint64_t *in_off, uint64_t T,
+                                                      uint32_t C, uint32_t tpw, uint64_t blk_stride, uint32_t nt_stores,
+                                                      uint8_t *__restrict__ out)
+{
+    constexpr uint32_t kPieceBytes = PK == 4 ? 8 : 4;
+    __shared__ __attribute__((aligned(16))) uint32_t tile[kTr2T * (kTr2C / 4)];
+    // grid order as k_interleave: channel strip fastest
+    const uint32_t nstrip = (C + kTr2C - 1) / kTr2C;
+    const uint32_t c0 = (blockIdx.x % nstrip) * kTr2C;
+    const uint32_t cw = C - c0 < (uint32_t)kTr2C ? C - c0 : (uint32_t)kTr2C;
+    const uint64_t ntiles = (T + kTr2T - 1) / kTr2T;
+    const uint64_t gx = gridDim.x / nstrip;
+    for (uint64_t tile0 = (uint64_t)(blockIdx.x / nstrip) * tpw; tile0 < ntiles; tile0 += gx * tpw) {
+        const uint64_t tend = tile0 + tpw < ntiles ? tile0 + tpw : ntiles;
+        for (uint64_t tl = tile0; tl < tend; ++tl) {
+            const uint64_t t0 = tl * kTr2T;
+            const uint32_t th = T - t0 < (uint64_t)kTr2T ? (uint32_t)(T - t0) : (uint32_t)kTr2T;
+            __syncthreads();  // previous tile fully written out
+#pragma unroll 1
+            for (int uu = 0; uu < 2; ++uu) {
+                const uint32_t id = threadIdx.x + 256u * uu, tb = id & 15u, cg = id >> 4;
+                if (cg * 4 >= cw || tb * 16 >= th) continue;
+                const uint64_t piece = (t0 >> 4) + tb;  // the item's piece of each of its channels
+                const uint64_t at = blk_stride ? (piece >> 10) * blk_stride + (piece & 1023u) * kPieceBytes : piece * kPieceBytes;
+                uint2 pc[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t c = cg * 4 + k;
+                    pc[k] = make_uint2(0u, 0u);
+                    if (c < cw) {
+                        const uint8_t *src = in + in_off[c0 + c] + at;
+                        if (PK == 4)
+                            pc[k] = *reinterpret_cast<const uint2 *>(src);
+                        else
+                            pc[k].x = *reinterpret_cast<const uint32_t *>(src);
+                    }
+                }
+                u32x4 x[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) x[k] = expand_piece<PK>(pc[k]);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {  // times 4m..4m+3 of the 4 channels -> one dword per time step
+                    const uint32_t a = x[0][m], b = x[1][m], c = x[2][m], e = x[3][m];
+                    const uint32_t t0_ = __builtin_amdgcn_perm(b, a, 0x05010400u);
+                    const uint32_t t1_ = __builtin_amdgcn_perm(e, c, 0x05010400u);
+                    const uint32_t t2_ = __builtin_amdgcn_perm(b, a, 0x07030602u);
+                    const uint32_t t3_ = __builtin_amdgcn_perm(e, c, 0x07030602u);
+                    const uint32_t d0 = __builtin_amdgcn_perm(t1_, t0_, 0x05040100u);
+                    const uint32_t d1 = __builtin_amdgcn_perm(t1_, t0_, 0x07060302u);
+                    const uint32_t d2 = __builtin_amdgcn_perm(t3_, t2_, 0x05040100u);
+                    const uint32_t d3 = __builtin_amdgcn_perm(t3_, t2_, 0x07060302u);
+                    const uint32_t r0 = tb * 16 + 4 * m, col = cg ^ (tb << 1);
+                    tile[(r0 + 0) * (kTr2C / 4) + (col ^ 0u)] = d0;
+                    tile[(r0 + 1) * (kTr2C / 4) + (col ^ 1u)] = d1;
+                    tile[(r0 + 2) * (kTr2C / 4) + (col ^ 2u)] = d2;
+                    tile[(r0 + 3) * (kTr2C / 4) + (col ^ 3u)] = d3;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t i = (uint32_t)j * 256 + threadIdx.x, row = i >> 3, q = (i & 7) * 16, q4 = (i & 7) * 4;
+                if (row >= th || q >= cw) continue;
+                const uint32_t sw = tr2_swz(row);
+                const uint32_t *r = tile + row * (kTr2C / 4);
+                const u32x4 v = {r[(q4 + 0) ^ sw], r[(q4 + 1) ^ sw], r[(q4 + 2) ^ sw], r[(q4 + 3) ^ sw]};
+                uint8_t *dst = out + (t0 + row) * C + c0 + q;
+                if (q + 16 > cw)
+                    tr2_store_partial(dst, v, cw - q);
+                else if (nt_stores)
+                    __builtin_nontemporal_store(v, reinterpret_cast<u32x4_u *>(dst));
+                else
+                    *reinterpret_cast<u32x4_u *>(dst) = v;
             }
         }
     }

@@ -328,6 +328,64 @@ static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a2, hipStream_t
     return launch_decode2<2, 2, 31, 2, true>(a2, st);
 }
 
+// Packed-output decoders (mh_decode_packed): the byte decoders' LDS layout and launch shape, PO bits per symbol.
+template <int K, int M, int NR, int RL, bool HY, int PO>
+static int launch_decpk(const mh::DecPkArgs &a, hipStream_t st)
+{
+    const size_t lds = ((size_t)mh::dec2_shared_dwords(a.a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
+    auto kern = mh::k_decpk<K, M, NR, RL, HY, PO>;
+    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
+    hipLaunchKernelGGL(kern, dim3(a.a.t.ntask), dim3(256), lds, st, a);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
+template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
+static int launch_decpkw(const mh::DecPkArgs &a, hipStream_t st)
+{
+    const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
+    auto kern = mh::k_decpkw<K, M, NR, RL, HY, DUAL, PO>;
+    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
+    hipLaunchKernelGGL(kern, dim3((a.a.t.ntask + 3) / 4), dim3(256), lds, st, a);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
+// output bits per symbol of mh_decode_packed: 2 while every symbol fits (S <= 4), else 4
+static inline uint32_t packed_out_bits(uint32_t S) { return S <= 4 ? 2u : 4u; }
+
+// The same choice as dispatch_decode, restricted to what a packed plan can reach.  The output width follows S
+// (packed_out_bits), and S bounds maxlen from below (S >= 5 needs a codeword of 3 bits or more), so:
+//   PO = 2 (S <= 4, L <= 3):  L <= 2            k_decpk<4, 4, 17, 1, false, 2>        k_decpkw<4, 4, 17, 1, false, false, 2>
+//                             L == 3            k_decpk<2, 2, 25, 2, false, 2>        k_decpkw<2, 2, 25, 2, false, false, 2>
+//   PO = 4 (S >= 5, L >= 3):  L == 3            k_decpk<2, 2, 25, 2, false, 4>        k_decpkw<2, 2, 25, 2, false, false, 4>
+//                             W >= 2L           k_decpk<2, 2, 32, 0, false, 4>        k_decpkw<2, 2, 32, 0, false, false, 4>
+//                             W < 2L            k_decpk<2, 2, 31, 2, true, 4>         k_decpkw<1, 2, 36, 2, false, true, 4>
+// (W >= 2L: L <= 5 for workgroup tasks, L <= 4 for wave tasks -- PlanHost::W.)  Ten instances; nothing else is built.
+template <int PO>
+static int dispatch_decode_packed(const mh_plan *p, const mh::DecPkArgs &a, hipStream_t st)
+{
+    const uint32_t L = p->h.info.maxlen;
+    if (PO == 2) {
+        if (p->h.use_wave_tasks)
+            return L <= 2 ? launch_decpkw<4, 4, 17, 1, false, false, 2>(a, st) : launch_decpkw<2, 2, 25, 2, false, false, 2>(a, st);
+        return L <= 2 ? launch_decpk<4, 4, 17, 1, false, 2>(a, st) : launch_decpk<2, 2, 25, 2, false, 2>(a, st);
+    }
+    if (p->h.use_wave_tasks) {
+        if (L == 3) return launch_decpkw<2, 2, 25, 2, false, false, 4>(a, st);
+        if (a.a.W >= 2 * L) return launch_decpkw<2, 2, 32, 0, false, false, 4>(a, st);
+        return launch_decpkw<1, 2, 36, 2, false, true, 4>(a, st);
+    }
+    if (L == 3) return launch_decpk<2, 2, 25, 2, false, 4>(a, st);
+    if (a.a.W >= 2 * L) return launch_decpk<2, 2, 32, 0, false, 4>(a, st);
+    return launch_decpk<2, 2, 31, 2, true, 4>(a, st);
+}
+
+static int dispatch_decode_packed(const mh_plan *p, const mh::DecPkArgs &a, hipStream_t st)
+{
+    return packed_out_bits(p->h.info.S) == 2 ? dispatch_decode_packed<2>(p, a, st) : dispatch_decode_packed<4>(p, a, st);
+}
+
 // raise the dynamic-LDS limits of the kernels this plan will launch (once, at plan creation)
 static int prepare_kernels(const mh_plan *p)
 {
@@ -338,6 +396,11 @@ static int prepare_kernels(const mh_plan *p)
     g_prepare_only = true;
     int rc = dispatch_encode(p, e, nullptr);
     if (rc == MH_OK) rc = dispatch_decode(p, d, nullptr);
+    if (rc == MH_OK && p->h.input_bits == packed_out_bits(p->h.info.S)) {  // a plan mh_decode_packed accepts
+        mh::DecPkArgs pd{};
+        pd.a.W = p->h.W;
+        rc = dispatch_decode_packed(p, pd, nullptr);
+    }
     g_prepare_only = false;
     return rc;
 }
@@ -741,6 +804,45 @@ int mh_decode(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const
     return dispatch_decode(p, a2, st);
 }
 
+int mh_decode_packed(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                     const uint8_t *peak, const uint8_t *enc, uint8_t *out, void *stream)
+{
+    if (!p || !payload || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_packed: NULL argument");
+    if (p->h.input_bits == 8)
+        return fail(MH_ERR_ARG, "mh_decode_packed: this plan describes a byte layout; decode it with mh_decode");
+    if (p->h.input_bits != packed_out_bits(p->h.info.S))
+        return fail(MH_ERR_ARG, "mh_decode_packed: S=%u decodes to %u-bit pieces, the plan holds %u-bit ones", p->h.info.S,
+                    packed_out_bits(p->h.info.S), p->h.input_bits);
+    if (int rc_ = check_device(p->device, "mh_decode_packed")) return rc_;
+    hipStream_t st = (hipStream_t)stream;
+    if (p->h.info.n_segments == 0) return MH_OK;
+    mh::DecPkArgs pa;
+    mh::DecArgs &a = pa.a.d;
+    a.payload = payload;
+    a.ch_off = p->d_ch_off;
+    a.w0 = p->d_w0;
+    a.seg_ch = p->d_seg_ch;
+    a.seg_first = p->d_seg_first;
+    a.seg_n = p->d_seg_n;
+    a.seg_off = seg_off ? seg_off : p->d_seg_off;
+    a.out = out;
+    a.nseg = (uint32_t)p->h.info.n_segments;
+    a.payload_words = payload_words;
+    a.err = p->d_err;
+    a.epoch = 1u;  // the same sticky status word as mh_decode
+    pa.a.t = task_args(p);
+    pa.a.W = p->h.W;
+    pa.a.peak = peak;
+    pa.a.enc = enc;
+    pa.a.codes = p->d_codes;
+    pa.a.S = p->h.info.S;
+    pa.a.mode = p->h.info.mode;
+    pa.a.nK = p->h.info.K;
+    pa.a.plan_slots = seg_off ? 0u : 1u;
+    pa.cstride = p->h.chunk_stride ? p->h.chunk_stride : (uint64_t)(MH_CHUNK / MH_PIECE) * p->h.input_bits * 2;
+    return dispatch_decode_packed(p, pa, st);
+}
+
 int mh_decode_status(mh_plan *p, uint32_t *flags, void *stream)
 {
     if (!p || !flags) return fail(MH_ERR_ARG, "mh_decode_status: NULL argument");
@@ -971,6 +1073,30 @@ int mh_interleave(const uint8_t *in, const uint64_t *in_off, uint64_t T, uint32_
     if (by > 65535) return fail(MH_ERR_ARG, "mh_interleave: C=%u too large", C);
     hipLaunchKernelGGL(mh::k_interleave, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T, C,
                        tpw, out);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
+int mh_interleave_packed(const uint8_t *in, const uint64_t *in_off, uint64_t T, uint32_t C, uint32_t bits,
+                         uint64_t chunk_stride, uint8_t *out, void *stream)
+{
+    if (!in || !in_off || !out || C == 0) return fail(MH_ERR_ARG, "mh_interleave_packed: bad argument");
+    if (bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mh_interleave_packed: bits=%u (4 or 2)", bits);
+    if (chunk_stride && (chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * bits / 8))
+        return fail(MH_ERR_ARG, "mh_interleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
+    if (T == 0) return MH_OK;
+    const uint32_t tpw = 4;
+    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
+    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
+    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
+    if (by > 65535) return fail(MH_ERR_ARG, "mh_interleave_packed: C=%u too large", C);
+    const uint32_t nt = 1u;  // non-temporal row stores, as k_interleave (profiles/r04_stream_decode.txt)
+    if (bits == 4)
+        hipLaunchKernelGGL(mh::k_interleave_p<4>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
+                           C, tpw, chunk_stride, nt, out);
+    else
+        hipLaunchKernelGGL(mh::k_interleave_p<2>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
+                           C, tpw, chunk_stride, nt, out);
     MH_HIP(hipGetLastError());
     return MH_OK;
 }

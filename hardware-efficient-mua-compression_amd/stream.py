@@ -11,6 +11,9 @@ is PACKED: the encoder clips at S-1 anyway, so the de-interleaver writes min(x, 
 per sample -- min(x, 3) in 2 bits when S <= 4 -- (mh_deinterleave_packed) and the encoder reads
 those pieces directly; the intermediate's round trip through HBM shrinks from 2 x 1 byte per
 sample to 2 x 1/2 resp. 2 x 1/4.
+`StreamDecoder` is the receiving end of the same link: per block, the preset stream is decoded straight into packed
+pieces of the same layout (mh_decode_packed) and re-interleaved to time-major bytes from them (mh_interleave_packed),
+so the receive side skips the byte-per-sample intermediate as the send side does.
 """
 import numpy as np
 import torch
@@ -126,3 +129,112 @@ class StreamEncoder:
         if cs.C == 0:
             return np.zeros((0, 0), np.uint8)
         return cs.to_time_major().cpu().numpy()
+
+
+class StreamDecoder:
+    """Receiving end of StreamEncoder: [Tb, C] time-major min(x, S-1) from the dense stream of a block.
+
+    Per block: an exclusive scan of the segment sizes (skipped when the caller has the offsets, e.g. the `seg_off` of
+    the compaction that StreamEncoder.encode_block_device ran), mh_decode_packed into a packed, chunk-blocked
+    intermediate of 2 (S <= 4) or 4 bits per sample, then mh_interleave_packed to time-major bytes.  Plan and buffers
+    are cached per block shape, so after the first block of a shape nothing is planned, allocated or synchronised."""
+
+    def __init__(self, C, S, sclv, mode=MODE_APPROX, seg_chunks=2, device="cuda"):
+        self.C, self.S, self.mode = int(C), int(S), int(mode)
+        self.sclv = np.ascontiguousarray(np.asarray(sclv, dtype=np.uint8).reshape(-1, self.S))
+        self.seg_chunks = int(seg_chunks)
+        self.device = torch.device(device, torch.cuda.current_device()) if device == "cuda" else torch.device(device)
+        self.bits = 2 if self.S <= 4 else 4
+        self._slots = {}
+
+    def _slot(self, Tb):
+        """Packed plan (same C, Tb, S, seg_chunks as the encoder's block plan: the segment boundaries match), pieces,
+        segment offsets and the [Tb, C] output, built once per block shape."""
+        slot = self._slots.get(Tb)
+        if slot is None:
+            cb = 1024 * 2 * self.bits  # bytes of one chunk of pieces; chunk j of channel c at (j * C + c) * cb
+            nchunks = (Tb + 16383) // 16384
+            pieces = torch.zeros(nchunks * self.C * cb, dtype=torch.uint8, device=self.device)
+            ch_off = np.arange(self.C, dtype=np.uint64) * np.uint64(cb)
+            plan = codec.Plan(ch_off, np.full(self.C, Tb, np.uint64), self.S, 0, self.mode, WIN_FULL, self.sclv,
+                              seg_chunks=self.seg_chunks, input_bits=self.bits, chunk_stride=self.C * cb)
+            slot = dict(plan=plan, pieces=pieces,
+                        d_off=torch.from_numpy(ch_off.astype(np.int64)).to(self.device),
+                        seg_off=torch.zeros(max(plan.n_segments, 1), dtype=torch.int64, device=self.device),
+                        out=torch.empty((Tb, self.C), dtype=torch.uint8, device=self.device))
+            self._slots[Tb] = slot
+        return slot
+
+    def decode_block_device(self, payload, seg_words, peak, enc, Tb, seg_off=None):
+        """Enqueues the decode of one block on the current stream and returns its [Tb, C] uint8 device tensor of
+        min(x, S-1), without synchronising.  payload: int32 device words of the dense stream (readable to its end:
+        payload_words = payload.numel()); seg_words: int64 [n_segments] device sizes; peak / enc: uint8 [C] device RAM
+        word; seg_off: optional int64 device segment offsets (else scanned from seg_words here).  The stream is not
+        validated (the decoder never reads outside `payload`; ok() tells whether it had to abandon a segment).
+        The returned tensor belongs to the shape's slot and is OVERWRITTEN by the next block of the same shape."""
+        import ctypes as ct
+
+        from . import _lib
+        Tb = int(Tb)
+        slot = self._slot(Tb)
+        plan = slot["plan"]
+        n = plan.n_segments
+        if seg_words.numel() < n or (seg_off is not None and seg_off.numel() < n):
+            raise ValueError("a block of %d steps has %d segments" % (Tb, n))
+        if peak.numel() < self.C or enc.numel() < self.C:
+            raise ValueError("the RAM word needs %d channels" % self.C)
+        st = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if seg_off is None:
+            seg_off = slot["seg_off"]
+            if n > 1:  # exclusive scan: seg_off[0] stays 0
+                torch.cumsum(seg_words[:n - 1], 0, out=seg_off[1:n])
+        _lib.check(_lib.lib().mh_decode_packed(plan._h, ct.c_void_p(payload.data_ptr()), payload.numel(),
+                                               ct.c_void_p(seg_off.data_ptr()), ct.c_void_p(peak.data_ptr()),
+                                               ct.c_void_p(enc.data_ptr()), ct.c_void_p(slot["pieces"].data_ptr()), st))
+        out = slot["out"]
+        _lib.check(_lib.lib().mh_interleave_packed(ct.c_void_p(slot["pieces"].data_ptr()),
+                                                   ct.c_void_p(slot["d_off"].data_ptr()), Tb, self.C, self.bits,
+                                                   plan.chunk_stride, ct.c_void_p(out.data_ptr()), st))
+        return out
+
+    def ok(self):
+        """True when no decode since the previous ok() had to abandon a segment (mh_decode_status over every slot's
+        plan; synchronises, clears the flags)."""
+        good = True
+        for slot in self._slots.values():
+            good = slot["plan"].decode_ok() and good
+        return good
+
+    def decode_block(self, c):
+        """Checked host form: c = container_io.Compressed of one block as StreamEncoder.encode_block writes it ->
+        [Tb, C] numpy array of min(x, S-1).  Raises ValueError when the container does not belong to this decoder or
+        its stream is corrupt (mh_validate_stream, as container_io.decompress)."""
+        hd = c.header
+        ch_len = np.asarray(c.ch_len, np.uint64)
+        if (int(hd.get("S", -1)) != self.S or int(hd.get("mode", -1)) != self.mode or
+                int(hd.get("window", -1)) != WIN_FULL or int(hd.get("seg_chunks", -1)) != self.seg_chunks):
+            raise ValueError("container (S, mode, window, seg_chunks) = (%s, %s, %s, %s) is not this decoder's (%d, %d, %d, %d)"
+                             % (hd.get("S"), hd.get("mode"), hd.get("window"), hd.get("seg_chunks"), self.S, self.mode,
+                                WIN_FULL, self.seg_chunks))
+        if np.asarray(hd.get("sclv"), np.int64).reshape(-1).tolist() != self.sclv.astype(np.int64).reshape(-1).tolist():
+            raise ValueError("container SCLV rows are not this decoder's")
+        if len(ch_len) != self.C or ch_len.size == 0 or (ch_len != ch_len[0]).any():
+            raise ValueError("a stream block holds %d channels of one length" % self.C)
+        container_io.validate(c)
+        Tb = int(ch_len[0])
+        dev = self.device
+        pay = torch.zeros(c.payload.size + 4, dtype=torch.int32, device=dev)
+        if c.payload.size:
+            pay[:c.payload.size] = torch.from_numpy(np.ascontiguousarray(c.payload).view(np.int32)).to(dev)
+        segw = torch.from_numpy(np.ascontiguousarray(c.seg_words).astype(np.int64)).to(dev)
+        peak = torch.from_numpy(np.ascontiguousarray(c.peak, np.uint8)).to(dev)
+        enc = torch.from_numpy(np.ascontiguousarray(c.enc, np.uint8)).to(dev)
+        out = self.decode_block_device(pay, segw, peak, enc, Tb)
+        if not self.ok():  # synchronises
+            raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
+        return out.cpu().numpy()
+
+    def close(self):
+        for slot in self._slots.values():
+            slot["plan"].close()
+        self._slots = {}

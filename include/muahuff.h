@@ -16,7 +16,8 @@
  *     allocates and owns every buffer;
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); device work is
  *     enqueued asynchronously on it and nothing in mh_measure/mh_encode/mh_decode/
- *     mh_compact/mh_synth_poisson/mh_rebin/mh_deinterleave/mh_interleave/mh_power_draws/
+ *     mh_compact/mh_synth_poisson/mh_rebin/mh_deinterleave/mh_interleave/mh_decode_packed/
+ *     mh_interleave_packed/mh_power_draws/
  *     mh_reduce_rows synchronises, allocates or frees, so they can be captured into a hipGraph;
  *   - a plan is bound to the device that was current when it was created and may be used
  *     from one stream at a time (it owns per-channel scratch tables).
@@ -32,6 +33,9 @@ extern "C" {
 #endif
 
 #define MH_VERSION 103 /* 0.1.3 ; container format revision 3 (reads revision 2) */
+/* Additions within 0.1.3 (additive: no existing behaviour changes, MH_VERSION stays):
+ *   mh_decode_packed     -- decode into the packed 2- / 4-bit pieces of a packed plan (receiving side of the stream path)
+ *   mh_interleave_packed -- packed pieces -> time-major bytes, the inverse of mh_deinterleave_packed */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
@@ -185,7 +189,8 @@ int mh_encode_preset(mh_plan *plan, const uint8_t *data, const uint8_t *peak, co
 
 /* Inverse of mh_encode: writes clip(x) = min(x, S-1) for every window sample into `out`
  * (same channel layout as the plan's data buffer; bytes outside the windows are left
- * untouched).  seg_off (device, words) = where each segment starts in `payload`; NULL means
+ * untouched).  A packed plan (mh_plan_create_packed) gets MH_ERR_ARG here: mh_decode_packed
+ * decodes into its pieces.  seg_off (device, words) = where each segment starts in `payload`; NULL means
  * the plan's slot offsets.  payload_words = words readable at `payload` (the dense stream plus
  * 4 words of slack, or the plan's payload_cap_words).
  * Memory-safe on ANY stream: the kernel follows the chunk headers it finds, but every read it
@@ -196,6 +201,15 @@ int mh_encode_preset(mh_plan *plan, const uint8_t *data, const uint8_t *peak, co
  * which also detects inconsistencies that stay inside the buffer. */
 int mh_decode(mh_plan *plan, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
               const uint8_t *peak, const uint8_t *enc, uint8_t *out, void *stream);
+/* mh_decode into PACKED pieces: `plan` is a packed plan (mh_plan_create_packed, contiguous or chunk-blocked) whose
+ * input_bits is 2 when S <= 4 and 4 when S >= 5 (else MH_ERR_ARG).  Writes min(x, S-1) of every sample in exactly the
+ * bit layout of mh_deinterleave_packed: channel c's chunk j at out + ch_off[c] + j * chunk_stride (contiguous pieces
+ * when chunk_stride is 0); a cut last piece is written whole, zero-padded, in one store; nothing outside the channels'
+ * pieces is written.  The rest as mh_decode: the stream of an ordinary plan with the same channel lengths, S, mode and
+ * seg_chunks (segment boundaries depend on nothing else), seg_off / payload_words / (peak, enc) alike, memory-safe on
+ * any stream, an abandoned segment raises the plan's status word (mh_decode_status).  Enqueues one launch. */
+int mh_decode_packed(mh_plan *plan, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                     const uint8_t *peak, const uint8_t *enc, uint8_t *out, void *stream);
 /* flags (host) <- 1 when any mh_decode on this plan since the previous mh_decode_status (or since
  * plan creation) had to abandon a segment, else 0; the flag is cleared by the call.  Sticky on purpose:
  * replays of a hipGraph that captured mh_decode report through it like direct calls.  Call it after the
@@ -255,6 +269,12 @@ int mh_deinterleave_packed(const uint8_t *in, uint64_t T, uint32_t C, uint32_t b
  * to a consumer of the implant-order stream).  in, in_off, out: device. */
 int mh_interleave(const uint8_t *in, const uint64_t *in_off, uint64_t T, uint32_t C, uint8_t *out,
                   void *stream);
+/* The inverse of mh_deinterleave_packed: channel c = ceil(T / 16) pieces of `bits` (2 or 4) bits per sample at
+ * in + in_off[c] (in_off[c] a multiple of 16; chunk_stride as there: 0 = contiguous, else chunk j of channel c at
+ * in_off[c] + j * chunk_stride)  ->  out[t*C + c] = the sample as a byte, for t < T.  Exactly T*C bytes of `out` are
+ * written.  in, in_off, out: device. */
+int mh_interleave_packed(const uint8_t *in, const uint64_t *in_off, uint64_t T, uint32_t C, uint32_t bits,
+                         uint64_t chunk_stride, uint8_t *out, void *stream);
 
 /* ---- fused sweep histograms (all design points from ONE pass over the data) --------------
  * The two BR scripts loop S = 2..10 and histogram sizes 2^h (get_BR_with_approx_sort.py:107,157)
