@@ -971,6 +971,9 @@ struct Dec2Args {
     const uint32_t *codes;
     uint32_t S, mode, nK;
     uint32_t plan_slots;  // 1: segments sit in the plan's slots (offset in the task record)
+    // packed output only: bytes from one chunk of a channel's pieces to the next (the plan's chunk_stride or 1024
+    // pieces).  Last, so that the byte decoders' kernel arguments keep their offsets.
+    uint64_t cstride;
 };
 
 // LDS dwords of the workgroup-shared tables: multi-symbol table (2 dwords per entry for K = 4,
@@ -1637,7 +1640,12 @@ __device__ __forceinline__ uint32_t build_decode_tables(const Dec2Args &a, uint3
     return mask1;
 }
 
-template <int K, int M, int NR, int RL, bool HY>
+// PO: output packing (decode_segment).  0 = one byte per symbol into the byte layout (mh_decode); 2 / 4 = pieces of
+// PO bits per symbol into the layout of a PACKED plan (mh_decode_packed, mh_plan_create_packed) -- the pieces
+// mh_deinterleave_packed writes and the preset encoder reads.  The two differ only in where a segment's output starts.
+// (One family for both: PO = 0 compiles to the plain byte decoder, and Dec2Args::cstride, which only PO != 0 reads,
+// is the last kernel argument, so the byte decoders' arguments keep their offsets.)
+template <int K, int M, int NR, int RL, bool HY, int PO>
 __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2(Dec2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -1655,18 +1663,24 @@ __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2(Dec2Args a)
     uint8_t *tab1 = reinterpret_cast<uint8_t *>(smem + (K == 1 ? 0u : kEntDw << W));
     // tables built by the workgroup itself from the channel's (peak, encoder) word: no table kernel in front of
     // the decoder, no per-channel tables in global memory
-    const uint32_t mask1 = build_decode_tables<K, 256>(a, ch, tab, tab1, (int)threadIdx.x, lane);
+    const uint32_t mask1 = build_decode_tables<K, 256, PO>(a, ch, tab, tab1, (int)threadIdx.x, lane);
     if ((uint32_t)wave >= nseg) return;
     uint32_t *stage = smem + dec2_shared_dwords(W, K) + (size_t)wave * dec2_stage_dwords(NR);
     const uint32_t seg = seg0 + (uint32_t)wave;
-    decode_segment<K, M, NR, RL, HY>(a.d, a.d.seg_off[seg], a.d.out + a.d.ch_off[ch] + a.d.w0[ch] + a.d.seg_first[seg],
-                                     a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane);
+    const auto seg_out = [&]() -> uint8_t * {
+        if constexpr (PO == 0) return a.d.out + a.d.ch_off[ch] + a.d.w0[ch] + a.d.seg_first[seg];
+        // packed: all but a task's last segment hold seg_chunks whole chunks -- the wave's pieces by arithmetic, as
+        // the packed encoder reads them
+        else return a.d.out + t.src_off + (uint64_t)wave * a.t.seg_src_stride;
+    };
+    decode_segment<K, M, NR, RL, HY, false, PO>(a.d, a.d.seg_off[seg], seg_out(), a.d.seg_n[seg], tab, 0u, (1u << W) - 1u,
+                                                tab1, mask1, stage, lane, (size_t)a.cstride);
 }
 
 // Short channels: one WAVE per segment of any channel, tables per wave (see k_encode2w).  The wave
 // derives its tables from the channel's (peak, encoder) word and the plan's codebooks itself, so
 // this decode is ONE launch: no table kernel in front of it.
-template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
+template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
 __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2w(Dec2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -1681,73 +1695,15 @@ __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode2w(Dec2Args a)
     uint8_t *tab1 = reinterpret_cast<uint8_t *>(tab + (K == 1 ? 0u : kEntDw << W));
     const uint64_t pos = a.plan_slots ? t.dst_off : a.d.seg_off[t.seg];
     // a (peak, encoder) word outside the plan's ranges (corrupt metadata) decodes as (0, 0)
-    const uint32_t mask1 = build_decode_tables<K, 64>(a, t.ch, tab, tab1, lane, lane);
-    const uint32_t tbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)tab;
-    if constexpr (DUAL)
-        decode_segment_dual<K, M, NR, RL, HY>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
-                                        tab + dec2_shared_dwords(W, K), lane);
-    else
-        decode_segment<K, M, NR, RL, HY, true>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
-                                         tab + dec2_shared_dwords(W, K), lane);
-}
-
-// Packed-output decoders (mh_decode_packed): the same tables, pipeline and bounds checks as k_decode2 / k_decode2w,
-// with every piece written as PO = 2 / 4 bits per symbol into the layout of a PACKED plan (mh_plan_create_packed) --
-// the pieces mh_deinterleave_packed writes and the preset encoder reads.  A segment's output starts at the planner's
-// packed source offset (the task record's src_off, as the packed encoder reads it), chunk c of it cstride bytes further.
-// (Own names: the byte-output kernels k_decode2* keep their symbols and their code.)
-struct DecPkArgs {
-    Dec2Args a;
-    uint64_t cstride;  // bytes from one chunk of a channel's pieces to the next: the plan's chunk_stride or 1024 pieces
-};
-
-template <int K, int M, int NR, int RL, bool HY, int PO>
-__global__ __launch_bounds__(256, kDecMinBlocks) void k_decpk(DecPkArgs p)
-{
-    static_assert(PO == 2 || PO == 4, "packed output: 2 or 4 bits per symbol");
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const Dec2Args &a = p.a;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const WgTask t = a.t.wg[blockIdx.x];
-    const uint32_t seg0 = t.seg0, nseg = t.nseg, ch = t.ch;
-    const uint32_t W = a.W;
-    constexpr uint32_t kEntDw = K == 4 ? 2 : 1;
-    uint32_t *tab = smem;
-    uint8_t *tab1 = reinterpret_cast<uint8_t *>(smem + (K == 1 ? 0u : kEntDw << W));
-    const uint32_t mask1 = build_decode_tables<K, 256, PO>(a, ch, tab, tab1, (int)threadIdx.x, lane);
-    if ((uint32_t)wave >= nseg) return;
-    uint32_t *stage = smem + dec2_shared_dwords(W, K) + (size_t)wave * dec2_stage_dwords(NR);
-    const uint32_t seg = seg0 + (uint32_t)wave;
-    // all but a task's last segment hold seg_chunks whole chunks: the wave's pieces by arithmetic, as the encoder reads
-    decode_segment<K, M, NR, RL, HY, false, PO>(a.d, a.d.seg_off[seg], a.d.out + t.src_off + (uint64_t)wave * a.t.seg_src_stride,
-                                                a.d.seg_n[seg], tab, 0u, (1u << W) - 1u, tab1, mask1, stage, lane,
-                                                (size_t)p.cstride);
-}
-
-template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
-__global__ __launch_bounds__(256, kDecMinBlocks) void k_decpkw(DecPkArgs p)
-{
-    static_assert(PO == 2 || PO == 4, "packed output: 2 or 4 bits per symbol");
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const Dec2Args &a = p.a;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const uint32_t slot = blockIdx.x * 4 + (uint32_t)wave;
-    if (slot >= a.t.ntask) return;
-    const WaveTask t = a.t.wt[slot];
-    const uint32_t W = a.W;
-    constexpr uint32_t kEntDw = K == 4 ? 2 : 1;
-    const uint32_t wdw = dec2_shared_dwords(W, K) + dec2_stage_dwords(NR);
-    uint32_t *tab = smem + (size_t)wave * wdw;
-    uint8_t *tab1 = reinterpret_cast<uint8_t *>(tab + (K == 1 ? 0u : kEntDw << W));
-    const uint64_t pos = a.plan_slots ? t.dst_off : a.d.seg_off[t.seg];
     const uint32_t mask1 = build_decode_tables<K, 64, PO>(a, t.ch, tab, tab1, lane, lane);
     const uint32_t tbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)tab;
+    // (the task record's src_off is the segment's output in the byte and the packed layout alike)
     if constexpr (DUAL)
         decode_segment_dual<K, M, NR, RL, HY, PO>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
-                                                  tab + dec2_shared_dwords(W, K), lane, (size_t)p.cstride);
+                                                  tab + dec2_shared_dwords(W, K), lane, (size_t)a.cstride);
     else
-        decode_segment<K, M, NR, RL, HY, true, PO>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1, mask1,
-                                                   tab + dec2_shared_dwords(W, K), lane, (size_t)p.cstride);
+        decode_segment<K, M, NR, RL, HY, true, PO>(a.d, pos, a.d.out + t.src_off, t.n, tab, tbase, (1u << W) - 1u, tab1,
+                                                   mask1, tab + dec2_shared_dwords(W, K), lane, (size_t)a.cstride);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -512,8 +512,8 @@ struct DecArgs {
     uint8_t *out;
     uint32_t nseg;
     // every read of the stream stays below payload + payload_words whatever the stream holds; a
-    // segment whose headers point outside is abandoned and *err raised to this call's epoch
-    // (mh_decode_status compares; nothing has to be cleared between calls)
+    // segment whose headers point outside is abandoned and *err raised to epoch (always 1): a
+    // sticky flag that mh_decode_status reads and clears
     uint64_t payload_words;
     uint32_t *err;
     uint32_t epoch;

@@ -227,7 +227,7 @@ static int launch_encode2w(const mh::Enc2Args &a, hipStream_t st)
 }
 
 // workgroup tasks (long channels)
-template <int K, int M, int NR, int RL, bool HY>
+template <int K, int M, int NR, int RL, bool HY, int PO>
 static int launch_decode2(const mh::Dec2Args &a, hipStream_t st)
 {
     size_t lds = ((size_t)mh::dec2_shared_dwords(a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
@@ -235,9 +235,10 @@ static int launch_decode2(const mh::Dec2Args &a, hipStream_t st)
     // writes FASTER with fewer waves streaming at once: 3 workgroups per CU instead of the 4 its registers
     // allow, enforced through the LDS request (160 KiB / 41 KiB = 3): 1024 ch x 1e7 bins decode 2.25 -> 2.04 ms
     // on one box; 2 per CU: 2.40 ms (profiles/r03_occupancy_ab.txt).  The pair-table decoders (S >= 4) are
-    // bound by their dependent lookup chain and lose with fewer waves (S = 5: 2.27 -> 2.38 ms).
-    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
-    auto kern = mh::k_decode2<K, M, NR, RL, HY>;
+    // bound by their dependent lookup chain and lose with fewer waves (S = 5: 2.27 -> 2.38 ms).  (Measured with
+    // byte output; the packed decoders request only the LDS they use.)
+    if (K == 4 && PO == 0 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
+    auto kern = mh::k_decode2<K, M, NR, RL, HY, PO>;
     if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
     hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
     MH_HIP(hipGetLastError());
@@ -245,11 +246,11 @@ static int launch_decode2(const mh::Dec2Args &a, hipStream_t st)
 }
 
 // wave tasks (short channels)
-template <int K, int M, int NR, int RL, bool HY, bool DUAL = false>
+template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
 static int launch_decode2w(const mh::Dec2Args &a, hipStream_t st)
 {
     const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    auto kern = mh::k_decode2w<K, M, NR, RL, HY, DUAL>;
+    auto kern = mh::k_decode2w<K, M, NR, RL, HY, DUAL, PO>;
     if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
     hipLaunchKernelGGL(kern, dim3((a.t.ntask + 3) / 4), dim3(256), lds, st, a);
     MH_HIP(hipGetLastError());
@@ -263,127 +264,93 @@ static int launch_decode2w(const mh::Dec2Args &a, hipStream_t st)
 // (MH_STAGE_AT), which needs the row count the kernel class was compiled for.
 static inline uint32_t enc_stage_dw(uint32_t maxlen) { return maxlen <= 2 ? 16 : 32; }
 
-// packed input (time-major path): the same kernels reading 4-bit resp. 2-bit pieces
+// the encoder instance in the plan's task form
+template <int LC, int PB, int PK>
+static int launch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
+{
+    return p->h.use_wave_tasks ? launch_encode2w<LC, PB, PK>(a, st) : launch_encode2<LC, PB, PK>(a, st);
+}
+
+// Pair packing PB of code class LC.  Byte input packs pairs in 3 bits while every symbol fits 3 bits (S <= 8; always
+// at L <= 2), the longest class in 4 only; 4-bit pieces: a byte of the stream is the PB = 4 pair index; 2-bit pieces:
+// the four-symbol table (PB unused).
+template <int LC, int PK>
+static int encode_rung(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
+{
+    constexpr int PB = PK == 0 && LC < 3 ? 3 : 4;
+    if constexpr (PB == 3 && LC > 0)
+        if (p->h.info.S > 8) return launch_encode<LC, 4, PK>(p, a, st);
+    return launch_encode<LC, PB, PK>(p, a, st);
+}
+
+// code class LC of maxlen L: <= 2, <= 4, <= 8, longer (2-bit pieces mean S <= 4, so L <= 3)
 template <int PK>
-static int dispatch_encode_packed(const mh_plan *p, const mh::Enc2Args &a2, hipStream_t st)
+static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
 {
     const uint32_t L = p->h.info.maxlen;
-    if (PK == 2) {  // S <= 4 only: maxlen <= 3; the table is the four-symbol one (PB unused)
-        if (p->h.use_wave_tasks) return L <= 2 ? launch_encode2w<0, 4, 2>(a2, st) : launch_encode2w<1, 4, 2>(a2, st);
-        return L <= 2 ? launch_encode2<0, 4, 2>(a2, st) : launch_encode2<1, 4, 2>(a2, st);
+    if (L <= 2) return encode_rung<0, PK>(p, a, st);
+    if constexpr (PK != 2) {
+        if (L > 8) return encode_rung<3, PK>(p, a, st);
+        if (L > 4) return encode_rung<2, PK>(p, a, st);
     }
-    // 4-bit pieces: a byte of the stream is the PB = 4 pair index
-    if (p->h.use_wave_tasks) {
-        if (L <= 2) return launch_encode2w<0, 4, 4>(a2, st);
-        if (L <= 4) return launch_encode2w<1, 4, 4>(a2, st);
-        if (L <= 8) return launch_encode2w<2, 4, 4>(a2, st);
-        return launch_encode2w<3, 4, 4>(a2, st);
-    }
-    if (L <= 2) return launch_encode2<0, 4, 4>(a2, st);
-    if (L <= 4) return launch_encode2<1, 4, 4>(a2, st);
-    if (L <= 8) return launch_encode2<2, 4, 4>(a2, st);
-    return launch_encode2<3, 4, 4>(a2, st);
+    return encode_rung<1, PK>(p, a, st);
 }
 
-static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a2, hipStream_t st)
+static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
 {
-    const uint32_t L = p->h.info.maxlen;
-    const bool pb3 = p->h.info.S <= 8;  // 3-bit pair packing when every symbol fits 3 bits
-    if (p->h.input_bits == 4) return dispatch_encode_packed<4>(p, a2, st);
-    if (p->h.input_bits == 2) return dispatch_encode_packed<2>(p, a2, st);
-    // (maxlen <= 2 means S <= 4: always 3-bit pairs)
-    if (p->h.use_wave_tasks) {
-        if (L <= 2) return launch_encode2w<0, 3>(a2, st);
-        if (L <= 4) return pb3 ? launch_encode2w<1, 3>(a2, st) : launch_encode2w<1, 4>(a2, st);
-        if (L <= 8) return pb3 ? launch_encode2w<2, 3>(a2, st) : launch_encode2w<2, 4>(a2, st);
-        return launch_encode2w<3, 4>(a2, st);
-    }
-    if (L <= 2) return launch_encode2<0, 3>(a2, st);
-    if (L <= 4) return pb3 ? launch_encode2<1, 3>(a2, st) : launch_encode2<1, 4>(a2, st);
-    if (L <= 8) return pb3 ? launch_encode2<2, 3>(a2, st) : launch_encode2<2, 4>(a2, st);
-    return launch_encode2<3, 4>(a2, st);
-}
-
-static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a2, hipStream_t st)
-{
-    const uint32_t L = p->h.info.maxlen;
-    // window maintenance (decode_staged_chunk): 1 = reload, 0 = branchy top-up, 2 = select top-up;
-    // the choices are the measured best per variant (profiles/README.md)
-    if (p->h.use_wave_tasks) {
-        if (L <= 2) return launch_decode2w<4, 4, 17, 1, false>(a2, st);
-        if (L == 3) return launch_decode2w<2, 2, 25, 2, false>(a2, st);
-        if (a2.W >= 2 * L) return launch_decode2w<2, 2, 32, 0, false>(a2, st);
-        // Long codes on SHORT channels (wave tasks, where every wave builds its own tables): the one-symbol decoder -- a
-        // 2^maxlen-byte table instead of a 256-entry hybrid pair table whose flagged entries make almost every lookup of
-        // the wave take the slow path (8 index bits) -- with the two chunks of a segment side by side (decode_staged_pair1).
-        // 10 000 x 20 000: decode S=8 82 -> 74 us, S=10 92 -> 77 us; 2400 x 72 000: 70 -> 68 us.  On long channels (shared
-        // 1024-entry tables) it loses: S=8 2.35 -> 2.82 ms -- twice the LDS lookups, and those decoders are bound by LDS
-        // bank-conflict throughput, not by the latency of the chain (profiles/r03_k1_pair_decoding_ab.txt).
-        return launch_decode2w<1, 2, 36, 2, false, true>(a2, st);
-    }
-    if (L <= 2) return launch_decode2<4, 4, 17, 1, false>(a2, st);  // worst-case chunk = 1027 words: never oversize
-    if (L == 3) return launch_decode2<2, 2, 25, 2, false>(a2, st);
-    if (a2.W >= 2 * L) return launch_decode2<2, 2, 32, 0, false>(a2, st);
-    // hybrid pair table: W < 2 * maxlen index bits, one-symbol entries flagged (31 staging registers: PlanHost::dec_NR)
-    return launch_decode2<2, 2, 31, 2, true>(a2, st);
-}
-
-// Packed-output decoders (mh_decode_packed): the byte decoders' LDS layout and launch shape, PO bits per symbol.
-template <int K, int M, int NR, int RL, bool HY, int PO>
-static int launch_decpk(const mh::DecPkArgs &a, hipStream_t st)
-{
-    const size_t lds = ((size_t)mh::dec2_shared_dwords(a.a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    auto kern = mh::k_decpk<K, M, NR, RL, HY, PO>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
-    hipLaunchKernelGGL(kern, dim3(a.a.t.ntask), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
-}
-
-template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
-static int launch_decpkw(const mh::DecPkArgs &a, hipStream_t st)
-{
-    const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    auto kern = mh::k_decpkw<K, M, NR, RL, HY, DUAL, PO>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
-    hipLaunchKernelGGL(kern, dim3((a.a.t.ntask + 3) / 4), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    if (p->h.input_bits == 4) return dispatch_encode<4>(p, a, st);
+    if (p->h.input_bits == 2) return dispatch_encode<2>(p, a, st);
+    return dispatch_encode<0>(p, a, st);
 }
 
 // output bits per symbol of mh_decode_packed: 2 while every symbol fits (S <= 4), else 4
 static inline uint32_t packed_out_bits(uint32_t S) { return S <= 4 ? 2u : 4u; }
 
-// The same choice as dispatch_decode, restricted to what a packed plan can reach.  The output width follows S
-// (packed_out_bits), and S bounds maxlen from below (S >= 5 needs a codeword of 3 bits or more), so:
-//   PO = 2 (S <= 4, L <= 3):  L <= 2            k_decpk<4, 4, 17, 1, false, 2>        k_decpkw<4, 4, 17, 1, false, false, 2>
-//                             L == 3            k_decpk<2, 2, 25, 2, false, 2>        k_decpkw<2, 2, 25, 2, false, false, 2>
-//   PO = 4 (S >= 5, L >= 3):  L == 3            k_decpk<2, 2, 25, 2, false, 4>        k_decpkw<2, 2, 25, 2, false, false, 4>
-//                             W >= 2L           k_decpk<2, 2, 32, 0, false, 4>        k_decpkw<2, 2, 32, 0, false, false, 4>
-//                             W < 2L            k_decpk<2, 2, 31, 2, true, 4>         k_decpkw<1, 2, 36, 2, false, true, 4>
-// (W >= 2L: L <= 5 for workgroup tasks, L <= 4 for wave tasks -- PlanHost::W.)  Ten instances; nothing else is built.
-template <int PO>
-static int dispatch_decode_packed(const mh_plan *p, const mh::DecPkArgs &a, hipStream_t st)
+// the decoder instance in the plan's task form
+template <int K, int M, int NR, int RL, bool HY, int PO>
+static int launch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t st)
 {
-    const uint32_t L = p->h.info.maxlen;
-    if (PO == 2) {
-        if (p->h.use_wave_tasks)
-            return L <= 2 ? launch_decpkw<4, 4, 17, 1, false, false, 2>(a, st) : launch_decpkw<2, 2, 25, 2, false, false, 2>(a, st);
-        return L <= 2 ? launch_decpk<4, 4, 17, 1, false, 2>(a, st) : launch_decpk<2, 2, 25, 2, false, 2>(a, st);
-    }
-    if (p->h.use_wave_tasks) {
-        if (L == 3) return launch_decpkw<2, 2, 25, 2, false, false, 4>(a, st);
-        if (a.a.W >= 2 * L) return launch_decpkw<2, 2, 32, 0, false, false, 4>(a, st);
-        return launch_decpkw<1, 2, 36, 2, false, true, 4>(a, st);
-    }
-    if (L == 3) return launch_decpk<2, 2, 25, 2, false, 4>(a, st);
-    if (a.a.W >= 2 * L) return launch_decpk<2, 2, 32, 0, false, 4>(a, st);
-    return launch_decpk<2, 2, 31, 2, true, 4>(a, st);
+    return p->h.use_wave_tasks ? launch_decode2w<K, M, NR, RL, HY, false, PO>(a, st) : launch_decode2<K, M, NR, RL, HY, PO>(a, st);
 }
 
-static int dispatch_decode_packed(const mh_plan *p, const mh::DecPkArgs &a, hipStream_t st)
+// The decoder from maxlen L, the table width W and the task form; PO = 0 for mh_decode, packed_out_bits(S) for
+// mh_decode_packed.  S <= 4 has no code longer than 3 bits and S >= 5 none shorter than 3, so PO = 2 stops at L = 3
+// and PO = 4 starts there.  Instances (PO is the last template argument):
+//   L <= 2    PO = 0, 2    k_decode2<4, 4, 17, 1, false>    k_decode2w<4, 4, 17, 1, false, false>
+//   L == 3    PO = 0, 2, 4 k_decode2<2, 2, 25, 2, false>    k_decode2w<2, 2, 25, 2, false, false>
+//   W >= 2L   PO = 0, 4    k_decode2<2, 2, 32, 0, false>    k_decode2w<2, 2, 32, 0, false, false>
+//   W < 2L    PO = 0, 4    k_decode2<2, 2, 31, 2, true>     k_decode2w<1, 2, 36, 2, false, true>
+// (W >= 2L: L <= 5 for workgroup tasks, L <= 4 for wave tasks -- PlanHost::W.)  18 instances; nothing else is built.
+// Window maintenance RL (decode_staged_chunk): 1 = reload, 0 = branchy top-up, 2 = select top-up; the choices are
+// the measured best per variant (profiles/README.md).
+template <int PO>
+static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t st)
 {
-    return packed_out_bits(p->h.info.S) == 2 ? dispatch_decode_packed<2>(p, a, st) : dispatch_decode_packed<4>(p, a, st);
+    const uint32_t L = p->h.info.maxlen;
+    if constexpr (PO != 4)
+        if (L <= 2) return launch_decode<4, 4, 17, 1, false, PO>(p, a, st);  // worst-case chunk = 1027 words: never oversize
+    if constexpr (PO != 2)
+        if (L != 3) {
+            if (a.W >= 2 * L) return launch_decode<2, 2, 32, 0, false, PO>(p, a, st);
+            // Long codes on SHORT channels (wave tasks, where every wave builds its own tables): the one-symbol decoder
+            // -- a 2^maxlen-byte table instead of a 256-entry hybrid pair table whose flagged entries make almost every
+            // lookup of the wave take the slow path (8 index bits) -- with the two chunks of a segment side by side
+            // (decode_staged_pair1).  10 000 x 20 000: decode S=8 82 -> 74 us, S=10 92 -> 77 us; 2400 x 72 000: 70 -> 68 us.
+            // On long channels (shared 1024-entry tables) it loses: S=8 2.35 -> 2.82 ms -- twice the LDS lookups, and
+            // those decoders are bound by LDS bank-conflict throughput, not by the latency of the chain
+            // (profiles/r03_k1_pair_decoding_ab.txt).
+            if (p->h.use_wave_tasks) return launch_decode2w<1, 2, 36, 2, false, true, PO>(a, st);
+            // hybrid pair table: W < 2 * maxlen index bits, one-symbol entries flagged (31 staging registers: PlanHost::dec_NR)
+            return launch_decode2<2, 2, 31, 2, true, PO>(a, st);
+        }
+    return launch_decode<2, 2, 25, 2, false, PO>(p, a, st);
+}
+
+static int dispatch_decode(const mh_plan *p, uint32_t po, const mh::Dec2Args &a, hipStream_t st)
+{
+    if (po == 2) return dispatch_decode<2>(p, a, st);
+    if (po == 4) return dispatch_decode<4>(p, a, st);
+    return dispatch_decode<0>(p, a, st);
 }
 
 // raise the dynamic-LDS limits of the kernels this plan will launch (once, at plan creation)
@@ -395,12 +362,9 @@ static int prepare_kernels(const mh_plan *p)
     d.W = p->h.W;
     g_prepare_only = true;
     int rc = dispatch_encode(p, e, nullptr);
-    if (rc == MH_OK) rc = dispatch_decode(p, d, nullptr);
-    if (rc == MH_OK && p->h.input_bits == packed_out_bits(p->h.info.S)) {  // a plan mh_decode_packed accepts
-        mh::DecPkArgs pd{};
-        pd.a.W = p->h.W;
-        rc = dispatch_decode_packed(p, pd, nullptr);
-    }
+    if (rc == MH_OK) rc = dispatch_decode(p, 0, d, nullptr);
+    if (rc == MH_OK && p->h.input_bits == packed_out_bits(p->h.info.S))  // a plan mh_decode_packed accepts
+        rc = dispatch_decode(p, p->h.input_bits, d, nullptr);
     g_prepare_only = false;
     return rc;
 }
@@ -767,6 +731,36 @@ int mh_encode_preset(mh_plan *p, const uint8_t *data, const uint8_t *peak, const
     return encode_common(p, data, payload, seg_words, ch_bits, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, st);
 }
 
+// arguments of mh_decode / mh_decode_packed: both kernel families build their tables themselves from (peak, enc), one launch
+static mh::Dec2Args decode_args(const mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                                const uint8_t *peak, const uint8_t *enc, uint8_t *out)
+{
+    mh::Dec2Args a;
+    a.d.payload = payload;
+    a.d.ch_off = p->d_ch_off;
+    a.d.w0 = p->d_w0;
+    a.d.seg_ch = p->d_seg_ch;
+    a.d.seg_first = p->d_seg_first;
+    a.d.seg_n = p->d_seg_n;
+    a.d.seg_off = seg_off ? seg_off : p->d_seg_off;
+    a.d.out = out;
+    a.d.nseg = (uint32_t)p->h.info.n_segments;
+    a.d.payload_words = payload_words;
+    a.d.err = p->d_err;
+    a.d.epoch = 1u;  // the status word is a sticky flag (mh_decode_status reads and clears it)
+    a.t = task_args(p);
+    a.W = p->h.W;
+    a.peak = peak;
+    a.enc = enc;
+    a.codes = p->d_codes;
+    a.S = p->h.info.S;
+    a.mode = p->h.info.mode;
+    a.nK = p->h.info.K;
+    a.plan_slots = seg_off ? 0u : 1u;
+    a.cstride = p->h.chunk_stride ? p->h.chunk_stride : (uint64_t)(MH_CHUNK / MH_PIECE) * p->h.input_bits * 2;
+    return a;
+}
+
 int mh_decode(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
               const uint8_t *peak, const uint8_t *enc, uint8_t *out, void *stream)
 {
@@ -774,34 +768,8 @@ int mh_decode(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const
     if (p->h.input_bits != 8)  // a packed plan's offsets describe the packed buffer, not a byte layout to decode into
         return fail(MH_ERR_ARG, "mh_decode: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
     if (int rc_ = check_device(p->device, "mh_decode")) return rc_;
-    hipStream_t st = (hipStream_t)stream;
     if (p->h.info.n_segments == 0) return MH_OK;
-    mh::DecArgs a;
-    a.payload = payload;
-    a.ch_off = p->d_ch_off;
-    a.w0 = p->d_w0;
-    a.seg_ch = p->d_seg_ch;
-    a.seg_first = p->d_seg_first;
-    a.seg_n = p->d_seg_n;
-    a.seg_off = seg_off ? seg_off : p->d_seg_off;
-    a.out = out;
-    a.nseg = (uint32_t)p->h.info.n_segments;
-    a.payload_words = payload_words;
-    a.err = p->d_err;
-    a.epoch = 1u;  // the status word is a sticky flag (mh_decode_status reads and clears it)
-    mh::Dec2Args a2;
-    a2.d = a;
-    a2.t = task_args(p);
-    a2.W = p->h.W;
-    a2.peak = peak;
-    a2.enc = enc;
-    a2.codes = p->d_codes;
-    a2.S = p->h.info.S;
-    a2.mode = p->h.info.mode;
-    a2.nK = p->h.info.K;
-    a2.plan_slots = seg_off ? 0u : 1u;
-    // both kernel families build their tables themselves from (peak, enc): one launch
-    return dispatch_decode(p, a2, st);
+    return dispatch_decode(p, 0, decode_args(p, payload, payload_words, seg_off, peak, enc, out), (hipStream_t)stream);
 }
 
 int mh_decode_packed(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
@@ -814,33 +782,9 @@ int mh_decode_packed(mh_plan *p, const uint32_t *payload, uint64_t payload_words
         return fail(MH_ERR_ARG, "mh_decode_packed: S=%u decodes to %u-bit pieces, the plan holds %u-bit ones", p->h.info.S,
                     packed_out_bits(p->h.info.S), p->h.input_bits);
     if (int rc_ = check_device(p->device, "mh_decode_packed")) return rc_;
-    hipStream_t st = (hipStream_t)stream;
     if (p->h.info.n_segments == 0) return MH_OK;
-    mh::DecPkArgs pa;
-    mh::DecArgs &a = pa.a.d;
-    a.payload = payload;
-    a.ch_off = p->d_ch_off;
-    a.w0 = p->d_w0;
-    a.seg_ch = p->d_seg_ch;
-    a.seg_first = p->d_seg_first;
-    a.seg_n = p->d_seg_n;
-    a.seg_off = seg_off ? seg_off : p->d_seg_off;
-    a.out = out;
-    a.nseg = (uint32_t)p->h.info.n_segments;
-    a.payload_words = payload_words;
-    a.err = p->d_err;
-    a.epoch = 1u;  // the same sticky status word as mh_decode
-    pa.a.t = task_args(p);
-    pa.a.W = p->h.W;
-    pa.a.peak = peak;
-    pa.a.enc = enc;
-    pa.a.codes = p->d_codes;
-    pa.a.S = p->h.info.S;
-    pa.a.mode = p->h.info.mode;
-    pa.a.nK = p->h.info.K;
-    pa.a.plan_slots = seg_off ? 0u : 1u;
-    pa.cstride = p->h.chunk_stride ? p->h.chunk_stride : (uint64_t)(MH_CHUNK / MH_PIECE) * p->h.input_bits * 2;
-    return dispatch_decode_packed(p, pa, st);
+    return dispatch_decode(p, p->h.input_bits, decode_args(p, payload, payload_words, seg_off, peak, enc, out),
+                           (hipStream_t)stream);
 }
 
 int mh_decode_status(mh_plan *p, uint32_t *flags, void *stream)

@@ -22,6 +22,20 @@ from . import MODE_APPROX, WIN_FULL, codec, container_io
 from .container import ChannelSet
 
 
+def _packed_block(owner, Tb, slack=0):
+    """The packed, chunk-blocked layout of a block of Tb time steps, the same on both ends of the link: min(x, S-1) in
+    2 (S <= 4) or 4 bits per sample, chunk j (16384 samples = 1024 pieces) of channel c at (j * C + c) * cb -- the chunks
+    of one time range are neighbours.  owner: a StreamEncoder or StreamDecoder.  -> (zeroed buffer of the pieces plus
+    `slack` bytes, ch_off, plan); the buffer is allocated before the plan."""
+    bits = 2 if owner.S <= 4 else 4
+    cb = 1024 * 2 * bits
+    buf = torch.zeros((Tb + 16383) // 16384 * owner.C * cb + slack, dtype=torch.uint8, device=owner.device)
+    ch_off = np.arange(owner.C, dtype=np.uint64) * np.uint64(cb)
+    plan = codec.Plan(ch_off, np.full(owner.C, Tb, np.uint64), owner.S, 0, owner.mode, WIN_FULL, owner.sclv,
+                      seg_chunks=owner.seg_chunks, input_bits=bits, chunk_stride=owner.C * cb)
+    return buf, ch_off, plan
+
+
 class StreamEncoder:
     def __init__(self, C, S, hist_bits, sclv, mode=MODE_APPROX, seg_chunks=2, device="cuda"):
         self.C, self.S, self.h, self.mode = int(C), int(S), int(hist_bits), int(mode)
@@ -50,15 +64,8 @@ class StreamEncoder:
         per block."""
         slot = self._slots.get(Tb)
         if slot is None:
-            bits = 2 if self.S <= 4 else 4
-            # packed, chunk-blocked intermediate: chunk j (16384 samples = 1024 pieces) of channel c at
-            # (j * C + c) * chunk_bytes -- the chunks of one time range are neighbours
-            cb = 1024 * 2 * bits
-            nchunks = (Tb + 16383) // 16384
-            buf = torch.zeros(nchunks * self.C * cb + 16, dtype=torch.uint8, device=self.device)
-            cs = ChannelSet(buf, np.arange(self.C, dtype=np.uint64) * np.uint64(cb), np.full(self.C, Tb, np.uint64))
-            plan = codec.Plan(cs.ch_off, cs.ch_len, self.S, 0, self.mode, WIN_FULL, self.sclv,
-                              seg_chunks=self.seg_chunks, input_bits=bits, chunk_stride=self.C * cb)
+            buf, ch_off, plan = _packed_block(self, Tb, slack=16)
+            cs = ChannelSet(buf, ch_off, np.full(self.C, Tb, np.uint64))
             e = plan.alloc_encoded()
             # the block's Encoded record points at the stored RAM word: nothing to copy per block
             e = codec.Encoded(e.payload, e.seg_words, e.ch_bits, self.peak, self.enc, e.skipped, e.seg_off, e.dense)
@@ -144,7 +151,6 @@ class StreamDecoder:
         self.sclv = np.ascontiguousarray(np.asarray(sclv, dtype=np.uint8).reshape(-1, self.S))
         self.seg_chunks = int(seg_chunks)
         self.device = torch.device(device, torch.cuda.current_device()) if device == "cuda" else torch.device(device)
-        self.bits = 2 if self.S <= 4 else 4
         self._slots = {}
 
     def _slot(self, Tb):
@@ -152,12 +158,7 @@ class StreamDecoder:
         segment offsets and the [Tb, C] output, built once per block shape."""
         slot = self._slots.get(Tb)
         if slot is None:
-            cb = 1024 * 2 * self.bits  # bytes of one chunk of pieces; chunk j of channel c at (j * C + c) * cb
-            nchunks = (Tb + 16383) // 16384
-            pieces = torch.zeros(nchunks * self.C * cb, dtype=torch.uint8, device=self.device)
-            ch_off = np.arange(self.C, dtype=np.uint64) * np.uint64(cb)
-            plan = codec.Plan(ch_off, np.full(self.C, Tb, np.uint64), self.S, 0, self.mode, WIN_FULL, self.sclv,
-                              seg_chunks=self.seg_chunks, input_bits=self.bits, chunk_stride=self.C * cb)
+            pieces, ch_off, plan = _packed_block(self, Tb)
             slot = dict(plan=plan, pieces=pieces,
                         d_off=torch.from_numpy(ch_off.astype(np.int64)).to(self.device),
                         seg_off=torch.zeros(max(plan.n_segments, 1), dtype=torch.int64, device=self.device),
@@ -193,7 +194,7 @@ class StreamDecoder:
                                                ct.c_void_p(enc.data_ptr()), ct.c_void_p(slot["pieces"].data_ptr()), st))
         out = slot["out"]
         _lib.check(_lib.lib().mh_interleave_packed(ct.c_void_p(slot["pieces"].data_ptr()),
-                                                   ct.c_void_p(slot["d_off"].data_ptr()), Tb, self.C, self.bits,
+                                                   ct.c_void_p(slot["d_off"].data_ptr()), Tb, self.C, plan.input_bits,
                                                    plan.chunk_stride, ct.c_void_p(out.data_ptr()), st))
         return out
 

@@ -1,10 +1,11 @@
 """The codec kernels the production library ships, one cell per instance (a plain module, not a conftest).
 
 libmuahuff.so compiles a fixed set of k_encode2 / k_encode2w / k_decode2 / k_decode2w template instances, and
-dispatch_encode, dispatch_encode_packed and dispatch_decode (csrc/muahuff.hip) choose among them from the plan:
-maxlen L (the longest codeword of the plan's SCLV rows), S <= 8 (3-bit pair packing) or not, input_bits (8, or
-packed 4 / 2), the planner's wave-task rule (csrc/mh_planner.hpp) and, for the decoder, the table width W and the
-staging registers dec_NR.  Every CELL names one instance and the plans that land on it:
+dispatch_encode and dispatch_decode (csrc/muahuff.hip) choose among them from the plan: maxlen L (the longest
+codeword of the plan's SCLV rows), S <= 8 (3-bit pair packing) or not, input_bits (8, or packed 4 / 2), the
+planner's wave-task rule (csrc/mh_planner.hpp) and, for the decoder, the output (bytes for mh_decode, 2- / 4-bit
+pieces for mh_decode_packed: input_bits of the packed cells), the table width W and the staging registers dec_NR.
+decoder_symbol is that decoder choice in Python.  Every CELL names one instance and the plans that land on it:
 
   cases    (S, SCLV rows) pairs -- each row Kraft-complete and non-decreasing -- with the maxlen they give; decoder
            cells also give the planner's W, dec_K and dec_NR for that case
@@ -13,8 +14,8 @@ staging registers dec_NR.  Every CELL names one instance and the plans that land
            wave in 16 idle, workgroup tasks otherwise
 
 tests/test_host_kernel_cells.py checks without a GPU that the cells and the shipped symbols are the same set and
-that the host planner puts every case and layout where its cell says; tests/test_gpu_kernel_cells.py runs them
-against the CPU oracle.
+that the host planner puts every case and layout where its cell says; tests/test_gpu_kernel_cells.py (encoders,
+byte decoders) and tests/test_gpu_stream_decode.py (packed decoders) run them against the CPU oracle.
 """
 from dataclasses import dataclass
 
@@ -47,14 +48,19 @@ class Cell:
     @property
     def key(self):
         """Name of the cell's GPU tests and seed of their data.  It keeps the symbol's form from when the table was
-        written, before k_encode2 lost its ablation level (always 0, before PK) and k_decode2 its DUAL flag (always
-        false), so that every cell keeps its test ids and its data across that rename."""
+        written, before k_encode2 lost its ablation level (always 0, before PK), k_decode2 its DUAL flag (always
+        false) and the decoders gained PO: the byte decoders (PO = 0) keep the names without it, the packed ones
+        (PO = 2 / 4) the names of their former kernels k_decpk / k_decpkw.  So every cell keeps its test ids and its
+        data across those renames."""
         head, args = self.symbol[:-1].split("<")
         if head == "mh::k_encode2":
             lc, pb, pk = args.split(", ")
             return "%s<%s, %s, 0, %s>" % (head, lc, pb, pk)
-        if head == "mh::k_decode2":
-            return "%s<%s, false>" % (head, args)
+        if self.decoder:
+            rest, po = args.rsplit(", ", 1)
+            if po != "0":
+                return "%s<%s, %s>" % (head.replace("k_decode2", "k_decpk"), rest, po)
+            return "%s<%s, false>" % (head, rest) if head == "mh::k_decode2" else "%s<%s>" % (head, rest)
         return self.symbol
 
 
@@ -68,6 +74,7 @@ R = {
     (3, 2): _row(1, 2, 2),
     (4, 2): _row(2, 2, 2, 2),
     (4, 3): _row(1, 2, 3, 3),
+    (5, 3): _row(2, 2, 2, 3, 3),    # the shortest code a 4-bit packed decoder can have
     (5, 4): _row(1, 2, 3, 4, 4),
     (8, 3): _row(*[3] * 8),
     (8, 4): _row(2, 2, 3, 3, 4, 4, 4, 4),
@@ -134,28 +141,70 @@ ENCODER_CELLS = tuple(
 )
 
 DECODER_CELLS = (
-    # workgroup form: shared tables of up to 10 index bits
-    Cell("mh::k_decode2<4, 4, 17, 1, false>", False, 8, 1,
+    # byte output; workgroup form: shared tables of up to 10 index bits
+    Cell("mh::k_decode2<4, 4, 17, 1, false, 0>", False, 8, 1,
          (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32)), WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 25, 2, false>", False, 8, 0,
+    Cell("mh::k_decode2<2, 2, 25, 2, false, 0>", False, 8, 0,
          (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 32, 0, false>", False, 8, 1,      # L = 5 is the last with W = 2L
+    Cell("mh::k_decode2<2, 2, 32, 0, false, 0>", False, 8, 1,      # L = 5 is the last with W = 2L
          (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32), _c(8, 5, W=10, dec_K=2, dec_NR=32)),
          WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 31, 2, true>", False, 8, 0,       # L = 6 is the first hybrid one
+    Cell("mh::k_decode2<2, 2, 31, 2, true, 0>", False, 8, 0,       # L = 6 is the first hybrid one
          (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31), _c(9, 8, W=10, dec_K=2, dec_NR=31)),
          WG_LAYOUTS),
     # wave form: per-wave tables of up to 8 index bits
-    Cell("mh::k_decode2w<4, 4, 17, 1, false, false>", True, 8, 0,
+    Cell("mh::k_decode2w<4, 4, 17, 1, false, false, 0>", True, 8, 0,
          (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)), WAVE_LAYOUTS),
-    Cell("mh::k_decode2w<2, 2, 25, 2, false, false>", True, 8, 1,
+    Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 0>", True, 8, 1,
          (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
-    Cell("mh::k_decode2w<2, 2, 32, 0, false, false>", True, 8, 0,      # L = 4 is the last with W = 2L
+    Cell("mh::k_decode2w<2, 2, 32, 0, false, false, 0>", True, 8, 0,      # L = 4 is the last with W = 2L
          (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(8, 4, W=8, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
-    Cell("mh::k_decode2w<1, 2, 36, 2, false, true>", True, 8, 1,       # L = 5 is the first one-symbol one
+    Cell("mh::k_decode2w<1, 2, 36, 2, false, true, 0>", True, 8, 1,       # L = 5 is the first one-symbol one
          (_c(6, 5, W=8, dec_K=2, dec_NR=31), _c(9, 5, W=8, dec_K=2, dec_NR=31),
           _c(10, 9, W=9, dec_K=2, dec_NR=31)),                          # (W >= L: an entry holds its first code)
          WAVE_LAYOUTS),
 )
 
-CELLS = ENCODER_CELLS + DECODER_CELLS
+# packed output (mh_decode_packed), 2 / 4 bits per symbol (input_bits): the byte decoders' choice, restricted to what S
+# allows.  Planned like StreamDecoder's blocks: no calibration window (h = 0), mode 1.
+PACKED_DECODER_CELLS = (
+    # 2-bit pieces (S <= 4): the four-symbol table for L <= 2, the pair table for L = 3
+    Cell("mh::k_decode2<4, 4, 17, 1, false, 2>", False, 2, 1,
+         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)),
+         WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 25, 2, false, 2>", False, 2, 1, (_c(4, 3, W=6, dec_K=2, dec_NR=32),), WG_LAYOUTS),
+    Cell("mh::k_decode2w<4, 4, 17, 1, false, false, 2>", True, 2, 1,
+         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)),
+         WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 2>", True, 2, 1, (_c(4, 3, W=6, dec_K=2, dec_NR=32),), WAVE_LAYOUTS),
+    # 4-bit pieces (S >= 5)
+    Cell("mh::k_decode2<2, 2, 25, 2, false, 4>", False, 4, 1,
+         (_c(5, 3, W=6, dec_K=2, dec_NR=32), _c(8, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 32, 0, false, 4>", False, 4, 1,     # L = 5 is the last with W = 2L
+         (_c(5, 4, W=8, dec_K=2, dec_NR=32), _c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32)),
+         WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 31, 2, true, 4>", False, 4, 1,      # hybrid pair table from L = 6
+         (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31)), WG_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 4>", True, 4, 1,
+         (_c(5, 3, W=6, dec_K=2, dec_NR=32), _c(8, 3, W=6, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 32, 0, false, false, 4>", True, 4, 1,  # L = 4 is the last with W = 2L
+         (_c(5, 4, W=8, dec_K=2, dec_NR=32), _c(10, 4, W=8, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<1, 2, 36, 2, false, true, 4>", True, 4, 1,   # one-symbol pairs from L = 5
+         (_c(6, 5, W=8, dec_K=2, dec_NR=31), _c(10, 9, W=9, dec_K=2, dec_NR=31)), WAVE_LAYOUTS),
+)
+
+CELLS = ENCODER_CELLS + DECODER_CELLS + PACKED_DECODER_CELLS
+
+
+def decoder_symbol(po, wave, L, W):
+    """dispatch_decode<PO> (csrc/muahuff.hip) in Python: the decoder a plan launches, from the output bits PO (0 =
+    bytes), the task form, maxlen L and the table width W"""
+    if po != 4 and L <= 2:
+        args = "4, 4, 17, 1, false"
+    elif po == 2 or L == 3:
+        args = "2, 2, 25, 2, false"
+    elif W >= 2 * L:
+        args = "2, 2, 32, 0, false"
+    else:
+        return "mh::k_decode2w<1, 2, 36, 2, false, true, %d>" % po if wave else "mh::k_decode2<2, 2, 31, 2, true, %d>" % po
+    return "mh::k_decode2w<%s, false, %d>" % (args, po) if wave else "mh::k_decode2<%s, %d>" % (args, po)

@@ -1,5 +1,5 @@
-"""Every production codec kernel instance (tests/kernel_cells.py) against the CPU oracle, with the data that sends a
-kernel down its rare paths.
+"""Every production encoder and byte-output decoder instance (tests/kernel_cells.py; the packed-output decoders run in
+tests/test_gpu_stream_decode.py) against the CPU oracle, with the data that sends a kernel down its rare paths.
 
 Each encoder cell runs four patterns over the layouts of its task form (seg_chunks 1..4, lengths below 16, off
 multiples of 16, whole chunks and one past), NOSORT and APPROX in turn:

@@ -1,5 +1,5 @@
-"""The receiving side of the stream path on the device: mh_interleave_packed, mh_decode_packed (every k_decpk /
-k_decpkw instance, tests/test_host_stream_decode.py) and stream.StreamDecoder.  Expected values come from the CPU
+"""The receiving side of the stream path on the device: mh_interleave_packed, mh_decode_packed (every packed-output
+decoder instance, kernel_cells.PACKED_DECODER_CELLS) and stream.StreamDecoder.  Expected values come from the CPU
 oracle (streams, decodes) or from plain torch / NumPy ops (bit packing, clipping), never from the kernels under test."""
 import ctypes as ct
 
@@ -11,7 +11,6 @@ import oracle
 from tests import helpers
 from tests import kernel_cells as kc
 from tests.test_gpu_parity import _bitpack
-from tests.test_host_stream_decode import PACKED_CELLS
 
 pytestmark = pytest.mark.gpu
 
@@ -194,23 +193,23 @@ def test_interleave_packed_inverts_the_deinterleaver_above_the_store_switch(mh):
 
 # ---- 2. mh_decode_packed, every instance ----------------------------------------------------------------------------
 def _cell_id(c):
-    return c.symbol.replace("mh::", "").replace(" ", "")
+    return c.key.replace("mh::", "").replace(" ", "")
 
 
-@pytest.mark.parametrize("cell", PACKED_CELLS, ids=_cell_id)
+@pytest.mark.parametrize("cell", kc.PACKED_DECODER_CELLS, ids=_cell_id)
 def test_decode_packed_cell_against_the_oracle(mh, cell):
     import zlib
-    rng = np.random.RandomState(zlib.crc32(cell.symbol.encode()) & 0x7FFFFFFF)
+    rng = np.random.RandomState(zlib.crc32(cell.key.encode()) & 0x7FFFFFFF)
     for ci, k in enumerate(cell.cases):
         for li, (lens, sc) in enumerate(cell.layouts):
             blocked = (li + ci) % 2 == 1
             pattern = "long" if li % 2 == 0 else "poisson"
             chans, oe, _p = _stream_case(rng, k.S, k.rows, list(lens), sc, pattern, mode=(li % 2))
-            off, stride, size = _layout(lens, cell.po, blocked)
+            off, stride, size = _layout(lens, cell.input_bits, blocked)
             plan = mh.codec.Plan(off, np.asarray(lens, np.uint64), k.S, 6, li % 2, mh.WIN_FULL, np.asarray(k.rows, np.uint8),
-                                 seg_chunks=sc, input_bits=cell.po, chunk_stride=stride)
+                                 seg_chunks=sc, input_bits=cell.input_bits, chunk_stride=stride)
             assert plan.n_segments == len(oe["seg_words"])
-            want, _mask = _expected_pieces(chans, k.S, cell.po, off, stride, size)
+            want, _mask = _expected_pieces(chans, k.S, cell.input_bits, off, stride, size)
             tag = (cell.symbol, k.S, lens, sc, blocked, pattern)
             # the slotted stream (plan_slots) and the same stream compacted (dense seg_off)
             pay_d, off_d = _dense(oe)
