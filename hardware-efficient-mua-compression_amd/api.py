@@ -43,9 +43,24 @@ def compress(channels, S=3, hist_bits=6, approx=True, sclv_rows=None, path=None)
     return c
 
 
-def decompress(c_or_path, channels=None):
+def decompress(c_or_path, channels=None, start=None, stop=None):
     """-> list of uint8 arrays: min(x, S-1) after the calibration window, zeros before it.
-    channels: optional list of channel indices to decode (random access through the directory)."""
+    channels: optional list of channel indices to decode (random access through the directory).
+    start / stop (either given): only samples [start, stop) of each channel (defaults 0 and the longest channel's
+    length), zero past a channel's end; a path is then opened with container_io.open, so only the header, the
+    directory and the payload of the segments that overlap the range are read."""
     from . import container_io
-    c = container_io.load(c_or_path) if isinstance(c_or_path, (str, bytes)) or hasattr(c_or_path, "__fspath__") else c_or_path
-    return container_io.decompress(c, channels=channels).to_channels()
+    is_path = isinstance(c_or_path, (str, bytes)) or hasattr(c_or_path, "__fspath__")
+    if start is None and stop is None:
+        c = container_io.load(c_or_path) if is_path else c_or_path
+        return container_io.decompress(c, channels=channels).to_channels()
+
+    def rows(src):
+        lo = 0 if start is None else int(start)
+        hi = int(np.max(src.ch_len)) if stop is None else int(stop)
+        host = container_io.decompress_range(src, lo, hi, channels=channels).cpu().numpy()
+        return [r.copy() for r in host]
+    if is_path:
+        with container_io.open(c_or_path) as f:
+            return rows(f)
+    return rows(c_or_path)

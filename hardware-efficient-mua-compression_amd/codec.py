@@ -188,6 +188,37 @@ class Plan:
                                                _ptr(enc.peak), _ptr(enc.enc), _ptr(out), _stream()))
         return out
 
+    def decode_range(self, payload, seg_off, peak, enc, sel, start, stop, out=None):
+        """Random access in time (mh_decode_range): samples [start, stop) of the channels `sel` (indices, output rows in
+        that order, repeats allowed; None = all) -> uint8 [len(sel), stop - start], row i = min(x, S-1) of channel sel[i]
+        inside its window and 0 outside it and past its length.  payload: int32 words; seg_off: int64 [n_segments], where
+        each segment starts in payload (only the entries of segments that overlap the range are read); peak / enc: uint8
+        [C].  out: optional uint8 [len(sel), stop - start] tensor with unit stride along time (any row stride); without
+        it the rows are placed so that sample t sits at a byte address congruent to t mod 128 (the decoder's interior row
+        stores are then as aligned as mh_decode's) and a strided view is returned.  Not capturable into a graph: the work
+        list is built on the host and uploaded (the call synchronises the current stream first)."""
+        start, stop = int(start), int(stop)
+        max_len = int(self.ch_len.max()) if self.ch_len.size else 0
+        if not (0 <= start <= stop <= max_len):
+            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
+        sel = np.arange(self.C, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
+        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
+            raise IndexError("channel index out of range")
+        sel32 = np.ascontiguousarray(sel, dtype=np.uint32)
+        n, rows = stop - start, int(sel.size)
+        if out is None:
+            phase = start % 128
+            pitch = (n + phase + 127) // 128 * 128
+            buf = torch.empty(max(rows * pitch, 1), dtype=torch.uint8, device=self.device)
+            out = buf.as_strided((rows, n), (pitch, 1), phase)
+        elif tuple(out.shape) != (rows, n) or out.dtype != torch.uint8 or (n > 1 and rows and out.stride(1) != 1):
+            raise ValueError("out must be a uint8 [%d, %d] tensor with unit stride along time" % (rows, n))
+        pitch = out.stride(0) if rows > 1 else n
+        _lib.check(_lib.lib().mh_decode_range(self._h, _ptr(payload), payload.numel(), _ptr(seg_off),
+                                              sel32.ctypes.data if rows else None, rows, start, stop, _ptr(peak),
+                                              _ptr(enc), _ptr(out) if rows and n else None, pitch, _stream()))
+        return out
+
     def decode_ok(self):
         """True when every decode() on this plan since the previous decode_ok() (direct calls and graph
         replays alike) stayed inside its payload; reading clears the flag (synchronises)."""

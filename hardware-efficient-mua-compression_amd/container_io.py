@@ -15,6 +15,7 @@ Per channel the stream only needs (peak, enc) -- the 3+2-bit RAM word of the ref
 closed form of the calibration peak.  `payload` is the dense concatenation of all segments in
 directory order (mh_compact); segment s starts at word sum(seg_words[:s]).
 """
+import builtins
 import io
 import json
 import struct
@@ -93,12 +94,12 @@ def read(f):
 
 
 def save(path, c):
-    with open(path, "wb") as f:
+    with builtins.open(path, "wb") as f:
         write(f, c)
 
 
 def load(path):
-    with open(path, "rb") as f:
+    with builtins.open(path, "rb") as f:
         return read(f)
 
 
@@ -170,17 +171,9 @@ def window_lengths(ch_len, h, window):
     raise ValueError("unknown window rule %r" % (window,))
 
 
-def validate(c):
-    """Structural check of a container before it goes to the GPU.  The header fields are range-
-    checked here; the walk over every chunk header of every segment -- header sizes, sub-stream
-    lengths possible for the channel's code, chunk sizes adding up exactly to the directory and the
-    payload -- is mh_validate_stream (host-only C, no GPU needed).  mh_decode itself never reads
-    outside the payload it is given, so this check is about detecting corruption, not about
-    memory safety.  Raises ValueError."""
-    import ctypes as ct
-
+def _header_fields(hd):
+    """The range checks of validate() on a container header -> (S, K, h, window, seg_chunks, mode, sclv [K, S])."""
     from . import _lib
-    hd = c.header
     try:
         S, K, h, window, seg_chunks, mode = (int(hd[k]) for k in ("S", "K", "h", "window", "seg_chunks", "mode"))
         sclv = np.ascontiguousarray(np.array(hd["sclv"], np.int64).reshape(K, S))
@@ -192,6 +185,21 @@ def validate(c):
         raise ValueError("container header: S / K / code lengths out of range")
     if not (0 <= h <= 30) or not (0 <= window <= 3) or not (0 <= mode <= 1) or not (1 <= seg_chunks <= 0xFFFFFFFF // (_lib.PIECE * _lib.LANES * _lib.ROWS)):
         raise ValueError("container header: h / window / mode / seg_chunks out of range")
+    return S, K, h, window, seg_chunks, mode, sclv
+
+
+def validate(c):
+    """Structural check of a container before it goes to the GPU.  The header fields are range-
+    checked here; the walk over every chunk header of every segment -- header sizes, sub-stream
+    lengths possible for the channel's code, chunk sizes adding up exactly to the directory and the
+    payload -- is mh_validate_stream (host-only C, no GPU needed).  mh_decode itself never reads
+    outside the payload it is given, so this check is about detecting corruption, not about
+    memory safety.  Raises ValueError."""
+    import ctypes as ct
+
+    from . import _lib
+    hd = c.header
+    S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
     C = len(c.ch_len)
     if not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
         raise ValueError("container arrays disagree about the channel count")
@@ -266,3 +274,229 @@ def decompress(c, device="cuda", channels=None, check=True):
     if not ok:
         raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
     return cs
+
+
+# ---- random access in time -----------------------------------------------------------------------
+class ContainerFile:
+    """A container on disk with its payload left there: open() reads the magic, the header and the per-channel and
+    directory arrays, and remembers where the payload starts.  Same fields as `Compressed` but `payload`;
+    read_words() fetches a run of payload words (seek + readinto).  `bytes_read` counts every byte read from the file,
+    so that "a range query reads only what it needs" can be checked.  Caches one decode plan of the container's layout
+    (decompress_range)."""
+
+    def __init__(self, path):
+        self.path = str(path)
+        self.bytes_read = 0
+        self._plan = None
+        self._f = builtins.open(self.path, "rb")
+        try:
+            self._read_head()
+        except Exception:
+            self._f.close()
+            raise
+
+    def _read(self, n):
+        b = self._f.read(n)
+        self.bytes_read += len(b)
+        return b
+
+    def _read_head(self):
+        if self._read(8) != MAGIC:
+            raise ValueError("not a MUAHUFF1 container")
+        (n,) = struct.unpack("<I", self._read(4))
+        hdr = json.loads(self._read(n).decode())
+        if hdr.get("format_revision") not in READ_REVISIONS:
+            raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
+        pos = 12 + n
+        for name, dt in (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skipped", np.uint8),
+                         ("ch_bits", np.uint64), ("seg_words", np.uint64)):
+            nbytes = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
+            raw = self._read(nbytes)
+            if len(raw) != nbytes:
+                raise ValueError("truncated container (%s)" % name)
+            pos += nbytes + (-nbytes % 8)
+            self._f.seek(pos)
+            setattr(self, name, np.frombuffer(raw, dtype=dt).copy())
+        self.header = hdr
+        self.payload_offset = pos                      # file offset of payload word 0
+        self.payload_words = int(hdr["sizes"]["payload"])
+        self.head_bytes = self.bytes_read              # what open() read
+
+    def read_words(self, first, n):
+        """payload words [first, first + n) as uint32 (ValueError past the end of the file)"""
+        out = np.empty(int(n), dtype=np.uint32)
+        if n:
+            self._f.seek(self.payload_offset + 4 * int(first))
+            got = self._f.readinto(memoryview(out).cast("B"))
+            self.bytes_read += got
+            if got != out.nbytes:
+                raise ValueError("truncated container (payload)")
+        return out
+
+    def plan(self):
+        """The cached decode plan of this container's layout (created on first use, on the current device)."""
+        if self._plan is None:
+            self._plan = _range_plan(self)
+        return self._plan
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+
+def open(path):  # noqa: A001  (shadows the builtin in this module only: save / load use builtins.open)
+    """-> ContainerFile: header and directory read, payload left on disk."""
+    return ContainerFile(path)
+
+
+def _range_plan(c):
+    from . import codec
+    hd = c.header
+    return codec.Plan(np.zeros(len(c.ch_len), np.uint64), c.ch_len, hd["S"], hd["h"], hd["mode"], plan_window(hd),
+                      np.array(hd["sclv"], np.uint8), seg_chunks=hd["seg_chunks"])
+
+
+def window_bounds(ch_len, h, window):
+    """(w0, w1): the encoded window [w0, w1) of each channel, in channel samples (include/muahuff.h)."""
+    from . import WIN_FULL
+    T = np.asarray(ch_len, dtype=np.int64)
+    n = window_lengths(T, h, window)
+    w0 = np.zeros_like(T) if window == WIN_FULL else np.minimum(np.int64(1) << int(h), T)
+    return w0, w0 + n
+
+
+def range_segments(ch_len, h, window, seg_chunks, start, stop, revision=FORMAT_REVISION):
+    """Directory entries that hold samples [start, stop) of each channel, by arithmetic on the layout: int64 arrays
+    (first, end) -- channel c's overlapping segments are entries first[c] .. end[c] - 1 (first == end: none, the range
+    misses the channel's window).  A channel's segments are consecutive in the directory and in the payload."""
+    from . import CHUNK
+    T = np.asarray(ch_len, dtype=np.int64)
+    w0, w1 = window_bounds(T, h, window)
+    nseg = segments_per_channel(T, h, window, seg_chunks, revision)
+    base = np.concatenate([[0], np.cumsum(nseg)[:-1]]).astype(np.int64) if T.size else np.zeros(0, np.int64)
+    seg = int(seg_chunks) * CHUNK
+    if int(revision) == 2:
+        head = np.zeros_like(T)
+    else:
+        head = np.where((w1 - w0 >= 16 * CHUNK) & (w0 % 128 != 0), 128 - w0 % 128, 0)
+    a = np.maximum(int(start), w0) - w0                # window samples [a, b)
+    b = np.minimum(int(stop), w1) - w0
+    hit = a < b
+
+    def index(r):  # segment of window sample r within its channel
+        return np.where(head > 0, np.where(r < head, 0, 1 + (r - head) // seg), r // seg)
+    first = np.where(hit, base + index(np.maximum(a, 0)), base)
+    end = np.where(hit, base + index(np.maximum(b - 1, 0)) + 1, base)
+    return first, end
+
+
+def gather_range(src, start, stop, sel):
+    """The payload a range query reads: for each distinct channel of `sel`, the one contiguous run of stored words of
+    its segments that overlap [start, stop) (slices of a `Compressed`, seek + readinto for a `ContainerFile`), back to
+    back.  -> (payload uint32, seg_off uint64 [n_segments]: where each of those segments starts in it -- 0 for the
+    others --, seg_idx uint64: their directory entries)."""
+    hd = src.header
+    h, window, seg_chunks = int(hd["h"]), int(hd["window"]), int(hd["seg_chunks"])
+    rev = int(hd.get("format_revision", FORMAT_REVISION))
+    first, end = range_segments(src.ch_len, h, window, seg_chunks, start, stop, rev)
+    seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
+    dense = np.concatenate([[0], np.cumsum(seg_words)]).astype(np.int64)  # segment -> first word in the stored payload
+    stored_words = int(src.payload_words if isinstance(src, ContainerFile) else src.payload.size)
+    # one contiguous run of payload words per selected channel (once per channel, whatever the repeats)
+    runs, seg_off, idx, base = [], np.zeros(max(len(seg_words), 1), np.uint64), [], 0
+    for c in np.unique(sel):
+        s0, s1 = int(first[c]), int(end[c])
+        if s0 == s1:
+            continue
+        w0_, w1_ = int(dense[s0]), int(dense[s1])
+        if w1_ > stored_words:
+            raise ValueError("corrupt container: the directory points past the payload")
+        runs.append(src.read_words(w0_, w1_ - w0_) if isinstance(src, ContainerFile) else src.payload[w0_:w1_])
+        seg_off[s0:s1] = base + (dense[s0:s1] - w0_)
+        idx.append(np.arange(s0, s1, dtype=np.uint64))
+        base += w1_ - w0_
+    payload = np.ascontiguousarray(np.concatenate(runs) if runs else np.zeros(0, np.uint32), np.uint32)
+    segs = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0, np.uint64))
+    return payload, seg_off, segs
+
+
+def decompress_range(src, start, stop, channels=None, device="cuda", check=True, time_major=False):
+    """Samples [start, stop) of the selected channels of a `Compressed` or a `ContainerFile` (open()), reading and
+    decoding only the segments that overlap the range.  -> uint8 device tensor [n_sel, stop - start] (row i = channel
+    channels[i]: min(x, S-1) inside the channel's encoded window, 0 outside it and past its length -- exactly
+    decompress(src, channels).to_channels()[i][start:stop], zero-extended), or [stop - start, n_sel] with
+    time_major=True.  channels: None = all, else indices (rows in that order, repeats allowed).  check=True validates the
+    header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU; a decode that
+    had to abandon a segment raises ValueError as decompress() does."""
+    import ctypes as ct
+
+    import torch
+
+    from . import _lib
+    from .codec import _ptr, _stream
+    hd = src.header
+    S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
+    rev = int(hd.get("format_revision", FORMAT_REVISION))
+    ch_len = np.ascontiguousarray(src.ch_len, np.uint64)
+    C = len(ch_len)
+    max_len = int(ch_len.max()) if C else 0
+    start, stop = int(start), int(stop)
+    if not (0 <= start <= stop <= max_len):
+        raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
+    sel = np.arange(C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
+    if sel.size and (sel.min() < 0 or sel.max() >= C):
+        raise IndexError("channel index out of range")
+    nseg_ch = segments_per_channel(ch_len, h, window, seg_chunks, rev)
+    if int(nseg_ch.sum()) != len(src.seg_words):
+        raise ValueError("container directory does not match its header")
+    if C and int(ch_len.min()) == 0:
+        raise ValueError("container holds an empty channel")
+    n, rows = stop - start, int(sel.size)
+    if rows == 0 or n == 0:
+        z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
+        return z.t().contiguous() if time_major else z
+    payload, seg_off, segs = gather_range(src, start, stop, sel)
+    peak, enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
+    if check:
+        if not (len(peak) == len(enc) == C):
+            raise ValueError("container arrays disagree about the channel count")
+        rows_ = np.ascontiguousarray(sclv, np.uint8)
+        seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
+        rc = _lib.lib().mh_validate_segments(ch_len.ctypes.data, C, S, h, mode, plan_window(hd), rows_.ctypes.data, K,
+                                             seg_chunks, payload.ctypes.data if payload.size else None, payload.size,
+                                             seg_off.ctypes.data, seg_words.ctypes.data if seg_words.size else seg_off.ctypes.data,
+                                             len(seg_words), segs.ctypes.data if segs.size else None, segs.size,
+                                             peak.ctypes.data, enc.ctypes.data)
+        if rc != 0:
+            raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
+    own = not isinstance(src, ContainerFile)
+    plan = _range_plan(src) if own else src.plan()
+    try:
+        dev = plan.device
+        pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=dev)
+        if payload.size:
+            pay[:payload.size] = torch.from_numpy(payload.view(np.int32)).to(dev)
+        d_off = torch.from_numpy(seg_off.view(np.int64)).to(dev)
+        d_peak, d_enc = torch.from_numpy(peak.copy()).to(dev), torch.from_numpy(enc.copy()).to(dev)
+        out = plan.decode_range(pay, d_off, d_peak, d_enc, sel, start, stop)
+        ok = plan.decode_ok()  # synchronises
+    finally:
+        if own:
+            plan.close()
+    if not ok:
+        raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
+    if not time_major:
+        return out
+    tm = torch.empty((n, rows), dtype=torch.uint8, device=out.device)
+    in_off = torch.arange(rows, dtype=torch.int64, device=out.device) * (out.stride(0) if rows > 1 else 0)
+    _lib.check(_lib.lib().mh_interleave(_ptr(out), _ptr(in_off), n, rows, _ptr(tm), _stream()))
+    return tm

@@ -1035,7 +1035,7 @@ __device__ __forceinline__ ChunkHdr scan_header(uint32_t hw32, int lane)
 // PO: output packing.  0 = one byte per symbol (mh_decode); 2 / 4 = packed pieces (mh_decode_packed): the tables hold
 // their symbols already packed (build_decode_tables), a row is assembled with shifts and ORs into the lane's 4- / 8-byte
 // piece and leaves in one global store (ST is not used); the cut piece of a partial chunk is written whole, zero-padded.
-template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0, int PO = 0>
+template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0, int PO = 0, int TAG = 0>
 __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *tabw, uint32_t tbase, uint32_t maskW,
                                                     const uint8_t *tab1, uint32_t mask1,
                                                     const uint32_t *stage, uint8_t *__restrict__ out,
@@ -1282,7 +1282,7 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
 // reads of this chunk's own words), the whole payload copied to LDS in one batch of loads, then
 // decode_staged_chunk<PARTIAL>.  A chunk too large for the staging area takes the per-symbol
 // routine on global memory.
-template <int K, int M, int RL, bool HY, int PO = 0>
+template <int K, int M, int RL, bool HY, int PO = 0, int TAG = 0>
 __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict__ in, uint32_t m, const uint32_t *tabw,
                                                   uint32_t tbase, uint32_t maskW, const uint8_t *tab1, uint32_t mask1,
                                                   uint32_t *stage, uint32_t cap_words, uint8_t *__restrict__ out,
@@ -1326,7 +1326,7 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    decode_staged_chunk<K, M, RL, HY, true, 0, PO>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m);
+    decode_staged_chunk<K, M, RL, HY, true, 0, PO, TAG>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m);
 }
 
 // One segment, one wave: the chunks of segment `seg` through the wave's tables (`tab` multi-symbol
@@ -1348,7 +1348,10 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
 // by chunk through decode_chunk (adversarial data only).
 // PO != 0 (packed output): `out` is the segment's first piece and chunk c starts at out + c * cstride (the plan's
 // chunk_stride, or 1024 pieces when they are contiguous); PO = 0 ignores cstride (chunks are kChunk bytes apart).
-template <int K, int M, int NR, int RL, bool HY, bool WT = false, int PO = 0>
+// TAG (also of decode_staged_chunk / decode_partial_chunk) changes nothing in the code: a caller outside the codec
+// kernels (k_decode_range) passes its own, so that the lambdas of these templates are instances of its own -- a lambda
+// shared with a second kernel loses its single-call-site inlining bonus and changes the first kernel's code.
+template <int K, int M, int NR, int RL, bool HY, bool WT = false, int PO = 0, int TAG = 0>
 __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,
                                                uint32_t mask1, uint32_t *stage, int lane, size_t cstride = 0)
@@ -1435,7 +1438,7 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
                 // flight before this chunk's stores
                 fetch(pay_n, avail_n);
                 hw_next = peek(pay_n, nx.nw, peek_n);
-                decode_staged_chunk<K, M, RL, HY, false, kSt, PO>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * cs, lane);
+                decode_staged_chunk<K, M, RL, HY, false, kSt, PO, TAG>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * cs, lane);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 ++c;
@@ -1476,7 +1479,7 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
         pos += h.hw + h.nw;
     }
     if (rem)
-        decode_partial_chunk<K, M, RL, HY, PO>(in, rem, tab, tbase, maskW, tab1, mask1, stage, kCap, out + (size_t)nfull * cs,
+        decode_partial_chunk<K, M, RL, HY, PO, TAG>(in, rem, tab, tbase, maskW, tab1, mask1, stage, kCap, out + (size_t)nfull * cs,
                                             lane, pos < lim ? lim - pos : 0, d.err, d.epoch);
 #undef MH_DEC_BAIL
 }

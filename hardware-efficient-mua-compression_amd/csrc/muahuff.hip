@@ -3,6 +3,7 @@
 // There is no CPU fallback anywhere in this library.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 #include "mh_codec2.hpp"
 #include "mh_layout.hpp"
 #include "mh_planner.hpp"
+#include "mh_range.hpp"
 // The library is built with -fvisibility=hidden: the C ABI of include/muahuff.h is ALL it exports
 // (tests/test_host.py compares the dynamic symbol table with the header's prototypes).
 #pragma GCC visibility push(default)
@@ -87,6 +89,17 @@ struct mh_plan {
     unsigned long long *d_calhist = nullptr;
     unsigned long long *d_acc = nullptr;  // wave-task encoder: per-channel {bits << 24 | finished records} (zero between launches)
     uint32_t *d_err = nullptr;  // decode status word (mh_decode_status): non-zero once a decode abandoned a segment
+    // mh_decode_range: the work list of the last call (host copy kept alive until the next call has synchronised),
+    // its device copy, the 16-KiB scratch slots of cut chunks, and each channel's first directory entry
+    std::vector<uint8_t> range_host;
+    uint8_t *d_range = nullptr, *d_range_scr = nullptr;
+    size_t range_cap = 0, range_scr_cap = 0;
+    // the query that work list answers (sel, t0, t1, out_pitch): the same query again reuses it as it is on the device
+    std::vector<uint32_t> range_sel;
+    uint64_t range_t0 = 0, range_t1 = 0, range_pitch = 0;
+    size_t range_b_task = 0, range_b_wg = 0, range_nwg = 0, range_nfill = 0;
+    uint64_t range_max_fill = 0;
+    std::vector<uint64_t> ch_seg0;
 };
 
 struct mh_sweep {
@@ -257,6 +270,19 @@ static int launch_decode2w(const mh::Dec2Args &a, hipStream_t st)
     return MH_OK;
 }
 
+// range decode (mh_decode_range): the workgroup form with shared tables, LDS as launch_decode2 requests it
+template <int K, int M, int NR, int RL, bool HY>
+static int launch_decode_range(const mh::RangeArgs &r, uint32_t nwg, hipStream_t st)
+{
+    size_t lds = ((size_t)mh::dec2_shared_dwords(r.a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
+    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;  // (see launch_decode2)
+    auto kern = mh::k_decode_range<K, M, NR, RL, HY>;
+    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, true);
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, r);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
 // lane-private LDS staging of the encoder: 16 dwords per lane for codes of at most 2 bits (the worst case of a
 // 256-sample sub-stream), else 32 (= 4 bits per sample on average: the worst case up to 4-bit codes; a clipped
 // spike-count channel at S <= 10 stays well below that, and chunks that outgrow it take the two-pass global slow
@@ -346,6 +372,21 @@ static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t 
     return launch_decode<2, 2, 25, 2, false, PO>(p, a, st);
 }
 
+// The range decoder on the rung dispatch_decode picks for the plan's maxlen L and table width W, always in the workgroup
+// form (a long range on long channels is the case that matters; the wave-task one-symbol rung has no workgroup form, its
+// plans take the hybrid pair table as long-channel plans do).  Instances: k_decode_range<4, 4, 17, 1, false> (L <= 2),
+// <2, 2, 25, 2, false> (L == 3), <2, 2, 32, 0, false> (W >= 2L), <2, 2, 31, 2, true> (W < 2L).
+static int dispatch_decode_range(const mh_plan *p, const mh::RangeArgs &r, uint32_t nwg, hipStream_t st)
+{
+    const uint32_t L = p->h.info.maxlen;
+    if (L <= 2) return launch_decode_range<4, 4, 17, 1, false>(r, nwg, st);
+    if (L != 3) {
+        if (r.a.W >= 2 * L) return launch_decode_range<2, 2, 32, 0, false>(r, nwg, st);
+        return launch_decode_range<2, 2, 31, 2, true>(r, nwg, st);
+    }
+    return launch_decode_range<2, 2, 25, 2, false>(r, nwg, st);
+}
+
 static int dispatch_decode(const mh_plan *p, uint32_t po, const mh::Dec2Args &a, hipStream_t st)
 {
     if (po == 2) return dispatch_decode<2>(p, a, st);
@@ -365,6 +406,11 @@ static int prepare_kernels(const mh_plan *p)
     if (rc == MH_OK) rc = dispatch_decode(p, 0, d, nullptr);
     if (rc == MH_OK && p->h.input_bits == packed_out_bits(p->h.info.S))  // a plan mh_decode_packed accepts
         rc = dispatch_decode(p, p->h.input_bits, d, nullptr);
+    if (rc == MH_OK && p->h.input_bits == 8) {  // a plan mh_decode_range accepts
+        mh::RangeArgs r{};
+        r.a = d;
+        rc = dispatch_decode_range(p, r, 0, nullptr);
+    }
     g_prepare_only = false;
     return rc;
 }
@@ -418,7 +464,8 @@ int mh_plan_destroy(mh_plan *p)
                     p->d_seg_ch, p->d_seg_first, p->d_seg_n, p->d_seg_off, p->d_tile_ch,
                     p->d_tile_n, p->d_tile_start, p->d_hist, p->d_peak, p->d_enc,
                     p->d_lut, p->d_wg_tasks, p->d_wave_tasks, p->d_scan,
-                    p->d_cal_tile_ch, p->d_cal_tile_n, p->d_cal_tile_start, p->d_calhist, p->d_err, p->d_acc};
+                    p->d_cal_tile_ch, p->d_cal_tile_n, p->d_cal_tile_start, p->d_calhist, p->d_err, p->d_acc,
+                    p->d_range, p->d_range_scr};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     delete p;
@@ -804,6 +851,186 @@ int mh_decode_status(mh_plan *p, uint32_t *flags, void *stream)
     return MH_OK;
 }
 
+// mh_decode_range's work list for (sel, t0, t1, out_pitch), built from the host directory and uploaded to the plan's
+// buffers (arguments already checked).  Synchronises `st` first: the previous range decode may still read them.
+static int range_work_list(mh_plan *p, const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint64_t out_pitch,
+                           hipStream_t st)
+{
+    const mh::PlanHost &H = p->h;
+    const uint32_t C = H.info.C;
+    const uint64_t len = t1 - t0;
+    p->range_sel.clear();  // (no valid list while this one is being built)
+    if (p->ch_seg0.empty()) {  // each channel's first directory entry (its segments are consecutive)
+        p->ch_seg0.assign((size_t)C + 1, 0);
+        for (uint32_t c : H.seg_ch) ++p->ch_seg0[(size_t)c + 1];
+        for (uint32_t c = 0; c < C; ++c) p->ch_seg0[(size_t)c + 1] += p->ch_seg0[c];
+    }
+    // ---- the work list, from the host directory
+    std::vector<mh::RangeTask> tasks;
+    std::vector<mh::RangeWg> wgs;
+    std::vector<mh::RangeFill> fills;
+    uint32_t nscr = 0;
+    uint64_t max_fill = 0;
+    auto fill = [&](uint64_t off, uint64_t n) {
+        fills.push_back(mh::RangeFill{off, n});
+        if (n > max_fill) max_fill = n;
+    };
+    for (uint32_t i = 0; i < n_sel; ++i) {
+        const uint32_t c = sel[i];
+        const uint64_t row = (uint64_t)i * out_pitch, w0 = H.w0[c], w1 = H.w1[c];
+        const uint64_t a = t0 > w0 ? t0 : w0, b = t1 < w1 ? t1 : w1;  // in-window part, channel samples
+        if (a >= b) {
+            fill(row, len);
+            continue;
+        }
+        if (a > t0) fill(row, a - t0);
+        if (b < t1) fill(row + (b - t0), t1 - b);
+        const uint64_t ra = a - w0, rb = b - w0;  // the same, window samples
+        const uint64_t *sf0 = H.seg_first.data();
+        uint64_t s = (uint64_t)(std::upper_bound(sf0 + p->ch_seg0[c], sf0 + p->ch_seg0[(size_t)c + 1], ra) - sf0) - 1;
+        const size_t task0 = tasks.size();
+        for (; s < p->ch_seg0[(size_t)c + 1] && H.seg_first[s] < rb; ++s) {
+            const uint64_t sf = H.seg_first[s], sn = H.seg_n[s];
+            const uint64_t lo = (ra > sf ? ra : sf) - sf, hi = (rb < sf + sn ? rb : sf + sn) - sf;
+            const uint64_t c0 = lo / MH_CHUNK, c1 = (hi - 1) / MH_CHUNK, base = c0 * MH_CHUNK;
+            mh::RangeTask t{};
+            t.dst = (int64_t)(row + w0 + sf + base) - (int64_t)t0;
+            t.seg = (uint32_t)s;
+            t.skip = (uint32_t)c0;
+            t.ncnk = (uint32_t)(c1 - c0 + 1);
+            t.n = (uint32_t)(sn - base < (uint64_t)t.ncnk * MH_CHUNK ? sn - base : (uint64_t)t.ncnk * MH_CHUNK);
+            t.lo = (uint32_t)(lo - base);
+            t.hi = (uint32_t)(hi - base);
+            t.scr = t.lo > 0 || t.hi < t.n ? nscr++ : 0u;
+            tasks.push_back(t);
+        }
+        for (size_t k = task0; k < tasks.size(); k += 4)
+            wgs.push_back(mh::RangeWg{(uint32_t)k, (uint32_t)(tasks.size() - k < 4 ? tasks.size() - k : 4), c, 0u});
+    }
+    // ---- upload (one copy)
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t b_task = up16(tasks.size() * sizeof(mh::RangeTask)), b_wg = up16(wgs.size() * sizeof(mh::RangeWg));
+    const size_t bytes = b_task + b_wg + fills.size() * sizeof(mh::RangeFill);
+    // the previous call's kernels may still read the task buffer and the scratch (one stream at a time per plan)
+    MH_HIP(hipStreamSynchronize(st));
+    if (bytes > p->range_cap) {
+        if (p->d_range) MH_HIP(hipFree(p->d_range));
+        p->d_range = nullptr;
+        p->range_cap = 0;
+        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_range), bytes));
+        p->range_cap = bytes;
+    }
+    const size_t scr_bytes = (size_t)(nscr ? nscr : 1) * MH_CHUNK;
+    if (scr_bytes > p->range_scr_cap) {
+        if (p->d_range_scr) MH_HIP(hipFree(p->d_range_scr));
+        p->d_range_scr = nullptr;
+        p->range_scr_cap = 0;
+        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_range_scr), scr_bytes));
+        p->range_scr_cap = scr_bytes;
+    }
+    p->range_host.assign(bytes, 0);
+    if (!tasks.empty()) memcpy(p->range_host.data(), tasks.data(), tasks.size() * sizeof(mh::RangeTask));
+    if (!wgs.empty()) memcpy(p->range_host.data() + b_task, wgs.data(), wgs.size() * sizeof(mh::RangeWg));
+    if (!fills.empty()) memcpy(p->range_host.data() + b_task + b_wg, fills.data(), fills.size() * sizeof(mh::RangeFill));
+    MH_HIP(hipMemcpyAsync(p->d_range, p->range_host.data(), bytes, hipMemcpyHostToDevice, st));
+    p->range_sel.assign(sel, sel + n_sel);
+    p->range_t0 = t0;
+    p->range_t1 = t1;
+    p->range_pitch = out_pitch;
+    p->range_b_task = b_task;
+    p->range_b_wg = b_wg;
+    p->range_nwg = wgs.size();
+    p->range_nfill = fills.size();
+    p->range_max_fill = max_fill;
+    return MH_OK;
+}
+
+int mh_decode_range(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                    const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, const uint8_t *peak, const uint8_t *enc,
+                    uint8_t *out, uint64_t out_pitch, void *stream)
+{
+    if (!p || (n_sel && !sel)) return fail(MH_ERR_ARG, "mh_decode_range: NULL argument");
+    if (p->h.input_bits != 8)
+        return fail(MH_ERR_ARG, "mh_decode_range: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
+    if (t0 > t1 || t1 > p->h.max_T)
+        return fail(MH_ERR_ARG, "mh_decode_range: [%llu, %llu) is not a range inside [0, %llu)", (unsigned long long)t0,
+                    (unsigned long long)t1, (unsigned long long)p->h.max_T);
+    const mh::PlanHost &H = p->h;
+    const uint32_t C = H.info.C;
+    for (uint32_t i = 0; i < n_sel; ++i)
+        if (sel[i] >= C) return fail(MH_ERR_ARG, "mh_decode_range: sel[%u] = %u, the plan has %u channels", i, sel[i], C);
+    const uint64_t len = t1 - t0;
+    if (n_sel > 1 && out_pitch < len)
+        return fail(MH_ERR_ARG, "mh_decode_range: out_pitch %llu below the row length %llu", (unsigned long long)out_pitch,
+                    (unsigned long long)len);
+    if (n_sel == 0 || len == 0) return MH_OK;
+    if (!payload || !seg_off || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_range: NULL argument");
+    int rc = check_device(p->device, "mh_decode_range");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool same = p->d_range && p->range_t0 == t0 && p->range_t1 == t1 && p->range_pitch == out_pitch &&
+                      p->range_sel.size() == n_sel && std::equal(sel, sel + n_sel, p->range_sel.begin());
+    if (!same && (rc = range_work_list(p, sel, n_sel, t0, t1, out_pitch, st))) return rc;
+    const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(p->d_range + p->range_b_task + p->range_b_wg);
+    if (p->range_nfill) {
+        const uint64_t per_block = 256 * 16 * 4;  // 64 KiB per workgroup and pass
+        const uint64_t nb = (p->range_max_fill + per_block - 1) / per_block;
+        const unsigned nx = (unsigned)(nb < 1 ? 1 : nb < 1024 ? nb : 1024);
+        for (size_t f = 0; f < p->range_nfill; f += 65535) {
+            const unsigned ny = (unsigned)(p->range_nfill - f < 65535 ? p->range_nfill - f : 65535);
+            hipLaunchKernelGGL(mh::k_range_fill, dim3(nx, ny), dim3(256), 0, st, out, d_fill + f);
+            MH_HIP(hipGetLastError());
+        }
+    }
+    if (p->range_nwg == 0) return MH_OK;
+    mh::RangeArgs r{};
+    r.a = decode_args(p, payload, payload_words, seg_off, peak, enc, out);
+    r.task = reinterpret_cast<const mh::RangeTask *>(p->d_range);
+    r.wg = reinterpret_cast<const mh::RangeWg *>(p->d_range + p->range_b_task);
+    r.out = out;
+    r.scratch = p->d_range_scr;
+    return dispatch_decode_range(p, r, (uint32_t)p->range_nwg, st);
+}
+
+// The chunk walk of one stored segment s (directory entry of H) whose words are payload[pos, end): header sizes,
+// sub-stream lengths possible for the channel's code (row = its SCLV row), chunk sizes adding up exactly to end.
+static int validate_segment(const mh::PlanHost &H, size_t s, const uint8_t *row, uint32_t S, const uint32_t *payload,
+                            uint64_t pos, uint64_t words)
+{
+    const uint64_t end = pos + words;
+    const uint64_t maxlen = row[S - 1];
+    uint64_t left = H.seg_n[s];
+    while (left) {
+        const uint64_t m = left < MH_CHUNK ? left : MH_CHUNK;
+        if (pos >= end) return fail(MH_ERR_STREAM, "segment %zu is shorter than its chunk headers say", s);
+        const uint32_t w0 = payload[pos];
+        const uint32_t mn = w0 & 0xFFFu, w = (w0 >> 12) & 15u;
+        if (w > 12) return fail(MH_ERR_STREAM, "segment %zu: chunk header field width %u above 12", s, w);
+        const uint64_t hw = (16u + 64u * w + 31u) >> 5;
+        if (pos + hw > end) return fail(MH_ERR_STREAM, "segment %zu: chunk header runs past the segment", s);
+        uint64_t sum = 0, longest = 0;
+        for (uint32_t l = 0; l < 64; ++l) {
+            uint64_t f = 0;
+            if (w) {
+                const uint32_t fb = 16u + l * w;
+                uint64_t v = payload[pos + (fb >> 5)];
+                if ((fb & 31) + w > 32) v |= (uint64_t)payload[pos + (fb >> 5) + 1] << 32;
+                f = (v >> (fb & 31)) & ((1u << w) - 1u);
+            }
+            sum += mn + f;
+            if (mn + f > longest) longest = mn + f;
+        }
+        // every codeword has 1..maxlen bits; a sub-stream holds <= 256 samples
+        if (longest > 256 * maxlen || sum > m * maxlen || sum < m)
+            return fail(MH_ERR_STREAM, "segment %zu: sub-stream lengths impossible for this code", s);
+        pos += hw + ((sum + 31) >> 5);
+        left -= m;
+    }
+    if (pos != end)
+        return fail(MH_ERR_STREAM, "segment %zu: chunk sizes do not add up to its %llu words", s, (unsigned long long)words);
+    return MH_OK;
+}
+
 int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
                        const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, const uint32_t *payload,
                        uint64_t payload_words, const uint64_t *seg_words, uint64_t n_segments,
@@ -828,41 +1055,44 @@ int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t 
         if (end < pos || end > payload_words)
             return fail(MH_ERR_STREAM, "segment %zu ends at word %llu, the payload has %llu", s,
                         (unsigned long long)end, (unsigned long long)payload_words);
-        const uint8_t *row = sclv + (size_t)enc[H.seg_ch[s]] * S;
-        const uint64_t maxlen = row[S - 1];
-        uint64_t left = H.seg_n[s];
-        while (left) {
-            const uint64_t m = left < MH_CHUNK ? left : MH_CHUNK;
-            if (pos >= end) return fail(MH_ERR_STREAM, "segment %zu is shorter than its chunk headers say", s);
-            const uint32_t w0 = payload[pos];
-            const uint32_t mn = w0 & 0xFFFu, w = (w0 >> 12) & 15u;
-            if (w > 12) return fail(MH_ERR_STREAM, "segment %zu: chunk header field width %u above 12", s, w);
-            const uint64_t hw = (16u + 64u * w + 31u) >> 5;
-            if (pos + hw > end) return fail(MH_ERR_STREAM, "segment %zu: chunk header runs past the segment", s);
-            uint64_t sum = 0, longest = 0;
-            for (uint32_t l = 0; l < 64; ++l) {
-                uint64_t f = 0;
-                if (w) {
-                    const uint32_t fb = 16u + l * w;
-                    uint64_t v = payload[pos + (fb >> 5)];
-                    if ((fb & 31) + w > 32) v |= (uint64_t)payload[pos + (fb >> 5) + 1] << 32;
-                    f = (v >> (fb & 31)) & ((1u << w) - 1u);
-                }
-                sum += mn + f;
-                if (mn + f > longest) longest = mn + f;
-            }
-            // every codeword has 1..maxlen bits; a sub-stream holds <= 256 samples
-            if (longest > 256 * maxlen || sum > m * maxlen || sum < m)
-                return fail(MH_ERR_STREAM, "segment %zu: sub-stream lengths impossible for this code", s);
-            pos += hw + ((sum + 31) >> 5);
-            left -= m;
-        }
-        if (pos != end) return fail(MH_ERR_STREAM, "segment %zu: chunk sizes do not add up to its %llu words", s,
-                                    (unsigned long long)seg_words[s]);
+        if (int rc = validate_segment(H, s, sclv + (size_t)enc[H.seg_ch[s]] * S, S, payload, pos, seg_words[s])) return rc;
+        pos = end;
     }
     if (pos != payload_words)
         return fail(MH_ERR_STREAM, "payload has %llu words, the directory accounts for %llu",
                     (unsigned long long)payload_words, (unsigned long long)pos);
+    return MH_OK;
+}
+
+int mh_validate_segments(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
+                         const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, const uint32_t *payload, uint64_t payload_words,
+                         const uint64_t *seg_off, const uint64_t *seg_words, uint64_t n_segments, const uint64_t *seg_idx,
+                         uint64_t n_idx, const uint8_t *peak, const uint8_t *enc)
+{
+    if (!ch_len || !sclv || !seg_off || !seg_words || !peak || !enc || (n_idx && (!payload || !seg_idx)))
+        return fail(MH_ERR_ARG, "mh_validate_segments: NULL argument");
+    if (seg_chunks == 0) return fail(MH_ERR_ARG, "mh_validate_segments: a stored stream names its seg_chunks");
+    mh::PlanHost H;
+    if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &H.info)) return rc;
+    std::vector<uint64_t> off(C, 0);
+    mh::plan_host_build(H, off.data(), ch_len, sclv);
+    if (H.seg_ch.size() != n_segments)
+        return fail(MH_ERR_STREAM, "directory has %llu segments, the layout implies %zu",
+                    (unsigned long long)n_segments, H.seg_ch.size());
+    for (uint64_t j = 0; j < n_idx; ++j) {
+        const uint64_t s = seg_idx[j];
+        if (s >= n_segments)
+            return fail(MH_ERR_ARG, "mh_validate_segments: seg_idx[%llu] = %llu, the directory has %llu entries",
+                        (unsigned long long)j, (unsigned long long)s, (unsigned long long)n_segments);
+        const uint32_t c = H.seg_ch[s];
+        if (peak[c] >= S || enc[c] >= K)
+            return fail(MH_ERR_STREAM, "channel %u: (peak %u, encoder %u) outside (S=%u, K=%u)", c, peak[c], enc[c], S, K);
+        const uint64_t pos = seg_off[s], end = pos + seg_words[s];
+        if (end < pos || end > payload_words)
+            return fail(MH_ERR_STREAM, "segment %llu ends at word %llu, the payload has %llu", (unsigned long long)s,
+                        (unsigned long long)end, (unsigned long long)payload_words);
+        if (int rc = validate_segment(H, (size_t)s, sclv + (size_t)enc[c] * S, S, payload, pos, seg_words[s])) return rc;
+    }
     return MH_OK;
 }
 

@@ -35,7 +35,10 @@ extern "C" {
 #define MH_VERSION 103 /* 0.1.3 ; container format revision 3 (reads revision 2) */
 /* Additions within 0.1.3 (additive: no existing behaviour changes, MH_VERSION stays):
  *   mh_decode_packed     -- decode into the packed 2- / 4-bit pieces of a packed plan (receiving side of the stream path)
- *   mh_interleave_packed -- packed pieces -> time-major bytes, the inverse of mh_deinterleave_packed */
+ *   mh_interleave_packed -- packed pieces -> time-major bytes, the inverse of mh_deinterleave_packed
+ *   mh_decode_range      -- random access in time: samples [t0, t1) of selected channels, reading only the segments
+ *                           that overlap the range
+ *   mh_validate_segments -- mh_validate_stream restricted to listed segments (what a range query reads) */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
@@ -226,6 +229,33 @@ int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t 
                        uint32_t window, const uint8_t *sclv, uint32_t K, uint32_t seg_chunks,
                        const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_words,
                        uint64_t n_segments, const uint8_t *peak, const uint8_t *enc);
+
+/* Random access in time: decode samples [t0, t1) of the channels sel[0..n_sel) (host array; repeats allowed) of a
+ * stream of this plan's layout.  Row i (channel sel[i]) is written at out + i * out_pitch: byte k = min(x[t0 + k], S-1)
+ * inside the channel's window, 0 outside it and at k >= ch_len -- every byte [0, t1 - t0) of every row, and no other byte.
+ * Requires t0 <= t1 <= max(ch_len), sel[i] < C and out_pitch >= t1 - t0 (when n_sel > 1), else MH_ERR_ARG before any
+ * device work.  seg_off (device, n_segments entries): where each segment starts in `payload`; only the entries of
+ * segments that overlap [t0, t1) are read, so `payload` may hold just those segments.  peak / enc: device, the plan's C
+ * entries.  Memory-safe on any stream and reports through mh_decode_status like mh_decode.  A packed plan gets
+ * MH_ERR_ARG.  The work list (one record per overlapping segment) is built on the host from the plan's directory and
+ * uploaded: the call synchronises `stream` first and is NOT capturable into a hipGraph.  The plan keeps that list, and
+ * a call with the same (sel, t0, t1, out_pitch) as the previous one reuses it without synchronising.  Enqueues a zero
+ * fill (when a row reaches outside its window) and one decode launch. */
+int mh_decode_range(mh_plan *plan, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                    const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1,
+                    const uint8_t *peak, const uint8_t *enc, uint8_t *out, uint64_t out_pitch, void *stream);
+
+/* Host-only: mh_validate_stream restricted to the listed segments (seg_idx[0..n_idx), directory indices of the plan
+ * layout rebuilt from ch_len / h / window / seg_chunks, n_segments entries).  Segment s occupies the words
+ * [seg_off[s], seg_off[s] + seg_words[s]) of `payload` (payload_words long); seg_off and seg_words are host arrays of
+ * n_segments entries, of which only the listed ones are read.  Checks the listed segments' chunk headers as
+ * mh_validate_stream does and the (peak, enc) word of their channels; MH_ERR_STREAM + mh_last_error name the first
+ * inconsistency.  Segments that are not listed are not looked at. */
+int mh_validate_segments(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode,
+                         uint32_t window, const uint8_t *sclv, uint32_t K, uint32_t seg_chunks,
+                         const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                         const uint64_t *seg_words, uint64_t n_segments, const uint64_t *seg_idx, uint64_t n_idx,
+                         const uint8_t *peak, const uint8_t *enc);
 
 /* Pack the used words of all segments back to back (directory order) for storage or for
  * the RCCL gather: dense_off[s] = exclusive prefix of seg_words, total_words[0] = sum. */
