@@ -52,6 +52,7 @@ PROTOTYPES = {
     "mh_decode_status": (_int, [_vp, ct.POINTER(_u32), _vp]),
     "mh_validate_stream": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
     "mh_decode_range": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "mh_decode_rebin": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u64, _u64, _u32, _int, _vp, _vp, _vp, _u64, _vp]),
     "mh_validate_segments": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp,
                                     _u64, _vp, _vp]),
     "mh_power_draws": (_int, [_vp, _u32, _vp, _u32, _u64, ct.c_double, ct.c_double, ct.c_double, _vp, _u64, _vp]),

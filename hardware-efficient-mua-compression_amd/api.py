@@ -43,14 +43,31 @@ def compress(channels, S=3, hist_bits=6, approx=True, sclv_rows=None, path=None)
     return c
 
 
-def decompress(c_or_path, channels=None, start=None, stop=None):
+def decompress(c_or_path, channels=None, start=None, stop=None, bin=None):
     """-> list of uint8 arrays: min(x, S-1) after the calibration window, zeros before it.
     channels: optional list of channel indices to decode (random access through the directory).
     start / stop (either given): only samples [start, stop) of each channel (defaults 0 and the longest channel's
     length), zero past a channel's end; a path is then opened with container_io.open, so only the header, the
-    directory and the payload of the segments that overlap the range are read."""
+    directory and the payload of the segments that overlap the range are read.
+    bin=r: the same samples summed in bins of r (uint8, saturating at 255 as rebin_u8), decoded in one pass that never
+    stores the fine samples (container_io.decompress_binned).  Without a range channel i gets its own ceil(T_i / r)
+    bins; with one every row has ceil((stop - start) / r), and start must be a multiple of r."""
     from . import container_io
     is_path = isinstance(c_or_path, (str, bytes)) or hasattr(c_or_path, "__fspath__")
+    if bin is not None:
+        r = int(bin)
+
+        def binned(src):
+            host = container_io.decompress_binned(src, r, 0 if start is None else int(start),
+                                                  None if stop is None else int(stop), channels=channels).cpu().numpy()
+            if start is not None or stop is not None:
+                return [row.copy() for row in host]
+            sel = range(len(src.ch_len)) if channels is None else channels
+            return [row[:(int(src.ch_len[c]) + r - 1) // r].copy() for row, c in zip(host, sel)]
+        if is_path:
+            with container_io.open(c_or_path) as f:
+                return binned(f)
+        return binned(c_or_path)
     if start is None and stop is None:
         c = container_io.load(c_or_path) if is_path else c_or_path
         return container_io.decompress(c, channels=channels).to_channels()

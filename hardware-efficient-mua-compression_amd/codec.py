@@ -219,6 +219,36 @@ class Plan:
                                               _ptr(enc), _ptr(out) if rows and n else None, pitch, _stream()))
         return out
 
+    def decode_rebin(self, payload, seg_off, peak, enc, sel, start, stop, r, saturate=True, out=None):
+        """Decode straight to a coarser bin period (mh_decode_rebin): row i of decode_range(..., sel, start, stop) summed in
+        bins of r samples, without the byte-per-sample rows ever being stored.  -> [len(sel), ceil((stop - start) / r)],
+        uint8 = min(sum, 255) (saturate) or int32 exact sums; the last, partial bin is kept.  start must be a multiple of
+        r, 1 <= r <= 4096.  out: optional tensor of that shape and dtype with unit stride along the bins.  Arguments
+        otherwise as decode_range; not capturable into a graph."""
+        start, stop, r = int(start), int(stop), int(r)
+        if not 1 <= r <= 4096:
+            raise ValueError("bin factor %d outside 1..4096" % r)
+        max_len = int(self.ch_len.max()) if self.ch_len.size else 0
+        if not (0 <= start <= stop <= max_len):
+            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
+        if start % r:
+            raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
+        sel = np.arange(self.C, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
+        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
+            raise IndexError("channel index out of range")
+        sel32 = np.ascontiguousarray(sel, dtype=np.uint32)
+        nb, rows = (stop - start + r - 1) // r, int(sel.size)
+        dtype = torch.uint8 if saturate else torch.int32
+        if out is None:
+            out = torch.empty((rows, nb), dtype=dtype, device=self.device)
+        elif tuple(out.shape) != (rows, nb) or out.dtype != dtype or (nb > 1 and rows and out.stride(1) != 1):
+            raise ValueError("out must be a %s [%d, %d] tensor with unit stride along the bins" % (dtype, rows, nb))
+        pitch = out.stride(0) if rows > 1 else nb
+        _lib.check(_lib.lib().mh_decode_rebin(self._h, _ptr(payload), payload.numel(), _ptr(seg_off),
+                                              sel32.ctypes.data if rows else None, rows, start, stop, r, 1 if saturate else 0,
+                                              _ptr(peak), _ptr(enc), _ptr(out) if rows and nb else None, pitch, _stream()))
+        return out
+
     def decode_ok(self):
         """True when every decode() on this plan since the previous decode_ok() (direct calls and graph
         replays alike) stayed inside its payload; reading clears the flag (synchronises)."""

@@ -429,27 +429,17 @@ def gather_range(src, start, stop, sel):
     return payload, seg_off, segs
 
 
-def decompress_range(src, start, stop, channels=None, device="cuda", check=True, time_major=False):
-    """Samples [start, stop) of the selected channels of a `Compressed` or a `ContainerFile` (open()), reading and
-    decoding only the segments that overlap the range.  -> uint8 device tensor [n_sel, stop - start] (row i = channel
-    channels[i]: min(x, S-1) inside the channel's encoded window, 0 outside it and past its length -- exactly
-    decompress(src, channels).to_channels()[i][start:stop], zero-extended), or [stop - start, n_sel] with
-    time_major=True.  channels: None = all, else indices (rows in that order, repeats allowed).  check=True validates the
-    header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU; a decode that
-    had to abandon a segment raises ValueError as decompress() does."""
-    import ctypes as ct
-
-    import torch
-
+def _range_inputs(src, start, stop, channels, check):
+    """What a range query of a `Compressed` / `ContainerFile` needs on the host: argument checks, the payload of the
+    segments that overlap [start, stop) (gather_range) and, with check, their validation (mh_validate_segments).
+    -> (sel, payload, seg_off, peak, enc); payload is None when the query is empty (no channel or no sample)."""
     from . import _lib
-    from .codec import _ptr, _stream
     hd = src.header
     S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
     rev = int(hd.get("format_revision", FORMAT_REVISION))
     ch_len = np.ascontiguousarray(src.ch_len, np.uint64)
     C = len(ch_len)
     max_len = int(ch_len.max()) if C else 0
-    start, stop = int(start), int(stop)
     if not (0 <= start <= stop <= max_len):
         raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
     sel = np.arange(C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
@@ -460,10 +450,8 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
         raise ValueError("container directory does not match its header")
     if C and int(ch_len.min()) == 0:
         raise ValueError("container holds an empty channel")
-    n, rows = stop - start, int(sel.size)
-    if rows == 0 or n == 0:
-        z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
-        return z.t().contiguous() if time_major else z
+    if sel.size == 0 or stop == start:
+        return sel, None, None, None, None
     payload, seg_off, segs = gather_range(src, start, stop, sel)
     peak, enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
     if check:
@@ -478,6 +466,13 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
                                              peak.ctypes.data, enc.ctypes.data)
         if rc != 0:
             raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
+    return sel, payload, seg_off, peak, enc
+
+
+def _range_decode(src, payload, seg_off, peak, enc, run):
+    """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device; ValueError when the decode
+    had to abandon a segment."""
+    import torch
     own = not isinstance(src, ContainerFile)
     plan = _range_plan(src) if own else src.plan()
     try:
@@ -487,16 +482,61 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
             pay[:payload.size] = torch.from_numpy(payload.view(np.int32)).to(dev)
         d_off = torch.from_numpy(seg_off.view(np.int64)).to(dev)
         d_peak, d_enc = torch.from_numpy(peak.copy()).to(dev), torch.from_numpy(enc.copy()).to(dev)
-        out = plan.decode_range(pay, d_off, d_peak, d_enc, sel, start, stop)
+        out = run(plan, pay, d_off, d_peak, d_enc)
         ok = plan.decode_ok()  # synchronises
     finally:
         if own:
             plan.close()
     if not ok:
         raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
+    return out
+
+
+def decompress_range(src, start, stop, channels=None, device="cuda", check=True, time_major=False):
+    """Samples [start, stop) of the selected channels of a `Compressed` or a `ContainerFile` (open()), reading and
+    decoding only the segments that overlap the range.  -> uint8 device tensor [n_sel, stop - start] (row i = channel
+    channels[i]: min(x, S-1) inside the channel's encoded window, 0 outside it and past its length -- exactly
+    decompress(src, channels).to_channels()[i][start:stop], zero-extended), or [stop - start, n_sel] with
+    time_major=True.  channels: None = all, else indices (rows in that order, repeats allowed).  check=True validates the
+    header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU; a decode that
+    had to abandon a segment raises ValueError as decompress() does."""
+    import torch
+
+    from . import _lib
+    from .codec import _ptr, _stream
+    start, stop = int(start), int(stop)
+    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check)
+    n, rows = stop - start, int(sel.size)
+    if payload is None:
+        z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
+        return z.t().contiguous() if time_major else z
+    out = _range_decode(src, payload, seg_off, peak, enc,
+                        lambda plan, pay, off, pk, en: plan.decode_range(pay, off, pk, en, sel, start, stop))
     if not time_major:
         return out
     tm = torch.empty((n, rows), dtype=torch.uint8, device=out.device)
     in_off = torch.arange(rows, dtype=torch.int64, device=out.device) * (out.stride(0) if rows > 1 else 0)
     _lib.check(_lib.lib().mh_interleave(_ptr(out), _ptr(in_off), n, rows, _ptr(tm), _stream()))
     return tm
+
+
+def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, check=True, device="cuda"):
+    """Samples [start, stop) of the selected channels summed in bins of r samples (mh_decode_rebin): what
+    decompress_range(src, start, stop, channels) re-binned by r gives, decoded in one pass that never stores the
+    byte-per-sample rows.  -> device tensor [n_sel, ceil((stop - start) / r)], uint8 = min(sum, 255) (saturate, the form
+    ChannelSet.rebin has) or int32 exact sums; the last, partial bin is kept.  stop=None: the longest channel's length.
+    ValueError for r outside 1..4096, start % r != 0 or a bad range, IndexError for a bad channel -- before anything
+    reaches the GPU; check and the status handling as decompress_range."""
+    import torch
+    r, start = int(r), int(start)
+    stop = (int(np.max(src.ch_len)) if len(src.ch_len) else 0) if stop is None else int(stop)
+    if not 1 <= r <= 4096:
+        raise ValueError("bin factor %d outside 1..4096" % r)
+    if start % r:
+        raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
+    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check)
+    nb, rows = (stop - start + r - 1) // r, int(sel.size)
+    if payload is None:
+        return torch.zeros((rows, nb), dtype=torch.uint8 if saturate else torch.int32, device=device)
+    return _range_decode(src, payload, seg_off, peak, enc,
+                         lambda plan, pay, off, pk, en: plan.decode_rebin(pay, off, pk, en, sel, start, stop, r, saturate))

@@ -1035,12 +1035,18 @@ __device__ __forceinline__ ChunkHdr scan_header(uint32_t hw32, int lane)
 // PO: output packing.  0 = one byte per symbol (mh_decode); 2 / 4 = packed pieces (mh_decode_packed): the tables hold
 // their symbols already packed (build_decode_tables), a row is assembled with shifts and ORs into the lane's 4- / 8-byte
 // piece and leaves in one global store (ST is not used); the cut piece of a partial chunk is written whole, zero-padded.
-template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0, int PO = 0, int TAG = 0>
+// SINK (not NoSink; PO = 0): nothing is stored.  Every decoded row goes to sink->row(the lane's 16 bytes, index of its
+// first sample) with all 64 lanes active, and `out` is not an address but the index of the chunk's first sample
+// (sink_index).  A PARTIAL chunk then decodes all 64 pieces of every row that holds a sample -- the lanes past the last
+// sample from whatever follows in the staging area (a few words, inside LDS) -- and the sink drops the samples past m.
+template <int K, int M, int RL, bool HY, bool PARTIAL = false, int ST = 0, int PO = 0, int TAG = 0, class SINK = NoSink>
 __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *tabw, uint32_t tbase, uint32_t maskW,
                                                     const uint8_t *tab1, uint32_t mask1,
                                                     const uint32_t *stage, uint8_t *__restrict__ out,
-                                                    int lane, uint32_t m = kChunk)
+                                                    int lane, uint32_t m = kChunk, SINK *sink = nullptr)
 {
+    constexpr bool kSink = !std::is_same<SINK, NoSink>::value;
+    static_assert(!kSink || PO == 0, "a sink takes bytes");
     // Bit window: 64 bits starting at word `wi` of the staged payload, `bp` bits already used.
     // RL (reload): every M lookups the window is simply RE-READ from LDS at the lane's absolute bit
     //   position -- branch-free; a conditional refill runs for the whole wave almost every step
@@ -1075,7 +1081,7 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
     const auto rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0x7FFFFFFF, 0x00020000);  // (ST != 0)
     auto row = [&](int k) {
         const uint32_t piece = (uint32_t)k * kLanes + lane;
-        if (PARTIAL && piece >= nfp) {
+        if (PARTIAL && !kSink && piece >= nfp) {
             if (piece == nfp && (m & 15u)) {  // the cut piece: m % 16 symbols, one lane of the chunk
                 uint8_t *q = out + piece * MH_PIECE;
                 uint2 pw = make_uint2(0u, 0u);  // (PO != 0) the piece, zero-padded
@@ -1171,6 +1177,10 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
             o[d] = w;
         }
         const uint32_t krow = (uint32_t)k;
+        if constexpr (kSink) {
+            sink->row(o, sink_index(out) + piece * MH_PIECE);
+            return;
+        }
         if constexpr (PO != 0) {
             store_piece<PO>(out, krow * kLanes + lane, make_uint2(pw[0], pw[1]));
             return;
@@ -1282,11 +1292,12 @@ __device__ __forceinline__ void decode_staged_pair1(ChunkHdr hA, ChunkHdr hB, co
 // reads of this chunk's own words), the whole payload copied to LDS in one batch of loads, then
 // decode_staged_chunk<PARTIAL>.  A chunk too large for the staging area takes the per-symbol
 // routine on global memory.
-template <int K, int M, int RL, bool HY, int PO = 0, int TAG = 0>
+template <int K, int M, int RL, bool HY, int PO = 0, int TAG = 0, class SINK = NoSink>
 __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict__ in, uint32_t m, const uint32_t *tabw,
                                                   uint32_t tbase, uint32_t maskW, const uint8_t *tab1, uint32_t mask1,
                                                   uint32_t *stage, uint32_t cap_words, uint8_t *__restrict__ out,
-                                                  int lane, uint64_t avail, uint32_t *err, uint32_t epoch)
+                                                  int lane, uint64_t avail, uint32_t *err, uint32_t epoch,
+                                                  SINK *sink = nullptr)
 {
     // avail = words readable from `in` on; the chunk's header, payload and 3 words of read-ahead
     // must lie inside, else the chunk is abandoned (corrupt or truncated stream)
@@ -1309,7 +1320,7 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
     const uint32_t ns = h.nw + 3;
     if (avail < (uint64_t)h.hw + ns) { if (lane == 0) atomicMax(err, epoch); return; }
     if (ns > cap_words) {
-        decode_chunk<3, false, PO>(in, m, tab1, mask1, out, lane);
+        decode_chunk<3, false, PO>(in, m, tab1, mask1, out, lane, sink);
         return;
     }
     const uint32_t *pay = in + h.hw;
@@ -1326,7 +1337,7 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    decode_staged_chunk<K, M, RL, HY, true, 0, PO, TAG>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m);
+    decode_staged_chunk<K, M, RL, HY, true, 0, PO, TAG>(h, tabw, tbase, maskW, tab1, mask1, stage, out, lane, m, sink);
 }
 
 // One segment, one wave: the chunks of segment `seg` through the wave's tables (`tab` multi-symbol
@@ -1351,10 +1362,12 @@ __device__ __forceinline__ void decode_partial_chunk(const uint32_t *__restrict_
 // TAG (also of decode_staged_chunk / decode_partial_chunk) changes nothing in the code: a caller outside the codec
 // kernels (k_decode_range) passes its own, so that the lambdas of these templates are instances of its own -- a lambda
 // shared with a second kernel loses its single-call-site inlining bonus and changes the first kernel's code.
-template <int K, int M, int NR, int RL, bool HY, bool WT = false, int PO = 0, int TAG = 0>
+// SINK: see decode_staged_chunk (k_decode_rebin); `out` = sink_base().
+template <int K, int M, int NR, int RL, bool HY, bool WT = false, int PO = 0, int TAG = 0, class SINK = NoSink>
 __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,
-                                               uint32_t mask1, uint32_t *stage, int lane, size_t cstride = 0)
+                                               uint32_t mask1, uint32_t *stage, int lane, size_t cstride = 0,
+                                               SINK *sink = nullptr)
 {
     const size_t cs = PO != 0 ? cstride : (size_t)kChunk;  // bytes from one chunk's output to the next
     constexpr bool kHdrDpp = WT || HY;  // see scan_header
@@ -1438,7 +1451,7 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
                 // flight before this chunk's stores
                 fetch(pay_n, avail_n);
                 hw_next = peek(pay_n, nx.nw, peek_n);
-                decode_staged_chunk<K, M, RL, HY, false, kSt, PO, TAG>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * cs, lane);
+                decode_staged_chunk<K, M, RL, HY, false, kSt, PO, TAG>(hc, tab, tbase, maskW, tab1, mask1, stage, out + (size_t)c * cs, lane, kChunk, sink);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 ++c;
@@ -1474,13 +1487,13 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
         if (!room(pos, 32)) MH_DEC_BAIL();
         const ChunkHdr h = scan_header<kHdrDpp>(in[lane & 31], lane);
         if (h.nw < kMinFull || !room(pos, (uint64_t)h.hw + h.nw + 3)) MH_DEC_BAIL();
-        decode_chunk<3, true, PO>(in, kChunk, tab1, mask1, out + (size_t)c * cs, lane);
+        decode_chunk<3, true, PO>(in, kChunk, tab1, mask1, out + (size_t)c * cs, lane, sink);
         in += h.hw + h.nw;
         pos += h.hw + h.nw;
     }
     if (rem)
         decode_partial_chunk<K, M, RL, HY, PO, TAG>(in, rem, tab, tbase, maskW, tab1, mask1, stage, kCap, out + (size_t)nfull * cs,
-                                            lane, pos < lim ? lim - pos : 0, d.err, d.epoch);
+                                            lane, pos < lim ? lim - pos : 0, d.err, d.epoch, sink);
 #undef MH_DEC_BAIL
 }
 

@@ -11,6 +11,8 @@
 //
 // All integer / bit work, HBM-bound: no MFMA anywhere.
 #pragma once
+#include <type_traits>
+
 #include "mh_device.hpp"
 
 namespace mh {
@@ -555,10 +557,17 @@ __device__ __forceinline__ void store_piece(uint8_t *out, uint32_t piece, uint2 
 
 // PO = 0: one byte per symbol (mh_decode); 2 / 4: packed pieces (mh_decode_packed), `out` = the chunk's first piece,
 // a cut last piece written whole and zero-padded
-template <int FI, bool FULL, int PO = 0>
+// Decoders with a sink (decode_staged_chunk in mh_codec2.hpp) store nothing: every row goes to SINK::row(bytes, index of
+// the lane's first sample), all lanes active.  Their `out` is no address: it carries the index of the chunk's first
+// sample, counted from sink_base().
+struct NoSink {};
+__device__ __forceinline__ uint8_t *sink_base() { return reinterpret_cast<uint8_t *>((uintptr_t)1 << 32); }
+__device__ __forceinline__ uint32_t sink_index(const uint8_t *out) { return (uint32_t)reinterpret_cast<uintptr_t>(out); }
+
+template <int FI, bool FULL, int PO = 0, class SINK = NoSink>
 __device__ __forceinline__ uint32_t decode_chunk(const uint32_t *__restrict__ in, uint32_t m,
                                                  const uint8_t *dtab, uint32_t mask,
-                                                 uint8_t *__restrict__ out, int lane)
+                                                 uint8_t *__restrict__ out, int lane, SINK *sink = nullptr)
 {
     // header (format revision 2, mh_device.hpp): two dependent reads, only words of this chunk
     const uint32_t w0 = in[0];
@@ -606,7 +615,9 @@ __device__ __forceinline__ uint32_t decode_chunk(const uint32_t *__restrict__ in
                 }
             }
         }
-        if constexpr (PO != 0) {
+        if constexpr (!std::is_same<SINK, NoSink>::value) {
+            sink->row(o, sink_index(out) + base);  // (o is 0 past the chunk's last sample)
+        } else if constexpr (PO != 0) {
             if (cnt > 0) store_piece<PO>(out, (uint32_t)k * kLanes + lane, pack_piece<PO>(o));
         } else if (FULL || cnt == MH_PIECE) {
             *reinterpret_cast<u32x4_u *>(out + base) = o;

@@ -16,6 +16,7 @@
 #include "mh_layout.hpp"
 #include "mh_planner.hpp"
 #include "mh_range.hpp"
+#include "mh_rebin_decode.hpp"
 // The library is built with -fvisibility=hidden: the C ABI of include/muahuff.h is ALL it exports
 // (tests/test_host.py compares the dynamic symbol table with the header's prototypes).
 #pragma GCC visibility push(default)
@@ -100,6 +101,17 @@ struct mh_plan {
     size_t range_b_task = 0, range_b_wg = 0, range_nwg = 0, range_nfill = 0;
     uint64_t range_max_fill = 0;
     std::vector<uint64_t> ch_seg0;
+    // mh_decode_rebin: the same for its work list (tasks, workgroups, fix-up and fill records) and the u32 side array
+    // of the bins that several tasks add up
+    std::vector<uint8_t> rebin_host;
+    uint8_t *d_rebin = nullptr;
+    uint32_t *d_rebin_side = nullptr;
+    size_t rebin_cap = 0, rebin_side_cap = 0;
+    std::vector<uint32_t> rebin_sel;
+    uint64_t rebin_t0 = 0, rebin_t1 = 0, rebin_pitch = 0;
+    uint32_t rebin_r = 0;
+    size_t rebin_b_task = 0, rebin_b_wg = 0, rebin_b_fix = 0, rebin_nwg = 0, rebin_nfix = 0, rebin_nfill = 0, rebin_nside = 0;
+    uint64_t rebin_max_fill = 0;
 };
 
 struct mh_sweep {
@@ -283,6 +295,26 @@ static int launch_decode_range(const mh::RangeArgs &r, uint32_t nwg, hipStream_t
     return MH_OK;
 }
 
+// fused decode + re-bin (mh_decode_rebin): launch_decode_range's LDS plus each wave's row buffer; 64 bytes of slack
+// behind the last wave's staging area, which a cut last chunk may read past by a few words (decode_staged_chunk, SINK)
+template <int K, int M, int NR, int RL, bool HY>
+static int launch_decode_rebin(const mh::RebinArgs &r, bool sat, uint32_t nwg, hipStream_t st)
+{
+    size_t lds = ((size_t)mh::dec2_shared_dwords(r.a.W, K) + 4 * ((size_t)mh::dec2_stage_dwords(NR) + mh::kRebinRowDwords)) *
+                     sizeof(uint32_t) + 64;
+    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;  // (see launch_decode2)
+    auto ks = mh::k_decode_rebin<K, M, NR, RL, HY, true>;
+    auto kw = mh::k_decode_rebin<K, M, NR, RL, HY, false>;
+    if (g_prepare_only) {
+        const int rc = prepare_kernel(reinterpret_cast<const void *>(ks), lds, true);
+        return rc ? rc : prepare_kernel(reinterpret_cast<const void *>(kw), lds, true);
+    }
+    if (sat) hipLaunchKernelGGL(ks, dim3(nwg), dim3(256), lds, st, r);
+    else hipLaunchKernelGGL(kw, dim3(nwg), dim3(256), lds, st, r);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
 // lane-private LDS staging of the encoder: 16 dwords per lane for codes of at most 2 bits (the worst case of a
 // 256-sample sub-stream), else 32 (= 4 bits per sample on average: the worst case up to 4-bit codes; a clipped
 // spike-count channel at S <= 10 stays well below that, and chunks that outgrow it take the two-pass global slow
@@ -387,6 +419,18 @@ static int dispatch_decode_range(const mh_plan *p, const mh::RangeArgs &r, uint3
     return launch_decode_range<2, 2, 25, 2, false>(r, nwg, st);
 }
 
+// the fused decode + re-bin kernel on the same rungs
+static int dispatch_decode_rebin(const mh_plan *p, const mh::RebinArgs &r, bool sat, uint32_t nwg, hipStream_t st)
+{
+    const uint32_t L = p->h.info.maxlen;
+    if (L <= 2) return launch_decode_rebin<4, 4, 17, 1, false>(r, sat, nwg, st);
+    if (L != 3) {
+        if (r.a.W >= 2 * L) return launch_decode_rebin<2, 2, 32, 0, false>(r, sat, nwg, st);
+        return launch_decode_rebin<2, 2, 31, 2, true>(r, sat, nwg, st);
+    }
+    return launch_decode_rebin<2, 2, 25, 2, false>(r, sat, nwg, st);
+}
+
 static int dispatch_decode(const mh_plan *p, uint32_t po, const mh::Dec2Args &a, hipStream_t st)
 {
     if (po == 2) return dispatch_decode<2>(p, a, st);
@@ -410,6 +454,9 @@ static int prepare_kernels(const mh_plan *p)
         mh::RangeArgs r{};
         r.a = d;
         rc = dispatch_decode_range(p, r, 0, nullptr);
+        mh::RebinArgs b{};
+        b.a = d;
+        if (rc == MH_OK) rc = dispatch_decode_rebin(p, b, true, 0, nullptr);
     }
     g_prepare_only = false;
     return rc;
@@ -465,7 +512,7 @@ int mh_plan_destroy(mh_plan *p)
                     p->d_tile_n, p->d_tile_start, p->d_hist, p->d_peak, p->d_enc,
                     p->d_lut, p->d_wg_tasks, p->d_wave_tasks, p->d_scan,
                     p->d_cal_tile_ch, p->d_cal_tile_n, p->d_cal_tile_start, p->d_calhist, p->d_err, p->d_acc,
-                    p->d_range, p->d_range_scr};
+                    p->d_range, p->d_range_scr, p->d_rebin, p->d_rebin_side};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     delete p;
@@ -990,6 +1037,196 @@ int mh_decode_range(mh_plan *p, const uint32_t *payload, uint64_t payload_words,
     r.out = out;
     r.scratch = p->d_range_scr;
     return dispatch_decode_range(p, r, (uint32_t)p->range_nwg, st);
+}
+
+// mh_decode_rebin's work list for (sel, t0, t1, r, out_pitch), as range_work_list builds mh_decode_range's: one task per
+// overlapping segment, plus what the bins need.  The tasks of a row cover consecutive sample spans, so the bins they
+// touch are consecutive too: a bin is shared when a task's first bin is the previous task's last one -- those get a
+// side slot and a fix-up record; the bins of a row in front of the first task's and behind the last task's are zeroed.
+static int rebin_work_list(mh_plan *p, const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r,
+                           uint64_t out_pitch, hipStream_t st)
+{
+    const mh::PlanHost &H = p->h;
+    const uint32_t C = H.info.C;
+    const uint64_t len = t1 - t0, nb = (len + r - 1) / r;
+    p->rebin_sel.clear();  // (no valid list while this one is being built)
+    if (p->ch_seg0.empty()) {  // each channel's first directory entry (its segments are consecutive)
+        p->ch_seg0.assign((size_t)C + 1, 0);
+        for (uint32_t c : H.seg_ch) ++p->ch_seg0[(size_t)c + 1];
+        for (uint32_t c = 0; c < C; ++c) p->ch_seg0[(size_t)c + 1] += p->ch_seg0[c];
+    }
+    std::vector<mh::RebinTask> tasks;
+    std::vector<mh::RangeWg> wgs;
+    std::vector<mh::RebinFix> fixes;
+    std::vector<mh::RangeFill> fills;
+    uint32_t nside = 0;
+    uint64_t max_fill = 0;
+    auto fill = [&](uint64_t off, uint64_t n) {
+        if (n == 0) return;
+        fills.push_back(mh::RangeFill{off, n});
+        if (n > max_fill) max_fill = n;
+    };
+    for (uint32_t i = 0; i < n_sel; ++i) {
+        const uint32_t c = sel[i];
+        const uint64_t row = (uint64_t)i * out_pitch, w0 = H.w0[c], w1 = H.w1[c];
+        const uint64_t a = t0 > w0 ? t0 : w0, b = t1 < w1 ? t1 : w1;  // in-window part, channel samples
+        if (a >= b) {
+            fill(row, nb);
+            continue;
+        }
+        fill(row, (a - t0) / r);                                      // bins in front of sample a's
+        fill(row + (b - 1 - t0) / r + 1, nb - ((b - 1 - t0) / r + 1));  // bins behind sample (b - 1)'s
+        const uint64_t ra = a - w0, rb = b - w0;  // the same, window samples
+        const uint64_t *sf0 = H.seg_first.data();
+        uint64_t s = (uint64_t)(std::upper_bound(sf0 + p->ch_seg0[c], sf0 + p->ch_seg0[(size_t)c + 1], ra) - sf0) - 1;
+        const size_t task0 = tasks.size();
+        uint64_t prev_last = 0;  // the previous task's last bin (of the row)
+        for (; s < p->ch_seg0[(size_t)c + 1] && H.seg_first[s] < rb; ++s) {
+            const uint64_t sf = H.seg_first[s], sn = H.seg_n[s];
+            const uint64_t lo = (ra > sf ? ra : sf) - sf, hi = (rb < sf + sn ? rb : sf + sn) - sf;
+            const uint64_t c0 = lo / MH_CHUNK, c1 = (hi - 1) / MH_CHUNK, base = c0 * MH_CHUNK;
+            const uint64_t ncnk = c1 - c0 + 1;
+            // sample 0 of the task (chunk c0's first) sits at g0 in the range, possibly in front of it (then in bin -1)
+            const int64_t g0 = (int64_t)(w0 + sf + base) - (int64_t)t0;
+            const int64_t b0 = g0 >= 0 ? g0 / (int64_t)r : -(((-g0) + (int64_t)r - 1) / (int64_t)r);
+            mh::RebinTask t{};
+            t.ph = (uint32_t)(g0 - b0 * (int64_t)r);
+            t.dst = (int64_t)row + b0;
+            t.seg = (uint32_t)s;
+            t.skip = (uint32_t)c0;
+            t.n = (uint32_t)(sn - base < ncnk * MH_CHUNK ? sn - base : ncnk * MH_CHUNK);
+            t.lo = (uint32_t)(lo - base);
+            t.hi = (uint32_t)(hi - base);
+            t.jfirst = (uint32_t)((t.ph + (uint64_t)t.lo) / r);
+            t.jlast = (uint32_t)((t.ph + (uint64_t)t.hi - 1) / r);
+            t.head = t.tail = mh::kNoSlot;
+            const uint64_t first = (uint64_t)(b0 + (int64_t)t.jfirst), last = (uint64_t)(b0 + (int64_t)t.jlast);
+            if (tasks.size() > task0 && first == prev_last) {  // shared with the previous task (and maybe the ones before)
+                mh::RebinTask &q = tasks.back();
+                uint32_t slot = q.jfirst == q.jlast && q.head != mh::kNoSlot ? q.head : q.tail;
+                if (slot == mh::kNoSlot) {
+                    slot = nside++;
+                    fixes.push_back(mh::RebinFix{row + first, slot, 0u});
+                }
+                q.tail = slot;
+                t.head = slot;
+            }
+            prev_last = last;
+            tasks.push_back(t);
+        }
+        for (size_t k = task0; k < tasks.size(); k += 4)
+            wgs.push_back(mh::RangeWg{(uint32_t)k, (uint32_t)(tasks.size() - k < 4 ? tasks.size() - k : 4), c, 0u});
+    }
+    // ---- upload (one copy)
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t b_task = up16(tasks.size() * sizeof(mh::RebinTask)), b_wg = up16(wgs.size() * sizeof(mh::RangeWg));
+    const size_t b_fix = up16(fixes.size() * sizeof(mh::RebinFix));
+    const size_t bytes = b_task + b_wg + b_fix + fills.size() * sizeof(mh::RangeFill);
+    // the previous call's kernels may still read the task buffer and the side array (one stream at a time per plan)
+    MH_HIP(hipStreamSynchronize(st));
+    if (bytes > p->rebin_cap) {
+        if (p->d_rebin) MH_HIP(hipFree(p->d_rebin));
+        p->d_rebin = nullptr;
+        p->rebin_cap = 0;
+        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_rebin), bytes));
+        p->rebin_cap = bytes;
+    }
+    const size_t side_bytes = (size_t)(nside ? nside : 1) * sizeof(uint32_t);
+    if (side_bytes > p->rebin_side_cap) {
+        if (p->d_rebin_side) MH_HIP(hipFree(p->d_rebin_side));
+        p->d_rebin_side = nullptr;
+        p->rebin_side_cap = 0;
+        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_rebin_side), side_bytes));
+        p->rebin_side_cap = side_bytes;
+    }
+    p->rebin_host.assign(bytes, 0);
+    uint8_t *hp = p->rebin_host.data();
+    if (!tasks.empty()) memcpy(hp, tasks.data(), tasks.size() * sizeof(mh::RebinTask));
+    if (!wgs.empty()) memcpy(hp + b_task, wgs.data(), wgs.size() * sizeof(mh::RangeWg));
+    if (!fixes.empty()) memcpy(hp + b_task + b_wg, fixes.data(), fixes.size() * sizeof(mh::RebinFix));
+    if (!fills.empty()) memcpy(hp + b_task + b_wg + b_fix, fills.data(), fills.size() * sizeof(mh::RangeFill));
+    if (bytes) MH_HIP(hipMemcpyAsync(p->d_rebin, hp, bytes, hipMemcpyHostToDevice, st));
+    p->rebin_sel.assign(sel, sel + n_sel);
+    p->rebin_t0 = t0;
+    p->rebin_t1 = t1;
+    p->rebin_r = r;
+    p->rebin_pitch = out_pitch;
+    p->rebin_b_task = b_task;
+    p->rebin_b_wg = b_wg;
+    p->rebin_b_fix = b_fix;
+    p->rebin_nwg = wgs.size();
+    p->rebin_nfix = fixes.size();
+    p->rebin_nfill = fills.size();
+    p->rebin_nside = nside;
+    p->rebin_max_fill = max_fill;
+    return MH_OK;
+}
+
+extern "C++" template <class T>
+static int rebin_fill_fix(const mh_plan *p, T *out, bool fix, hipStream_t st)
+{
+    const uint8_t *base = p->d_rebin + p->rebin_b_task + p->rebin_b_wg;
+    if (fix) {
+        hipLaunchKernelGGL(mh::k_rebin_fix<T>, dim3((unsigned)((p->rebin_nfix + 255) / 256)), dim3(256), 0, st, out,
+                           reinterpret_cast<const mh::RebinFix *>(base), (uint32_t)p->rebin_nfix, p->d_rebin_side);
+        MH_HIP(hipGetLastError());
+        return MH_OK;
+    }
+    const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(base + p->rebin_b_fix);
+    const uint64_t per_block = 256 * 16;
+    const uint64_t nbk = (p->rebin_max_fill + per_block - 1) / per_block;
+    const unsigned nx = (unsigned)(nbk < 1 ? 1 : nbk < 1024 ? nbk : 1024);
+    for (size_t f = 0; f < p->rebin_nfill; f += 65535) {
+        const unsigned ny = (unsigned)(p->rebin_nfill - f < 65535 ? p->rebin_nfill - f : 65535);
+        hipLaunchKernelGGL(mh::k_rebin_fill<T>, dim3(nx, ny), dim3(256), 0, st, out, d_fill + f);
+        MH_HIP(hipGetLastError());
+    }
+    return MH_OK;
+}
+
+int mh_decode_rebin(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                    const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r, int saturate,
+                    const uint8_t *peak, const uint8_t *enc, void *out, uint64_t out_pitch, void *stream)
+{
+    if (!p || (n_sel && !sel)) return fail(MH_ERR_ARG, "mh_decode_rebin: NULL argument");
+    if (p->h.input_bits != 8)
+        return fail(MH_ERR_ARG, "mh_decode_rebin: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
+    if (r < 1 || r > 4096) return fail(MH_ERR_ARG, "mh_decode_rebin: bin factor %u outside 1..4096", r);
+    if (t0 > t1 || t1 > p->h.max_T)
+        return fail(MH_ERR_ARG, "mh_decode_rebin: [%llu, %llu) is not a range inside [0, %llu)", (unsigned long long)t0,
+                    (unsigned long long)t1, (unsigned long long)p->h.max_T);
+    if (t0 % r) return fail(MH_ERR_ARG, "mh_decode_rebin: t0 = %llu is not a multiple of the bin factor %u", (unsigned long long)t0, r);
+    const uint32_t C = p->h.info.C;
+    for (uint32_t i = 0; i < n_sel; ++i)
+        if (sel[i] >= C) return fail(MH_ERR_ARG, "mh_decode_rebin: sel[%u] = %u, the plan has %u channels", i, sel[i], C);
+    const uint64_t nb = (t1 - t0 + r - 1) / r;
+    if (n_sel > 1 && out_pitch < nb)
+        return fail(MH_ERR_ARG, "mh_decode_rebin: out_pitch %llu below the row length %llu", (unsigned long long)out_pitch,
+                    (unsigned long long)nb);
+    if (n_sel == 0 || nb == 0) return MH_OK;
+    if (!payload || !seg_off || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_rebin: NULL argument");
+    int rc = check_device(p->device, "mh_decode_rebin");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool same = p->d_rebin && p->rebin_t0 == t0 && p->rebin_t1 == t1 && p->rebin_r == r && p->rebin_pitch == out_pitch &&
+                      p->rebin_sel.size() == n_sel && std::equal(sel, sel + n_sel, p->rebin_sel.begin());
+    if (!same && (rc = rebin_work_list(p, sel, n_sel, t0, t1, r, out_pitch, st))) return rc;
+    const bool sat = saturate != 0;
+    if (p->rebin_nfill && (rc = sat ? rebin_fill_fix(p, (uint8_t *)out, false, st) : rebin_fill_fix(p, (uint32_t *)out, false, st)))
+        return rc;
+    if (p->rebin_nwg == 0) return MH_OK;
+    if (p->rebin_nside) MH_HIP(hipMemsetAsync(p->d_rebin_side, 0, p->rebin_nside * sizeof(uint32_t), st));
+    mh::RebinArgs a{};
+    a.a = decode_args(p, payload, payload_words, seg_off, peak, enc, nullptr);
+    a.task = reinterpret_cast<const mh::RebinTask *>(p->d_rebin);
+    a.wg = reinterpret_cast<const mh::RangeWg *>(p->d_rebin + p->rebin_b_task);
+    a.out = out;
+    a.side = p->d_rebin_side;
+    a.r = r;
+    a.rmagic = r > 1 ? (uint32_t)((1ull << 32) / r) + 1u : 0u;
+    if ((rc = dispatch_decode_rebin(p, a, sat, (uint32_t)p->rebin_nwg, st))) return rc;
+    if (p->rebin_nfix) rc = sat ? rebin_fill_fix(p, (uint8_t *)out, true, st) : rebin_fill_fix(p, (uint32_t *)out, true, st);
+    return rc;
 }
 
 // The chunk walk of one stored segment s (directory entry of H) whose words are payload[pos, end): header sizes,

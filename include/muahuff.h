@@ -38,7 +38,8 @@ extern "C" {
  *   mh_interleave_packed -- packed pieces -> time-major bytes, the inverse of mh_deinterleave_packed
  *   mh_decode_range      -- random access in time: samples [t0, t1) of selected channels, reading only the segments
  *                           that overlap the range
- *   mh_validate_segments -- mh_validate_stream restricted to listed segments (what a range query reads) */
+ *   mh_validate_segments -- mh_validate_stream restricted to listed segments (what a range query reads)
+ *   mh_decode_rebin      -- mh_decode_range + mh_rebin in one pass: sums of r decoded samples, no byte-per-sample buffer */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
@@ -244,6 +245,21 @@ int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t 
 int mh_decode_range(mh_plan *plan, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
                     const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1,
                     const uint8_t *peak, const uint8_t *enc, uint8_t *out, uint64_t out_pitch, void *stream);
+
+/* Decode straight to a coarser bin period: row i of mh_decode_range(sel, t0, t1) summed in bins of r samples, without
+ * the byte-per-sample rows ever reaching memory.  out_i[b] = sum of y_i[b*r .. min(b*r + r, t1 - t0)) for
+ * b < nb = ceil((t1 - t0) / r), where y_i is the range-decoded row (min(x, S-1) inside the channel's window, 0 outside it
+ * and past ch_len); the last, partial bin is kept.  saturate != 0: `out` holds uint8_t, min(sum, 255) (as mh_rebin);
+ * saturate == 0: uint32_t, exact.  Row i is at out + i * out_pitch ELEMENTS; elements [0, nb) of every row are written
+ * and nothing else.  Requires 1 <= r <= 4096, t0 % r == 0, t0 <= t1 <= max(ch_len), sel[i] < C, out_pitch >= nb (when
+ * n_sel > 1) and a byte-layout plan, else MH_ERR_ARG before any device work.  Everything else as mh_decode_range: only
+ * the segments overlapping the range are read, the host-built work list is kept by the plan and reused by a call with
+ * the same (sel, t0, t1, r, out_pitch), memory-safe on any stream, status through mh_decode_status, not capturable.
+ * Results are integer sums: identical from run to run.  Enqueues a clear of the plan's side array, a zero fill of bins
+ * outside the window, the decode launch and a short launch that writes the bins cut by segment boundaries. */
+int mh_decode_rebin(mh_plan *plan, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
+                    const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r, int saturate,
+                    const uint8_t *peak, const uint8_t *enc, void *out, uint64_t out_pitch, void *stream);
 
 /* Host-only: mh_validate_stream restricted to the listed segments (seg_idx[0..n_idx), directory indices of the plan
  * layout rebuilt from ch_len / h / window / seg_chunks, n_segments entries).  Segment s occupies the words
