@@ -15,10 +15,16 @@
  *     "device" pointers are HIP device pointers (e.g. torch.Tensor.data_ptr()); the caller
  *     allocates and owns every buffer;
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); device work is
- *     enqueued asynchronously on it and nothing in mh_measure/mh_encode/mh_decode/
- *     mh_compact/mh_synth_poisson/mh_rebin/mh_deinterleave/mh_interleave/mh_decode_packed/
- *     mh_interleave_packed/mh_power_draws/
+ *     enqueued asynchronously on it and nothing in mh_measure/mh_encode/mh_encode_preset/mh_decode/
+ *     mh_compact/mh_synth_poisson/mh_rebin/mh_deinterleave/mh_deinterleave_packed/mh_interleave/
+ *     mh_decode_packed/mh_interleave_packed/mh_sweep_run/mh_power_draws/
  *     mh_reduce_rows synchronises, allocates or frees, so they can be captured into a hipGraph;
+ *     the library's own memsets, table builds and zero fills go to `stream` as well, never to the
+ *     null stream, so the calls are ordered with the caller's work on a non-blocking stream.
+ *     mh_decode_status, mh_decode_range and mh_decode_rebin synchronise `stream` (the latter two
+ *     also allocate and upload a work list unless they reuse the previous one), plan / sweep
+ *     creation and destruction allocate, free and synchronise the device: none of these may be
+ *     captured;
  *   - a plan is bound to the device that was current when it was created and may be used
  *     from one stream at a time (it owns per-channel scratch tables).
  */

@@ -7,6 +7,8 @@
 // With --cells (tests/kernel_cells.py) each case carries input_bits after seg_chunks,
 //     C S h mode window K seg_chunks input_bits  len[0..C)  sclv[0..K*S)
 // and the program prints only where the kernel dispatch lands:  "maxlen wave_tasks W dec_K dec_NR".
+// With --forms (tests/async_table.py) the same input gives the form of the plan, which decides what each call enqueues:
+// "wave_tasks measure_fused fused_calibration tickets_fit cal_tiles head_segments skipped short_channels".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,7 +24,7 @@
         }                                                              \
     } while (0)
 
-static int cells()
+static int cells(bool forms)
 {
     unsigned C, S, h, mode, window, K, sc, bits;
     while (scanf("%u %u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc, &bits) == 8) {
@@ -53,6 +55,16 @@ static int cells()
         p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
         p.input_bits = bits;
         mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+        if (forms) {
+            unsigned heads = 0, shorter = 0;
+            for (unsigned c = 0; c < C; ++c) {
+                heads += mh::head_samples(p.w0[c], p.w1[c], window) ? 1u : 0u;
+                shorter += len[c] < ((uint64_t)1 << h) ? 1u : 0u;
+            }
+            printf("%d %d %d %d %zu %u %llu %u\n", (int)p.use_wave_tasks, (int)p.measure_fused, (int)p.fused_calibration,
+                   (int)p.tickets_fit, p.cal_tile_ch.size(), heads, (unsigned long long)p.info.n_skipped, shorter);
+            continue;
+        }
         printf("%u %d %u %u %u\n", p.info.maxlen, (int)p.use_wave_tasks, p.W, p.dec_K, p.dec_NR);
     }
     return 0;
@@ -60,7 +72,8 @@ static int cells()
 
 int main(int argc, char **argv)
 {
-    if (argc > 1 && !strcmp(argv[1], "--cells")) return cells();
+    if (argc > 1 && !strcmp(argv[1], "--cells")) return cells(false);
+    if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);
     unsigned C, S, h, mode, window, K, sc;
     while (scanf("%u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc) == 7) {
         std::vector<uint64_t> len(C), off(C);
