@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "libmuahuff.so")
 SOURCES = ["csrc/muahuff.hip"]
-HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csrc/mh_codec2.hpp", "csrc/mh_range.hpp", "csrc/mh_rebin_decode.hpp", "csrc/mh_layout.hpp",
+HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csrc/mh_codec2.hpp", "csrc/mh_range.hpp", "csrc/mh_rebin_decode.hpp", "csrc/mh_layout.hpp", "csrc/mh_packed_measure.hpp",
            "csrc/mh_planner.hpp", "csrc/mh_analysis.hpp", "../include/muahuff.h"]
 
 

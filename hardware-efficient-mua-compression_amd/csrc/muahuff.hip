@@ -14,6 +14,7 @@
 #include "mh_analysis.hpp"
 #include "mh_codec2.hpp"
 #include "mh_layout.hpp"
+#include "mh_packed_measure.hpp"
 #include "mh_planner.hpp"
 #include "mh_range.hpp"
 #include "mh_rebin_decode.hpp"
@@ -88,6 +89,7 @@ struct mh_plan {
     uint32_t *d_cal_tile_ch = nullptr, *d_cal_tile_n = nullptr;
     uint64_t *d_cal_tile_start = nullptr;
     unsigned long long *d_calhist = nullptr;
+    size_t packed_cal_tiles = 0;  // packed plans: calibration tiles on the device (every window: the pieces are never scanned by k_calibrate)
     unsigned long long *d_acc = nullptr;  // wave-task encoder: per-channel {bits << 24 | finished records} (zero between launches)
     uint32_t *d_err = nullptr;  // decode status word (mh_decode_status): non-zero once a decode abandoned a segment
     // mh_decode_range: the work list of the last call (host copy kept alive until the next call has synchronised),
@@ -190,6 +192,37 @@ static mh::CalArgs calibrate_args(const mh_plan *p, const uint8_t *data, uint64_
     a.lut = p->d_lut;
     a.pre_hist = nullptr;
     return a;
+}
+
+// window or calibration histogram of a packed plan over `nt` of its tiles (mh_packed_measure.hpp)
+static void launch_hist_packed(const mh_plan *p, const uint8_t *data, const uint32_t *tile_ch, const uint64_t *tile_start,
+                               const uint32_t *tile_n, unsigned long long *hist, size_t nt, hipStream_t st)
+{
+    mh::PackedHistArgs a;
+    a.data = data;
+    a.ch_off = p->d_ch_off;
+    a.tile_ch = tile_ch;
+    a.tile_start = tile_start;
+    a.tile_n = tile_n;
+    a.hist = hist;
+    a.stride = p->h.chunk_stride ? p->h.chunk_stride : (uint64_t)MH_CHUNK * p->h.input_bits / 8;
+    a.S = p->h.info.S;
+    const dim3 g((unsigned)nt), b(256);
+    if (p->h.input_bits == 2) {
+        hipLaunchKernelGGL((mh::k_hist_packed<2, 3>), g, b, 0, st, a);
+        return;
+    }
+    switch (a.S) {
+    case 2: hipLaunchKernelGGL((mh::k_hist_packed<4, 1>), g, b, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((mh::k_hist_packed<4, 2>), g, b, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((mh::k_hist_packed<4, 3>), g, b, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((mh::k_hist_packed<4, 4>), g, b, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((mh::k_hist_packed<4, 5>), g, b, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((mh::k_hist_packed<4, 6>), g, b, 0, st, a); break;
+    case 8: hipLaunchKernelGGL((mh::k_hist_packed<4, 7>), g, b, 0, st, a); break;
+    case 9: hipLaunchKernelGGL((mh::k_hist_packed<4, 8>), g, b, 0, st, a); break;
+    default: hipLaunchKernelGGL((mh::k_hist_packed<4, 9>), g, b, 0, st, a); break;
+    }
 }
 
 template <int NS>
@@ -548,6 +581,24 @@ static int plan_upload(mh_plan *p)
                  (rc = upload(&p->d_cal_tile_start, H.cal_tile_start)) ||
                  (rc = alloc(&p->d_calhist, (size_t)C * mh::kHistStride)))))
         return rc;
+    if (H.input_bits != 8) {
+        // mh_measure on packed pieces histograms EVERY calibration window with the tiled kernel: the planner's tiles
+        // above kCalDirect samples, else one tile per channel, built here (the planner's lists stay what byte plans use)
+        p->packed_cal_tiles = H.cal_tile_ch.size();
+        if (!cal) {
+            std::vector<uint32_t> tch(C), tn(C);
+            const std::vector<uint64_t> tstart(C, 0);
+            const uint64_t lim = (uint64_t)1 << H.info.h;
+            for (uint32_t c = 0; c < C; ++c) {
+                tch[c] = c;
+                tn[c] = (uint32_t)(H.ch_len[c] < lim ? H.ch_len[c] : lim);
+            }
+            if ((rc = upload(&p->d_cal_tile_ch, tch)) || (rc = upload(&p->d_cal_tile_n, tn)) ||
+                (rc = upload(&p->d_cal_tile_start, tstart)) || (rc = alloc(&p->d_calhist, (size_t)C * mh::kHistStride)))
+                return rc;
+            p->packed_cal_tiles = C;
+        }
+    }
     return MH_OK;
 }
 
@@ -666,7 +717,6 @@ int mh_measure(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_
                uint8_t *skipped, void *stream)
 {
     if (!p || !data) return fail(MH_ERR_ARG, "mh_measure: NULL argument");
-    if (p->h.input_bits != 8) return fail(MH_ERR_ARG, "mh_measure: this plan reads packed pieces (mh_encode_preset only)");
     if (int rc_ = check_device(p->device, "mh_measure")) return rc_;
     hipStream_t st = (hipStream_t)stream;
     uint8_t *pk = peak ? peak : p->d_peak, *en = enc ? enc : p->d_enc;
@@ -688,6 +738,21 @@ int mh_measure(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_
     // Launch-bound shapes (mh_planner.hpp: kFusedMeasureChannels): ONE launch.
     // The workgroup that adds a channel's last tile to the histogram calibrates and prices the channel
     // (measure_tail); the histogram scratch and the tickets are left zero for the next call.
+    if (p->h.input_bits != 8) {
+        // Packed pieces: the tiled bit-count kernel histograms the calibration windows, k_calibrate turns those counts
+        // into (peak, encoder) -- it never looks at the pieces -- and clears the window histogram, which the same
+        // kernel then fills over the planner's window tiles.  Never the one-launch form: its tail calibrates by scanning
+        // bytes.  Five enqueues on `stream`, nothing else.
+        MH_HIP(hipMemsetAsync(p->d_calhist, 0, (size_t)f.C * mh::kHistStride * sizeof(unsigned long long), st));
+        launch_hist_packed(p, data, p->d_cal_tile_ch, p->d_cal_tile_start, p->d_cal_tile_n, p->d_calhist, p->packed_cal_tiles, st);
+        mh::CalArgs a = calibrate_args(p, data, cutoff, cal_hist, pk, en, p->d_hist, nullptr, nullptr);
+        a.pre_hist = p->d_calhist;
+        hipLaunchKernelGGL(mh::k_calibrate, dim3((a.C + 3) / 4), dim3(256), 0, st, a);
+        launch_hist_packed(p, data, p->d_tile_ch, p->d_tile_start, p->d_tile_n, p->d_hist, p->h.tile_ch.size(), st);
+        hipLaunchKernelGGL(mh::k_finalize, dim3((f.C + 255) / 256), dim3(256), 0, st, f);
+        MH_HIP(hipGetLastError());
+        return MH_OK;
+    }
     const bool fused = p->h.measure_fused;
     if (!fused) {
         int rc = launch_calibrate(p, data, cutoff, cal_hist, pk, en, st, p->d_hist, nullptr, nullptr);

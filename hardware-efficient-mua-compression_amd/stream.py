@@ -11,6 +11,10 @@ is PACKED: the encoder clips at S-1 anyway, so the de-interleaver writes min(x, 
 per sample -- min(x, 3) in 2 bits when S <= 4 -- (mh_deinterleave_packed) and the encoder reads
 those pieces directly; the intermediate's round trip through HBM shrinks from 2 x 1 byte per
 sample to 2 x 1/2 resp. 2 x 1/4.
+Firing rates drift, and a preset word goes stale.  encode_block_device(block, track=True) also measures the block's
+packed pieces with a fresh calibration (mh_measure on a second packed plan with h = hist_bits: one more read of the
+intermediate, nothing allocated, nothing synchronised); drift() tells per channel how many bits the stale word cost over
+the fresh one, and adopt() takes the fresh word over on the device for the channels where that pays.
 `StreamDecoder` is the receiving end of the same link: per block, the preset stream is decoded straight into packed
 pieces of the same layout (mh_decode_packed) and re-interleaved to time-major bytes from them (mh_interleave_packed),
 so the receive side skips the byte-per-sample intermediate as the send side does.
@@ -22,13 +26,18 @@ from . import MODE_APPROX, WIN_FULL, codec, container_io
 from .container import ChannelSet
 
 
+def _packed_layout(owner):
+    """-> (bits per sample, bytes of one packed chunk) of the owner's blocks"""
+    bits = 2 if owner.S <= 4 else 4
+    return bits, 1024 * 2 * bits
+
+
 def _packed_block(owner, Tb, slack=0):
     """The packed, chunk-blocked layout of a block of Tb time steps, the same on both ends of the link: min(x, S-1) in
     2 (S <= 4) or 4 bits per sample, chunk j (16384 samples = 1024 pieces) of channel c at (j * C + c) * cb -- the chunks
     of one time range are neighbours.  owner: a StreamEncoder or StreamDecoder.  -> (zeroed buffer of the pieces plus
     `slack` bytes, ch_off, plan); the buffer is allocated before the plan."""
-    bits = 2 if owner.S <= 4 else 4
-    cb = 1024 * 2 * bits
+    bits, cb = _packed_layout(owner)
     buf = torch.zeros((Tb + 16383) // 16384 * owner.C * cb + slack, dtype=torch.uint8, device=owner.device)
     ch_off = np.arange(owner.C, dtype=np.uint64) * np.uint64(cb)
     plan = codec.Plan(ch_off, np.full(owner.C, Tb, np.uint64), owner.S, 0, owner.mode, WIN_FULL, owner.sclv,
@@ -77,10 +86,29 @@ class StreamEncoder:
             self._slots[Tb] = slot
         return slot
 
-    def encode_block_device(self, block):
+    def _monitor(self, slot):
+        """The slot's monitor plan, built on first tracked use: a second packed plan over the same pieces and layout
+        with h = hist_bits (the block plan has h = 0: it never calibrates), and the Measured record it fills."""
+        if "monitor" not in slot:
+            bits, cb = _packed_layout(self)
+            cs = slot["cs"]
+            slot["monitor"] = codec.Plan(cs.ch_off, cs.ch_len, self.S, self.h, self.mode, WIN_FULL, self.sclv,
+                                         seg_chunks=self.seg_chunks, input_bits=bits, chunk_stride=self.C * cb)
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+            slot["fresh"] = codec.Measured(z(self.C, torch.int64), z((self.C, self.S), torch.int32),
+                                           z(self.C, torch.uint8), z(self.C, torch.uint8),
+                                           z((self.C, self.S), torch.int64), z(self.C, torch.int64),
+                                           z(self.C, torch.uint8))
+        return slot["monitor"]
+
+    def encode_block_device(self, block, track=False):
         """block: [Tb, C] time-major counts (device tensor or host array).  Enqueues
         de-interleave + preset encode + compaction on the current stream and returns
-        (dense Encoded, total_words tensor, slot) without synchronising.  The buffers (dense
+        (dense Encoded, total_words tensor, slot) without synchronising.
+        track=True also enqueues, behind the de-interleave and on the same stream, a measure of the block's packed
+        pieces with a FRESH calibration (on the block's own first 2^hist_bits steps): slot["fresh"] is the
+        codec.Measured of this block, overwritten per block like the other slot buffers -- see drift() and adopt().
+        The block itself is always coded with the word in force when it was enqueued.  The buffers (dense
         words, sizes, total) belong to the shape's slot and are OVERWRITTEN by the next block of
         the same shape: a consumer that keeps a block in flight while the next one is enqueued
         (dist.gather_payload_pipelined) must copy them out -- or read the total and record an
@@ -101,6 +129,8 @@ class StreamEncoder:
                                                      ct.c_void_p(cs.data.data_ptr()),
                                                      ct.c_void_p(slot["d_off"].data_ptr()), plan.chunk_stride,
                                                      ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if track:
+            self._monitor(slot).measure(cs.data, out=slot["fresh"])
         enc = slot["enc"]
         _lib.check(_lib.lib().mh_encode_preset(plan._h, ct.c_void_p(cs.data.data_ptr()), ct.c_void_p(self.peak.data_ptr()),
                                                ct.c_void_p(self.enc.data_ptr()), ct.c_void_p(enc.payload.data_ptr()),
@@ -124,9 +154,33 @@ class StreamEncoder:
                                        enc.seg_words.cpu().numpy().astype(np.uint64)[:plan.n_segments],
                                        dense.payload[:total].cpu().numpy().view(np.uint32).copy())
 
+    def drift(self, slot):
+        """int64 device tensor [C]: the code bits the slot's last tracked block spent under the word it was coded with,
+        minus what it would have cost under a word calibrated on its own first 2^hist_bits steps (enc.ch_bits -
+        fresh.bits).  Positive = the stored word is stale for this channel; it can be negative, since a word from 2^h
+        steps may lose to the stored one over the whole block.  Enqueued on the current stream, no synchronisation."""
+        if "fresh" not in slot:
+            raise RuntimeError("no tracked block in this slot: encode_block_device(block, track=True) first")
+        return slot["enc"].ch_bits - slot["fresh"].bits
+
+    def adopt(self, slot, min_excess_bits=1):
+        """Take the fresh (peak, enc) of the slot's last tracked block over for every channel whose drift() is at least
+        min_excess_bits, on the device and without synchronising; returns the boolean device mask [C] of those
+        channels.  self.peak / self.enc are updated IN PLACE: every slot's Encoded record and every later
+        mh_encode_preset read those tensors.  A block is always coded with the word in force when it was enqueued, so
+        the new word applies from the next block on; encode_block() ships (peak, enc) with every block, and the
+        decoder needs nothing new."""
+        take = self.drift(slot) >= int(min_excess_bits)
+        fresh = slot["fresh"]
+        torch.where(take, fresh.peak, self.peak, out=self.peak)
+        torch.where(take, fresh.enc, self.enc, out=self.enc)
+        return take
+
     def close(self):
         for slot in self._slots.values():
             slot["plan"].close()
+            if "monitor" in slot:
+                slot["monitor"].close()
         self._slots = {}
 
     @staticmethod

@@ -45,7 +45,8 @@ extern "C" {
  *   mh_decode_range      -- random access in time: samples [t0, t1) of selected channels, reading only the segments
  *                           that overlap the range
  *   mh_validate_segments -- mh_validate_stream restricted to listed segments (what a range query reads)
- *   mh_decode_rebin      -- mh_decode_range + mh_rebin in one pass: sums of r decoded samples, no byte-per-sample buffer */
+ *   mh_decode_rebin      -- mh_decode_range + mh_rebin in one pass: sums of r decoded samples, no byte-per-sample buffer
+ *   mh_measure           -- also on packed plans: calibrates and prices the 2- / 4-bit pieces directly (drift tracking) */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
@@ -136,10 +137,11 @@ int mh_plan_create(mh_plan **plan, const uint64_t *ch_off, const uint64_t *ch_le
 /* The same for a PACKED input buffer, the intermediate of the time-major (implant-order) path:
  * input_bits = 4 or 2 means channel i is ceil(ch_len[i] / 16) pieces of 8 resp. 4 bytes at ch_off[i]
  * (bytes), as mh_deinterleave_packed writes them; input_bits = 8 is mh_plan_create.  Packed plans
- * cover whole channels (MH_WIN_FULL), 2-bit ones need S <= 4, and only mh_encode_preset reads
- * them (a calibrate-then-stream encoder has its (peak, encoder) word already); mh_measure, mh_encode
- * and mh_decode return MH_ERR_ARG on such a plan -- its stream decodes with an ordinary byte-layout plan
- * over the same channel lengths (segment boundaries depend on lengths and seg_chunks only).
+ * cover whole channels (MH_WIN_FULL) and 2-bit ones need S <= 4.  mh_encode_preset encodes the pieces (a
+ * calibrate-then-stream encoder has its (peak, encoder) word already) and mh_measure calibrates and prices them, which is
+ * how such an encoder notices that its word has gone stale; mh_decode_packed writes them.  mh_encode and mh_decode return MH_ERR_ARG
+ * on such a plan -- its stream decodes with an ordinary byte-layout plan over the same channel lengths (segment boundaries
+ * depend on lengths and seg_chunks only).
  * chunk_stride = 0: a channel's pieces are contiguous.  chunk_stride = B (a multiple of 16, at least
  * one chunk = 1024 pieces): CHUNK-BLOCKED buffer -- the j-th 16384-sample chunk of channel i starts at
  * ch_off[i] + j * B.  With ch_off[i] = i * chunk bytes and B = C * chunk bytes, all channels' chunks
@@ -174,7 +176,14 @@ int mh_plan_query(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, ui
  * Outputs (device, any may be NULL): cutoff[C]; cal_hist[C*S] and post_hist[C*S] in RANK
  * order (what the reference stores in val_histograms / val_histograms_post); peak[C];
  * enc[C]; bits[C]; skipped[C] (post_hist row is all zero and bits 0 for a skipped channel,
- * which the reference's float formula turns into NaN). */
+ * which the reference's float formula turns into NaN).
+ * On a packed plan (mh_plan_create_packed, input_bits 2 or 4, any S the plan accepts) `data` holds the pieces as
+ * mh_deinterleave_packed writes them, contiguous or chunk-blocked as the plan says, and every output is exactly what a
+ * byte-layout plan with the same (ch_len, S, h, mode, MH_WIN_FULL, sclv, K) gives on the unpacked samples: the stored
+ * symbol is min(x, 3) resp. min(x, 15), its bin min(symbol, S-1), the window [0, T) with c = min(2^h, T), skipped 0.
+ * The padding fields of a cut last piece are not counted, whatever they hold, and nothing behind a channel's last piece
+ * is read.  The histograms are counted from the bit fields (no byte-per-sample form): one read of the pieces, a quarter
+ * resp. half of the bytes of the byte layout.  Enqueues a clear of the plan's calibration scratch and four launches. */
 int mh_measure(mh_plan *plan, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_hist,
                uint8_t *peak, uint8_t *enc, uint64_t *post_hist, uint64_t *bits,
                uint8_t *skipped, void *stream);
