@@ -51,9 +51,18 @@ def decompress(c_or_path, channels=None, start=None, stop=None, bin=None):
     directory and the payload of the segments that overlap the range are read.
     bin=r: the same samples summed in bins of r (uint8, saturating at 255 as rebin_u8), decoded in one pass that never
     stores the fine samples (container_io.decompress_binned).  Without a range channel i gets its own ceil(T_i / r)
-    bins; with one every row has ceil((stop - start) / r), and start must be a multiple of r."""
+    bins; with one every row has ceil((stop - start) / r), and start must be a multiple of r.
+    A path that holds a recording archive (archive.py) is answered from the archive: rows of global samples [start,
+    stop) (defaults 0 and the archive's T) across its blocks, the same shapes as for a container."""
     from . import container_io
     is_path = isinstance(c_or_path, (str, bytes)) or hasattr(c_or_path, "__fspath__")
+    if is_path:
+        from . import archive
+        if archive.is_archive(c_or_path):
+            with archive.open(c_or_path) as a:
+                host = a.read(0 if start is None else int(start), a.T if stop is None else int(stop), channels=channels,
+                              bin=None if bin is None else int(bin)).cpu().numpy()
+            return [row.copy() for row in host]
     if bin is not None:
         r = int(bin)
 

@@ -1,0 +1,562 @@
+"""Recording archive: the blocks of a stream appended to ONE file, any time range read back by global time.
+
+A recorder calibrates on its first block and then codes block after block with the stored RAM word (stream.StreamEncoder);
+this module keeps those blocks in one append-only file and answers "channels 3, 17, 40 from step a to step b at bins of r"
+across them.  File layout (little-endian):
+
+    b"MUAHARC1" | u32 header_len | header (UTF-8 JSON: archive_revision, C, S, mode, seg_chunks, hist_bits, K, sclv, meta)
+    block records, back to back:
+        b"MUAHBLK1" | u64 record_len (prefix included) | u64 t_first | u64 Tb | the container_io.write bytes of the block
+    trailer, written by close():
+        b"MUAHIDX1" | u64 n | n x (u64 offset of the block's container bytes, u64 container bytes, u64 t_first, u64 Tb)
+        | u64 offset of the trailer | b"MUAHEND1"
+
+A block is a complete container (container_io.read at its offset returns it, container_io.ContainerFile(path, offset)
+reads it lazily) coded with the word it carries, so a reader needs nothing but the file.  A file without a valid trailer
+-- the writer crashed, or the last record is cut short -- opens by walking the record prefixes; what follows the last
+complete record is ignored and `truncated` is set.  open(path, "a") cuts that tail (and an old trailer) off and goes on
+appending with the word of the last complete block.
+"""
+import builtins
+import json
+import os
+import struct
+from collections import OrderedDict, namedtuple
+
+import numpy as np
+
+from . import MODE_APPROX, MODE_NOSORT, WIN_FULL
+from . import container_io as cio
+
+MAGIC, BLOCK_MAGIC, INDEX_MAGIC, END_MAGIC = b"MUAHARC1", b"MUAHBLK1", b"MUAHIDX1", b"MUAHEND1"
+ARCHIVE_REVISION = 1
+PREFIX = struct.Struct("<8sQQQ")      # block magic, record_len, t_first, Tb
+ENTRY = struct.Struct("<QQQQ")        # offset, nbytes, t_first, Tb
+OPEN_BLOCK_FILES = 16                 # block files a reader keeps open at once (one descriptor each)
+
+Block = namedtuple("Block", "t_first Tb offset nbytes")  # offset / nbytes: the block's container bytes in the file
+
+
+def is_archive(path):
+    with builtins.open(path, "rb") as f:
+        return f.read(8) == MAGIC
+
+
+def block_ranges(t_first, Tb, start, stop):
+    """Global samples [start, stop) over blocks i = [t_first[i], t_first[i] + Tb[i]) (ascending, back to back) ->
+    [(i, a, b)]: block i holds the samples as its local [a, b), a < b; blocks the range misses are not listed."""
+    t_first, Tb = np.asarray(t_first, np.int64), np.asarray(Tb, np.int64)
+    start, stop = int(start), int(stop)
+    if stop <= start or t_first.size == 0:
+        return []
+    end = t_first + Tb
+    i0 = int(np.searchsorted(end, start, side="right"))      # first block that ends after start
+    i1 = int(np.searchsorted(t_first, stop, side="left"))    # first block that begins at or after stop
+    return [(i, max(start - int(t_first[i]), 0), min(stop, int(end[i])) - int(t_first[i])) for i in range(i0, i1)]
+
+
+# ---- index ---------------------------------------------------------------------------------------
+def _load(f, size):
+    """Header and block index of an open archive -> (header, header_bytes, blocks, end of the last complete record,
+    truncated, trailer_bytes, bytes read)."""
+    f.seek(0)
+    head = f.read(12)
+    if len(head) != 12 or head[:8] != MAGIC:
+        raise ValueError("not a MUAHARC1 archive")
+    (n,) = struct.unpack("<I", head[8:])
+    blob = f.read(n)
+    if len(blob) != n:
+        raise ValueError("truncated archive header")
+    hdr = json.loads(blob.decode())
+    if hdr.get("archive_revision") != ARCHIVE_REVISION:
+        raise ValueError("unsupported archive revision %r" % (hdr.get("archive_revision"),))
+    data0, nread = 12 + n, 12 + n
+    # the trailer, when the back pointer leads to one whose entries chain from the header to itself
+    if size >= data0 + 32:
+        f.seek(size - 16)
+        tail = f.read(16)
+        nread += len(tail)
+        idx = struct.unpack("<Q", tail[:8])[0]
+        if tail[8:] == END_MAGIC and data0 <= idx <= size - 32:
+            f.seek(idx)
+            t = f.read(size - 16 - idx)
+            nread += len(t)
+            if t[:8] == INDEX_MAGIC and len(t) == 16 + ENTRY.size * struct.unpack("<Q", t[8:16])[0]:
+                blocks, pos, T = [], data0, 0
+                for k in range((len(t) - 16) // ENTRY.size):
+                    off, nb, t0, Tb = ENTRY.unpack_from(t, 16 + k * ENTRY.size)
+                    if off != pos + PREFIX.size or t0 != T or Tb < 1 or nb < 12:
+                        break
+                    blocks.append(Block(t0, Tb, off, nb))
+                    pos, T = off + nb, T + Tb
+                else:
+                    if pos == idx:
+                        return hdr, data0, blocks, pos, False, size - idx, nread
+    # no trailer: walk the record prefixes
+    blocks, pos, T = [], data0, 0
+    while pos + PREFIX.size + 8 <= size:
+        f.seek(pos)
+        p = f.read(PREFIX.size + 8)
+        nread += len(p)
+        magic, rec, t0, Tb = PREFIX.unpack_from(p)
+        if magic != BLOCK_MAGIC or p[PREFIX.size:] != cio.MAGIC or rec < PREFIX.size + 12 or pos + rec > size or t0 != T or Tb < 1:
+            break
+        blocks.append(Block(t0, Tb, pos + PREFIX.size, rec - PREFIX.size))
+        pos, T = pos + rec, T + Tb
+    return hdr, data0, blocks, pos, True, 0, nread
+
+
+def _archive_fields(hdr):
+    try:
+        C, S, mode, sc, h = (int(hdr[k]) for k in ("C", "S", "mode", "seg_chunks", "hist_bits"))
+        rows = np.ascontiguousarray(np.array(hdr["sclv"], np.uint8).reshape(-1, S))
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError("archive header: %r" % (e,))
+    if C < 1:
+        raise ValueError("archive header: no channels")
+    return C, S, mode, sc, h, rows
+
+
+# ---- reader --------------------------------------------------------------------------------------
+class _BlockFile(cio.ContainerFile):
+    """One block of an archive as a lazily read container; the decode plan belongs to the archive (one per block
+    length), so closing the block closes its descriptor only."""
+
+    def __init__(self, reader, offset):
+        self._reader = reader
+        super().__init__(reader.path, offset)
+
+    def plan(self):
+        return self._reader._plan_for(self)
+
+    def close(self):
+        self._f.close()
+
+
+class Reader:
+    """archive.open(path): C, S, T (total steps), meta, truncated, blocks (Block tuples), block(i), words(), read()."""
+
+    def __init__(self, path):
+        self.path = str(path)
+        self._f = builtins.open(self.path, "rb")
+        try:
+            size = os.fstat(self._f.fileno()).st_size
+            (self.header, self.header_bytes, self.blocks, self._end, self.truncated, self.trailer_bytes,
+             self._own_read) = _load(self._f, size)
+            self.C, self.S, self.mode, self.seg_chunks, self.hist_bits, self.sclv = _archive_fields(self.header)
+        except Exception:
+            self._f.close()
+            raise
+        self.meta = self.header.get("meta", {})
+        self.T = int(sum(b.Tb for b in self.blocks))
+        self._t_first = np.array([b.t_first for b in self.blocks], np.int64)
+        self._Tb = np.array([b.Tb for b in self.blocks], np.int64)
+        self._files = OrderedDict()       # block index -> _BlockFile, least recently used first
+        self._retired_read = 0
+        self._plans = {}
+
+    @property
+    def bytes_read(self):
+        """every byte read from the file so far: header, trailer or prefixes, block heads, payload words"""
+        return self._own_read + self._retired_read + sum(b.bytes_read for b in self._files.values())
+
+    def block(self, i):
+        """-> container_io.Compressed of block i, read whole"""
+        b = self.blocks[i]
+        self._f.seek(b.offset)
+        c = cio.read(self._f)
+        self._own_read += b.nbytes
+        return c
+
+    def block_file(self, i):
+        """-> block i as a container_io.ContainerFile (head read, payload left in the file); cached, at most
+        OPEN_BLOCK_FILES stay open"""
+        bf = self._files.pop(i, None)
+        if bf is None:
+            bf = _BlockFile(self, self.blocks[i].offset)
+            while len(self._files) >= OPEN_BLOCK_FILES:
+                _k, old = self._files.popitem(last=False)
+                self._retired_read += old.bytes_read
+                old.close()
+        self._files[i] = bf
+        return bf
+
+    def words(self):
+        """-> (peak, enc): uint8 [n_blocks, C], the word each block was coded with"""
+        n = len(self.blocks)
+        peak, enc = np.zeros((n, self.C), np.uint8), np.zeros((n, self.C), np.uint8)
+        for i in range(n):
+            bf = self.block_file(i)
+            peak[i], enc[i] = bf.peak, bf.enc
+        return peak, enc
+
+    def _plan_for(self, bf):
+        """one decode plan per distinct block length: segment boundaries depend on the lengths and seg_chunks only"""
+        key = (int(bf.ch_len[0]), int(bf.header["h"]))
+        if key not in self._plans:
+            self._plans[key] = cio._range_plan(bf)
+        return self._plans[key]
+
+    def _checked_block_file(self, i):
+        bf = self.block_file(i)
+        b = self.blocks[i]
+        _check_member(bf, self.C, self.S, self.mode, self.seg_chunks, self.sclv, payload_words=bf.payload_words)
+        if int(bf.ch_len[0]) != b.Tb:
+            raise ValueError("corrupt archive: block %d holds %d steps, its record says %d" % (i, int(bf.ch_len[0]), b.Tb))
+        return bf
+
+    def read(self, start, stop, channels=None, bin=None, saturate=True, time_major=False, check=True, out=None):  # noqa: A002
+        """Global samples [start, stop) of the selected channels -> device tensor.
+        bin=None: uint8 [n_sel, stop - start], row i = min(x, S-1) of channel channels[i] (None = all; any order,
+        repeats allowed), or [stop - start, n_sel] with time_major.
+        bin=r (1..4096, start % r == 0): element b of a row is the sum of the global samples [start + b*r, min(start +
+        b*r + r, stop)) -- uint8 = min(sum, 255) (saturate) or int32 exact sums, [n_sel, ceil((stop - start) / r)]; a
+        bin that straddles a block boundary is summed over both blocks and saturated after that.
+        Only the blocks that overlap the range are opened, and of those only the segments of the selected channels that
+        overlap it are read.  check=True validates those segments (mh_validate_segments) before anything is launched; a
+        decode that had to abandon a segment raises ValueError.  out: optional tensor of the result's shape and dtype
+        with unit stride along its last axis (not with time_major); the rows are written there and nothing else is."""
+        import torch
+        start, stop = int(start), int(stop)
+        if not (0 <= start <= stop <= self.T):
+            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, self.T))
+        sel = np.arange(self.C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
+        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
+            raise IndexError("channel index out of range")
+        r = None if bin is None else int(bin)
+        if r is not None:
+            if not 1 <= r <= 4096:
+                raise ValueError("bin factor %d outside 1..4096" % r)
+            if start % r:
+                raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
+        n, rows = stop - start, int(sel.size)
+        cols = n if r is None else (n + r - 1) // r
+        dtype = torch.uint8 if r is None or saturate else torch.int32
+        if out is not None and (time_major or tuple(out.shape) != (rows, cols) or out.dtype != dtype or
+                                (cols > 1 and rows and out.stride(1) != 1)):
+            raise ValueError("out must be a %s [%d, %d] tensor with unit stride along its last axis" % (dtype, rows, cols))
+        # host side first: every block's words gathered and validated before anything is launched
+        jobs = []
+        if rows and n:
+            for i, a, b in block_ranges(self._t_first, self._Tb, start, stop):
+                bf = self._checked_block_file(i)
+                _sel, payload, seg_off, peak, enc = cio._range_inputs(bf, a, b, sel, check)
+                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc))
+        if not jobs:
+            z = torch.zeros((rows, cols), dtype=dtype, device="cuda") if out is None else out.zero_()
+            return z.t().contiguous() if time_major else z
+        plans = []
+        try:
+            res = self._decode(torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans)
+        finally:
+            ok = all([p.decode_ok() for p in plans])      # synchronises; every plan's flag is read and cleared
+        if not ok:
+            raise ValueError("corrupt archive: a chunk header points outside the payload (decode abandoned)")
+        if not time_major:
+            return res
+        if r is not None:
+            return res.t().contiguous()
+        from . import _lib
+        from .codec import _ptr, _stream
+        tm = torch.empty((n, rows), dtype=torch.uint8, device=res.device)
+        in_off = torch.arange(rows, dtype=torch.int64, device=res.device) * (res.stride(0) if rows > 1 else 0)
+        _lib.check(_lib.lib().mh_interleave(_ptr(res), _ptr(in_off), n, rows, _ptr(tm), _stream()))
+        return tm
+
+    def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans):
+        """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride)."""
+        def launch(job, fn):
+            bf, a, b, g0, payload, seg_off, peak, enc = job
+            plan = self._plan_for(bf)
+            if plan not in plans:
+                plans.append(plan)
+            dev = plan.device
+            pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=dev)
+            if payload.size:
+                pay[:payload.size] = torch.from_numpy(payload.view(np.int32)).to(dev)
+            d_off = torch.from_numpy(seg_off.view(np.int64)).to(dev)
+            fn(plan, pay, d_off, torch.from_numpy(peak.copy()).to(dev), torch.from_numpy(enc.copy()).to(dev), a, b, g0)
+
+        if r is None:
+            if out is None:     # the first block's local sample t at a byte address congruent to t mod 128 (codec.decode_range)
+                phase = jobs[0][1] % 128
+                pitch = (n + phase + 127) // 128 * 128
+                out = torch.empty(rows * pitch, dtype=torch.uint8, device="cuda").as_strided((rows, n), (pitch, 1), phase)
+            for job in jobs:
+                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
+                       plan.decode_range(pay, off, pk, en, sel, a, b, out=out[:, g0:g0 + b - a]))
+            return out
+        # a block whose t_first - start is a multiple of r decodes straight to sums; every bin it touches begins in it
+        aligned = [(job[3] - job[1]) % r == 0 for job in jobs]   # g0 - a == t_first - start: mh_decode_rebin's local rule holds
+        if all(aligned):        # then no bin has samples in two blocks either
+            res = torch.empty((rows, cols), dtype=dtype, device="cuda") if out is None else out
+            for job in jobs:
+                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
+                       plan.decode_rebin(pay, off, pk, en, sel, a, b, r, saturate,
+                                         out=res[:, g0 // r:g0 // r + (b - a + r - 1) // r]))
+            return res
+        # otherwise exact int32 sums: aligned blocks write their bins (in time order, so before any later block adds to
+        # their last, cut bin); the others have no local multiple of r on a global bin boundary -- their samples are
+        # range-decoded behind g0 % r leading zeros and summed per bin on the device
+        acc = torch.zeros((rows, cols), dtype=torch.int32, device="cuda")
+        for job, al in zip(jobs, aligned):
+            if al:
+                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
+                       plan.decode_rebin(pay, off, pk, en, sel, a, b, r, False,
+                                         out=acc[:, g0 // r:g0 // r + (b - a + r - 1) // r]))
+            else:
+                def edge(plan, pay, off, pk, en, a, b, g0):
+                    lead = g0 % r
+                    k = (lead + b - a + r - 1) // r
+                    tmp = torch.zeros((rows, k * r), dtype=torch.uint8, device=plan.device)
+                    plan.decode_range(pay, off, pk, en, sel, a, b, out=tmp[:, lead:lead + b - a])
+                    acc[:, g0 // r:g0 // r + k] += tmp.view(rows, k, r).sum(dim=2, dtype=torch.int32)
+                launch(job, edge)
+        res = acc.clamp_(max=255).to(torch.uint8) if saturate else acc
+        return res if out is None else out.copy_(res)
+
+    def close(self):
+        for p in self._plans.values():
+            p.close()
+        self._plans = {}
+        for bf in self._files.values():
+            self._retired_read += bf.bytes_read
+            bf.close()
+        self._files = OrderedDict()
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ---- writer --------------------------------------------------------------------------------------
+def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None):
+    """ValueError unless c (a Compressed or a ContainerFile) is a block of an archive with these parameters: the check
+    StreamDecoder.decode_block makes, plus the array sizes the directory arithmetic relies on."""
+    hd = c.header
+    cio._header_fields(hd)
+    if (int(hd["S"]) != S or int(hd["mode"]) != mode or int(hd["window"]) != WIN_FULL or int(hd["seg_chunks"]) != seg_chunks):
+        raise ValueError("block (S, mode, window, seg_chunks) = (%s, %s, %s, %s) is not this archive's (%d, %d, %d, %d)"
+                         % (hd["S"], hd["mode"], hd["window"], hd["seg_chunks"], S, mode, WIN_FULL, seg_chunks))
+    if int(hd.get("format_revision", -1)) != cio.FORMAT_REVISION:
+        raise ValueError("an archive block has container format revision %d" % cio.FORMAT_REVISION)
+    if np.asarray(hd["sclv"], np.int64).reshape(-1).tolist() != sclv.astype(np.int64).reshape(-1).tolist():
+        raise ValueError("block SCLV rows are not this archive's")
+    ch_len = np.asarray(c.ch_len, np.uint64)
+    if len(ch_len) != C or int(ch_len[0]) < 1 or (ch_len != ch_len[0]).any():
+        raise ValueError("an archive block holds %d channels of one length" % C)
+    if not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
+        raise ValueError("block arrays disagree about the channel count")
+    nseg = int(cio.segments_per_channel(ch_len, int(hd["h"]), WIN_FULL, seg_chunks).sum())
+    words = int(c.payload.size) if payload_words is None else int(payload_words)
+    if len(c.seg_words) != nseg or int(np.asarray(c.seg_words, np.uint64).sum()) != words:
+        raise ValueError("block directory does not match its header and payload")
+
+
+class Writer:
+    """archive.create(...) / archive.open(path, "a"): append(block), append_compressed(c), flush(), close()."""
+
+    def __init__(self, f, path, header, blocks, word, recalibrate, pipeline):
+        self._f, self.path, self.header = f, str(path), header
+        self.C, self.S, self.mode, self.seg_chunks, self.hist_bits, self.sclv = _archive_fields(header)
+        self.blocks = list(blocks)
+        self.T = int(sum(b.Tb for b in self.blocks))
+        if recalibrate is not None and int(recalibrate) < 1:
+            raise ValueError("recalibrate is None or an excess of at least 1 bit")
+        self.recalibrate = None if recalibrate is None else int(recalibrate)
+        self.pipeline = bool(pipeline)
+        self._word = word                  # (peak, enc) host arrays to go on with, or None: calibrate on the next block
+        self._gpu = None
+        self._pending = None
+        self._n = 0
+        self._block_header = cio.make_header(self.S, 0, self.mode, WIN_FULL, self.seg_chunks, self.sclv)
+        self._block_header["preset"] = True    # what StreamEncoder.encode_block writes
+
+    # -- records
+    def _write_record(self, c, Tb):
+        nb = cio.nbytes(c)
+        pos = self._f.tell()
+        self._f.write(PREFIX.pack(BLOCK_MAGIC, PREFIX.size + nb, self.T, Tb))
+        cio.write(self._f, c)
+        assert self._f.tell() == pos + PREFIX.size + nb
+        self.blocks.append(Block(self.T, Tb, pos + PREFIX.size, nb))
+        self.T += Tb
+
+    def append_compressed(self, c):
+        """Append a block that is already encoded (StreamEncoder.encode_block, or one received over a link).  Needs no
+        GPU.  ValueError when the block is not this archive's (S, mode, seg_chunks, SCLV rows, WIN_FULL, C channels of
+        one length)."""
+        _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv)
+        self._drain()
+        self._write_record(c, int(c.ch_len[0]))
+        self._word = (np.array(c.peak, np.uint8), np.array(c.enc, np.uint8))
+        if self._gpu is not None:       # later append()s go on with this block's word
+            g = self._gpu
+            if g["enc"][0].peak is not None:
+                torch = g["torch"]
+                g["enc"][0].peak.copy_(torch.from_numpy(self._word[0]))
+                g["enc"][0].enc.copy_(torch.from_numpy(self._word[1]))
+
+    # -- device side
+    def _device(self):
+        if self._gpu is None:
+            import torch
+
+            from .stream import StreamEncoder
+            encs = [StreamEncoder(self.C, self.S, self.hist_bits, self.sclv, mode=self.mode, seg_chunks=self.seg_chunks)
+                    for _ in range(2 if self.pipeline else 1)]      # two sets of slot buffers: blocks k and k + 1
+            pin = lambda n, dt: torch.empty(n, dtype=dt).pin_memory()  # noqa: E731
+            sets = [dict(done=None, dense=None, small={}, peak=pin(self.C, torch.uint8), enc=pin(self.C, torch.uint8),
+                         tot=pin(1, torch.int64)) for _ in encs]
+            self._gpu = dict(torch=torch, enc=encs, sets=sets, copy=torch.cuda.Stream(device=encs[0].device))
+        return self._gpu
+
+    def append(self, block):
+        """block: [Tb, C] time-major uint8 counts, host array or device tensor; blocks may differ in length.  Enqueues
+        de-interleave, preset encode (with the drift measure when recalibrate is set) and compaction on the current
+        stream, then the copies of the block's sizes to pinned memory on the archive's copy stream.  pipeline=True:
+        returns then, after writing the PREVIOUS block to the file while this one runs; pipeline=False: waits for this
+        block and writes it."""
+        g = self._device()
+        torch = g["torch"]
+        dev = g["enc"][0].device
+        t = block if isinstance(block, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(block, np.uint8))
+        if t.dim() != 2 or int(t.shape[1]) != self.C or int(t.shape[0]) < 1 or t.dtype != torch.uint8:
+            raise ValueError("a block is a uint8 [Tb >= 1, %d] array" % self.C)
+        t = t.to(dev).contiguous()
+        Tb = int(t.shape[0])
+        k = self._n % len(g["enc"])
+        se, st = g["enc"][k], g["sets"][k]
+        first = g["enc"][0]
+        if first.peak is None:
+            if self._word is None:
+                first.calibrate(t)     # the one device-wide synchronisation of a recording
+            else:
+                first.peak, first.enc = torch.from_numpy(self._word[0]).to(dev), torch.from_numpy(self._word[1]).to(dev)
+            for e in g["enc"][1:]:     # one word, updated in place by adopt(), for both sets
+                e.peak, e.enc = first.peak, first.enc
+        cur = torch.cuda.current_stream()
+        if st["done"] is not None:     # the set's previous block has left its buffers
+            cur.wait_event(st["done"])
+        dense, _tot, slot = se.encode_block_device(t, track=self.recalibrate is not None)
+        st["peak"].copy_(se.peak, non_blocking=True)    # the word this block was coded with: in stream order before adopt()
+        st["enc"].copy_(se.enc, non_blocking=True)
+        if self.recalibrate is not None:
+            se.adopt(slot, self.recalibrate)
+        coded = torch.cuda.Event()
+        coded.record(cur)
+        plan, e = slot["plan"], slot["enc"]
+        if Tb not in st["small"]:
+            st["small"][Tb] = (torch.empty(plan.n_segments, dtype=torch.int64).pin_memory(),
+                               torch.empty(self.C, dtype=torch.int64).pin_memory())
+        segw, bits = st["small"][Tb]
+        sizes = torch.cuda.Event()
+        with torch.cuda.stream(g["copy"]):
+            g["copy"].wait_event(coded)
+            st["tot"].copy_(slot["tot"], non_blocking=True)
+            segw.copy_(e.seg_words[:plan.n_segments], non_blocking=True)
+            bits.copy_(e.ch_bits, non_blocking=True)
+            sizes.record(g["copy"])
+        job = dict(st=st, Tb=Tb, dense=dense.payload, segw=segw, bits=bits, sizes=sizes)
+        self._n += 1
+        self._drain()                  # block k - 1 goes to the file while block k runs
+        self._pending = job
+        if not self.pipeline:
+            self._drain()
+
+    def _drain(self):
+        """Bring the pending block's payload to the host and write its record."""
+        job, self._pending = self._pending, None
+        if job is None:
+            return
+        g = self._gpu
+        torch, st = g["torch"], job["st"]
+        job["sizes"].synchronize()     # this block's kernels and small copies, nothing else
+        total = int(st["tot"][0])
+        if st["dense"] is None or st["dense"].numel() < total:
+            st["dense"] = torch.empty(total + total // 4 + 1024, dtype=torch.int32).pin_memory()
+        done = torch.cuda.Event()
+        with torch.cuda.stream(g["copy"]):
+            st["dense"][:total].copy_(job["dense"][:total], non_blocking=True)
+            done.record(g["copy"])
+        done.synchronize()
+        st["done"] = done
+        c = cio.Compressed(self._block_header, np.full(self.C, job["Tb"], np.uint64), st["peak"].numpy(), st["enc"].numpy(),
+                           np.zeros(self.C, np.uint8), job["bits"].numpy().astype(np.uint64),
+                           job["segw"].numpy().astype(np.uint64), st["dense"][:total].numpy().view(np.uint32))
+        self._write_record(c, job["Tb"])
+        self._word = (st["peak"].numpy().copy(), st["enc"].numpy().copy())
+
+    def flush(self):
+        """every appended block is in the file (not yet the trailer: close() writes it)"""
+        self._drain()
+        self._f.flush()
+
+    def close(self):
+        if self._f is None:
+            return
+        try:
+            self._drain()
+        finally:
+            idx = self._f.tell()
+            self._f.write(INDEX_MAGIC + struct.pack("<Q", len(self.blocks)))
+            for b in self.blocks:
+                self._f.write(ENTRY.pack(b.offset, b.nbytes, b.t_first, b.Tb))
+            self._f.write(struct.pack("<Q", idx) + END_MAGIC)
+            self._f.close()
+            self._f = None
+            if self._gpu is not None:
+                for e in self._gpu["enc"]:
+                    e.close()
+                self._gpu = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def create(path, C, S=3, hist_bits=6, sclv_rows=None, approx=True, seg_chunks=2, recalibrate=None, pipeline=True, meta=None):
+    """Start a new archive (an existing file is replaced) -> Writer, a context manager."""
+    from . import sclv
+    rows = np.asarray(sclv.table(S) if sclv_rows is None else sclv_rows, dtype=np.uint8).reshape(-1, int(S))
+    header = {"archive_revision": ARCHIVE_REVISION, "C": int(C), "S": int(S), "mode": MODE_APPROX if approx else MODE_NOSORT,
+              "seg_chunks": int(seg_chunks), "hist_bits": int(hist_bits), "K": int(rows.shape[0]),
+              "sclv": [[int(v) for v in r] for r in rows], "meta": dict(meta or {})}
+    cio._header_fields(cio.make_header(S, hist_bits, header["mode"], WIN_FULL, seg_chunks, rows))   # range checks
+    _archive_fields(header)
+    blob = json.dumps(header, sort_keys=True).encode()
+    f = builtins.open(path, "wb")
+    try:
+        f.write(MAGIC + struct.pack("<I", len(blob)) + blob)
+        return Writer(f, path, header, [], None, recalibrate, pipeline)
+    except Exception:
+        f.close()
+        raise
+
+
+def open(path, mode="r", recalibrate=None, pipeline=True):  # noqa: A001  (builtins.open is used by name in this module)
+    """mode "r" -> Reader.  mode "a" -> Writer that continues the archive: an incomplete tail and the old trailer are
+    cut off, the word of the last complete block is restored and appending goes on without recalibrating."""
+    if mode == "r":
+        return Reader(path)
+    if mode != "a":
+        raise ValueError("mode is 'r' or 'a'")
+    f = builtins.open(path, "r+b")
+    try:
+        header, _n, blocks, end, _trunc, _tb, _nread = _load(f, os.fstat(f.fileno()).st_size)
+        word = None
+        if blocks:
+            last = cio.ContainerFile(path, blocks[-1].offset)
+            word = (last.peak.copy(), last.enc.copy())
+            last.close()
+        f.truncate(end)
+        f.seek(end)
+        return Writer(f, path, header, blocks, word, recalibrate, pipeline)
+    except Exception:
+        f.close()
+        raise

@@ -60,17 +60,30 @@ def _arrays(c):
             ("seg_words", c.seg_words, np.uint64), ("payload", c.payload, np.uint32)]
 
 
-def write(f, c):
+def _header_blob(c):
     hdr = dict(c.header)
     hdr["sizes"] = {name: int(np.asarray(a).size) for name, a, _ in _arrays(c)}
-    blob = json.dumps(hdr, sort_keys=True).encode()
+    return json.dumps(hdr, sort_keys=True).encode()
+
+
+def nbytes(c):
+    """The number of bytes write() emits for c (archive.py puts it in front of the block)."""
+    n = 12 + len(_header_blob(c))
+    for _name, a, dt in _arrays(c):
+        raw = int(np.asarray(a).size) * np.dtype(dt).itemsize
+        n += raw + (-raw % 8)
+    return n
+
+
+def write(f, c):
+    blob = _header_blob(c)
     f.write(MAGIC)
     f.write(struct.pack("<I", len(blob)))
     f.write(blob)
     for _name, a, dt in _arrays(c):
-        raw = np.ascontiguousarray(a, dtype=dt).tobytes()
+        raw = np.ascontiguousarray(a, dtype=dt).reshape(-1).view(np.uint8)   # written from where it lies: no copy
         f.write(raw)
-        f.write(b"\0" * (-len(raw) % 8))
+        f.write(b"\0" * (-raw.size % 8))
 
 
 def read(f):
@@ -282,14 +295,16 @@ class ContainerFile:
     directory arrays, and remembers where the payload starts.  Same fields as `Compressed` but `payload`;
     read_words() fetches a run of payload words (seek + readinto).  `bytes_read` counts every byte read from the file,
     so that "a range query reads only what it needs" can be checked.  Caches one decode plan of the container's layout
-    (decompress_range)."""
+    (decompress_range).  offset: the byte of the file where the container starts (a block inside an archive, archive.py)."""
 
-    def __init__(self, path):
+    def __init__(self, path, offset=0):
         self.path = str(path)
+        self.offset = int(offset)
         self.bytes_read = 0
         self._plan = None
         self._f = builtins.open(self.path, "rb")
         try:
+            self._f.seek(self.offset)
             self._read_head()
         except Exception:
             self._f.close()
@@ -307,14 +322,14 @@ class ContainerFile:
         hdr = json.loads(self._read(n).decode())
         if hdr.get("format_revision") not in READ_REVISIONS:
             raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
-        pos = 12 + n
+        pos = self.offset + 12 + n
         for name, dt in (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skipped", np.uint8),
                          ("ch_bits", np.uint64), ("seg_words", np.uint64)):
-            nbytes = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
-            raw = self._read(nbytes)
-            if len(raw) != nbytes:
+            size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
+            raw = self._read(size)
+            if len(raw) != size:
                 raise ValueError("truncated container (%s)" % name)
-            pos += nbytes + (-nbytes % 8)
+            pos += size + (-size % 8)
             self._f.seek(pos)
             setattr(self, name, np.frombuffer(raw, dtype=dt).copy())
         self.header = hdr
@@ -353,9 +368,9 @@ class ContainerFile:
 
 
 
-def open(path):  # noqa: A001  (shadows the builtin in this module only: save / load use builtins.open)
+def open(path, offset=0):  # noqa: A001  (shadows the builtin in this module only: save / load use builtins.open)
     """-> ContainerFile: header and directory read, payload left on disk."""
-    return ContainerFile(path)
+    return ContainerFile(path, offset)
 
 
 def _range_plan(c):
