@@ -46,6 +46,7 @@ def __getattr__(name):  # torch-dependent modules load lazily
     import importlib
     if name in ("bit_rates", "compress", "decompress"):
         return getattr(importlib.import_module(".api", __name__), name)
-    if name in ("codec", "container", "container_io", "archive", "synth", "api", "sweep", "stream", "analysis", "functions_1", "drivers", "dist"):
+    if name in ("codec", "container", "container_io", "archive", "synth", "api", "sweep", "stream", "analysis", "functions_1", "drivers", "dist",
+                "events", "_ingest"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

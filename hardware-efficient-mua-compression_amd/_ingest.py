@@ -1,0 +1,52 @@
+"""ctypes binding of libmuahuff_ingest.so (include/muahuff_ingest.h), the front-end companion of libmuahuff.so: spike time
+stamps -> binned counts.  Fails loudly: there is no CPU path."""
+import ctypes as ct
+import os
+
+from ._lib import MH_OK, MuaHuffError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SO = os.path.join(HERE, "libmuahuff_ingest.so")
+
+_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
+
+# every symbol include/muahuff_ingest.h declares, with its prototype
+PROTOTYPES = {
+    "mhi_version": (_int, []),
+    "mhi_last_error": (ct.c_char_p, []),
+    "mhi_bin_events": (_int, [_vp, _vp, _u32, _u64, _u64, _u64, _u32, _vp, _vp, _u64, _vp]),
+}
+
+_lib = None
+
+
+def lib():
+    """Load libmuahuff_ingest.so.  Raises if it has not been built: the product has no fallback."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO):
+            raise ImportError(
+                "libmuahuff_ingest.so is missing (%s). Build it with `python __graft_entry__.py` or "
+                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
+        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
+        l = ct.CDLL(SO)
+        for name, (res, args) in PROTOTYPES.items():
+            f = getattr(l, name)
+            f.restype, f.argtypes = res, args
+        _lib = l
+    return _lib
+
+
+def check(rc):
+    if rc != MH_OK:
+        raise MuaHuffError(rc, lib().mhi_last_error().decode(errors="replace"))
+    return rc
+
+
+def bin_events(ev, origin, period, T, bits, out, d_off, chunk_stride=0):
+    """Enqueue mhi_bin_events on the current stream: the events of `ev` (an events.EventSet) into `out` (uint8 device
+    tensor) at the device offsets `d_off` (int64 / uint64 tensor of C entries)."""
+    import torch
+    check(lib().mhi_bin_events(_vp(ev.ticks.data_ptr()), _vp(ev.ev_off.data_ptr()), ev.C, int(origin), int(period), int(T),
+                               int(bits), _vp(out.data_ptr()), _vp(d_off.data_ptr()), int(chunk_stride),
+                               _vp(torch.cuda.current_stream().cuda_stream)))

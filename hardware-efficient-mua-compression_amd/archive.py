@@ -357,7 +357,8 @@ def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None):
 
 
 class Writer:
-    """archive.create(...) / archive.open(path, "a"): append(block), append_compressed(c), flush(), close()."""
+    """archive.create(...) / archive.open(path, "a"): append(block), append_events(ev, origin, period, T),
+    append_compressed(c), flush(), close()."""
 
     def __init__(self, f, path, header, blocks, word, recalibrate, pipeline):
         self._f, self.path, self.header = f, str(path), header
@@ -427,13 +428,32 @@ class Writer:
         if t.dim() != 2 or int(t.shape[1]) != self.C or int(t.shape[0]) < 1 or t.dtype != torch.uint8:
             raise ValueError("a block is a uint8 [Tb >= 1, %d] array" % self.C)
         t = t.to(dev).contiguous()
-        Tb = int(t.shape[0])
+        self._append(int(t.shape[0]), lambda se: se.calibrate(t),
+                     lambda se, track: se.encode_block_device(t, track=track))
+
+    def append_events(self, ev, origin, period, T):
+        """append() for the block of T bins that `ev` (an events.EventSet of C channels) fills from tick `origin` at
+        `period` ticks per bin: binned on the GPU straight into the encoder's packed pieces
+        (StreamEncoder.encode_events_device; a first block calibrates with calibrate_events), then the same pipeline.
+        The archive's time axis counts bins as before: this block is its next T steps."""
+        T = int(T)
+        if ev.C != self.C or T < 1:
+            raise ValueError("a block of events has %d channels and at least 1 bin" % self.C)
+        self._append(T, lambda se: se.calibrate_events(ev, origin, period, T),
+                     lambda se, track: se.encode_events_device(ev, origin, period, T, track=track))
+
+    def _append(self, Tb, calibrate, encode):
+        """The pipeline of one block: calibrate(encoder) on a first block, encode(encoder, track) -> what
+        encode_block_device returns."""
+        g = self._device()
+        torch = g["torch"]
+        dev = g["enc"][0].device
         k = self._n % len(g["enc"])
         se, st = g["enc"][k], g["sets"][k]
         first = g["enc"][0]
         if first.peak is None:
             if self._word is None:
-                first.calibrate(t)     # the one device-wide synchronisation of a recording
+                calibrate(first)       # the one device-wide synchronisation of a recording
             else:
                 first.peak, first.enc = torch.from_numpy(self._word[0]).to(dev), torch.from_numpy(self._word[1]).to(dev)
             for e in g["enc"][1:]:     # one word, updated in place by adopt(), for both sets
@@ -441,7 +461,7 @@ class Writer:
         cur = torch.cuda.current_stream()
         if st["done"] is not None:     # the set's previous block has left its buffers
             cur.wait_event(st["done"])
-        dense, _tot, slot = se.encode_block_device(t, track=self.recalibrate is not None)
+        dense, _tot, slot = encode(se, self.recalibrate is not None)
         st["peak"].copy_(se.peak, non_blocking=True)    # the word this block was coded with: in stream order before adopt()
         st["enc"].copy_(se.enc, non_blocking=True)
         if self.recalibrate is not None:

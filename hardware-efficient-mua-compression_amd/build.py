@@ -12,6 +12,11 @@ SO = os.path.join(HERE, "libmuahuff.so")
 SOURCES = ["csrc/muahuff.hip"]
 HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csrc/mh_codec2.hpp", "csrc/mh_range.hpp", "csrc/mh_rebin_decode.hpp", "csrc/mh_layout.hpp", "csrc/mh_packed_measure.hpp",
            "csrc/mh_planner.hpp", "csrc/mh_analysis.hpp", "../include/muahuff.h"]
+# the front-end companion (include/muahuff_ingest.h): spike time stamps -> binned counts
+INGEST_SO = os.path.join(HERE, "libmuahuff_ingest.so")
+INGEST_SOURCES = ["csrc/mh_ingest.hip"]
+INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_device.hpp", "../include/muahuff.h",
+                  "../include/muahuff_ingest.h"]
 
 
 def stale():
@@ -36,6 +41,24 @@ def build(force=False, verbose=False):
     return SO
 
 
+def build_ingest(force=False, verbose=False):
+    """libmuahuff_ingest.so, exporting the C ABI of include/muahuff_ingest.h and nothing else
+    (csrc/exports_ingest.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(INGEST_SO):
+        t = os.path.getmtime(INGEST_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in INGEST_SOURCES + INGEST_HEADERS):
+            return INGEST_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_ingest.map")]
+    cmd += [os.path.join(HERE, s) for s in INGEST_SOURCES] + ["-o", INGEST_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return INGEST_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -52,3 +75,4 @@ def build_example(force=False):
 
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
+    print(build_ingest(force=True, verbose=True))

@@ -103,6 +103,28 @@ class ChannelSet:
         return cs
 
     @classmethod
+    def from_events(cls, ev, origin, period, T):
+        """ev: events.EventSet of per-channel spike ticks.  Bin b of channel c = min(255, number of its events with
+        origin + b*period <= tick < origin + (b+1)*period), b < T: stage L0 of the reference (the loaders' histogram2 +
+        uint8(), Data/Load_and_bin_Sabes_store_as_mat_file.m:50-54; the RTL's binner_f) in integer ticks, binned on the
+        GPU (mhi_bin_events) straight into the set's own layout.  Enqueued on the current stream."""
+        from . import _ingest
+        T = int(T)
+        if T < 1:
+            raise ValueError("T is at least 1 bin")
+        off, ln, total = layout([T] * ev.C)
+        # the binner writes every bin: only the padding between and behind the channels is zeroed here
+        data = torch.empty(total + ALIGN, dtype=torch.uint8, device=ev.device)
+        pitch = total // ev.C
+        if pitch > T:
+            data[:total].view(ev.C, pitch)[:, T:] = 0
+        data[total:] = 0
+        cs = cls(data, off, ln)
+        d_off = torch.from_numpy(cs.ch_off.astype(np.int64)).to(ev.device)
+        _ingest.bin_events(ev, origin, period, T, 8, cs.data, d_off)
+        return cs
+
+    @classmethod
     def empty(cls, lengths, device="cuda"):
         off, ln, total = layout(lengths)
         return cls(torch.zeros(total + ALIGN, dtype=torch.uint8, device=device), off, ln)

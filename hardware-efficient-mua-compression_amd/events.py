@@ -1,0 +1,95 @@
+"""Spike events in CSR form on the device, the input of the binner (include/muahuff_ingest.h, mhi_bin_events).
+
+The reference's loaders hold ``spikes{chan}`` -- one vector of spike times per channel -- or a merged ``MUA_vec`` of
+(time, channel) pairs, and bin them with histogram2 over FLOAT edges built by MATLAB's colon operator, whose last bin is
+closed on both sides (Data/Load_and_bin_Sabes_store_as_mat_file.m:30-54).  Those float edges are deliberately NOT
+reproduced here.  The interface is integer ticks, as in the reference's RTL (binner_f counts detections per BIN_PERIOD
+clock ticks, FPGA implementation/1_binner_final.v:19-21): bin b of a channel counts the events with
+origin + b*period <= tick < origin + (b+1)*period, every bin half-open.  ticks_from_seconds() is the one place where
+seconds become ticks, by rounding to the nearest tick of the given clock."""
+import numpy as np
+import torch
+
+
+def ticks_from_seconds(t, rate_hz):
+    """np.rint(t * rate_hz) as uint64: spike times in seconds -> ticks of a clock of rate_hz."""
+    return np.rint(np.asarray(t, dtype=np.float64) * float(rate_hz)).astype(np.uint64)
+
+
+def _ticks_tensor(a, device):
+    if isinstance(a, torch.Tensor):
+        if a.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("ticks are 64-bit integers")
+        return a.reshape(-1).contiguous().to(device)
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind not in "ui":
+        raise ValueError("ticks are integers (ticks_from_seconds converts times)")
+    if a.dtype.kind == "i" and a.size and int(a.min()) < 0:
+        raise ValueError("ticks are not negative")
+    return torch.from_numpy(a.astype(np.uint64).view(np.int64).reshape(-1)).to(device)
+
+
+class EventSet:
+    """ticks: 64-bit device tensor, all channels' time stamps back to back (below 2^63); ev_off: C + 1 offsets into it,
+    channel c owns ticks[ev_off[c]:ev_off[c+1]], non-decreasing.  check=True verifies the offsets on the host and the
+    per-channel order on the device (one synchronising reduction) and raises ValueError."""
+
+    def __init__(self, ticks, ev_off, check=True, device="cuda"):
+        self.ticks = _ticks_tensor(ticks, device)
+        if self.ticks.dtype == torch.uint64:
+            self.ticks = self.ticks.view(torch.int64)
+        off = ev_off.cpu().numpy() if isinstance(ev_off, torch.Tensor) else np.asarray(ev_off)
+        off = np.ascontiguousarray(off).astype(np.uint64).reshape(-1)
+        if off.size < 2:
+            raise ValueError("ev_off has C + 1 entries, C >= 1")
+        self.offsets = off                         # host copy
+        self.ev_off = torch.from_numpy(off.view(np.int64).copy()).to(self.ticks.device)
+        if check:
+            n = int(self.ticks.numel())
+            if int(off[0]) != 0 or int(off[-1]) != n or (np.diff(off.astype(np.int64)) < 0).any():
+                raise ValueError("ev_off must rise from 0 to the number of ticks (%d)" % n)
+            if n:
+                if bool((self.ticks < 0).any()):
+                    raise ValueError("a tick is 2^63 or more")
+                if n > 1:
+                    down = self.ticks[1:] < self.ticks[:-1]
+                    starts = self.ev_off[1:-1]
+                    starts = starts[(starts > 0) & (starts < n)]
+                    down[starts - 1] = False       # a channel may begin below its predecessor's last tick
+                    if bool(down.any()):
+                        raise ValueError("the ticks of a channel are not in non-decreasing order")
+
+    @property
+    def C(self):
+        return int(self.offsets.size) - 1
+
+    @property
+    def device(self):
+        return self.ticks.device
+
+    @classmethod
+    def from_channels(cls, channels, check=True, device="cuda"):
+        """channels: one array of integer ticks per channel (the loader's spikes{chan} after ticks_from_seconds)."""
+        arrs = [np.ascontiguousarray(c).reshape(-1) for c in channels]
+        for a in arrs:
+            if a.size and a.dtype.kind not in "ui":
+                raise ValueError("ticks are integers (ticks_from_seconds converts times)")
+        off = np.zeros(len(arrs) + 1, np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs])
+        ticks = np.concatenate([a.astype(np.uint64) for a in arrs]) if arrs else np.zeros(0, np.uint64)
+        return cls(ticks, off, check=check, device=device)
+
+    @classmethod
+    def from_aer(cls, ticks, channels, C, check=True, device="cuda"):
+        """One merged list of (tick, channel) pairs in time order -- the MUA_vec of the loader -- stable-sorted by
+        channel, so that the time order within each channel is kept."""
+        ticks = np.ascontiguousarray(ticks).reshape(-1)
+        ch = np.ascontiguousarray(channels).reshape(-1).astype(np.int64)
+        if ticks.size != ch.size:
+            raise ValueError("one channel per tick")
+        if ch.size and (ch.min() < 0 or ch.max() >= int(C)):
+            raise ValueError("channel index outside 0..%d" % (int(C) - 1))
+        order = np.argsort(ch, kind="stable")
+        off = np.zeros(int(C) + 1, np.uint64)
+        off[1:] = np.cumsum(np.bincount(ch, minlength=int(C)))
+        return cls(ticks[order], off, check=check, device=device)

@@ -67,6 +67,20 @@ class StreamEncoder:
         self.close()  # cached block plans point at the previous RAM word
         return self.peak, self.enc
 
+    def calibrate_events(self, ev, origin, period, T):
+        """calibrate() on the T bins of `ev` (an events.EventSet) from `origin` at `period` ticks per bin: the counts
+        are binned on the GPU (ChannelSet.from_events), no time-major block is built."""
+        if ev.C != self.C:
+            raise ValueError("event set has %d channels, encoder was built for %d" % (ev.C, self.C))
+        cs = ChannelSet.from_events(ev, origin, period, T)
+        plan = codec.Plan(cs.ch_off, cs.ch_len, self.S, self.h, self.mode, WIN_FULL, self.sclv)
+        m = plan.measure(cs.data)
+        torch.cuda.synchronize()
+        self.peak, self.enc = m.peak.clone(), m.enc.clone()
+        plan.close()
+        self.close()
+        return self.peak, self.enc
+
     def _slot(self, Tb):
         """Plan and device buffers for blocks of Tb time steps, built once and reused: in the
         compression phase every block has the same shape, so nothing is planned or allocated
@@ -129,6 +143,32 @@ class StreamEncoder:
                                                      ct.c_void_p(cs.data.data_ptr()),
                                                      ct.c_void_p(slot["d_off"].data_ptr()), plan.chunk_stride,
                                                      ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self._encode_slot(slot, track)
+
+    def encode_events_device(self, ev, origin, period, T, track=False):
+        """encode_block_device for the block of T bins that `ev` (an events.EventSet) fills from `origin` at `period`
+        ticks per bin: the slot's packed chunk-blocked pieces are written by the binner (mhi_bin_events, min(count, 3)
+        in 2 bits for S <= 4, min(count, 15) in 4 bits for S >= 5) -- no time-major block, no de-interleave.  Everything
+        behind the pieces is the block path's, and so is the stream, byte for byte."""
+        from . import _ingest
+        if self.peak is None:
+            raise RuntimeError("calibrate() first")
+        if ev.C != self.C:
+            raise ValueError("event set has %d channels, encoder was built for %d" % (ev.C, self.C))
+        T = int(T)
+        if T < 1:
+            raise ValueError("T is at least 1 bin")
+        slot = self._slot(T)
+        cs, plan = slot["cs"], slot["plan"]
+        _ingest.bin_events(ev, origin, period, T, plan.input_bits, cs.data, slot["d_off"], plan.chunk_stride)
+        return self._encode_slot(slot, track)
+
+    def _encode_slot(self, slot, track):
+        """The block path behind the slot's packed pieces: optional drift measure, preset encode, compaction."""
+        import ctypes as ct
+
+        from . import _lib
+        cs, plan = slot["cs"], slot["plan"]
         if track:
             self._monitor(slot).measure(cs.data, out=slot["fresh"])
         enc = slot["enc"]
@@ -143,7 +183,9 @@ class StreamEncoder:
     def encode_block(self, block):
         """block: [Tb, C] time-major counts -> container_io.Compressed covering all Tb bins of
         every channel, coded with the stored RAM word."""
-        dense, tot, slot = self.encode_block_device(block)
+        return self._finish_block(*self.encode_block_device(block))
+
+    def _finish_block(self, dense, tot, slot):
         plan, cs, enc = slot["plan"], slot["cs"], slot["enc"]
         torch.cuda.synchronize()
         total = int(tot.item())
@@ -153,6 +195,10 @@ class StreamEncoder:
                                        enc.skipped.cpu().numpy(), enc.ch_bits.cpu().numpy().astype(np.uint64),
                                        enc.seg_words.cpu().numpy().astype(np.uint64)[:plan.n_segments],
                                        dense.payload[:total].cpu().numpy().view(np.uint32).copy())
+
+    def encode_events(self, ev, origin, period, T):
+        """encode_block for the T bins that `ev` fills from `origin` at `period` ticks per bin."""
+        return self._finish_block(*self.encode_events_device(ev, origin, period, T))
 
     def drift(self, slot):
         """int64 device tensor [C]: the code bits the slot's last tracked block spent under the word it was coded with,

@@ -1,0 +1,425 @@
+"""mhi_bin_events (include/muahuff_ingest.h) on the GPU, and the event entry points built on it.
+
+Every expectation is NumPy in this file: np.bincount((ticks - origin) // period) per channel, np.minimum(..., cap) and,
+for the pieces, the bit packing that muahuff.h documents for mh_deinterleave_packed.  Every call is checked at bits 8
+(contiguous, byte offsets that are no multiple of anything), 4 and 2 (contiguous and chunk-blocked), byte for byte over
+the WHOLE output buffer: it starts as canaries, and whatever is not a bin or a piece of a channel must still be one."""
+import ctypes as ct
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+CH = 16384
+CANARY = 0xA5
+LAYOUTS = [(8, False), (4, False), (4, True), (2, False), (2, True)]
+TOP = 1 << 63
+
+
+@pytest.fixture(scope="module")
+def mh():
+    importlib.import_module("hardware-efficient-mua-compression_amd.build").build_ingest()
+    import muahuff
+    assert torch.cuda.is_available(), "GPU tests need a MI355X"
+    assert "gfx950" in muahuff.device_info(0)["arch"]
+    torch.cuda.set_device(0)
+    return muahuff
+
+
+# ---- the yardstick -----------------------------------------------------------------------------------------------
+def counts_of(chans, origin, period, T):
+    """[C, T] int64: events per bin, from the definition"""
+    out = np.zeros((len(chans), T), np.int64)
+    o, span = np.uint64(origin), np.uint64(T * period)
+    for c, a in enumerate(chans):
+        a = np.asarray(a, dtype=np.uint64)
+        rel = a[a >= o] - o
+        rel = rel[rel < span]
+        out[c] = np.bincount((rel // np.uint64(period)).astype(np.int64), minlength=T)
+    return out
+
+
+def pack(row, bits):
+    """one channel's capped counts -> its pieces (muahuff.h: sample i in bits [i * bits, (i + 1) * bits), 16 per piece)"""
+    s = np.zeros((len(row) + 15) // 16 * 16, np.uint8)
+    s[:len(row)] = row
+    if bits == 4:
+        return s[0::2] | (s[1::2] << 4)
+    return s[0::4] | (s[1::4] << 2) | (s[2::4] << 4) | (s[3::4] << 6)
+
+
+class Layout:
+    """where the channels go in a canary buffer, and the expected image of that buffer"""
+
+    def __init__(self, C, T, bits, blocked):
+        self.C, self.T, self.bits, self.blocked = C, T, bits, blocked
+        self.stride = 0
+        if bits == 8:
+            self.off = 203 + np.arange(C, dtype=np.uint64) * np.uint64(T + 37)      # odd addresses, 37 guard bytes between
+            self.size = int(self.off[-1]) + T + 301
+        elif not blocked:
+            nbytes = (T + 15) // 16 * 2 * bits
+            self.off = 256 + np.arange(C, dtype=np.uint64) * np.uint64((nbytes + 15) // 16 * 16 + 16)
+            self.size = int(self.off[-1]) + nbytes + 272
+        else:
+            cb = CH * bits // 8
+            self.stride = C * cb + 48
+            self.off = 256 + np.arange(C, dtype=np.uint64) * np.uint64(cb)
+            self.size = 256 + (T + CH - 1) // CH * self.stride + 256
+
+    def image(self, counts, skip=()):
+        """-> (expected bytes, mask of the bytes that are compared: all but the regions of the channels in `skip`)"""
+        img = np.full(self.size, CANARY, np.uint8)
+        mask = np.ones(self.size, bool)
+        cap = (1 << self.bits) - 1
+        for c in range(self.C):
+            row = np.minimum(counts[c], cap).astype(np.uint8)
+            o = int(self.off[c])
+            if self.bits == 8:
+                spans = [(o, row)]
+            else:
+                p = pack(row, self.bits)
+                cb = CH * self.bits // 8
+                spans = [(o + j * self.stride, p[j * cb:(j + 1) * cb]) for j in range((self.T + CH - 1) // CH)] \
+                    if self.blocked else [(o, p)]
+            for at, b in spans:
+                img[at:at + len(b)] = b
+                if c in skip:
+                    mask[at:at + len(b)] = False
+        return img, mask
+
+
+class Events:
+    def __init__(self, mh, chans):
+        from muahuff import events
+        self.chans = [np.asarray(a, dtype=np.uint64) for a in chans]
+        self.ev = events.EventSet.from_channels(self.chans, check=False)
+
+
+def run(mh, ev, origin, period, T, bits, blocked, stream=None, lay=None, buf=None):
+    """one call into a fresh canary buffer -> (Layout, device buffer, return code)"""
+    lay = lay or Layout(ev.C, T, bits, blocked)
+    if buf is None:
+        buf = torch.full((lay.size,), CANARY, dtype=torch.uint8, device="cuda")
+    d_off = getattr(lay, "d_off", None)
+    if d_off is None:
+        d_off = lay.d_off = torch.from_numpy(lay.off.view(np.int64)).cuda()
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    rc = mh._ingest.lib().mhi_bin_events(ct.c_void_p(ev.ticks.data_ptr()), ct.c_void_p(ev.ev_off.data_ptr()), ev.C, origin,
+                                         period, T, bits, ct.c_void_p(buf.data_ptr()), ct.c_void_p(d_off.data_ptr()),
+                                         lay.stride, ct.c_void_p(st))
+    return lay, buf, rc
+
+
+def check_all_layouts(mh, chans, origin, period, T, tag, skip=()):
+    e = Events(mh, chans)
+    counts = counts_of(e.chans, origin, period, T)
+    for bits, blocked in LAYOUTS:
+        lay, buf, rc = run(mh, e.ev, origin, period, T, bits, blocked)
+        assert rc == 0, (tag, bits, blocked, mh._ingest.lib().mhi_last_error())
+        want, mask = lay.image(counts, skip)
+        got = buf.cpu().numpy()
+        bad = np.flatnonzero((got != want) & mask)
+        assert bad.size == 0, (tag, bits, blocked, "first differing byte %d of %d: got %d, want %d; %d differ"
+                               % (bad[0], lay.size, got[bad[0]], want[bad[0]], bad.size))
+    return counts
+
+
+# ---- 1. tile and piece edges -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [1, 15, 16, 17, 16383, 16384, 16385, 2 * 16384 + 7])
+def test_tile_and_piece_edges(mh, T):
+    origin, period = 1000, 7
+    end = origin + T * period
+    bins = [b for b in (0, 15, 16, 16383, 16384, T - 1) if b < T]
+    ticks = sorted(set([origin + b * period for b in bins] + [origin + b * period + period - 1 for b in bins]))
+    rng = np.random.default_rng(T)
+    chans = [
+        np.array(sorted([origin - 1] + ticks + [end - 1, end - 1, end])),              # placed on purpose, both bin edges
+        np.zeros(0, np.uint64),                                                         # no events at all
+        np.array([origin - 5, origin - 1, end, end, end + 1000]),                       # events only outside the range
+        origin + np.arange(T, dtype=np.uint64) * 7 + 3,                                 # one event in every bin
+        np.sort(rng.integers(origin - 50, end + 50, size=min(4 * T, 3000))),            # a few anywhere
+    ]
+    counts = check_all_layouts(mh, chans, origin, period, T, ("edges", T))
+    assert counts[1].sum() == 0 and counts[2].sum() == 0 and (counts[3] == 1).all()
+    assert counts[0][T - 1] >= 2 and counts[0].sum() == len(chans[0]) - 2      # all but origin - 1 and `end`
+
+
+# ---- 2. saturation and runs --------------------------------------------------------------------------------------
+def test_saturation_and_runs(mh):
+    origin, period, T = 77, 7, 2 * CH + 7
+    tick = lambda b, k=0: origin + b * period + k      # noqa: E731
+    runs = (2, 3, 4, 15, 16, 255, 256)
+    chans = []
+    # one bin per run length, equal ticks; a second bin with the same number of DIFFERENT ticks of one bin, repeated
+    a = []
+    for i, n in enumerate(runs):
+        a += [tick(100 + 3 * i)] * n
+    for i, n in enumerate(runs):
+        a += sorted(tick(5000 + 2 * i, k % period) for k in range(n))
+    chans.append(np.array(sorted(a)))
+    # 70 000 equal ticks in one bin between two single events: longer than any pass of the kernel
+    chans.append(np.array([tick(8999)] + [tick(9000, 3)] * 70000 + [tick(9001)]))
+    # 70 000 in-bin ticks in the last bin of chunk 0 AND in its neighbour, the first bin of chunk 1
+    k = np.sort(np.arange(70000) % period)
+    chans.append(np.concatenate([tick(CH - 1) + k, tick(CH) + k]).astype(np.uint64))
+    # the same around the second boundary, with the cut last chunk behind it
+    chans.append(np.concatenate([[tick(2 * CH - 2)], tick(2 * CH - 1) + k, [tick(2 * CH)] * 300, [tick(T - 1)] * 17]).astype(np.uint64))
+    counts = check_all_layouts(mh, chans, origin, period, T, "runs")
+    for i, n in enumerate(runs):
+        assert counts[0][100 + 3 * i] == n and counts[0][5000 + 2 * i] == n
+    assert counts[1][9000] == 70000 and counts[2][CH - 1] == 70000 and counts[2][CH] == 70000
+    # (what the library wrote there was compared above with min(count, 255 / 15 / 3))
+
+
+# ---- 3. arithmetic -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("period", [1, 7, 30, 24414, (1 << 18) - 1, 1 << 18, (1 << 40) + 12345])
+@pytest.mark.parametrize("where", ["zero", "2^62", "top"])
+def test_bin_arithmetic_is_exact(mh, period, where):
+    T = CH + 17
+    origin = {"zero": 0, "2^62": 1 << 62, "top": TOP - T * period}[where]     # "top": the last bin ends at tick 2^63 - 1
+    assert origin + T * period <= TOP
+    end = origin + T * period
+    rng = np.random.default_rng(period % 1000 + len(where))
+    edge = []
+    for b in (0, 1, 255, 256, CH - 1, CH, T - 2, T - 1):
+        edge += [origin + b * period, origin + b * period + period - 1, origin + b * period + period // 2]
+    some = [int(origin + int(x) * period + int(y)) for x, y in zip(rng.integers(0, T, 2000), rng.integers(0, period, 2000))]
+    a = sorted(edge + some + [end - 1] * 3 + ([origin - 1] if origin else []) + [t for t in (end, end + 1, TOP - 1) if t < TOP])
+    chans = [np.array(a, dtype=np.uint64), np.array([TOP - 1] * 5, dtype=np.uint64),
+             np.array(sorted(some[:700]), dtype=np.uint64)]
+    counts = check_all_layouts(mh, chans, origin, period, T, ("arith", period, where))
+    assert counts[0][T - 1] >= 3 and counts[0][0] >= 1
+    assert counts[1].sum() == (5 if end == TOP else 0)
+
+
+def test_a_range_beyond_2_63_is_refused(mh):
+    """origin + T * period may reach 2^63 (the case "top" above) and not exceed it: ticks are below 2^63, so nothing is
+    lost, and the bin bounds then never wrap.  The call is refused with MH_ERR_ARG and nothing is written."""
+    e = Events(mh, [np.array([5, 6, TOP - 1], dtype=np.uint64)])
+    for origin, period, T in ((1 << 62, 1 << 49, CH), (1, 1, TOP), (TOP - 99, 10, 10), ((1 << 64) - 1, 1, 1)):
+        lay = Layout(1, 100, 8, False)
+        lay, buf, rc = run(mh, e.ev, origin, period, T, 8, False, lay=lay)
+        assert rc == mh._lib.ERR_ARG and b"2^63" in mh._ingest.lib().mhi_last_error()
+        assert bool((buf == CANARY).all())
+    lay, buf, rc = run(mh, e.ev, TOP - 100, 10, 10, 8, False)
+    assert rc == 0 and buf.cpu().numpy()[int(lay.off[0]):][:10].tolist() == [0] * 9 + [1]
+
+
+# ---- 4. random ---------------------------------------------------------------------------------------------------
+def poisson_events(C, T, mean, origin, period, seed):
+    """-> per-channel sorted ticks with Poisson(mean) events per bin, spread over the ticks of their bin"""
+    rng = np.random.default_rng(seed)
+    n = rng.poisson(mean, size=C * T)
+    first = np.cumsum(n) - n
+    b = np.repeat(np.arange(C * T, dtype=np.int64), n)
+    rank = np.arange(b.size, dtype=np.int64) - np.repeat(first, n)
+    tick = (origin + (b % T) * period + rank * period // np.repeat(n, n)).astype(np.uint64)
+    cut = np.cumsum(n.reshape(C, T).sum(axis=1))[:-1]
+    return np.split(tick, cut)
+
+
+@pytest.mark.parametrize("mean", [0.03, 3.0])
+def test_random_poisson_events(mh, mean):
+    C, T, origin, period = 70, 147461, 123456789, 30
+    chans = poisson_events(C, T, mean, origin, period, seed=20240917)
+    counts = check_all_layouts(mh, chans, origin, period, T, ("poisson", mean))
+    assert abs(counts.mean() - mean) < 0.01 * max(mean, 1) and counts.max() >= (2 if mean < 1 else 10)
+
+
+# ---- 5. unsorted input -------------------------------------------------------------------------------------------
+def test_unsorted_input_stays_inside_its_channel(mh):
+    from muahuff import events
+    C, T, origin, period = 4, 2 * CH + 100, 500, 30
+    chans = poisson_events(C, T, 0.4, origin, period, seed=5)
+    chans[2] = chans[2][::-1].copy()                       # one channel in descending order
+    check_all_layouts(mh, chans, origin, period, T, "unsorted", skip=(2,))
+    with pytest.raises(ValueError, match="non-decreasing"):
+        events.EventSet.from_channels(chans, check=True)
+    chans[2] = chans[2][::-1].copy()
+    ev = events.EventSet.from_channels(chans, check=True)  # in order again: accepted
+    assert ev.C == C
+    with pytest.raises(ValueError):
+        events.EventSet(np.array([1, 2, TOP], dtype=np.uint64), [0, 3])     # a tick of 2^63
+    with pytest.raises(ValueError):
+        events.EventSet(np.array([1, 2, 3], dtype=np.uint64), [0, 2])       # offsets that do not cover the ticks
+    # the boundary between two channels is no order violation, and from_aer keeps the time order within a channel
+    aer = events.EventSet.from_aer(np.array([5, 6, 6, 9, 11, 12]), np.array([1, 0, 1, 1, 0, 1]), 3)
+    assert aer.offsets.tolist() == [0, 2, 6, 6] and aer.ticks.cpu().tolist() == [6, 11, 5, 6, 9, 12]
+
+
+# ---- 6. graph capture --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bits,blocked", LAYOUTS)
+def test_capture_and_replay(mh, bits, blocked):
+    """The call captured into a graph on a non-blocking stream and replayed, with the contents of the event buffers
+    replaced before every replay (the pattern of tests/test_gpu_async_contract.py::_replay)."""
+    C, T, origin, period = 6, 3 * CH + 11, 40, 30
+    sets = [poisson_events(C, T, m, origin, period, seed=s) for m, s in ((0.2, 1), (1.5, 2), (0.05, 3))]
+    want = [counts_of(ch, origin, period, T) for ch in sets]
+    cap = max(sum(len(a) for a in ch) for ch in sets)
+    pins = []
+    for ch in sets:
+        tk = torch.zeros(cap, dtype=torch.int64).pin_memory()
+        flat = np.concatenate(ch)
+        tk[:flat.size] = torch.from_numpy(flat.view(np.int64))
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(a) for a in ch])]).astype(np.int64)).pin_memory()
+        pins.append((tk, off))
+
+    class Ev:
+        pass
+    ev = Ev()
+    ev.C, ev.ticks, ev.ev_off = C, torch.zeros(cap, dtype=torch.int64, device="cuda"), torch.zeros(C + 1, dtype=torch.int64, device="cuda")
+    lay = Layout(C, T, bits, blocked)
+    buf = torch.full((lay.size,), CANARY, dtype=torch.uint8, device="cuda")
+    pin_out = torch.empty(lay.size, dtype=torch.uint8).pin_memory()
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+
+    def load(k):
+        ev.ticks.copy_(pins[k][0], non_blocking=True)
+        ev.ev_off.copy_(pins[k][1], non_blocking=True)
+        buf.fill_(CANARY)
+
+    def verify(k):
+        pin_out.copy_(buf, non_blocking=True)
+        side.synchronize()
+        img, _ = lay.image(want[k])
+        got = pin_out.numpy()
+        assert np.array_equal(got, img), (bits, blocked, k, int(np.flatnonzero(got != img)[0]))
+        return got.copy()
+
+    with torch.cuda.stream(side):
+        load(0)
+        assert run(mh, ev, origin, period, T, bits, blocked, stream=st, lay=lay, buf=buf)[2] == 0     # warm-up outside capture
+        verify(0)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        assert run(mh, ev, origin, period, T, bits, blocked, stream=st, lay=lay, buf=buf)[2] == 0
+    seen = {}
+    for k in (1, 2, 1, 0):
+        with torch.cuda.stream(side):
+            load(k)
+            g.replay()
+            got = verify(k)
+        assert k not in seen or np.array_equal(seen[k], got)
+        seen[k] = got
+
+
+# ---- 7. through the stack ----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def recording(mh):
+    """70 channels x 147 461 bins of events whose counts reach past S - 1 for both S, and the binned block"""
+    C, T, origin, period = 70, 147461, 1 << 40, 30
+    chans = poisson_events(C, T, 0.6, origin, period, seed=77)
+    counts = counts_of(chans, origin, period, T)
+    assert counts.max() >= 5
+    return dict(C=C, T=T, origin=origin, period=period, chans=chans, counts=np.minimum(counts, 255).astype(np.uint8))
+
+
+def _copy(t):
+    return t.detach().clone().cpu().numpy()
+
+
+@pytest.mark.parametrize("T", [40000, 147461])
+@pytest.mark.parametrize("S", [3, 5])
+def test_stream_encoder_from_events_equals_the_block_path(mh, recording, S, T):
+    from muahuff import events, sclv, stream
+    r = recording
+    C, origin, period = r["C"], r["origin"], r["period"]
+    binned = r["counts"][:, :T]
+    block = torch.from_numpy(np.ascontiguousarray(binned.T)).cuda()                 # [T, C] time-major
+    ev = events.EventSet.from_channels(r["chans"])                                  # events past T are ignored
+    tab = sclv.table(S)
+    a, b = stream.StreamEncoder(C, S, 6, tab), stream.StreamEncoder(C, S, 6, tab)
+    try:
+        a.calibrate(block[:64])
+        b.calibrate_events(ev, origin, period, 64)
+        assert torch.equal(a.peak, b.peak) and torch.equal(a.enc, b.enc)
+        # a stale word on purpose, the same for both: drift() then has something to say
+        a.peak.fill_(S - 1)
+        b.peak.fill_(S - 1)
+        da, ta, sa = a.encode_block_device(block, track=True)
+        db, tb, sb = b.encode_events_device(ev, origin, period, T, track=True)
+        n = sa["plan"].n_segments
+        assert sb["plan"].n_segments == n
+        tot = int(ta.item())
+        assert int(tb.item()) == tot and tot > 0
+        assert np.array_equal(_copy(db.payload[:tot]), _copy(da.payload[:tot])), "dense stream"
+        assert np.array_equal(_copy(db.seg_words[:n]), _copy(da.seg_words[:n])), "seg_words"
+        assert np.array_equal(_copy(sb["enc"].ch_bits), _copy(sa["enc"].ch_bits)), "ch_bits"
+        assert np.array_equal(_copy(sb["enc"].peak), _copy(sa["enc"].peak)) and np.array_equal(_copy(sb["enc"].enc), _copy(sa["enc"].enc))
+        dr = _copy(b.drift(sb))
+        assert np.array_equal(dr, _copy(a.drift(sa))) and (dr > 0).any()
+        # the pieces themselves: every byte the binner wrote is what the de-interleaver wrote
+        assert torch.equal(sb["cs"].data, sa["cs"].data)
+        sd = stream.StreamDecoder(C, S, tab)
+        try:
+            got = sd.decode_block_device(db.payload, db.seg_words, b.peak, b.enc, T, seg_off=db.seg_off)
+            assert sd.ok()
+            assert np.array_equal(got.cpu().numpy(), np.minimum(binned, S - 1).T)
+        finally:
+            sd.close()
+        took = b.adopt(sb)
+        assert bool(took.any())
+        # host form
+        c = b.encode_events(ev, origin, period, T)
+        assert np.array_equal(stream.StreamEncoder.decode_block(c), np.minimum(binned, S - 1).T)
+    finally:
+        a.close()
+        b.close()
+
+
+def test_channel_set_from_events_through_the_container(mh, recording):
+    import muahuff
+    from muahuff import container, events
+    r = recording
+    T, S, H = 40000, 4, 6
+    ev = events.EventSet.from_channels(r["chans"][:9])
+    cs = container.ChannelSet.from_events(ev, r["origin"], r["period"], T)
+    assert cs.C == 9 and (cs.ch_len == T).all()
+    binned = r["counts"][:9, :T]
+    assert np.array_equal(np.stack(cs.to_channels()), binned)
+    guard = cs.data.cpu().numpy()
+    for c in range(9):          # the set's padding between the channels is still zero
+        o = int(cs.ch_off[c]) + T
+        nxt = int(cs.ch_off[c + 1]) if c + 1 < 9 else guard.size
+        assert not guard[o:nxt].any()
+    got = muahuff.decompress(muahuff.compress(cs, S=S, hist_bits=H))
+    want = np.minimum(binned, S - 1)
+    want[:, :1 << H] = 0        # the container codes what follows the calibration window; zeros before it
+    assert np.array_equal(np.stack(got), want)
+
+
+def test_archive_append_events(mh, recording, tmp_path):
+    from muahuff import archive, events
+    r = recording
+    C, origin, period, S = r["C"], r["origin"], r["period"], 3
+    ev = events.EventSet.from_channels(r["chans"])
+    T0, T1 = 40000, 2 * CH + 5
+    fn = str(tmp_path / "ev.mua")
+    with archive.create(fn, C, S=S, hist_bits=6, recalibrate=8) as w:
+        w.append_events(ev, origin, period, T0)
+        w.append_events(ev, origin + T0 * period, period, T1)          # the same events, a later origin
+        with pytest.raises(ValueError):
+            w.append_events(events.EventSet.from_channels(r["chans"][:3]), origin, period, 100)
+    want = np.minimum(r["counts"][:, :T0 + T1], S - 1)
+    with archive.open(fn) as a:
+        assert a.T == T0 + T1 and [b.Tb for b in a.blocks] == [T0, T1]
+        assert np.array_equal(a.read(0, a.T).cpu().numpy(), want)
+        p, q = T0 - 1000, T0 + 3000
+        assert np.array_equal(a.read(p, q, channels=[5, 0, 69]).cpu().numpy(), want[[5, 0, 69], p:q])
+        for rb in (7, 50):
+            p_ = p - p % rb
+            x = want[:, p_:q].astype(np.int64)
+            pad = (-x.shape[1]) % rb
+            exp = np.pad(x, ((0, 0), (0, pad))).reshape(C, -1, rb).sum(axis=2)
+            assert np.array_equal(a.read(p_, q, bin=rb).cpu().numpy(), np.minimum(exp, 255))
+    # the block path writes the same file
+    fb = str(tmp_path / "blk.mua")
+    with archive.create(fb, C, S=S, hist_bits=6, recalibrate=8) as w:
+        w.append(np.ascontiguousarray(r["counts"][:, :T0].T))
+        w.append(np.ascontiguousarray(r["counts"][:, T0:T0 + T1].T))
+    assert open(fn, "rb").read() == open(fb, "rb").read()
