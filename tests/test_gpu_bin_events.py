@@ -3,7 +3,12 @@
 Every expectation is NumPy in this file: np.bincount((ticks - origin) // period) per channel, np.minimum(..., cap) and,
 for the pieces, the bit packing that muahuff.h documents for mh_deinterleave_packed.  Every call is checked at bits 8
 (contiguous, byte offsets that are no multiple of anything), 4 and 2 (contiguous and chunk-blocked), byte for byte over
-the WHOLE output buffer: it starts as canaries, and whatever is not a bin or a piece of a channel must still be one."""
+the WHOLE output buffer: it starts as canaries, and whatever is not a bin or a piece of a channel must still be one.
+
+Every shape in this file is small enough that mhi_bin_events gives each workgroup ONE chunk (span 1): what is tested
+here is the search, the passes, the run logic and the store of a single chunk.  The walk of one workgroup over 2, 4 and
+8 chunks -- the cursor carried on, the tile zeroed and reused, chunks without events in between -- is
+tests/test_gpu_bin_events_spans.py, which imports the yardstick and the helpers of this file."""
 import ctypes as ct
 import importlib
 
@@ -323,15 +328,13 @@ def _copy(t):
     return t.detach().clone().cpu().numpy()
 
 
-@pytest.mark.parametrize("T", [40000, 147461])
-@pytest.mark.parametrize("S", [3, 5])
-def test_stream_encoder_from_events_equals_the_block_path(mh, recording, S, T):
+def stream_events_equal_block(chans, binned, origin, period, S, T, host_form=True):
+    """StreamEncoder.encode_events_device on the events `chans` against encode_block_device on the time-major block of
+    their counts `binned` ([C, T] uint8): the same stream, byte for byte, and StreamDecoder gives min(counts, S - 1)"""
     from muahuff import events, sclv, stream
-    r = recording
-    C, origin, period = r["C"], r["origin"], r["period"]
-    binned = r["counts"][:, :T]
+    C = binned.shape[0]
     block = torch.from_numpy(np.ascontiguousarray(binned.T)).cuda()                 # [T, C] time-major
-    ev = events.EventSet.from_channels(r["chans"])                                  # events past T are ignored
+    ev = events.EventSet.from_channels(chans)                                       # events past T are ignored
     tab = sclv.table(S)
     a, b = stream.StreamEncoder(C, S, 6, tab), stream.StreamEncoder(C, S, 6, tab)
     try:
@@ -364,12 +367,19 @@ def test_stream_encoder_from_events_equals_the_block_path(mh, recording, S, T):
             sd.close()
         took = b.adopt(sb)
         assert bool(took.any())
-        # host form
-        c = b.encode_events(ev, origin, period, T)
-        assert np.array_equal(stream.StreamEncoder.decode_block(c), np.minimum(binned, S - 1).T)
+        if host_form:
+            c = b.encode_events(ev, origin, period, T)
+            assert np.array_equal(stream.StreamEncoder.decode_block(c), np.minimum(binned, S - 1).T)
     finally:
         a.close()
         b.close()
+
+
+@pytest.mark.parametrize("T", [40000, 147461])
+@pytest.mark.parametrize("S", [3, 5])
+def test_stream_encoder_from_events_equals_the_block_path(mh, recording, S, T):
+    r = recording
+    stream_events_equal_block(r["chans"], r["counts"][:, :T], r["origin"], r["period"], S, T)
 
 
 def test_channel_set_from_events_through_the_container(mh, recording):
@@ -423,3 +433,52 @@ def test_archive_append_events(mh, recording, tmp_path):
         w.append(np.ascontiguousarray(r["counts"][:, :T0].T))
         w.append(np.ascontiguousarray(r["counts"][:, T0:T0 + T1].T))
     assert open(fn, "rb").read() == open(fb, "rb").read()
+
+
+# ---- 8. the offset table in pinned host memory -------------------------------------------------------------------
+def _pinned_case(mh):
+    C, T, origin, period = 5, 2 * CH + 7, 1000, 7
+    chans = poisson_events(C, T, 0.5, origin, period, seed=8)
+    return C, T, origin, period, Events(mh, chans), counts_of(chans, origin, period, T)
+
+
+@pytest.mark.parametrize("blocked", [False, True])
+def test_pinned_offset_table_gives_the_device_tables_image(mh, blocked):
+    """out_off may live in pinned host memory: the library checks its alignment there and the kernel reads it in place"""
+    C, T, origin, period, e, counts = _pinned_case(mh)
+    lay, buf, rc = run(mh, e.ev, origin, period, T, 4, blocked)                    # the table in device memory
+    assert rc == 0, mh._ingest.lib().mhi_last_error()
+    pin = Layout(C, T, 4, blocked)
+    pin.d_off = torch.from_numpy(pin.off.view(np.int64).copy()).pin_memory()
+    assert pin.d_off.is_pinned() and not pin.d_off.is_cuda
+    _, got, rc = run(mh, e.ev, origin, period, T, 4, blocked, lay=pin)
+    assert rc == 0, mh._ingest.lib().mhi_last_error()
+    torch.cuda.synchronize()                                                        # the table is read until here
+    want, _ = lay.image(counts)
+    assert np.array_equal(buf.cpu().numpy(), want) and torch.equal(got, buf)
+
+
+@pytest.mark.parametrize("bits,blocked", [(4, False), (4, True), (2, True)])
+def test_misaligned_pinned_offset_table_is_refused(mh, bits, blocked):
+    """A host-readable table is checked before anything is enqueued: MH_ERR_ARG names the entry, nothing is written.
+    (A misaligned table in device-only memory is documented as unchecked and is not passed here.)"""
+    C, T, origin, period, e, _ = _pinned_case(mh)
+    for c, add in ((3, 8), (0, 1), (C - 1, 15)):
+        lay = Layout(C, T, bits, blocked)
+        off = lay.off.copy()
+        off[c] += np.uint64(add)
+        assert off[c] % 16 and all(off[k] % 16 == 0 for k in range(C) if k != c)
+        lay.d_off = torch.from_numpy(off.view(np.int64)).pin_memory()
+        _, buf, rc = run(mh, e.ev, origin, period, T, bits, blocked, lay=lay)
+        msg = mh._ingest.lib().mhi_last_error()
+        assert rc == mh._lib.ERR_ARG and (b"out_off[%d]=%d" % (c, int(off[c]))) in msg and b"multiple of 16" in msg, msg
+        torch.cuda.synchronize()
+        assert bool((buf == CANARY).all())
+    # at 8 bits there is no alignment to ask for: the same odd table is taken (offsets of the 8-bit layout are odd anyway)
+    lay = Layout(C, T, 8, False)
+    lay.d_off = torch.from_numpy(lay.off.view(np.int64).copy()).pin_memory()
+    assert (lay.off % 16 != 0).any()
+    _, buf, rc = run(mh, e.ev, origin, period, T, 8, False, lay=lay)
+    assert rc == 0, mh._ingest.lib().mhi_last_error()
+    torch.cuda.synchronize()
+    assert np.array_equal(buf.cpu().numpy(), lay.image(counts_of(e.chans, origin, period, T))[0])
