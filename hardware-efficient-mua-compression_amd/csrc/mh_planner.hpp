@@ -114,6 +114,7 @@ struct PlanHost {
     // segment directory
     std::vector<uint32_t> seg_ch;
     std::vector<uint64_t> seg_first, seg_n, seg_off;
+    std::vector<uint64_t> ch_seg0;  // C + 1: channel c's segments are the consecutive entries [ch_seg0[c], ch_seg0[c + 1])
     // workgroup tasks of the shared-table kernels: <= 4 consecutive segments of one channel
     std::vector<uint32_t> task_seg0;
     std::vector<uint8_t> task_n;
@@ -235,9 +236,11 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
     };
     p.seg_src_stride = src_bytes(seg_samples);
     p.slot_full = slot_words(seg_samples, I.maxlen);
+    p.ch_seg0.assign((size_t)C + 1, 0);
     for (uint32_t c = 0; c < C; ++c) {
         const uint64_t n = p.w1[c] - p.w0[c];
         size_t seg_begin = p.seg_ch.size();
+        p.ch_seg0[c] = seg_begin;
         auto add_segment = [&](uint64_t first, uint64_t m) {
             p.seg_ch.push_back(c);
             p.seg_first.push_back(first);
@@ -293,6 +296,7 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
     }
     p.measure_fused = ((uint64_t)1 << I.h) <= kCalDirect && C <= kFusedMeasureChannels && p.tile_ch.size() <= kFusedMeasureTiles;
     I.n_segments = p.seg_ch.size();
+    p.ch_seg0[C] = I.n_segments;
     I.payload_cap_words = slot + 4;  // decode reads <= 3 words past the last chunk
     // per-wave-table kernels when the shared-table tasks would leave more than 1 wave in 16 idle
     // (channels of a few segments); their wave tasks run longest first

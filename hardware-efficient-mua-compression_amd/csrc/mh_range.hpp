@@ -1,6 +1,7 @@
 // mh_range.hpp -- random access in time: decode samples [t0, t1) of selected channels (mh_decode_range).
 //
-// The work list is built on the host from the plan's directory (muahuff.hip, mh_decode_range): one RangeTask per
+// The work list is built on the host from the plan's directory (mh_worklist.hpp, which also holds the records RangeTask /
+// RangeWg / RangeFill; muahuff.hip caches and uploads it): one RangeTask per
 // segment that overlaps the range, up to four consecutive tasks of one output row per workgroup (RangeWg), so that
 // the channel's decode tables are built once per workgroup as in k_decode2.  A task names the chunks of its segment
 // that hold in-range samples: leading chunks before t0 are passed over by scanning their headers only, the decode
@@ -12,33 +13,9 @@
 #pragma once
 
 #include "mh_codec2.hpp"
+#include "mh_worklist.hpp"
 
 namespace mh {
-
-// One segment that overlaps the range (48 bytes).  Chunk c0 of the segment is the first one holding an in-range
-// sample; `ncnk` chunks from c0 on (n samples in all) are decoded, and of those the bytes [lo, hi) are written, at
-// out + dst + (sample index from chunk c0's first sample).  dst may be negative: nothing below lo is written.
-struct RangeTask {
-    int64_t dst;    // bytes from `out` to chunk c0's first sample in its output row
-    uint32_t seg;   // directory entry (its seg_off entry is read)
-    uint32_t skip;  // chunks in front of c0 (full chunks: header scanned, payload passed over)
-    uint32_t ncnk;  // chunks decoded
-    uint32_t n;     // samples in those chunks
-    uint32_t lo;    // first byte written (< 16384: inside chunk c0)
-    uint32_t hi;    // one past the last byte written (> (ncnk - 1) * 16384: inside the last chunk)
-    uint32_t scr;   // scratch slot of the task's cut chunks (16 KiB each; unused when lo == 0 and hi == n)
-    uint32_t pad_[3];
-};
-
-// Up to four consecutive tasks of one output row (one channel), one wave each; tables shared at LDS offset 0.
-struct RangeWg {
-    uint32_t task0, ntask, ch, pad_;
-};
-
-// Zero fill of bytes [off, off + n) of `out` (the parts of a row outside its channel's window).
-struct RangeFill {
-    uint64_t off, n;
-};
 
 struct RangeArgs {
     Dec2Args a;  // a.d: payload, payload_words, seg_off, err, epoch; a.W / peak / enc / codes / S / mode / nK: the tables

@@ -1,6 +1,7 @@
 // mh_rebin_decode.hpp -- decode straight to a coarser bin period (mh_decode_rebin): out[b] = sum of r decoded samples.
 //
-// The work list is mh_decode_range's (one RebinTask per segment that overlaps the range, up to four consecutive tasks
+// The work list (built by mh_worklist.hpp, which holds the records RebinTask / RebinFix and kNoSlot) is
+// mh_decode_range's (one RebinTask per segment that overlaps the range, up to four consecutive tasks
 // of one output row per workgroup, tables shared), but the decoded bytes never reach memory: decode_segment is
 // instantiated with a SINK (RebinSink) that receives every decoded row -- 1024 consecutive samples, 16 per lane --
 // in registers and turns it into bin sums:
@@ -20,28 +21,6 @@
 #include "mh_range.hpp"
 
 namespace mh {
-
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
-
-// One segment that overlaps the range (64 bytes).  Sample x of the task = sample x counted from the first sample of
-// chunk c0 (RangeTask); it lies in the task's bin (ph + x) / r, and the task's bin j is element dst + j of `out`.
-struct RebinTask {
-    int64_t dst;      // elements from `out` to the task's bin 0 (may be one bin before the row: nothing below jfirst is written)
-    uint32_t seg;     // directory entry
-    uint32_t skip;    // chunks in front of c0 (passed over)
-    uint32_t n;       // samples decoded (whole chunks from c0 on, or up to the segment's end)
-    uint32_t lo, hi;  // samples [lo, hi) of those are in range; the others count as 0
-    uint32_t ph;      // position of sample 0 inside its bin (< r)
-    uint32_t jfirst, jlast;  // bins of samples lo and hi - 1
-    uint32_t head, tail;     // side slot of bin jfirst / jlast when another task touches it too, else kNoSlot
-    uint32_t pad_[4];
-};
-
-// out[off] = side[slot] (saturated for the u8 form)
-struct RebinFix {
-    uint64_t off;
-    uint32_t slot, pad_;
-};
 
 struct RebinArgs {
     Dec2Args a;  // as RangeArgs

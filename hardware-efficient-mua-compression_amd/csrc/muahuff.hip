@@ -18,6 +18,7 @@
 #include "mh_planner.hpp"
 #include "mh_range.hpp"
 #include "mh_rebin_decode.hpp"
+#include "mh_worklist.hpp"
 // The library is built with -fvisibility=hidden: the C ABI of include/muahuff.h is ALL it exports
 // (tests/test_host.py compares the dynamic symbol table with the header's prototypes).
 #pragma GCC visibility push(default)
@@ -63,14 +64,33 @@ int alloc(T **dst, size_t n)
 
 }  // namespace
 
+// The work list of the last mh_decode_range / mh_decode_rebin call on a plan (mh_worklist.hpp): the same query again
+// reuses it as it is on the device.  w keeps the host copy alive until the next call has synchronised.
+struct ListCache {
+    std::vector<uint32_t> sel;  // the query the list answers; empty: no valid list
+    uint64_t t0 = 0, t1 = 0, pitch = 0;
+    uint32_t r = 0;  // (0: the range call)
+    mh::WorkList w;
+    uint8_t *d_list = nullptr, *d_aux = nullptr;  // w.blob; the list's w.naux scratch slots / side words
+    size_t cap = 0, aux_cap = 0;
+
+    bool same_query(const uint32_t *s, uint32_t n, uint64_t a, uint64_t b, uint32_t r_, uint64_t pitch_) const
+    {
+        return t0 == a && t1 == b && r == r_ && pitch == pitch_ && sel.size() == n && std::equal(s, s + n, sel.begin());
+    }
+    const uint8_t *wgs() const { return d_list + w.b_task; }
+    const uint8_t *fixes() const { return wgs() + w.b_wg; }
+    const uint8_t *fills() const { return fixes() + w.b_fix; }
+};
+
 struct mh_plan {
     int device = 0;
     mh::PlanHost h;  // everything the planner computed (host copies)
     // device tables
     uint64_t *d_ch_off = nullptr, *d_ch_len = nullptr, *d_w0 = nullptr, *d_w1 = nullptr;
     uint8_t *d_skip = nullptr, *d_sclv = nullptr;
-    uint32_t *d_sclv16 = nullptr;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_done = nullptr;  // fused measure: tiles per channel, arrival tickets  // the K rows padded to 16 bytes: one vector load per lane in the in-wave calibration
+    uint32_t *d_sclv16 = nullptr;  // the K rows padded to 16 bytes: one vector load per lane in the in-wave calibration
+    uint32_t *d_tile_cnt = nullptr, *d_tile_done = nullptr;  // fused measure: tiles per channel, arrival tickets
     uint32_t *d_codes = nullptr;
     uint32_t *d_seg_ch = nullptr;
     uint64_t *d_seg_first = nullptr, *d_seg_n = nullptr, *d_seg_off = nullptr;
@@ -92,28 +112,7 @@ struct mh_plan {
     size_t packed_cal_tiles = 0;  // packed plans: calibration tiles on the device (every window: the pieces are never scanned by k_calibrate)
     unsigned long long *d_acc = nullptr;  // wave-task encoder: per-channel {bits << 24 | finished records} (zero between launches)
     uint32_t *d_err = nullptr;  // decode status word (mh_decode_status): non-zero once a decode abandoned a segment
-    // mh_decode_range: the work list of the last call (host copy kept alive until the next call has synchronised),
-    // its device copy, the 16-KiB scratch slots of cut chunks, and each channel's first directory entry
-    std::vector<uint8_t> range_host;
-    uint8_t *d_range = nullptr, *d_range_scr = nullptr;
-    size_t range_cap = 0, range_scr_cap = 0;
-    // the query that work list answers (sel, t0, t1, out_pitch): the same query again reuses it as it is on the device
-    std::vector<uint32_t> range_sel;
-    uint64_t range_t0 = 0, range_t1 = 0, range_pitch = 0;
-    size_t range_b_task = 0, range_b_wg = 0, range_nwg = 0, range_nfill = 0;
-    uint64_t range_max_fill = 0;
-    std::vector<uint64_t> ch_seg0;
-    // mh_decode_rebin: the same for its work list (tasks, workgroups, fix-up and fill records) and the u32 side array
-    // of the bins that several tasks add up
-    std::vector<uint8_t> rebin_host;
-    uint8_t *d_rebin = nullptr;
-    uint32_t *d_rebin_side = nullptr;
-    size_t rebin_cap = 0, rebin_side_cap = 0;
-    std::vector<uint32_t> rebin_sel;
-    uint64_t rebin_t0 = 0, rebin_t1 = 0, rebin_pitch = 0;
-    uint32_t rebin_r = 0;
-    size_t rebin_b_task = 0, rebin_b_wg = 0, rebin_b_fix = 0, rebin_nwg = 0, rebin_nfix = 0, rebin_nfill = 0, rebin_nside = 0;
-    uint64_t rebin_max_fill = 0;
+    ListCache range, rebin;  // mh_decode_range (scratch slots of cut chunks) / mh_decode_rebin (side words of shared bins)
 };
 
 struct mh_sweep {
@@ -133,34 +132,6 @@ static int check_device(int device, const char *who)
     MH_HIP(hipGetDevice(&d));
     if (d != device)
         return fail(MH_ERR_ARG, "%s: the plan was created on device %d, the current device is %d", who, device, d);
-    return MH_OK;
-}
-
-static mh::CalArgs calibrate_args(const mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_hist,
-                                  uint8_t *peak, uint8_t *enc, unsigned long long *zero_hist,
-                                  unsigned long long *zero_bits, uint8_t *skip_dst);
-
-static int launch_calibrate(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_hist,
-                            uint8_t *peak, uint8_t *enc, hipStream_t st, unsigned long long *zero_hist,
-                            unsigned long long *zero_bits, uint8_t *skip_dst)
-{
-    const mh_plan_info_t &I = p->h.info;
-    mh::CalArgs a = calibrate_args(p, data, cutoff, cal_hist, peak, enc, zero_hist, zero_bits, skip_dst);
-    if (!p->h.cal_tile_ch.empty()) {  // long calibration windows (2^h > kCalDirect): tiled histogram first
-        MH_HIP(hipMemsetAsync(p->d_calhist, 0, (size_t)a.C * mh::kHistStride * sizeof(unsigned long long), st));
-        mh::HistArgs ha{};
-        ha.data = data;
-        ha.ch_off = p->d_ch_off;
-        ha.tile_ch = p->d_cal_tile_ch;
-        ha.tile_start = p->d_cal_tile_start;
-        ha.tile_n = p->d_cal_tile_n;
-        ha.hist = p->d_calhist;
-        ha.tile_slot = nullptr;
-        hipLaunchKernelGGL(mh::k_hist2<4>, dim3((unsigned)p->h.cal_tile_ch.size()), dim3(256), 0, st, ha, I.S);
-        a.pre_hist = p->d_calhist;
-    }
-    hipLaunchKernelGGL(mh::k_calibrate, dim3((a.C + 3) / 4), dim3(256), 0, st, a);
-    MH_HIP(hipGetLastError());
     return MH_OK;
 }
 
@@ -192,6 +163,30 @@ static mh::CalArgs calibrate_args(const mh_plan *p, const uint8_t *data, uint64_
     a.lut = p->d_lut;
     a.pre_hist = nullptr;
     return a;
+}
+
+static int launch_calibrate(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_hist,
+                            uint8_t *peak, uint8_t *enc, hipStream_t st, unsigned long long *zero_hist,
+                            unsigned long long *zero_bits, uint8_t *skip_dst)
+{
+    const mh_plan_info_t &I = p->h.info;
+    mh::CalArgs a = calibrate_args(p, data, cutoff, cal_hist, peak, enc, zero_hist, zero_bits, skip_dst);
+    if (!p->h.cal_tile_ch.empty()) {  // long calibration windows (2^h > kCalDirect): tiled histogram first
+        MH_HIP(hipMemsetAsync(p->d_calhist, 0, (size_t)a.C * mh::kHistStride * sizeof(unsigned long long), st));
+        mh::HistArgs ha{};
+        ha.data = data;
+        ha.ch_off = p->d_ch_off;
+        ha.tile_ch = p->d_cal_tile_ch;
+        ha.tile_start = p->d_cal_tile_start;
+        ha.tile_n = p->d_cal_tile_n;
+        ha.hist = p->d_calhist;
+        ha.tile_slot = nullptr;
+        hipLaunchKernelGGL(mh::k_hist2<4>, dim3((unsigned)p->h.cal_tile_ch.size()), dim3(256), 0, st, ha, I.S);
+        a.pre_hist = p->d_calhist;
+    }
+    hipLaunchKernelGGL(mh::k_calibrate, dim3((a.C + 3) / 4), dim3(256), 0, st, a);
+    MH_HIP(hipGetLastError());
+    return MH_OK;
 }
 
 // window or calibration histogram of a packed plan over `nt` of its tiles (mh_packed_measure.hpp)
@@ -437,31 +432,43 @@ static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t 
     return launch_decode<2, 2, 25, 2, false, PO>(p, a, st);
 }
 
-// The range decoder on the rung dispatch_decode picks for the plan's maxlen L and table width W, always in the workgroup
-// form (a long range on long channels is the case that matters; the wave-task one-symbol rung has no workgroup form, its
-// plans take the hybrid pair table as long-channel plans do).  Instances: k_decode_range<4, 4, 17, 1, false> (L <= 2),
-// <2, 2, 25, 2, false> (L == 3), <2, 2, 32, 0, false> (W >= 2L), <2, 2, 31, 2, true> (W < 2L).
+// The decoder rung of the range calls: the one dispatch_decode picks for maxlen L and table width W, always in the
+// workgroup form (a long range on long channels is the case that matters; the wave-task one-symbol rung has no workgroup
+// form, its plans take the hybrid pair table as long-channel plans do).  f is called with the rung's template arguments
+// <K, M, NR, RL, HY> as a Rung: <4, 4, 17, 1, false> (L <= 2), <2, 2, 25, 2, false> (L == 3), <2, 2, 32, 0, false>
+// (W >= 2L), <2, 2, 31, 2, true> (W < 2L).
+template <int K_, int M_, int NR_, int RL_, bool HY_>
+struct Rung {
+    static constexpr int K = K_, M = M_, NR = NR_, RL = RL_;
+    static constexpr bool HY = HY_;
+};
+
+template <class F>
+static int range_rung(uint32_t L, uint32_t W, F f)
+{
+    if (L <= 2) return f(Rung<4, 4, 17, 1, false>{});
+    if (L != 3) {
+        if (W >= 2 * L) return f(Rung<2, 2, 32, 0, false>{});
+        return f(Rung<2, 2, 31, 2, true>{});
+    }
+    return f(Rung<2, 2, 25, 2, false>{});
+}
+
 static int dispatch_decode_range(const mh_plan *p, const mh::RangeArgs &r, uint32_t nwg, hipStream_t st)
 {
-    const uint32_t L = p->h.info.maxlen;
-    if (L <= 2) return launch_decode_range<4, 4, 17, 1, false>(r, nwg, st);
-    if (L != 3) {
-        if (r.a.W >= 2 * L) return launch_decode_range<2, 2, 32, 0, false>(r, nwg, st);
-        return launch_decode_range<2, 2, 31, 2, true>(r, nwg, st);
-    }
-    return launch_decode_range<2, 2, 25, 2, false>(r, nwg, st);
+    return range_rung(p->h.info.maxlen, r.a.W, [&](auto g) {
+        using R = decltype(g);
+        return launch_decode_range<R::K, R::M, R::NR, R::RL, R::HY>(r, nwg, st);
+    });
 }
 
 // the fused decode + re-bin kernel on the same rungs
 static int dispatch_decode_rebin(const mh_plan *p, const mh::RebinArgs &r, bool sat, uint32_t nwg, hipStream_t st)
 {
-    const uint32_t L = p->h.info.maxlen;
-    if (L <= 2) return launch_decode_rebin<4, 4, 17, 1, false>(r, sat, nwg, st);
-    if (L != 3) {
-        if (r.a.W >= 2 * L) return launch_decode_rebin<2, 2, 32, 0, false>(r, sat, nwg, st);
-        return launch_decode_rebin<2, 2, 31, 2, true>(r, sat, nwg, st);
-    }
-    return launch_decode_rebin<2, 2, 25, 2, false>(r, sat, nwg, st);
+    return range_rung(p->h.info.maxlen, r.a.W, [&](auto g) {
+        using R = decltype(g);
+        return launch_decode_rebin<R::K, R::M, R::NR, R::RL, R::HY>(r, sat, nwg, st);
+    });
 }
 
 static int dispatch_decode(const mh_plan *p, uint32_t po, const mh::Dec2Args &a, hipStream_t st)
@@ -545,7 +552,7 @@ int mh_plan_destroy(mh_plan *p)
                     p->d_tile_n, p->d_tile_start, p->d_hist, p->d_peak, p->d_enc,
                     p->d_lut, p->d_wg_tasks, p->d_wave_tasks, p->d_scan,
                     p->d_cal_tile_ch, p->d_cal_tile_n, p->d_cal_tile_start, p->d_calhist, p->d_err, p->d_acc,
-                    p->d_range, p->d_range_scr, p->d_rebin, p->d_rebin_side};
+                    p->range.d_list, p->range.d_aux, p->rebin.d_list, p->rebin.d_aux};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     delete p;
@@ -963,97 +970,80 @@ int mh_decode_status(mh_plan *p, uint32_t *flags, void *stream)
     return MH_OK;
 }
 
-// mh_decode_range's work list for (sel, t0, t1, out_pitch), built from the host directory and uploaded to the plan's
-// buffers (arguments already checked).  Synchronises `st` first: the previous range decode may still read them.
-static int range_work_list(mh_plan *p, const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint64_t out_pitch,
-                           hipStream_t st)
+// grow-or-keep of one of a ListCache's device buffers
+static int grow(uint8_t **d, size_t *cap, size_t bytes)
 {
-    const mh::PlanHost &H = p->h;
-    const uint32_t C = H.info.C;
-    const uint64_t len = t1 - t0;
-    p->range_sel.clear();  // (no valid list while this one is being built)
-    if (p->ch_seg0.empty()) {  // each channel's first directory entry (its segments are consecutive)
-        p->ch_seg0.assign((size_t)C + 1, 0);
-        for (uint32_t c : H.seg_ch) ++p->ch_seg0[(size_t)c + 1];
-        for (uint32_t c = 0; c < C; ++c) p->ch_seg0[(size_t)c + 1] += p->ch_seg0[c];
-    }
-    // ---- the work list, from the host directory
-    std::vector<mh::RangeTask> tasks;
-    std::vector<mh::RangeWg> wgs;
-    std::vector<mh::RangeFill> fills;
-    uint32_t nscr = 0;
-    uint64_t max_fill = 0;
-    auto fill = [&](uint64_t off, uint64_t n) {
-        fills.push_back(mh::RangeFill{off, n});
-        if (n > max_fill) max_fill = n;
-    };
-    for (uint32_t i = 0; i < n_sel; ++i) {
-        const uint32_t c = sel[i];
-        const uint64_t row = (uint64_t)i * out_pitch, w0 = H.w0[c], w1 = H.w1[c];
-        const uint64_t a = t0 > w0 ? t0 : w0, b = t1 < w1 ? t1 : w1;  // in-window part, channel samples
-        if (a >= b) {
-            fill(row, len);
-            continue;
-        }
-        if (a > t0) fill(row, a - t0);
-        if (b < t1) fill(row + (b - t0), t1 - b);
-        const uint64_t ra = a - w0, rb = b - w0;  // the same, window samples
-        const uint64_t *sf0 = H.seg_first.data();
-        uint64_t s = (uint64_t)(std::upper_bound(sf0 + p->ch_seg0[c], sf0 + p->ch_seg0[(size_t)c + 1], ra) - sf0) - 1;
-        const size_t task0 = tasks.size();
-        for (; s < p->ch_seg0[(size_t)c + 1] && H.seg_first[s] < rb; ++s) {
-            const uint64_t sf = H.seg_first[s], sn = H.seg_n[s];
-            const uint64_t lo = (ra > sf ? ra : sf) - sf, hi = (rb < sf + sn ? rb : sf + sn) - sf;
-            const uint64_t c0 = lo / MH_CHUNK, c1 = (hi - 1) / MH_CHUNK, base = c0 * MH_CHUNK;
-            mh::RangeTask t{};
-            t.dst = (int64_t)(row + w0 + sf + base) - (int64_t)t0;
-            t.seg = (uint32_t)s;
-            t.skip = (uint32_t)c0;
-            t.ncnk = (uint32_t)(c1 - c0 + 1);
-            t.n = (uint32_t)(sn - base < (uint64_t)t.ncnk * MH_CHUNK ? sn - base : (uint64_t)t.ncnk * MH_CHUNK);
-            t.lo = (uint32_t)(lo - base);
-            t.hi = (uint32_t)(hi - base);
-            t.scr = t.lo > 0 || t.hi < t.n ? nscr++ : 0u;
-            tasks.push_back(t);
-        }
-        for (size_t k = task0; k < tasks.size(); k += 4)
-            wgs.push_back(mh::RangeWg{(uint32_t)k, (uint32_t)(tasks.size() - k < 4 ? tasks.size() - k : 4), c, 0u});
-    }
-    // ---- upload (one copy)
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t b_task = up16(tasks.size() * sizeof(mh::RangeTask)), b_wg = up16(wgs.size() * sizeof(mh::RangeWg));
-    const size_t bytes = b_task + b_wg + fills.size() * sizeof(mh::RangeFill);
-    // the previous call's kernels may still read the task buffer and the scratch (one stream at a time per plan)
+    if (bytes <= *cap) return MH_OK;
+    if (*d) MH_HIP(hipFree(*d));
+    *d = nullptr;
+    *cap = 0;
+    MH_HIP(hipMalloc(reinterpret_cast<void **>(d), bytes));
+    *cap = bytes;
+    return MH_OK;
+}
+
+// The list `w` of the query (sel, t0, t1, r, out_pitch) becomes the cache's: uploaded in one copy, with room for its
+// w.naux auxiliary slots of aux_unit bytes.  Synchronises `st` first: the previous call's kernels may still read the
+// buffers (one stream at a time per plan).  The cache holds no valid list from the first line until the copy is enqueued.
+static int upload_list(ListCache &c, mh::WorkList &&w, size_t aux_unit, const uint32_t *sel, uint32_t n_sel, uint64_t t0,
+                       uint64_t t1, uint32_t r, uint64_t out_pitch, hipStream_t st)
+{
+    c.sel.clear();
     MH_HIP(hipStreamSynchronize(st));
-    if (bytes > p->range_cap) {
-        if (p->d_range) MH_HIP(hipFree(p->d_range));
-        p->d_range = nullptr;
-        p->range_cap = 0;
-        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_range), bytes));
-        p->range_cap = bytes;
+    int rc;
+    if ((rc = grow(&c.d_list, &c.cap, w.blob.size())) || (rc = grow(&c.d_aux, &c.aux_cap, (size_t)(w.naux ? w.naux : 1) * aux_unit)))
+        return rc;
+    c.w = std::move(w);
+    // (never empty: every row of a non-empty query yields a task or a fill record)
+    MH_HIP(hipMemcpyAsync(c.d_list, c.w.blob.data(), c.w.blob.size(), hipMemcpyHostToDevice, st));
+    c.sel.assign(sel, sel + n_sel);
+    c.t0 = t0;
+    c.t1 = t1;
+    c.r = r;
+    c.pitch = out_pitch;
+    return MH_OK;
+}
+
+// What mh_decode_range and mh_decode_rebin (`who`) ask of their arguments.  r: the bin factor, 1 for the range call,
+// whose rows are then t1 - t0 elements long and whose bin-factor checks cannot fire.  *empty: nothing to decode.
+static int check_range_call(const char *who, const mh_plan *p, const uint32_t *payload, const uint64_t *seg_off, const uint32_t *sel,
+                            uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r, const uint8_t *peak, const uint8_t *enc,
+                            const void *out, uint64_t out_pitch, bool *empty)
+{
+    if (!p || (n_sel && !sel)) return fail(MH_ERR_ARG, "%s: NULL argument", who);
+    if (p->h.input_bits != 8)
+        return fail(MH_ERR_ARG, "%s: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan", who);
+    if (r < 1 || r > 4096) return fail(MH_ERR_ARG, "%s: bin factor %u outside 1..4096", who, r);
+    if (t0 > t1 || t1 > p->h.max_T)
+        return fail(MH_ERR_ARG, "%s: [%llu, %llu) is not a range inside [0, %llu)", who, (unsigned long long)t0,
+                    (unsigned long long)t1, (unsigned long long)p->h.max_T);
+    if (t0 % r) return fail(MH_ERR_ARG, "%s: t0 = %llu is not a multiple of the bin factor %u", who, (unsigned long long)t0, r);
+    const uint32_t C = p->h.info.C;
+    for (uint32_t i = 0; i < n_sel; ++i)
+        if (sel[i] >= C) return fail(MH_ERR_ARG, "%s: sel[%u] = %u, the plan has %u channels", who, i, sel[i], C);
+    const uint64_t nb = (t1 - t0 + r - 1) / r;
+    if (n_sel > 1 && out_pitch < nb)
+        return fail(MH_ERR_ARG, "%s: out_pitch %llu below the row length %llu", who, (unsigned long long)out_pitch,
+                    (unsigned long long)nb);
+    *empty = n_sel == 0 || nb == 0;
+    if (*empty) return MH_OK;
+    if (!payload || !seg_off || !peak || !enc || !out) return fail(MH_ERR_ARG, "%s: NULL argument", who);
+    return check_device(p->device, who);
+}
+
+// The cache's fill records, launch(grid, first record): y = up to 65535 records per launch, the workgroups of x stride
+// over the longest one (per_block elements per workgroup and pass).
+extern "C++" template <class Launch>
+static int launch_fills(const ListCache &c, uint64_t per_block, Launch launch)
+{
+    const uint64_t nb = (c.w.max_fill + per_block - 1) / per_block;
+    const unsigned nx = (unsigned)(nb < 1 ? 1 : nb < 1024 ? nb : 1024);
+    const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(c.fills());
+    for (size_t f = 0; f < c.w.nfill; f += 65535) {
+        const unsigned ny = (unsigned)(c.w.nfill - f < 65535 ? c.w.nfill - f : 65535);
+        launch(dim3(nx, ny), d_fill + f);
+        MH_HIP(hipGetLastError());
     }
-    const size_t scr_bytes = (size_t)(nscr ? nscr : 1) * MH_CHUNK;
-    if (scr_bytes > p->range_scr_cap) {
-        if (p->d_range_scr) MH_HIP(hipFree(p->d_range_scr));
-        p->d_range_scr = nullptr;
-        p->range_scr_cap = 0;
-        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_range_scr), scr_bytes));
-        p->range_scr_cap = scr_bytes;
-    }
-    p->range_host.assign(bytes, 0);
-    if (!tasks.empty()) memcpy(p->range_host.data(), tasks.data(), tasks.size() * sizeof(mh::RangeTask));
-    if (!wgs.empty()) memcpy(p->range_host.data() + b_task, wgs.data(), wgs.size() * sizeof(mh::RangeWg));
-    if (!fills.empty()) memcpy(p->range_host.data() + b_task + b_wg, fills.data(), fills.size() * sizeof(mh::RangeFill));
-    MH_HIP(hipMemcpyAsync(p->d_range, p->range_host.data(), bytes, hipMemcpyHostToDevice, st));
-    p->range_sel.assign(sel, sel + n_sel);
-    p->range_t0 = t0;
-    p->range_t1 = t1;
-    p->range_pitch = out_pitch;
-    p->range_b_task = b_task;
-    p->range_b_wg = b_wg;
-    p->range_nwg = wgs.size();
-    p->range_nfill = fills.size();
-    p->range_max_fill = max_fill;
     return MH_OK;
 }
 
@@ -1061,191 +1051,42 @@ int mh_decode_range(mh_plan *p, const uint32_t *payload, uint64_t payload_words,
                     const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, const uint8_t *peak, const uint8_t *enc,
                     uint8_t *out, uint64_t out_pitch, void *stream)
 {
-    if (!p || (n_sel && !sel)) return fail(MH_ERR_ARG, "mh_decode_range: NULL argument");
-    if (p->h.input_bits != 8)
-        return fail(MH_ERR_ARG, "mh_decode_range: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
-    if (t0 > t1 || t1 > p->h.max_T)
-        return fail(MH_ERR_ARG, "mh_decode_range: [%llu, %llu) is not a range inside [0, %llu)", (unsigned long long)t0,
-                    (unsigned long long)t1, (unsigned long long)p->h.max_T);
-    const mh::PlanHost &H = p->h;
-    const uint32_t C = H.info.C;
-    for (uint32_t i = 0; i < n_sel; ++i)
-        if (sel[i] >= C) return fail(MH_ERR_ARG, "mh_decode_range: sel[%u] = %u, the plan has %u channels", i, sel[i], C);
-    const uint64_t len = t1 - t0;
-    if (n_sel > 1 && out_pitch < len)
-        return fail(MH_ERR_ARG, "mh_decode_range: out_pitch %llu below the row length %llu", (unsigned long long)out_pitch,
-                    (unsigned long long)len);
-    if (n_sel == 0 || len == 0) return MH_OK;
-    if (!payload || !seg_off || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_range: NULL argument");
-    int rc = check_device(p->device, "mh_decode_range");
-    if (rc) return rc;
+    bool empty;
+    int rc = check_range_call("mh_decode_range", p, payload, seg_off, sel, n_sel, t0, t1, 1u, peak, enc, out, out_pitch, &empty);
+    if (rc || empty) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool same = p->d_range && p->range_t0 == t0 && p->range_t1 == t1 && p->range_pitch == out_pitch &&
-                      p->range_sel.size() == n_sel && std::equal(sel, sel + n_sel, p->range_sel.begin());
-    if (!same && (rc = range_work_list(p, sel, n_sel, t0, t1, out_pitch, st))) return rc;
-    const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(p->d_range + p->range_b_task + p->range_b_wg);
-    if (p->range_nfill) {
-        const uint64_t per_block = 256 * 16 * 4;  // 64 KiB per workgroup and pass
-        const uint64_t nb = (p->range_max_fill + per_block - 1) / per_block;
-        const unsigned nx = (unsigned)(nb < 1 ? 1 : nb < 1024 ? nb : 1024);
-        for (size_t f = 0; f < p->range_nfill; f += 65535) {
-            const unsigned ny = (unsigned)(p->range_nfill - f < 65535 ? p->range_nfill - f : 65535);
-            hipLaunchKernelGGL(mh::k_range_fill, dim3(nx, ny), dim3(256), 0, st, out, d_fill + f);
-            MH_HIP(hipGetLastError());
-        }
-    }
-    if (p->range_nwg == 0) return MH_OK;
+    ListCache &c = p->range;
+    if (!c.same_query(sel, n_sel, t0, t1, 0u, out_pitch) &&
+        (rc = upload_list(c, mh::range_work_list(p->h, sel, n_sel, t0, t1, out_pitch), MH_CHUNK, sel, n_sel, t0, t1, 0u, out_pitch, st)))
+        return rc;
+    rc = launch_fills(c, 256 * 16 * 4, [&](dim3 grid, const mh::RangeFill *fill) {  // 64 KiB per workgroup and pass
+        hipLaunchKernelGGL(mh::k_range_fill, grid, dim3(256), 0, st, out, fill);
+    });
+    if (rc || c.w.nwg == 0) return rc;
     mh::RangeArgs r{};
     r.a = decode_args(p, payload, payload_words, seg_off, peak, enc, out);
-    r.task = reinterpret_cast<const mh::RangeTask *>(p->d_range);
-    r.wg = reinterpret_cast<const mh::RangeWg *>(p->d_range + p->range_b_task);
+    r.task = reinterpret_cast<const mh::RangeTask *>(c.d_list);
+    r.wg = reinterpret_cast<const mh::RangeWg *>(c.wgs());
     r.out = out;
-    r.scratch = p->d_range_scr;
-    return dispatch_decode_range(p, r, (uint32_t)p->range_nwg, st);
+    r.scratch = c.d_aux;
+    return dispatch_decode_range(p, r, (uint32_t)c.w.nwg, st);
 }
 
-// mh_decode_rebin's work list for (sel, t0, t1, r, out_pitch), as range_work_list builds mh_decode_range's: one task per
-// overlapping segment, plus what the bins need.  The tasks of a row cover consecutive sample spans, so the bins they
-// touch are consecutive too: a bin is shared when a task's first bin is the previous task's last one -- those get a
-// side slot and a fix-up record; the bins of a row in front of the first task's and behind the last task's are zeroed.
-static int rebin_work_list(mh_plan *p, const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r,
-                           uint64_t out_pitch, hipStream_t st)
-{
-    const mh::PlanHost &H = p->h;
-    const uint32_t C = H.info.C;
-    const uint64_t len = t1 - t0, nb = (len + r - 1) / r;
-    p->rebin_sel.clear();  // (no valid list while this one is being built)
-    if (p->ch_seg0.empty()) {  // each channel's first directory entry (its segments are consecutive)
-        p->ch_seg0.assign((size_t)C + 1, 0);
-        for (uint32_t c : H.seg_ch) ++p->ch_seg0[(size_t)c + 1];
-        for (uint32_t c = 0; c < C; ++c) p->ch_seg0[(size_t)c + 1] += p->ch_seg0[c];
-    }
-    std::vector<mh::RebinTask> tasks;
-    std::vector<mh::RangeWg> wgs;
-    std::vector<mh::RebinFix> fixes;
-    std::vector<mh::RangeFill> fills;
-    uint32_t nside = 0;
-    uint64_t max_fill = 0;
-    auto fill = [&](uint64_t off, uint64_t n) {
-        if (n == 0) return;
-        fills.push_back(mh::RangeFill{off, n});
-        if (n > max_fill) max_fill = n;
-    };
-    for (uint32_t i = 0; i < n_sel; ++i) {
-        const uint32_t c = sel[i];
-        const uint64_t row = (uint64_t)i * out_pitch, w0 = H.w0[c], w1 = H.w1[c];
-        const uint64_t a = t0 > w0 ? t0 : w0, b = t1 < w1 ? t1 : w1;  // in-window part, channel samples
-        if (a >= b) {
-            fill(row, nb);
-            continue;
-        }
-        fill(row, (a - t0) / r);                                      // bins in front of sample a's
-        fill(row + (b - 1 - t0) / r + 1, nb - ((b - 1 - t0) / r + 1));  // bins behind sample (b - 1)'s
-        const uint64_t ra = a - w0, rb = b - w0;  // the same, window samples
-        const uint64_t *sf0 = H.seg_first.data();
-        uint64_t s = (uint64_t)(std::upper_bound(sf0 + p->ch_seg0[c], sf0 + p->ch_seg0[(size_t)c + 1], ra) - sf0) - 1;
-        const size_t task0 = tasks.size();
-        uint64_t prev_last = 0;  // the previous task's last bin (of the row)
-        for (; s < p->ch_seg0[(size_t)c + 1] && H.seg_first[s] < rb; ++s) {
-            const uint64_t sf = H.seg_first[s], sn = H.seg_n[s];
-            const uint64_t lo = (ra > sf ? ra : sf) - sf, hi = (rb < sf + sn ? rb : sf + sn) - sf;
-            const uint64_t c0 = lo / MH_CHUNK, c1 = (hi - 1) / MH_CHUNK, base = c0 * MH_CHUNK;
-            const uint64_t ncnk = c1 - c0 + 1;
-            // sample 0 of the task (chunk c0's first) sits at g0 in the range, possibly in front of it (then in bin -1)
-            const int64_t g0 = (int64_t)(w0 + sf + base) - (int64_t)t0;
-            const int64_t b0 = g0 >= 0 ? g0 / (int64_t)r : -(((-g0) + (int64_t)r - 1) / (int64_t)r);
-            mh::RebinTask t{};
-            t.ph = (uint32_t)(g0 - b0 * (int64_t)r);
-            t.dst = (int64_t)row + b0;
-            t.seg = (uint32_t)s;
-            t.skip = (uint32_t)c0;
-            t.n = (uint32_t)(sn - base < ncnk * MH_CHUNK ? sn - base : ncnk * MH_CHUNK);
-            t.lo = (uint32_t)(lo - base);
-            t.hi = (uint32_t)(hi - base);
-            t.jfirst = (uint32_t)((t.ph + (uint64_t)t.lo) / r);
-            t.jlast = (uint32_t)((t.ph + (uint64_t)t.hi - 1) / r);
-            t.head = t.tail = mh::kNoSlot;
-            const uint64_t first = (uint64_t)(b0 + (int64_t)t.jfirst), last = (uint64_t)(b0 + (int64_t)t.jlast);
-            if (tasks.size() > task0 && first == prev_last) {  // shared with the previous task (and maybe the ones before)
-                mh::RebinTask &q = tasks.back();
-                uint32_t slot = q.jfirst == q.jlast && q.head != mh::kNoSlot ? q.head : q.tail;
-                if (slot == mh::kNoSlot) {
-                    slot = nside++;
-                    fixes.push_back(mh::RebinFix{row + first, slot, 0u});
-                }
-                q.tail = slot;
-                t.head = slot;
-            }
-            prev_last = last;
-            tasks.push_back(t);
-        }
-        for (size_t k = task0; k < tasks.size(); k += 4)
-            wgs.push_back(mh::RangeWg{(uint32_t)k, (uint32_t)(tasks.size() - k < 4 ? tasks.size() - k : 4), c, 0u});
-    }
-    // ---- upload (one copy)
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t b_task = up16(tasks.size() * sizeof(mh::RebinTask)), b_wg = up16(wgs.size() * sizeof(mh::RangeWg));
-    const size_t b_fix = up16(fixes.size() * sizeof(mh::RebinFix));
-    const size_t bytes = b_task + b_wg + b_fix + fills.size() * sizeof(mh::RangeFill);
-    // the previous call's kernels may still read the task buffer and the side array (one stream at a time per plan)
-    MH_HIP(hipStreamSynchronize(st));
-    if (bytes > p->rebin_cap) {
-        if (p->d_rebin) MH_HIP(hipFree(p->d_rebin));
-        p->d_rebin = nullptr;
-        p->rebin_cap = 0;
-        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_rebin), bytes));
-        p->rebin_cap = bytes;
-    }
-    const size_t side_bytes = (size_t)(nside ? nside : 1) * sizeof(uint32_t);
-    if (side_bytes > p->rebin_side_cap) {
-        if (p->d_rebin_side) MH_HIP(hipFree(p->d_rebin_side));
-        p->d_rebin_side = nullptr;
-        p->rebin_side_cap = 0;
-        MH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_rebin_side), side_bytes));
-        p->rebin_side_cap = side_bytes;
-    }
-    p->rebin_host.assign(bytes, 0);
-    uint8_t *hp = p->rebin_host.data();
-    if (!tasks.empty()) memcpy(hp, tasks.data(), tasks.size() * sizeof(mh::RebinTask));
-    if (!wgs.empty()) memcpy(hp + b_task, wgs.data(), wgs.size() * sizeof(mh::RangeWg));
-    if (!fixes.empty()) memcpy(hp + b_task + b_wg, fixes.data(), fixes.size() * sizeof(mh::RebinFix));
-    if (!fills.empty()) memcpy(hp + b_task + b_wg + b_fix, fills.data(), fills.size() * sizeof(mh::RangeFill));
-    if (bytes) MH_HIP(hipMemcpyAsync(p->d_rebin, hp, bytes, hipMemcpyHostToDevice, st));
-    p->rebin_sel.assign(sel, sel + n_sel);
-    p->rebin_t0 = t0;
-    p->rebin_t1 = t1;
-    p->rebin_r = r;
-    p->rebin_pitch = out_pitch;
-    p->rebin_b_task = b_task;
-    p->rebin_b_wg = b_wg;
-    p->rebin_b_fix = b_fix;
-    p->rebin_nwg = wgs.size();
-    p->rebin_nfix = fixes.size();
-    p->rebin_nfill = fills.size();
-    p->rebin_nside = nside;
-    p->rebin_max_fill = max_fill;
-    return MH_OK;
-}
-
+// the two output forms of mh_decode_rebin around its decoder: zero fills in front, fix-ups of the shared bins behind
 extern "C++" template <class T>
-static int rebin_fill_fix(const mh_plan *p, T *out, bool fix, hipStream_t st)
+static int decode_rebin(const mh_plan *p, const mh::RebinArgs &a, bool sat, hipStream_t st)
 {
-    const uint8_t *base = p->d_rebin + p->rebin_b_task + p->rebin_b_wg;
-    if (fix) {
-        hipLaunchKernelGGL(mh::k_rebin_fix<T>, dim3((unsigned)((p->rebin_nfix + 255) / 256)), dim3(256), 0, st, out,
-                           reinterpret_cast<const mh::RebinFix *>(base), (uint32_t)p->rebin_nfix, p->d_rebin_side);
-        MH_HIP(hipGetLastError());
-        return MH_OK;
-    }
-    const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(base + p->rebin_b_fix);
-    const uint64_t per_block = 256 * 16;
-    const uint64_t nbk = (p->rebin_max_fill + per_block - 1) / per_block;
-    const unsigned nx = (unsigned)(nbk < 1 ? 1 : nbk < 1024 ? nbk : 1024);
-    for (size_t f = 0; f < p->rebin_nfill; f += 65535) {
-        const unsigned ny = (unsigned)(p->rebin_nfill - f < 65535 ? p->rebin_nfill - f : 65535);
-        hipLaunchKernelGGL(mh::k_rebin_fill<T>, dim3(nx, ny), dim3(256), 0, st, out, d_fill + f);
-        MH_HIP(hipGetLastError());
-    }
+    const ListCache &c = p->rebin;
+    T *out = static_cast<T *>(a.out);
+    int rc = launch_fills(c, 256 * 16, [&](dim3 grid, const mh::RangeFill *fill) {
+        hipLaunchKernelGGL(mh::k_rebin_fill<T>, grid, dim3(256), 0, st, out, fill);
+    });
+    if (rc || c.w.nwg == 0) return rc;
+    if (c.w.naux) MH_HIP(hipMemsetAsync(c.d_aux, 0, c.w.naux * sizeof(uint32_t), st));
+    if ((rc = dispatch_decode_rebin(p, a, sat, (uint32_t)c.w.nwg, st)) || c.w.nfix == 0) return rc;
+    hipLaunchKernelGGL(mh::k_rebin_fix<T>, dim3((unsigned)((c.w.nfix + 255) / 256)), dim3(256), 0, st, out,
+                       reinterpret_cast<const mh::RebinFix *>(c.fixes()), (uint32_t)c.w.nfix, a.side);
+    MH_HIP(hipGetLastError());
     return MH_OK;
 }
 
@@ -1253,45 +1094,24 @@ int mh_decode_rebin(mh_plan *p, const uint32_t *payload, uint64_t payload_words,
                     const uint32_t *sel, uint32_t n_sel, uint64_t t0, uint64_t t1, uint32_t r, int saturate,
                     const uint8_t *peak, const uint8_t *enc, void *out, uint64_t out_pitch, void *stream)
 {
-    if (!p || (n_sel && !sel)) return fail(MH_ERR_ARG, "mh_decode_rebin: NULL argument");
-    if (p->h.input_bits != 8)
-        return fail(MH_ERR_ARG, "mh_decode_rebin: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
-    if (r < 1 || r > 4096) return fail(MH_ERR_ARG, "mh_decode_rebin: bin factor %u outside 1..4096", r);
-    if (t0 > t1 || t1 > p->h.max_T)
-        return fail(MH_ERR_ARG, "mh_decode_rebin: [%llu, %llu) is not a range inside [0, %llu)", (unsigned long long)t0,
-                    (unsigned long long)t1, (unsigned long long)p->h.max_T);
-    if (t0 % r) return fail(MH_ERR_ARG, "mh_decode_rebin: t0 = %llu is not a multiple of the bin factor %u", (unsigned long long)t0, r);
-    const uint32_t C = p->h.info.C;
-    for (uint32_t i = 0; i < n_sel; ++i)
-        if (sel[i] >= C) return fail(MH_ERR_ARG, "mh_decode_rebin: sel[%u] = %u, the plan has %u channels", i, sel[i], C);
-    const uint64_t nb = (t1 - t0 + r - 1) / r;
-    if (n_sel > 1 && out_pitch < nb)
-        return fail(MH_ERR_ARG, "mh_decode_rebin: out_pitch %llu below the row length %llu", (unsigned long long)out_pitch,
-                    (unsigned long long)nb);
-    if (n_sel == 0 || nb == 0) return MH_OK;
-    if (!payload || !seg_off || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_rebin: NULL argument");
-    int rc = check_device(p->device, "mh_decode_rebin");
-    if (rc) return rc;
+    bool empty;
+    int rc = check_range_call("mh_decode_rebin", p, payload, seg_off, sel, n_sel, t0, t1, r, peak, enc, out, out_pitch, &empty);
+    if (rc || empty) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool same = p->d_rebin && p->rebin_t0 == t0 && p->rebin_t1 == t1 && p->rebin_r == r && p->rebin_pitch == out_pitch &&
-                      p->rebin_sel.size() == n_sel && std::equal(sel, sel + n_sel, p->rebin_sel.begin());
-    if (!same && (rc = rebin_work_list(p, sel, n_sel, t0, t1, r, out_pitch, st))) return rc;
-    const bool sat = saturate != 0;
-    if (p->rebin_nfill && (rc = sat ? rebin_fill_fix(p, (uint8_t *)out, false, st) : rebin_fill_fix(p, (uint32_t *)out, false, st)))
+    ListCache &c = p->rebin;
+    if (!c.same_query(sel, n_sel, t0, t1, r, out_pitch) &&
+        (rc = upload_list(c, mh::rebin_work_list(p->h, sel, n_sel, t0, t1, r, out_pitch), sizeof(uint32_t), sel, n_sel, t0, t1, r,
+                          out_pitch, st)))
         return rc;
-    if (p->rebin_nwg == 0) return MH_OK;
-    if (p->rebin_nside) MH_HIP(hipMemsetAsync(p->d_rebin_side, 0, p->rebin_nside * sizeof(uint32_t), st));
     mh::RebinArgs a{};
     a.a = decode_args(p, payload, payload_words, seg_off, peak, enc, nullptr);
-    a.task = reinterpret_cast<const mh::RebinTask *>(p->d_rebin);
-    a.wg = reinterpret_cast<const mh::RangeWg *>(p->d_rebin + p->rebin_b_task);
+    a.task = reinterpret_cast<const mh::RebinTask *>(c.d_list);
+    a.wg = reinterpret_cast<const mh::RangeWg *>(c.wgs());
     a.out = out;
-    a.side = p->d_rebin_side;
+    a.side = reinterpret_cast<uint32_t *>(c.d_aux);
     a.r = r;
     a.rmagic = r > 1 ? (uint32_t)((1ull << 32) / r) + 1u : 0u;
-    if ((rc = dispatch_decode_rebin(p, a, sat, (uint32_t)p->rebin_nwg, st))) return rc;
-    if (p->rebin_nfix) rc = sat ? rebin_fill_fix(p, (uint8_t *)out, true, st) : rebin_fill_fix(p, (uint32_t *)out, true, st);
-    return rc;
+    return saturate ? decode_rebin<uint8_t>(p, a, true, st) : decode_rebin<uint32_t>(p, a, false, st);
 }
 
 // The chunk walk of one stored segment s (directory entry of H) whose words are payload[pos, end): header sizes,

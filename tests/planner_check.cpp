@@ -9,12 +9,18 @@
 // and the program prints only where the kernel dispatch lands:  "maxlen wave_tasks W dec_K dec_NR".
 // With --forms (tests/async_table.py) the same input gives the form of the plan, which decides what each call enqueues:
 // "wave_tasks measure_fused fused_calibration tickets_fit cal_tiles head_segments skipped short_channels".
+// With --worklist (tests/test_host_worklist.py) a case in the first format is followed by a query count and that many
+// queries  n_sel sel[0..n_sel) t0 t1 r out_pitch  (r = 0: mh_decode_range's list, else mh_decode_rebin's), built by
+// csrc/mh_worklist.hpp as the library builds them.  Output: "D nseg" and the directory's ch / first / n lines, then per
+// query "L ntask nwg nfix nfill naux max_fill" + the blob offsets of the workgroup, fix and fill sections + its size,
+// and one line per record: T (task fields in struct order, without padding), W task0 ntask ch, X off slot, F off n.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "mh_planner.hpp"
+#include "mh_worklist.hpp"
 
 #define CHECK(cond)                                                    \
     do {                                                               \
@@ -24,37 +30,51 @@
         }                                                              \
     } while (0)
 
+// One plan case from stdin (with_bits: input_bits after seg_chunks) -> p.  1: built; 2: the arguments were rejected
+// ("error <code>" printed); 0: end of input; -1: a malformed case.
+static int read_plan(bool with_bits, mh::PlanHost &p)
+{
+    unsigned C, S, h, mode, window, K, sc, bits = 8;
+    if (scanf("%u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc) != 7) return 0;
+    if (with_bits && scanf("%u", &bits) != 1) return -1;
+    std::vector<uint64_t> len(C), off(C);
+    std::vector<uint8_t> sclv((size_t)K * S);
+    uint64_t o = 0;
+    for (unsigned c = 0; c < C; ++c) {
+        unsigned long long v;
+        if (scanf("%llu", &v) != 1) return -1;
+        len[c] = v;
+        off[c] = o;
+        o += (v + 15) & ~15ull;
+    }
+    for (auto &b : sclv) {
+        unsigned v;
+        if (scanf("%u", &v) != 1) return -1;
+        b = (uint8_t)v;
+    }
+    const char *msg = "";
+    uint32_t arg = 0, maxlen = 0;
+    const int rc = mh::plan_check_args(len.data(), C, S, h, mode, window, sclv.data(), K, &maxlen, &msg, &arg);
+    if (rc != MH_OK) {
+        printf("error %d\n", rc);
+        return 2;
+    }
+    p = mh::PlanHost();
+    p.info.C = C; p.info.S = S; p.info.h = h; p.info.mode = mode; p.info.window = window;
+    p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
+    p.input_bits = bits;
+    mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+    return 1;
+}
+
 static int cells(bool forms)
 {
-    unsigned C, S, h, mode, window, K, sc, bits;
-    while (scanf("%u %u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc, &bits) == 8) {
-        std::vector<uint64_t> len(C), off(C);
-        std::vector<uint8_t> sclv((size_t)K * S);
-        uint64_t o = 0;
-        for (unsigned c = 0; c < C; ++c) {
-            unsigned long long v;
-            if (scanf("%llu", &v) != 1) return 1;
-            len[c] = v;
-            off[c] = o;
-            o += (v + 15) & ~15ull;
-        }
-        for (auto &b : sclv) {
-            unsigned v;
-            if (scanf("%u", &v) != 1) return 1;
-            b = (uint8_t)v;
-        }
-        const char *msg = "";
-        uint32_t arg = 0, maxlen = 0;
-        const int rc = mh::plan_check_args(len.data(), C, S, h, mode, window, sclv.data(), K, &maxlen, &msg, &arg);
-        if (rc != MH_OK) {
-            printf("error %d\n", rc);
-            continue;
-        }
-        mh::PlanHost p;
-        p.info.C = C; p.info.S = S; p.info.h = h; p.info.mode = mode; p.info.window = window;
-        p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
-        p.input_bits = bits;
-        mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+    mh::PlanHost p;
+    int got;
+    while ((got = read_plan(true, p)) > 0) {
+        if (got == 2) continue;
+        const unsigned C = p.info.C, h = p.info.h, window = p.info.window;
+        const std::vector<uint64_t> &len = p.ch_len;
         if (forms) {
             unsigned heads = 0, shorter = 0;
             for (unsigned c = 0; c < C; ++c) {
@@ -67,41 +87,92 @@ static int cells(bool forms)
         }
         printf("%u %d %u %u %u\n", p.info.maxlen, (int)p.use_wave_tasks, p.W, p.dec_K, p.dec_NR);
     }
-    return 0;
+    return got < 0;
+}
+
+// --worklist: every record of a packed list, read back from the blob at its section offsets
+static void print_list(const mh::WorkList &w, bool rebin)
+{
+    const size_t o_wg = w.b_task, o_fix = o_wg + w.b_wg, o_fill = o_fix + w.b_fix;
+    printf("L %zu %zu %zu %zu %u %llu %zu %zu %zu %zu\n", w.ntask, w.nwg, w.nfix, w.nfill, w.naux,
+           (unsigned long long)w.max_fill, o_wg, o_fix, o_fill, w.blob.size());
+    const uint8_t *b = w.blob.data();
+    for (size_t i = 0; i < w.ntask; ++i) {
+        if (rebin) {
+            mh::RebinTask t;
+            memcpy(&t, b + i * sizeof(t), sizeof(t));
+            printf("T %lld %u %u %u %u %u %u %u %u %u %u\n", (long long)t.dst, t.seg, t.skip, t.n, t.lo, t.hi, t.ph, t.jfirst,
+                   t.jlast, t.head, t.tail);
+        } else {
+            mh::RangeTask t;
+            memcpy(&t, b + i * sizeof(t), sizeof(t));
+            printf("T %lld %u %u %u %u %u %u %u\n", (long long)t.dst, t.seg, t.skip, t.ncnk, t.n, t.lo, t.hi, t.scr);
+        }
+    }
+    for (size_t i = 0; i < w.nwg; ++i) {
+        mh::RangeWg g;
+        memcpy(&g, b + o_wg + i * sizeof(g), sizeof(g));
+        printf("W %u %u %u\n", g.task0, g.ntask, g.ch);
+    }
+    for (size_t i = 0; i < w.nfix; ++i) {
+        mh::RebinFix x;
+        memcpy(&x, b + o_fix + i * sizeof(x), sizeof(x));
+        printf("X %llu %u\n", (unsigned long long)x.off, x.slot);
+    }
+    for (size_t i = 0; i < w.nfill; ++i) {
+        mh::RangeFill f;
+        memcpy(&f, b + o_fill + i * sizeof(f), sizeof(f));
+        printf("F %llu %llu\n", (unsigned long long)f.off, (unsigned long long)f.n);
+    }
+}
+
+static int worklist()
+{
+    mh::PlanHost p;
+    int got;
+    while ((got = read_plan(false, p)) > 0) {
+        if (got == 2) continue;
+        const size_t n = p.seg_ch.size();
+        printf("D %zu\n", n);
+        for (size_t s = 0; s < n; ++s) printf("%u ", p.seg_ch[s]);
+        printf("\n");
+        for (size_t s = 0; s < n; ++s) printf("%llu ", (unsigned long long)p.seg_first[s]);
+        printf("\n");
+        for (size_t s = 0; s < n; ++s) printf("%llu ", (unsigned long long)p.seg_n[s]);
+        printf("\n");
+        unsigned nq;
+        if (scanf("%u", &nq) != 1) return 1;
+        for (unsigned q = 0; q < nq; ++q) {
+            unsigned n_sel, r;
+            unsigned long long t0, t1, pitch;
+            if (scanf("%u", &n_sel) != 1) return 1;
+            std::vector<uint32_t> sel(n_sel);
+            for (auto &c : sel)
+                if (scanf("%u", &c) != 1 || c >= p.info.C) return 1;
+            if (scanf("%llu %llu %u %llu", &t0, &t1, &r, &pitch) != 4) return 1;
+            // what mh_decode_range / mh_decode_rebin check before they build a list (but r <= 4096: the limit of the
+            // kernels' division, not of the builder -- a bin longer than a segment is how one bin meets three tasks)
+            const unsigned long long nb = r ? (t1 - t0 + r - 1) / r : t1 - t0;
+            if (t0 >= t1 || t1 > p.max_T || (r && t0 % r) || n_sel == 0 || pitch < nb) return 1;
+            if (r) print_list(mh::rebin_work_list(p, sel.data(), n_sel, t0, t1, r, pitch), true);
+            else print_list(mh::range_work_list(p, sel.data(), n_sel, t0, t1, pitch), false);
+        }
+    }
+    return got < 0;
 }
 
 int main(int argc, char **argv)
 {
     if (argc > 1 && !strcmp(argv[1], "--cells")) return cells(false);
     if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);
-    unsigned C, S, h, mode, window, K, sc;
-    while (scanf("%u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc) == 7) {
-        std::vector<uint64_t> len(C), off(C);
-        std::vector<uint8_t> sclv((size_t)K * S);
-        uint64_t o = 0;
-        for (unsigned c = 0; c < C; ++c) {
-            unsigned long long v;
-            if (scanf("%llu", &v) != 1) return 1;
-            len[c] = v;
-            off[c] = o;
-            o += (v + 15) & ~15ull;
-        }
-        for (auto &b : sclv) {
-            unsigned v;
-            if (scanf("%u", &v) != 1) return 1;
-            b = (uint8_t)v;
-        }
-        const char *msg = "";
-        uint32_t arg = 0, maxlen = 0;
-        const int rc = mh::plan_check_args(len.data(), C, S, h, mode, window, sclv.data(), K, &maxlen, &msg, &arg);
-        if (rc != MH_OK) {
-            printf("error %d\n", rc);
-            continue;
-        }
-        mh::PlanHost p;
-        p.info.C = C; p.info.S = S; p.info.h = h; p.info.mode = mode; p.info.window = window;
-        p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
-        mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+    if (argc > 1 && !strcmp(argv[1], "--worklist")) return worklist();
+    mh::PlanHost p;
+    int got;
+    while ((got = read_plan(false, p)) > 0) {
+        if (got == 2) continue;
+        const unsigned C = p.info.C, h = p.info.h;
+        const uint32_t maxlen = p.info.maxlen;
+        const std::vector<uint64_t> &len = p.ch_len, &off = p.ch_off;
         const size_t n = p.seg_ch.size();
         CHECK(p.info.n_segments == n && p.seg_first.size() == n && p.seg_n.size() == n && p.seg_off.size() == n);
         // segments tile every window exactly, in order; slots do not overlap and fit the capacity
@@ -115,6 +186,12 @@ int main(int argc, char **argv)
             samples += p.seg_n[s];
         }
         CHECK(samples == p.info.window_samples);
+        // each channel's run of the directory
+        CHECK(p.ch_seg0.size() == (size_t)C + 1 && p.ch_seg0[0] == 0 && p.ch_seg0[C] == n);
+        for (unsigned c = 0; c < C; ++c) {
+            CHECK(p.ch_seg0[c] <= p.ch_seg0[c + 1]);
+            for (uint64_t s = p.ch_seg0[c]; s < p.ch_seg0[c + 1]; ++s) CHECK(p.seg_ch[s] == c);
+        }
         if (n) CHECK(p.seg_off[n - 1] + mh::slot_words(p.seg_n[n - 1], maxlen) + 4 == p.info.payload_cap_words);
         // shared-table tasks: every segment once, <= 4 consecutive ones of one channel
         size_t covered = 0;
@@ -196,5 +273,5 @@ int main(int argc, char **argv)
         for (size_t s = 0; s < n; ++s) printf("%llu ", (unsigned long long)p.seg_off[s]);
         printf("\n");
     }
-    return 0;
+    return got < 0;
 }

@@ -218,6 +218,26 @@ def test_guards_pitch_determinism_and_list_reuse(gpu):
     plan.close()
 
 
+def test_range_and_rebin_lists_of_one_plan_do_not_disturb_each_other(gpu):
+    """mh_decode_range and mh_decode_rebin keep a work list each in the plan, in caches of one type: interleaved calls
+    -- the same query under both, a list reused after the other call rebuilt its own -- all give the oracle's answer"""
+    torch = gpu
+    c, full = _container(LENS, 5, 6, 2, 2, 3, seed=2)
+    plan, pay, seg_off, peak, enc = _plan_and_stream(torch, c)
+    q1 = ([6, 0, 2, 2, 7], CH - 34, 3 * CH + 5)
+    q2 = ([4, 1], 7 * 900, 5 * CH + 11)
+    for sel, a, b, r in (q1 + (0,), q1 + (50,), q1 + (0,), q2 + (7,), q1 + (0,), q1 + (50,)):
+        if r:
+            got = _got(plan.decode_rebin(pay, seg_off, peak, enc, sel, a, b, r, saturate=False))
+            want = _want(full, sel, a, b, r, False)
+        else:
+            got = _got(plan.decode_range(pay, seg_off, peak, enc, sel, a, b))
+            want = _want(full, sel, a, b, 1, True)     # bins of one sample: the slice itself
+        assert plan.decode_ok()
+        assert got.shape == want.shape and np.array_equal(got, want), (sel, a, b, r)
+    plan.close()
+
+
 def test_packed_plan_is_refused(gpu):
     torch = gpu
     from muahuff import MODE_APPROX, WIN_FULL, codec, sclv
