@@ -15,7 +15,10 @@ PROTOTYPES = {
     "mhi_version": (_int, []),
     "mhi_last_error": (ct.c_char_p, []),
     "mhi_bin_events": (_int, [_vp, _vp, _u32, _u64, _u64, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "mhi_aer_scratch_bytes": (_int, [_u64, _u32, ct.POINTER(_u64)]),
+    "mhi_aer_to_csr": (_int, [_vp, _vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
+AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
 
 _lib = None
 
@@ -49,4 +52,22 @@ def bin_events(ev, origin, period, T, bits, out, d_off, chunk_stride=0):
     import torch
     check(lib().mhi_bin_events(_vp(ev.ticks.data_ptr()), _vp(ev.ev_off.data_ptr()), ev.C, int(origin), int(period), int(T),
                                int(bits), _vp(out.data_ptr()), _vp(d_off.data_ptr()), int(chunk_stride),
+                               _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def aer_scratch_bytes(n, C):
+    """mhi_aer_scratch_bytes: host arithmetic, no device."""
+    b = _u64(0)
+    check(lib().mhi_aer_scratch_bytes(int(n), int(C), ct.byref(b)))
+    return int(b.value)
+
+
+def aer_to_csr(ticks, channels, C, out_ticks, ev_off, dropped, scratch):
+    """Enqueue mhi_aer_to_csr on the current stream: the pairs (ticks[i], channels[i]) -- 64-bit and 16- or 32-bit device
+    tensors -- partitioned by channel into out_ticks (64-bit, n entries), ev_off (64-bit, C + 1) and dropped (64-bit, 1);
+    scratch: uint8 device tensor of at least aer_scratch_bytes(n, C) bytes."""
+    import torch
+    check(lib().mhi_aer_to_csr(_vp(ticks.data_ptr()), _vp(channels.data_ptr()), 8 * channels.element_size(),
+                               int(ticks.numel()), int(C), _vp(out_ticks.data_ptr()), _vp(ev_off.data_ptr()),
+                               _vp(dropped.data_ptr()), _vp(scratch.data_ptr()), int(scratch.numel()),
                                _vp(torch.cuda.current_stream().cuda_stream)))

@@ -442,6 +442,12 @@ class Writer:
         self._append(T, lambda se: se.calibrate_events(ev, origin, period, T),
                      lambda se, track: se.encode_events_device(ev, origin, period, T, track=track))
 
+    def append_aer(self, ticks, channels, origin, period, T):
+        """append_events() for one merged, time-ordered list of (tick, channel) pairs on the device
+        (events.EventSet.from_aer: partitioned by channel there).  The same file as from the host-sorted EventSet."""
+        from . import events
+        self.append_events(events.EventSet.from_aer(ticks, channels, self.C), origin, period, T)
+
     def _append(self, Tb, calibrate, encode):
         """The pipeline of one block: calibrate(encoder) on a first block, encode(encoder, track) -> what
         encode_block_device returns."""

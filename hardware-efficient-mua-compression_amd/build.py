@@ -15,7 +15,8 @@ HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csr
 # the front-end companion (include/muahuff_ingest.h): spike time stamps -> binned counts
 INGEST_SO = os.path.join(HERE, "libmuahuff_ingest.so")
 INGEST_SOURCES = ["csrc/mh_ingest.hip"]
-INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_device.hpp", "../include/muahuff.h",
+INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_aer.hpp", "csrc/mh_aer_layout.hpp",
+                  "csrc/mh_device.hpp", "../include/muahuff.h",
                   "../include/muahuff_ingest.h"]
 
 

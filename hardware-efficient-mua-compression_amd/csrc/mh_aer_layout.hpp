@@ -1,0 +1,89 @@
+// mh_aer_layout.hpp -- the tile rule and the scratch layout of mhi_aer_to_csr (include/muahuff_ingest.h): how a list of
+// n (tick, channel) pairs over C channels is cut into wave sub-runs and tiles, and where the count matrix, the scan's
+// partials and the per-row drop counts sit in the caller's scratch.  Pure C++ (no HIP, no device), as mh_planner.hpp
+// and mh_worklist.hpp: mh_ingest.hip launches from it, mhi_aer_scratch_bytes IS aer_layout().bytes, and
+// tests/aer_layout_check.cpp prints it under -fsanitize=address,undefined.  Everything is a function of (n, C).
+//
+//   sub-run  W consecutive pairs, owned by ONE wave in the count and in the scatter kernel; row r of the count matrix
+//            belongs to pairs [r * W, (r + 1) * W).  W is a multiple of 64:
+//              n <= 2048 * 1024          W = 1024                               (rows = ceil(n / 1024) <= 2048)
+//              else                      W = min(roundup64(ceil(n / 2048)), Wmax(C))    (about 2048 rows, then more)
+//            Wmax = 16 * C rounded up to a power of two, within 4096 .. 65536: a row of the matrix costs 4 * C bytes
+//            and is moved five times (count, group sums, bases, bases again, scatter), 20 C bytes against the 22 W
+//            bytes of the row's pairs -- at most a sixth at W = 4 C ... a twentieth at W = 16 C.
+//   tile     the sub-runs of one workgroup: waves * W pairs.  Every wave keeps C 32-bit counters / cursors in LDS, and
+//            a workgroup stays within 64 KiB of it: 4 waves up to 4096 channels, 2 up to 8192, 1 up to 16384 = the
+//            published limit MHI_AER_MAX_CHANNELS.
+//   group    64 consecutive rows: the scan sums a group's rows per channel (partials), scans the partials, and walks
+//            each group again to turn counts into output positions.
+// Output positions are 32-bit in the matrix and in LDS, hence n < 2^32.
+// The scratch sections are sized by rows_alloc >= rows, which -- unlike rows -- never falls when n rises, so that
+// mhi_aer_scratch_bytes is non-decreasing in n: a scratch that served n pairs serves any shorter list.
+#pragma once
+#include <stdint.h>
+
+namespace mh {
+
+constexpr uint32_t kAerMaxChannels = 16384;     // == MHI_AER_MAX_CHANNELS
+constexpr uint64_t kAerMaxPairs = 0xFFFFFFFFull;
+constexpr uint32_t kAerMinRun = 1024;
+constexpr uint32_t kAerRowsTarget = 2048;
+constexpr uint32_t kAerGroupRows = 64;
+
+struct AerLayout {
+    uint32_t run;          // W: pairs per wave sub-run
+    uint32_t waves;        // waves per workgroup
+    uint32_t tile;         // waves * run
+    uint32_t nbits;        // ceil(log2 C): ballots per 64-pair step
+    uint32_t lds_bytes;    // per workgroup: waves * C * 4
+    uint64_t rows;         // ceil(n / run)
+    uint64_t groups;       // ceil(rows / 64)
+    uint64_t rows_alloc;   // what the sections are sized by
+    uint64_t groups_alloc;
+    uint64_t off_matrix;   // u32[rows][C]
+    uint64_t off_partial;  // u32[groups + 1][C]: the row behind the partials holds the channels' totals
+    uint64_t off_drop;     // u32[rows]
+    uint64_t bytes;        // == mhi_aer_scratch_bytes (a multiple of 16, never 0)
+};
+
+inline uint32_t aer_run_max(uint32_t C)
+{
+    uint32_t w = 4096;
+    while (w < 65536u && w < 16u * C) w <<= 1;
+    return w;
+}
+
+inline uint32_t aer_waves(uint32_t C) { return C <= 4096u ? 4u : C <= 8192u ? 2u : 1u; }
+
+// 0, or -1: C == 0 or above kAerMaxChannels; -2: n above kAerMaxPairs
+inline int aer_layout(uint64_t n, uint32_t C, AerLayout *L)
+{
+    if (C == 0 || C > kAerMaxChannels) return -1;
+    if (n > kAerMaxPairs) return -2;
+    const uint64_t wmax = aer_run_max(C);
+    const uint64_t knee = (uint64_t)kAerRowsTarget * kAerMinRun;
+    uint64_t w = kAerMinRun;
+    if (n > knee) {
+        w = ((n + kAerRowsTarget - 1) / kAerRowsTarget + 63) & ~63ull;
+        if (w > wmax) w = wmax;
+    }
+    L->run = (uint32_t)w;
+    L->waves = aer_waves(C);
+    L->tile = L->waves * L->run;
+    L->nbits = 0;
+    while (L->nbits < 32 && (1ull << L->nbits) < C) ++L->nbits;
+    L->lds_bytes = L->waves * C * 4u;
+    L->rows = (n + w - 1) / w;
+    L->groups = (L->rows + kAerGroupRows - 1) / kAerGroupRows;
+    const uint64_t by_max = (n + wmax - 1) / wmax;
+    L->rows_alloc = n <= knee ? (n + kAerMinRun - 1) / kAerMinRun : by_max > kAerRowsTarget ? by_max : kAerRowsTarget;
+    L->groups_alloc = (L->rows_alloc + kAerGroupRows - 1) / kAerGroupRows;
+    const auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    L->off_matrix = 0;
+    L->off_partial = up16(L->rows_alloc * C * 4);
+    L->off_drop = L->off_partial + up16((L->groups_alloc + 1) * C * 4);
+    L->bytes = L->off_drop + up16(L->rows_alloc * 4) + 16;
+    return 0;
+}
+
+}  // namespace mh

@@ -1,10 +1,13 @@
-// mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp: argument checks and the
-// launch.  A companion of libmuahuff.so, not part of it; there is no CPU fallback here either.
+// mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp and the pair-list partition
+// in mh_aer.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
+// fallback here either.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
 
+#include "mh_aer.hpp"
+#include "mh_aer_layout.hpp"
 #include "mh_ingest.hpp"
 // built with -fvisibility=hidden: the mhi_* functions of the header are ALL the library exports
 #pragma GCC visibility push(default)
@@ -37,6 +40,29 @@ Where where_is(const void *p)
     if (a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged) return Where::kBoth;
     if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) return Where::kDevice;
     return Where::kHostOnly;
+}
+
+template <typename CH>
+void aer_launch(const uint64_t *ticks, const void *channels, uint64_t n, uint32_t C, const mh::AerLayout &L, uint8_t *scratch,
+                uint64_t *out_ticks, uint64_t *ev_off, uint64_t *dropped, hipStream_t st)
+{
+    uint32_t *const matrix = reinterpret_cast<uint32_t *>(scratch + L.off_matrix);
+    uint32_t *const partial = reinterpret_cast<uint32_t *>(scratch + L.off_partial);
+    uint32_t *const drop = reinterpret_cast<uint32_t *>(scratch + L.off_drop);
+    const CH *const ch = static_cast<const CH *>(channels);
+    const dim3 tiles((unsigned)((L.rows + L.waves - 1) / L.waves)), waves(64u * L.waves);
+    const dim3 cols((C + mh::kAerColThreads - 1) / mh::kAerColThreads, (unsigned)L.groups), col(mh::kAerColThreads);
+    if (L.rows) {
+        hipLaunchKernelGGL(mh::k_aer_count<CH>, tiles, waves, L.lds_bytes, st, ch, n, C, L.run, L.rows, matrix, drop);
+        hipLaunchKernelGGL(mh::k_aer_group_sum, cols, col, 0, st, matrix, C, L.rows, mh::kAerGroupRows, partial);
+    }
+    hipLaunchKernelGGL(mh::k_aer_scan, dim3(1), dim3(mh::kAerScanThreads), 0, st, partial, drop, C, L.rows, L.groups, ev_off,
+                       dropped);
+    if (L.rows) {
+        hipLaunchKernelGGL(mh::k_aer_bases, cols, col, 0, st, matrix, partial, ev_off, C, L.rows, mh::kAerGroupRows);
+        hipLaunchKernelGGL(mh::k_aer_scatter<CH>, tiles, waves, L.lds_bytes, st, ticks, ch, n, C, L.nbits, L.run, L.rows, matrix,
+                           out_ticks);
+    }
 }
 
 }  // namespace
@@ -93,6 +119,47 @@ int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, ui
                            div_mode, out, out_off, chunk_stride);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_bin_events: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_aer_scratch_bytes(uint64_t n, uint32_t C, uint64_t *bytes)
+{
+    static_assert(mh::kAerMaxChannels == MHI_AER_MAX_CHANNELS, "the header publishes the layout's limit");
+    if (!bytes) return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: NULL pointer");
+    mh::AerLayout L;
+    const int rc = mh::aer_layout(n, C, &L);
+    if (rc == -1)
+        return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: C=%u (1 .. MHI_AER_MAX_CHANNELS = %u)", C, mh::kAerMaxChannels);
+    if (rc) return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: n=%llu (below 2^32: positions are 32-bit)", (unsigned long long)n);
+    *bytes = L.bytes;
+    return MH_OK;
+}
+
+int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits, uint64_t n, uint32_t C,
+                   uint64_t *out_ticks, uint64_t *ev_off, uint64_t *dropped, void *scratch, uint64_t scratch_bytes,
+                   void *stream)
+{
+    if (!ticks || !channels || !out_ticks || !ev_off || !dropped || !scratch)
+        return fail(MH_ERR_ARG, "mhi_aer_to_csr: NULL pointer");
+    if (ch_bits != 16 && ch_bits != 32) return fail(MH_ERR_ARG, "mhi_aer_to_csr: ch_bits=%u (16 or 32)", ch_bits);
+    mh::AerLayout L;
+    const int rc = mh::aer_layout(n, C, &L);
+    if (rc == -1) return fail(MH_ERR_ARG, "mhi_aer_to_csr: C=%u (1 .. MHI_AER_MAX_CHANNELS = %u)", C, mh::kAerMaxChannels);
+    if (rc) return fail(MH_ERR_ARG, "mhi_aer_to_csr: n=%llu (below 2^32: positions are 32-bit)", (unsigned long long)n);
+    if (scratch_bytes < L.bytes)
+        return fail(MH_ERR_ARG, "mhi_aer_to_csr: scratch_bytes=%llu, mhi_aer_scratch_bytes asks for %llu",
+                    (unsigned long long)scratch_bytes, (unsigned long long)L.bytes);
+    const uintptr_t a = (uintptr_t)ticks, b = (uintptr_t)out_ticks;
+    if (n && a < b + n * 8 && b < a + n * 8) return fail(MH_ERR_ARG, "mhi_aer_to_csr: out_ticks overlaps ticks");
+    if ((uintptr_t)scratch % 16)
+        return fail(MH_ERR_ARG, "mhi_aer_to_csr: scratch is not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (ch_bits == 16)
+        aer_launch<uint16_t>(ticks, channels, n, C, L, (uint8_t *)scratch, out_ticks, ev_off, dropped, st);
+    else
+        aer_launch<uint32_t>(ticks, channels, n, C, L, (uint8_t *)scratch, out_ticks, ev_off, dropped, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_aer_to_csr: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

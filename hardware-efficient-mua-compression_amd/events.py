@@ -82,7 +82,11 @@ class EventSet:
     @classmethod
     def from_aer(cls, ticks, channels, C, check=True, device="cuda"):
         """One merged list of (tick, channel) pairs in time order -- the MUA_vec of the loader -- stable-sorted by
-        channel, so that the time order within each channel is kept."""
+        channel, so that the time order within each channel is kept.  Host arrays take the NumPy route and are uploaded;
+        device tensors (64-bit ticks; 16- / 32-bit channels as they are, int64 channels narrowed on the device) are
+        partitioned where they are by mhi_aer_to_csr, and only the C + 1 offsets come back to the host."""
+        if isinstance(ticks, torch.Tensor) and ticks.is_cuda:
+            return cls._from_aer_device(ticks, channels, C, check)
         ticks = np.ascontiguousarray(ticks).reshape(-1)
         ch = np.ascontiguousarray(channels).reshape(-1).astype(np.int64)
         if ticks.size != ch.size:
@@ -93,3 +97,48 @@ class EventSet:
         off = np.zeros(int(C) + 1, np.uint64)
         off[1:] = np.cumsum(np.bincount(ch, minlength=int(C)))
         return cls(ticks[order], off, check=check, device=device)
+
+    @classmethod
+    def _from_aer_device(cls, ticks, channels, C, check):
+        from . import _ingest
+        C = int(C)
+        if not (isinstance(channels, torch.Tensor) and channels.device == ticks.device):
+            raise ValueError("ticks and channels are tensors of one device")
+        if ticks.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("ticks are 64-bit integers")
+        ticks, ch = ticks.reshape(-1).contiguous(), channels.reshape(-1).contiguous()
+        if ticks.numel() != ch.numel():
+            raise ValueError("one channel per tick")
+        if ch.dtype == torch.int64:    # below 0 or at / above 2^31: -1, which no C reaches as an unsigned number
+            ch = torch.where((ch < 0) | (ch > 0x7FFFFFFF), -1, ch).to(torch.int32)
+        elif ch.dtype not in (torch.int16, torch.uint16, torch.int32, torch.uint32):
+            raise ValueError("channels are 16-, 32- or 64-bit integers")
+        n, dev = int(ticks.numel()), ticks.device
+        with torch.cuda.device(dev):
+            out = torch.empty(n, dtype=torch.int64, device=dev)
+            meta = torch.empty(C + 2, dtype=torch.int64, device=dev)        # ev_off[0..C], dropped
+            scratch = torch.empty(_ingest.aer_scratch_bytes(n, C), dtype=torch.uint8, device=dev)
+            _ingest.aer_to_csr(ticks, ch, C, out, meta, meta[C + 1:], scratch)
+            meta = meta.cpu().numpy()  # the one synchronisation: an EventSet keeps host offsets
+        if int(meta[C + 1]):
+            raise ValueError("channel index outside 0..%d" % (C - 1))
+        return cls(out, meta[:C + 1].view(np.uint64), check=check, device=dev)
+
+
+def aer_time_slice(ticks, t0, t1):
+    """(i0, i1): the pairs of a time-ordered 64-bit tick tensor with t0 <= tick < t1 are ticks[i0:i1] -- how a long
+    merged list is cut into blocks for EventSet.from_aer / archive.Writer.append_aer.  Ticks are below 2^63, as
+    everywhere in an EventSet, and so are the bounds (0 <= t <= 2^63 - 1): anything else raises ValueError."""
+    t = ticks.reshape(-1)
+    if t.dtype == torch.uint64:
+        t = t.view(torch.int64)
+    elif t.dtype != torch.int64:
+        raise ValueError("ticks are 64-bit integers")
+    t0, t1 = int(t0), int(t1)
+    if not (0 <= t0 < 1 << 63 and 0 <= t1 < 1 << 63):
+        raise ValueError("the bounds of a time slice lie in 0 .. 2^63 - 1")
+    if t.numel() and (int(t[-1]) < 0 or int(t[0]) < 0):   # time-ordered: the ends bound the rest
+        raise ValueError("a tick is 2^63 or more")
+    i = torch.searchsorted(t, torch.tensor([t0, t1], dtype=torch.int64, device=t.device))
+    i0, i1 = i.tolist()
+    return i0, max(i0, i1)

@@ -8,6 +8,10 @@
  * channels the codec reads or, directly, the packed 2- / 4-bit chunk-blocked pieces of the stream path -- the
  * time-major block and mh_deinterleave_packed drop out of that path.
  *
+ * Recordings arrive as ONE merged list of (time, channel) pairs in time order (the loaders' MUA_vec), not per channel:
+ * mhi_aer_to_csr brings such a list, resident on the device, into the per-channel form mhi_bin_events reads -- a stable
+ * partition by channel (count, scan, scatter), not a sort -- so that no stage in front of the codec runs on the host.
+ *
  * A binner is not a codec operation, so it is not part of muahuff.h: that ABI is closed.  The conventions are the
  * same: every function returns MH_OK or a negative MH_ERR_* code of muahuff.h and never throws, mhi_last_error()
  * returns a thread-local message for the last failure on this thread, every argument check comes before any device
@@ -46,6 +50,35 @@ const char *mhi_last_error(void);
  * Memory-safe on unsorted input: the counts are then unspecified, but no store leaves the channel's own bins. */
 int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, uint64_t origin, uint64_t period,
                    uint64_t T, uint32_t bits, uint8_t *out, const uint64_t *out_off, uint64_t chunk_stride,
+                   void *stream);
+
+/* The largest C of mhi_aer_to_csr: every wave keeps one 32-bit cursor per channel in LDS (64 KiB). */
+#define MHI_AER_MAX_CHANNELS 16384
+
+/* Bytes of scratch mhi_aer_to_csr needs for n pairs over C channels.  Host arithmetic only: no device is needed or
+ * touched.  Non-decreasing in n for a fixed C, never 0.  MH_ERR_ARG: bytes NULL, C == 0, C > MHI_AER_MAX_CHANNELS,
+ * n >= 2^32. */
+int mhi_aer_scratch_bytes(uint64_t n, uint32_t C, uint64_t *bytes);
+
+/* Stable partition of n (tick, channel) pairs by channel.  ticks: device, n entries; channels: device, n entries of
+ * ch_bits = 16 or 32 bits, unsigned, pair i = (ticks[i], channels[i]).
+ * out_ticks[ev_off[c] + k] is the tick of the k-th input pair, in input order, whose channel is c: with a list in time
+ * order, (out_ticks, ev_off) is the input of mhi_bin_events.  ev_off[0] == 0 and ev_off[C] is the number of pairs kept.
+ * A pair whose channel is >= C is dropped and counted: dropped[0] = the number of such pairs (0 when there are none).
+ * Written: out_ticks[0 .. ev_off[C]), ev_off[0 .. C], dropped[0] and the scratch -- nothing at or after
+ * out_ticks[ev_off[C]], nothing else.
+ * Tick values are never inspected: a list that is not in time order gives the same stable partition, and no index
+ * depends on data other than a channel that was compared with C first -- every store stays in the buffers above
+ * whatever the list holds.
+ * n == 0 is valid: ev_off all zero, dropped zero.  C >= 1.
+ * MH_ERR_ARG, before any device work: a NULL pointer (with n == 0 as well), ch_bits other than 16 / 32, C == 0,
+ * C > MHI_AER_MAX_CHANNELS, n >= 2^32 (output positions are 32-bit inside), scratch_bytes below what
+ * mhi_aer_scratch_bytes(n, C) returns, scratch not 16-byte aligned, out_ticks[0 .. n) overlapping ticks[0 .. n).
+ * out_ticks, ev_off, dropped: device, n / C + 1 / 1 entries.  scratch need not be zeroed or kept between calls.
+ * Only enqueues on `stream`: no synchronisation, allocation or free, so it can be captured into a hipGraph, and two
+ * calls in a row on the same scratch are ordered by the stream. */
+int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits, uint64_t n, uint32_t C,
+                   uint64_t *out_ticks, uint64_t *ev_off, uint64_t *dropped, void *scratch, uint64_t scratch_bytes,
                    void *stream);
 
 #ifdef __cplusplus

@@ -1,0 +1,168 @@
+"""The pair-list partition of the companion library (mhi_aer_to_csr, mhi_aer_scratch_bytes; include/muahuff_ingest.h), the
+part that needs no GPU: every argument error comes back before a pointer is used, the scratch size is host arithmetic and
+equals what tests/aer_layout_check.cpp -- csrc/mh_aer_layout.hpp built alone under AddressSanitizer + UBSan -- prints,
+and EventSet.from_aer on host arrays is what it was."""
+import ctypes as ct
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from muahuff import _ingest, _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "aer_layout_check.cpp")
+EXE = os.path.join(ROOT, "tests", "aer_layout_check_asan")
+FIELDS = ("run", "waves", "tile", "nbits", "lds_bytes", "rows", "groups", "rows_alloc", "groups_alloc", "off_matrix",
+          "off_partial", "off_drop", "bytes")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    importlib.import_module("hardware-efficient-mua-compression_amd.build").build_ingest()
+
+
+@pytest.fixture(scope="module")
+def exe():
+    deps = [SRC, os.path.join(CSRC, "mh_aer_layout.hpp")]
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, SRC, "-o", EXE])
+    return EXE
+
+
+def layouts(exe_path, pairs):
+    """[(n, C)] -> [dict of FIELDS, or None where the layout rejects the pair], under the sanitizers"""
+    text = "".join("%d %d\n" % p for p in pairs)
+    r = subprocess.run([exe_path], input=text, capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(pairs)
+    return [None if ln.startswith("error") else dict(zip(FIELDS, (int(v) for v in ln.split()))) for ln in lines]
+
+
+def published_limit():
+    hdr = open(os.path.join(ROOT, "include", "muahuff_ingest.h")).read()
+    return int(re.search(r"#define\s+MHI_AER_MAX_CHANNELS\s+(\d+)", hdr).group(1))
+
+
+def scratch_bytes(n, C):
+    b = ct.c_uint64(0)
+    rc = _ingest.lib().mhi_aer_scratch_bytes(n, C, ct.byref(b))
+    return rc, b.value
+
+
+def _call(n=100, C=4, ch_bits=16, short=0, overlap=False, **null):
+    """mhi_aer_to_csr with host stand-ins for the device buffers: an argument error must come back before any of them is
+    used as a device pointer.  null: name=None for a NULL pointer."""
+    rc, need = scratch_bytes(n, min(max(C, 1), published_limit()))
+    assert rc == _lib.MH_OK
+    keep = dict(ticks=np.zeros(2 * n + 8, np.uint64), channels=np.zeros(n + 8, np.uint32), out_ticks=np.zeros(n + 8, np.uint64),
+                ev_off=np.zeros(min(C, 1 << 16) + 2, np.uint64), dropped=np.zeros(1, np.uint64),
+                scratch=np.zeros(need // 8 + 2, np.uint64))
+    ptr = {k: None if k in null else ct.c_void_p(v.ctypes.data + (-v.ctypes.data) % 16) for k, v in keep.items()}
+    if overlap:
+        ptr["out_ticks"] = ct.c_void_p(ptr["ticks"].value + 8 * (n - 1))     # its first entry is the last input tick
+    L = _ingest.lib()
+    rc = L.mhi_aer_to_csr(ptr["ticks"], ptr["channels"], ch_bits, n, C, ptr["out_ticks"], ptr["ev_off"], ptr["dropped"],
+                          ptr["scratch"], need - short, None)
+    return rc, L.mhi_last_error().decode()
+
+
+BAD = [dict(ticks=None), dict(channels=None), dict(out_ticks=None), dict(ev_off=None), dict(dropped=None),
+       dict(scratch=None), dict(C=0), dict(ch_bits=0), dict(ch_bits=8), dict(ch_bits=64), dict(C="limit+1"), dict(short=1),
+       dict(overlap=True), dict(n=1 << 32)]
+
+
+@pytest.mark.parametrize("bad", BAD, ids=lambda d: ",".join("%s=%s" % kv for kv in d.items()))
+def test_argument_errors_come_before_any_device_work(bad):
+    bad = dict(bad)
+    if bad.get("C") == "limit+1":
+        bad["C"] = published_limit() + 1
+    if bad.get("n") == 1 << 32:          # the bound the 32-bit positions impose; no buffer of that size is made
+        L = _ingest.lib()
+        one = np.zeros(4, np.uint64)
+        p = ct.c_void_p(one.ctypes.data)
+        rc = L.mhi_aer_to_csr(p, p, 16, 1 << 32, 4, p, p, p, p, 1 << 40, None)
+        msg = L.mhi_last_error().decode()
+    else:
+        rc, msg = _call(**bad)
+    assert rc == _lib.ERR_ARG, (rc, msg)
+    assert "mhi_aer_to_csr" in msg, msg
+
+
+def test_the_published_limit_holds_the_large_channel_sets():
+    assert published_limit() >= 16384 and published_limit() == _ingest.AER_MAX_CHANNELS
+    assert scratch_bytes(1000, published_limit())[0] == _lib.MH_OK
+    rc, _ = scratch_bytes(1000, published_limit() + 1)
+    assert rc == _lib.ERR_ARG and "mhi_aer_scratch_bytes" in _ingest.lib().mhi_last_error().decode()
+    assert scratch_bytes(1000, 0)[0] == _lib.ERR_ARG and scratch_bytes(1 << 32, 4)[0] == _lib.ERR_ARG
+    assert _ingest.lib().mhi_aer_scratch_bytes(10, 4, None) == _lib.ERR_ARG
+
+
+def _pairs():
+    rng = np.random.RandomState(23)
+    lim = published_limit()
+    out = [(int(rng.choice([0, 1, 63, 1024, 4097, 10 ** 5, 2 ** 21, 2 ** 21 + 1, 3 * 10 ** 6, 10 ** 7, 5 * 10 ** 8, 2 ** 32 - 1]))
+            + int(rng.randint(0, 3)) * (i % 2), int(rng.choice([1, 2, 3, 64, 255, 256, 257, 1000, 1024, 4096, 4097, 8192, 8193,
+                                                                10000, lim]))) for i in range(40)]
+    out = [(min(n, 2 ** 32 - 1), c) for n, c in out]
+    return out + [(307_200_000, 1024), (300_000_000, 10000)]
+
+
+def test_scratch_bytes_is_the_layout_programs_under_the_sanitizers(exe):
+    pairs = _pairs()
+    assert len({c for _, c in pairs}) > 8 and len({n for n, _ in pairs}) > 12
+    for (n, C), lay in zip(pairs, layouts(exe, pairs)):
+        rc, b = scratch_bytes(n, C)
+        assert rc == _lib.MH_OK and lay is not None and b == lay["bytes"] and b > 0, (n, C, b, lay)
+    bad = layouts(exe, [(5, 0), (5, published_limit() + 1), (1 << 32, 4), (5, 1 << 33)])
+    assert bad == [None] * 4
+
+
+@pytest.mark.parametrize("C", [1, 1000, 4097, 16384])
+def test_scratch_bytes_never_falls_when_n_rises(C):
+    """the sub-run grows with n, so the number of rows does fall here and there: the sections are sized by a bound of it
+    that does not"""
+    knee = 2048 * 1024
+    ns = sorted(set(list(range(0, 5000, 7)) + list(range(knee - 3000, knee + 70000, 997)) +
+                    [int(x) for x in np.geomspace(1, 2 ** 32 - 1, 600)] + [2 ** 32 - 1]))
+    got = [scratch_bytes(n, C) for n in ns]
+    assert all(rc == _lib.MH_OK for rc, _ in got)
+    b = np.array([v for _, v in got], dtype=np.float64)
+    assert (np.diff(b) >= 0).all()
+
+
+def test_the_layouts_rows_do_fall_but_stay_within_the_sections(exe):
+    knee = 2048 * 1024
+    a, b = layouts(exe, [(2 * knee - 1000, 64), (2 * knee + 64, 64)])
+    assert a["run"] < b["run"] and a["rows"] <= a["rows_alloc"] and b["rows"] <= b["rows_alloc"]
+    assert b["bytes"] >= a["bytes"]
+
+
+def test_from_aer_on_host_arrays_is_the_stable_partition():
+    """pinned against a partition written out here: pair by pair, appended to its channel's list.  The host route is
+    unchanged by design, so this case alone also passes without the feature: it pins what must stay."""
+    from muahuff import events
+    rng = np.random.RandomState(4)
+    C, n = 7, 500
+    ch = rng.randint(0, C, size=n)
+    ch[ch == 3] = 2                                    # channel 3 has no pair
+    ticks = np.sort(rng.randint(0, 300, size=n)).astype(np.uint64)   # runs of equal ticks, across channels too
+    lists = [[] for _ in range(C)]
+    for t, c in zip(ticks.tolist(), ch.tolist()):
+        lists[c].append(t)
+    want_off = np.cumsum([0] + [len(x) for x in lists])
+    for dt in (np.int64, np.int16, np.uint32):
+        ev = events.EventSet.from_aer(ticks, ch.astype(dt), C, device="cpu")
+        assert ev.offsets.tolist() == want_off.tolist() and ev.C == C
+        assert ev.ticks.numpy().tolist() == [t for x in lists for t in x]
+    with pytest.raises(ValueError):
+        events.EventSet.from_aer(ticks, np.where(ch == 0, C, ch), C, device="cpu")
+    with pytest.raises(ValueError):
+        events.EventSet.from_aer(ticks, ch[:-1], C, device="cpu")
