@@ -17,6 +17,7 @@
 #include "mh_kernels.hpp"
 #include "mh_layout.hpp"
 #include "mh_planner.hpp"
+#include "mh_select.hpp"
 
 namespace mh {
 
@@ -39,11 +40,6 @@ struct Enc2Args {
 };
 
 constexpr uint32_t kEncSharedDw = 512 + 32;  // pair table (256 x uint2) + single table (16 x uint2)
-
-__host__ __device__ inline uint32_t enc2_wave_dwords(uint32_t stage_dw)
-{
-    return 96 + stage_dw * 64;  // carried tail (64) + header room (32) + staging / image area
-}
 
 // Slow path for a chunk (m <= 16384 samples) whose sub-streams do not fit the capped LDS staging
 // (more than 3 bits/sample in some lane): two passes straight from global memory -- lengths,
@@ -833,13 +829,7 @@ __global__ __launch_bounds__(256, 4) void k_encode2(Enc2Args a)
 // so a workgroup packs segments of four different channels and no wave idles.  One 32-byte record
 // per wave task (the planner orders them longest first) replaces the task -> segment -> channel
 // chain of dependent loads, and the segment's first rows are requested before the tables are built.
-// (a wave's tables: the pair table has 4^PB entries -- 64 for S <= 8 -- plus the 16 single-symbol entries; the
-// four-symbol table of 2-bit input has 256.  Sized exactly: with 3-bit pairs four workgroups fit a CU at the
-// largest staging as well.)
-template <int PB, int PK>
-__host__ __device__ constexpr uint32_t enc2w_table_dwords() { return (PK == 2 ? 512u : 2u << (2 * PB)) + 32u; }
-template <int PB, int PK>
-__host__ __device__ inline uint32_t enc2w_wave_dwords(uint32_t stage_dw) { return enc2w_table_dwords<PB, PK>() + enc2_wave_dwords(stage_dw); }
+// (a wave's LDS: enc2w_table_dwords + enc2_wave_dwords, mh_select.hpp)
 
 template <int LC, int PB, int PK = 0>
 __global__ __launch_bounds__(256, 4) void k_encode2w(Enc2Args a)
@@ -976,15 +966,7 @@ struct Dec2Args {
     uint64_t cstride;
 };
 
-// LDS dwords of the workgroup-shared tables: multi-symbol table (2 dwords per entry for K = 4,
-// 1 for the pair table) + the 512-byte per-symbol table used by partial / oversize chunks
-__host__ __device__ inline uint32_t dec2_shared_dwords(uint32_t W, uint32_t K)
-{
-    return (K == 1 ? 0u : (K == 4 ? 2u : 1u) << W) + kDtab / 4;  // K = 1: the per-symbol table is all there is
-}
-
-// staging dwords per wave: whole 16-byte-per-lane vectors (1 KiB each) covering NR * 64 words
-__host__ __device__ inline uint32_t dec2_stage_dwords(uint32_t NR) { return ((NR + 3) / 4) * 256; }
+// (LDS areas: dec2_shared_dwords and dec2_stage_dwords, mh_select.hpp)
 
 // Per-chunk pipeline state: the scanned header of the chunk about to be decoded.
 struct ChunkHdr {
@@ -1053,7 +1035,7 @@ __device__ __forceinline__ void decode_staged_chunk(ChunkHdr h, const uint32_t *
     //   because some lane always needs one (S=3 decode 2.29 -> 2.11 ms).
     // RL == 0: the window is shifted and topped up from a one-word read-ahead when 32 bits are
     //   used up; better where the extra LDS read in the dependent chain costs more than the
-    //   divergent branch (chosen per variant by measurement, see dispatch_decode).
+    //   divergent branch (chosen per variant by measurement, see kDecRungs, mh_select.hpp).
     // RL == 2: the same top-up written with selects instead of a branch (the read-ahead word is
     //   re-read every time, off the dependent chain).
     // Window bound (!RL, HY, M = 2, W <= 12, maxlen <= 9): bp < 32 after a top-up; a pair lookup
@@ -1502,7 +1484,7 @@ __device__ __forceinline__ void decode_segment(const DecArgs &d, uint64_t pos, u
 // payload B -- contiguous in the stream -- into the wave's staging area, and the two chunks decode side by side.
 // Whatever does not fit that scheme goes through decode_segment: a pair too large for the staging area, the odd full
 // chunk, the partial chunk.  Same bounds rules: every header-steered read is checked against lim first.
-// (Wave-task plans only: on long channels the one-symbol decoder loses, see dispatch_decode.)
+// (Wave-task plans only: on long channels the one-symbol decoder loses, see dec_pick, mh_select.hpp.)
 template <int K, int M, int NR, int RL, bool HY, int PO = 0>
 __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t pos, uint8_t *__restrict__ out, uint64_t n,
                                                     const uint32_t *tab, uint32_t tbase, uint32_t maskW, const uint8_t *tab1,

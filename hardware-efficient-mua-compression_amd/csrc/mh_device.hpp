@@ -17,7 +17,6 @@ constexpr int kRows = MH_ROWS;
 constexpr int kChunk = MH_CHUNK;
 constexpr int kHdrWords = MH_HDR_WORDS;
 constexpr int kLut = 16;      // symbol LUT entries: index min(raw value, 15)
-constexpr int kDtab = 512;    // decode table bytes per channel (2^maxlen <= 512)
 constexpr int kHistStride = 16;
 #define MH_LUT_SYMS 10  // S <= 10 (the reference sweeps S = 2..10)
 

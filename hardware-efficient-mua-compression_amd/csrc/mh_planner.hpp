@@ -1,5 +1,5 @@
 // mh_planner.hpp -- the host-side planner of libmuahuff: windows, segment directory, slots,
-// workgroup tasks, histogram tiles, codebooks, decoder geometry.  Pure C++ (no HIP, no device):
+// workgroup tasks, histogram tiles, codebooks.  Pure C++ (no HIP, no device):
 // muahuff.hip uploads what it computes; tests/planner_check.cpp compiles the same header with
 // -fsanitize=address,undefined and checks it against the CPU oracle's directory.
 #pragma once
@@ -9,6 +9,7 @@
 #include <numeric>
 #include <vector>
 
+#include "mh_select.hpp"
 #include "muahuff.h"
 
 namespace mh {
@@ -116,9 +117,7 @@ struct PlanHost {
     std::vector<uint64_t> seg_first, seg_n, seg_off;
     std::vector<uint64_t> ch_seg0;  // C + 1: channel c's segments are the consecutive entries [ch_seg0[c], ch_seg0[c + 1])
     // workgroup tasks of the shared-table kernels: <= 4 consecutive segments of one channel
-    std::vector<uint32_t> task_seg0;
-    std::vector<uint8_t> task_n;
-    std::vector<WgTask> wg_tasks;   // the same tasks as self-contained records (what the kernels read)
+    std::vector<WgTask> wg_tasks;   // self-contained records (what the kernels read)
     uint64_t seg_src_stride = 0;    // bytes between the sources of consecutive full segments of a channel
     uint64_t slot_full = 0;         // slot words of a full segment
     // wave tasks of the per-wave-table kernels: every segment once, longest first
@@ -130,8 +129,7 @@ struct PlanHost {
     // window-histogram tiles, calibration tiles (windows above kCalDirect samples)
     std::vector<uint32_t> tile_ch, tile_n, tile_cnt, cal_tile_ch, cal_tile_n;  // tile_cnt: tiles per channel
     std::vector<uint64_t> tile_start, cal_tile_start;
-    // decoder geometry
-    uint32_t W = 0, dec_K = 4, dec_NR = 32;
+    uint32_t W = 0;  // index bits of the decode table (dec_table_bits, mh_select.hpp)
 };
 
 // Head segment of a window [w0, w1) (container format revision 3, include/muahuff.h): samples up to the next
@@ -260,16 +258,12 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
             t.ch = c;
             t.seg0 = (uint32_t)seg_begin;
             t.nseg = 1;
-            p.task_seg0.push_back((uint32_t)seg_begin);
-            p.task_n.push_back(1);
             p.wg_tasks.push_back(t);
             padded_waves += 1;  // (its three idle waves leave at once: not what the wave-task rule below is about)
             ++seg_begin;
         }
         for (size_t s0 = seg_begin; s0 < p.seg_ch.size(); s0 += 4) {
             const uint32_t cnt = (uint32_t)(p.seg_ch.size() - s0 < 4 ? p.seg_ch.size() - s0 : 4);
-            p.task_seg0.push_back((uint32_t)s0);
-            p.task_n.push_back((uint8_t)cnt);
             WgTask t{};
             t.src_off = ch_off[c] + src_bytes(p.w0[c] + p.seg_first[s0]);
             t.dst_off = p.seg_off[s0];
@@ -351,20 +345,7 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
                 p.cal_tile_n.push_back((uint32_t)(n - first < kHistTileBytes ? n - first : kHistTileBytes));
             }
         }
-    // decode table: K symbols per lookup, W index bits.  maxlen <= 5: W = K * maxlen (<= 10), every
-    // entry holds K whole codewords; longer codes (and W capped below 2 * maxlen): hybrid pair table of 10 index bits and 31
-    // staging registers, which keeps 4 workgroups per CU (tables + staging <= 40 KiB of LDS).
-    p.dec_K = I.maxlen <= 2 ? 4 : 2;
-    p.W = p.dec_K * I.maxlen;
-    p.dec_NR = 32;
-    if (p.dec_K == 2) {
-        // (wave-task plans build the table once per WAVE: 256 entries instead of 1024 cost a few more flagged
-        // entries but a quarter of the build and 3 KiB less LDS per wave -- 2400 x 72 000, S = 8: 66 -> 58 us)
-        uint32_t cap = p.use_wave_tasks ? 8u : 10u;
-        if (cap < I.maxlen) cap = I.maxlen;  // a flagged entry still holds its first codeword
-        if (p.W > cap) p.W = cap;
-        if (p.W < 2 * I.maxlen) p.dec_NR = 31;
-    }
+    p.W = dec_table_bits(I.maxlen, p.use_wave_tasks);
     // codebooks by rank: bit-reversed code (first code bit at bit 0) | len << 16
     p.codes.assign((size_t)K * 16, 0);
     for (uint32_t k = 0; k < K; ++k) {

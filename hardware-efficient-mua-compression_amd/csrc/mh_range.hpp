@@ -52,7 +52,7 @@ __device__ __forceinline__ void range_copy_cut(const uint8_t *scr, uint8_t *dst,
 
 constexpr int kRangeTag = 1;  // decode_segment's TAG: instances of its own (the codec kernels' code stays as it is)
 
-// Workgroup form (shared tables, as k_decode2): the decoder rung dispatch_decode picks for a workgroup-task plan.
+// Workgroup form (shared tables, as k_decode2): the decoder rung dec_pick (mh_select.hpp) picks for a workgroup-task plan.
 template <int K, int M, int NR, int RL, bool HY>
 __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode_range(RangeArgs r)
 {

@@ -31,8 +31,6 @@ struct RebinArgs {
     uint32_t r, rmagic;  // bin factor; floor(2^32 / r) + 1 (r >= 2): n / r == mulhi(n, rmagic) for n < 2^20
 };
 
-constexpr uint32_t kRebinRowDwords = 256 + 64;  // LDS row buffer per wave: 1024 byte prefixes + 64 lane prefixes
-
 template <bool SAT>
 struct RebinSink {
     typedef typename std::conditional<SAT, uint8_t, uint32_t>::type elem;
@@ -130,7 +128,7 @@ struct RebinSink {
     }
 };
 
-// The rungs of k_decode_range (dispatch_decode_range); SAT: uint8_t output, min(sum, 255), else uint32_t.
+// The rungs of k_decode_range (dec_pick, mh_select.hpp); SAT: uint8_t output, min(sum, 255), else uint32_t.
 template <int K, int M, int NR, int RL, bool HY, bool SAT>
 __global__ __launch_bounds__(256, kDecMinBlocks) void k_decode_rebin(RebinArgs r)
 {

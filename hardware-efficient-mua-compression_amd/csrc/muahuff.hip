@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "mh_analysis.hpp"
@@ -18,6 +19,7 @@
 #include "mh_planner.hpp"
 #include "mh_range.hpp"
 #include "mh_rebin_decode.hpp"
+#include "mh_select.hpp"
 #include "mh_worklist.hpp"
 // The library is built with -fvisibility=hidden: the C ABI of include/muahuff.h is ALL it exports
 // (tests/test_host.py compares the dynamic symbol table with the header's prototypes).
@@ -83,6 +85,13 @@ struct ListCache {
     const uint8_t *fills() const { return fixes() + w.b_fix; }
 };
 
+// A codec kernel instance and its dynamic-LDS request, resolved at plan creation (resolve_kernels): the entry points
+// launch what the plan holds: mh_encode / mh_decode issue nothing but stream work and stay capturable into a hipGraph.
+struct Kernel {
+    const void *fn = nullptr;
+    size_t lds = 0;
+};
+
 struct mh_plan {
     int device = 0;
     mh::PlanHost h;  // everything the planner computed (host copies)
@@ -112,6 +121,7 @@ struct mh_plan {
     size_t packed_cal_tiles = 0;  // packed plans: calibration tiles on the device (every window: the pieces are never scanned by k_calibrate)
     unsigned long long *d_acc = nullptr;  // wave-task encoder: per-channel {bits << 24 | finished records} (zero between launches)
     uint32_t *d_err = nullptr;  // decode status word (mh_decode_status): non-zero once a decode abandoned a segment
+    Kernel k_enc, k_dec, k_dec_packed, k_range, k_rebin_sat, k_rebin_wide;  // what the entry points launch (resolve_kernels)
     ListCache range, rebin;  // mh_decode_range (scratch slots of cut chunks) / mh_decode_rebin (side words of shared bins)
 };
 
@@ -226,12 +236,12 @@ static void launch_hist(const mh::HistArgs &a, uint64_t n_tiles, hipStream_t st)
     hipLaunchKernelGGL(mh::k_hist<NS>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
 }
 
-// The launch helpers double as "prepare" helpers: with this thread-local flag set they only
-// raise the kernel's dynamic-LDS limit (hipFuncSetAttribute), check that the kernel has no static
-// LDS (the decoders address their table by raw LDS offset) and do not launch.  mh_plan_create
-// runs them once that way, so mh_encode / mh_decode issue nothing but stream work and stay
-// capturable into a hipGraph.
-static thread_local bool g_prepare_only = false;
+static int launch(const Kernel &k, uint32_t grid, const void *args, hipStream_t st)
+{
+    void *argv[] = {const_cast<void *>(args)};
+    MH_HIP(hipLaunchKernel(k.fn, dim3(grid), dim3(256), argv, k.lds, st));
+    return MH_OK;
+}
 
 static int prepare_kernel(const void *kern, size_t lds, bool needs_lds_base_0)
 {
@@ -247,259 +257,103 @@ static int prepare_kernel(const void *kern, size_t lds, bool needs_lds_base_0)
     return MH_OK;
 }
 
-constexpr size_t kDecK4LdsFloor = 41 * 1024;  // 3 workgroups per CU (see launch_decode2, launch_encode2)
+// f(std::integral_constant<size_t, i>) for every i < N in turn: the entries of a selection table as constant expressions.
+// The instances a visitor names are compiled in its order, which is their order in the code object.
+template <class F, size_t... I>
+static void for_each_index(F f, std::index_sequence<I...>) { (..., f(std::integral_constant<size_t, I>{})); }
 
-template <int LC, int PB, int PK = 0>
-static int launch_encode2(const mh::Enc2Args &a, hipStream_t st)
+// THE place an encoder pick becomes its template instance ...
+static const void *encoder_instance(const mh::EncPick &p)
 {
-    size_t lds = 4 * (size_t)mh::enc2_wave_dwords(a.e.stage_dw) * sizeof(uint32_t);  // + the static tables
-    // The short-code byte-input encoder (S <= 3), like the S <= 3 decoder, is bound by the memory system and not by its
-    // arithmetic, and runs FASTER with 3 workgroups per CU than with the 4 its registers allow: 1024 ch x 1e7 bins
-    // 2.02-2.16 -> 1.975 ms with placement-probed payload buffers, and no longer sensitive to where the input sits
-    // (profiles/r03_occupancy_ab.txt).  The longer-code encoders are compute-bound before their stores and lose
-    // (S = 8: +4 %), S = 4..6 are indifferent (-0.8 %): only LC = 0 is capped, through the LDS request.
-    // Only where the launch has many rounds of workgroups: with 2640 tasks (96 ch x 3.6e6 bins) a quarter fewer slots cost
-    // a whole extra round (77.7 -> 80.2 us).
-    if (LC == 0 && PK == 0 && a.t.ntask >= 16384 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
-    auto kern = mh::k_encode2<LC, PB, PK>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
-    hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    const void *k = nullptr;
+    for_each_index([&](auto i) {
+        constexpr mh::EncPick E = mh::kEncInsts[decltype(i)::value];
+        if (E.LC == p.LC && E.PB == p.PB && E.PK == p.PK)
+            k = p.wave ? (const void *)mh::k_encode2w<E.LC, E.PB, E.PK> : (const void *)mh::k_encode2<E.LC, E.PB, E.PK>;
+    }, std::make_index_sequence<sizeof(mh::kEncInsts) / sizeof(mh::kEncInsts[0])>{});
+    return k;
 }
 
-template <int LC, int PB, int PK = 0>
-static int launch_encode2w(const mh::Enc2Args &a, hipStream_t st)
+// ... and a decoder pick its (nullptr: not built, mh::dec_built)
+template <size_t I, mh::DecForm F, uint32_t PO>
+static const void *decoder_instance()
 {
-    const size_t lds = 4 * (size_t)mh::enc2w_wave_dwords<PB, PK>(a.e.stage_dw) * sizeof(uint32_t);
-    auto kern = mh::k_encode2w<LC, PB, PK>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
-    hipLaunchKernelGGL(kern, dim3((a.t.ntask + 3) / 4), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    constexpr mh::DecRung R = mh::kDecRungs[I];
+    if constexpr (!mh::dec_built(I, F, PO)) return nullptr;
+    else if constexpr (F == mh::kDecode2w) return (const void *)mh::k_decode2w<R.K, R.M, R.NR, R.RL, R.HY, R.DUAL, PO>;
+    else if constexpr (F == mh::kDecode2) return (const void *)mh::k_decode2<R.K, R.M, R.NR, R.RL, R.HY, PO>;
+    else if constexpr (F == mh::kDecodeRange) return (const void *)mh::k_decode_range<R.K, R.M, R.NR, R.RL, R.HY>;
+    else return (const void *)mh::k_decode_rebin<R.K, R.M, R.NR, R.RL, R.HY, F == mh::kDecodeRebinSat>;
 }
 
-// workgroup tasks (long channels)
-template <int K, int M, int NR, int RL, bool HY, int PO>
-static int launch_decode2(const mh::Dec2Args &a, hipStream_t st)
+static const void *decoder_instance(const mh::DecPick &p)
 {
-    size_t lds = ((size_t)mh::dec2_shared_dwords(a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    // The four-symbol decoder (S <= 3) is bound by its 1-KiB row stores, not by its arithmetic, and the part
-    // writes FASTER with fewer waves streaming at once: 3 workgroups per CU instead of the 4 its registers
-    // allow, enforced through the LDS request (160 KiB / 41 KiB = 3): 1024 ch x 1e7 bins decode 2.25 -> 2.04 ms
-    // on one box; 2 per CU: 2.40 ms (profiles/r03_occupancy_ab.txt).  The pair-table decoders (S >= 4) are
-    // bound by their dependent lookup chain and lose with fewer waves (S = 5: 2.27 -> 2.38 ms).  (Measured with
-    // byte output; the packed decoders request only the LDS they use.)
-    if (K == 4 && PO == 0 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;
-    auto kern = mh::k_decode2<K, M, NR, RL, HY, PO>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, K == 2);
-    hipLaunchKernelGGL(kern, dim3(a.t.ntask), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    struct Group { mh::DecForm a, b; uint32_t po; };  // two forms side by side per rung; all rungs of a group before the next
+    static constexpr Group G[] = {{mh::kDecodeRange, mh::kDecodeRange, 0}, {mh::kDecodeRebinSat, mh::kDecodeRebinWide, 0},
+                                  {mh::kDecode2w, mh::kDecode2, 2}, {mh::kDecode2w, mh::kDecode2, 4}, {mh::kDecode2w, mh::kDecode2, 0}};
+    const void *k = nullptr;
+    for_each_index([&](auto i) {
+        constexpr Group g = G[decltype(i)::value / mh::kDecRungCount];
+        constexpr size_t I = decltype(i)::value % mh::kDecRungCount;
+        const void *a = decoder_instance<I, g.a, g.po>(), *b = decoder_instance<I, g.b, g.po>();
+        if (I == p.rung && g.po == p.po && (p.form == g.a || p.form == g.b)) k = p.form == g.a ? a : b;
+    }, std::make_index_sequence<5 * mh::kDecRungCount>{});
+    return k;
 }
 
-// wave tasks (short channels)
-template <int K, int M, int NR, int RL, bool HY, bool DUAL, int PO>
-static int launch_decode2w(const mh::Dec2Args &a, hipStream_t st)
+// The kernel of a pick and its LDS request, prepared: the dynamic-LDS limit raised where the request needs it, and no
+// static LDS in the kernels that address their table by raw LDS offset (k_decode2 with K = 2, range, re-bin).
+static int resolve(Kernel *k, const void *fn, size_t lds, bool needs_lds_base_0)
 {
-    const size_t lds = 4 * ((size_t)mh::dec2_shared_dwords(a.W, K) + mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    auto kern = mh::k_decode2w<K, M, NR, RL, HY, DUAL, PO>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, false);
-    hipLaunchKernelGGL(kern, dim3((a.t.ntask + 3) / 4), dim3(256), lds, st, a);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    if (!fn) return fail(MH_ERR_ARG, "mh_plan_create: no kernel instance is built for this plan");
+    *k = Kernel{fn, lds};
+    return prepare_kernel(fn, lds, needs_lds_base_0);
 }
 
-// range decode (mh_decode_range): the workgroup form with shared tables, LDS as launch_decode2 requests it
-template <int K, int M, int NR, int RL, bool HY>
-static int launch_decode_range(const mh::RangeArgs &r, uint32_t nwg, hipStream_t st)
+static int resolve(Kernel *k, const mh::DecPick &p, uint32_t W)
 {
-    size_t lds = ((size_t)mh::dec2_shared_dwords(r.a.W, K) + 4 * (size_t)mh::dec2_stage_dwords(NR)) * sizeof(uint32_t);
-    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;  // (see launch_decode2)
-    auto kern = mh::k_decode_range<K, M, NR, RL, HY>;
-    if (g_prepare_only) return prepare_kernel(reinterpret_cast<const void *>(kern), lds, true);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, r);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    const bool base0 = p.form != mh::kDecode2w && (p.form != mh::kDecode2 || mh::kDecRungs[p.rung].K == 2);
+    return resolve(k, decoder_instance(p), mh::dec_lds_bytes(p, W), base0);
 }
 
-// fused decode + re-bin (mh_decode_rebin): launch_decode_range's LDS plus each wave's row buffer; 64 bytes of slack
-// behind the last wave's staging area, which a cut last chunk may read past by a few words (decode_staged_chunk, SINK)
-template <int K, int M, int NR, int RL, bool HY>
-static int launch_decode_rebin(const mh::RebinArgs &r, bool sat, uint32_t nwg, hipStream_t st)
+static mh::TaskArgs task_args(const mh_plan *p)
 {
-    size_t lds = ((size_t)mh::dec2_shared_dwords(r.a.W, K) + 4 * ((size_t)mh::dec2_stage_dwords(NR) + mh::kRebinRowDwords)) *
-                     sizeof(uint32_t) + 64;
-    if (K == 4 && lds < kDecK4LdsFloor) lds = kDecK4LdsFloor;  // (see launch_decode2)
-    auto ks = mh::k_decode_rebin<K, M, NR, RL, HY, true>;
-    auto kw = mh::k_decode_rebin<K, M, NR, RL, HY, false>;
-    if (g_prepare_only) {
-        const int rc = prepare_kernel(reinterpret_cast<const void *>(ks), lds, true);
-        return rc ? rc : prepare_kernel(reinterpret_cast<const void *>(kw), lds, true);
+    mh::TaskArgs t{};
+    if (p->h.use_wave_tasks) {  // one wave per segment, longest first
+        t.wt = p->d_wave_tasks;
+        t.ntask = (uint32_t)p->h.wave_tasks.size();
+    } else {                    // one workgroup per <= 4 consecutive segments of a channel
+        t.wg = p->d_wg_tasks;
+        t.ntask = (uint32_t)p->h.wg_tasks.size();
+        t.seg_samples = p->h.info.seg_chunks * MH_CHUNK;
+        t.seg_src_stride = p->h.seg_src_stride;
+        t.slot_full = p->h.slot_full;
     }
-    if (sat) hipLaunchKernelGGL(ks, dim3(nwg), dim3(256), lds, st, r);
-    else hipLaunchKernelGGL(kw, dim3(nwg), dim3(256), lds, st, r);
-    MH_HIP(hipGetLastError());
-    return MH_OK;
+    return t;
 }
 
-// lane-private LDS staging of the encoder: 16 dwords per lane for codes of at most 2 bits (the worst case of a
-// 256-sample sub-stream), else 32 (= 4 bits per sample on average: the worst case up to 4-bit codes; a clipped
-// spike-count channel at S <= 10 stays well below that, and chunks that outgrow it take the two-pass global slow
-// path).  Always 4 * stage_ne(LC) rows: the staging rows are permuted so that the merge gathers consecutive dwords
-// (MH_STAGE_AT), which needs the row count the kernel class was compiled for.
-static inline uint32_t enc_stage_dw(uint32_t maxlen) { return maxlen <= 2 ? 16 : 32; }
-
-// the encoder instance in the plan's task form
-template <int LC, int PB, int PK>
-static int launch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
+// launch of a codec kernel (a: Enc2Args, Dec2Args) in the plan's task form: a workgroup per workgroup task or per four wave tasks
+template <class A>
+static int launch_tasks(const mh_plan *p, const Kernel &k, const A &a, hipStream_t st)
 {
-    return p->h.use_wave_tasks ? launch_encode2w<LC, PB, PK>(a, st) : launch_encode2<LC, PB, PK>(a, st);
+    return launch(k, p->h.use_wave_tasks ? (a.t.ntask + 3) / 4 : a.t.ntask, &a, st);
 }
 
-// Pair packing PB of code class LC.  Byte input packs pairs in 3 bits while every symbol fits 3 bits (S <= 8; always
-// at L <= 2), the longest class in 4 only; 4-bit pieces: a byte of the stream is the PB = 4 pair index; 2-bit pieces:
-// the four-symbol table (PB unused).
-template <int LC, int PK>
-static int encode_rung(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
+// the kernels this plan will launch (once, at plan creation)
+static int resolve_kernels(mh_plan *p)
 {
-    constexpr int PB = PK == 0 && LC < 3 ? 3 : 4;
-    if constexpr (PB == 3 && LC > 0)
-        if (p->h.info.S > 8) return launch_encode<LC, 4, PK>(p, a, st);
-    return launch_encode<LC, PB, PK>(p, a, st);
-}
-
-// code class LC of maxlen L: <= 2, <= 4, <= 8, longer (2-bit pieces mean S <= 4, so L <= 3)
-template <int PK>
-static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
-{
-    const uint32_t L = p->h.info.maxlen;
-    if (L <= 2) return encode_rung<0, PK>(p, a, st);
-    if constexpr (PK != 2) {
-        if (L > 8) return encode_rung<3, PK>(p, a, st);
-        if (L > 4) return encode_rung<2, PK>(p, a, st);
-    }
-    return encode_rung<1, PK>(p, a, st);
-}
-
-static int dispatch_encode(const mh_plan *p, const mh::Enc2Args &a, hipStream_t st)
-{
-    if (p->h.input_bits == 4) return dispatch_encode<4>(p, a, st);
-    if (p->h.input_bits == 2) return dispatch_encode<2>(p, a, st);
-    return dispatch_encode<0>(p, a, st);
-}
-
-// output bits per symbol of mh_decode_packed: 2 while every symbol fits (S <= 4), else 4
-static inline uint32_t packed_out_bits(uint32_t S) { return S <= 4 ? 2u : 4u; }
-
-// the decoder instance in the plan's task form
-template <int K, int M, int NR, int RL, bool HY, int PO>
-static int launch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t st)
-{
-    return p->h.use_wave_tasks ? launch_decode2w<K, M, NR, RL, HY, false, PO>(a, st) : launch_decode2<K, M, NR, RL, HY, PO>(a, st);
-}
-
-// The decoder from maxlen L, the table width W and the task form; PO = 0 for mh_decode, packed_out_bits(S) for
-// mh_decode_packed.  S <= 4 has no code longer than 3 bits and S >= 5 none shorter than 3, so PO = 2 stops at L = 3
-// and PO = 4 starts there.  Instances (PO is the last template argument):
-//   L <= 2    PO = 0, 2    k_decode2<4, 4, 17, 1, false>    k_decode2w<4, 4, 17, 1, false, false>
-//   L == 3    PO = 0, 2, 4 k_decode2<2, 2, 25, 2, false>    k_decode2w<2, 2, 25, 2, false, false>
-//   W >= 2L   PO = 0, 4    k_decode2<2, 2, 32, 0, false>    k_decode2w<2, 2, 32, 0, false, false>
-//   W < 2L    PO = 0, 4    k_decode2<2, 2, 31, 2, true>     k_decode2w<1, 2, 36, 2, false, true>
-// (W >= 2L: L <= 5 for workgroup tasks, L <= 4 for wave tasks -- PlanHost::W.)  18 instances; nothing else is built.
-// Window maintenance RL (decode_staged_chunk): 1 = reload, 0 = branchy top-up, 2 = select top-up; the choices are
-// the measured best per variant (profiles/README.md).
-template <int PO>
-static int dispatch_decode(const mh_plan *p, const mh::Dec2Args &a, hipStream_t st)
-{
-    const uint32_t L = p->h.info.maxlen;
-    if constexpr (PO != 4)
-        if (L <= 2) return launch_decode<4, 4, 17, 1, false, PO>(p, a, st);  // worst-case chunk = 1027 words: never oversize
-    if constexpr (PO != 2)
-        if (L != 3) {
-            if (a.W >= 2 * L) return launch_decode<2, 2, 32, 0, false, PO>(p, a, st);
-            // Long codes on SHORT channels (wave tasks, where every wave builds its own tables): the one-symbol decoder
-            // -- a 2^maxlen-byte table instead of a 256-entry hybrid pair table whose flagged entries make almost every
-            // lookup of the wave take the slow path (8 index bits) -- with the two chunks of a segment side by side
-            // (decode_staged_pair1).  10 000 x 20 000: decode S=8 82 -> 74 us, S=10 92 -> 77 us; 2400 x 72 000: 70 -> 68 us.
-            // On long channels (shared 1024-entry tables) it loses: S=8 2.35 -> 2.82 ms -- twice the LDS lookups, and
-            // those decoders are bound by LDS bank-conflict throughput, not by the latency of the chain
-            // (profiles/r03_k1_pair_decoding_ab.txt).
-            if (p->h.use_wave_tasks) return launch_decode2w<1, 2, 36, 2, false, true, PO>(a, st);
-            // hybrid pair table: W < 2 * maxlen index bits, one-symbol entries flagged (31 staging registers: PlanHost::dec_NR)
-            return launch_decode2<2, 2, 31, 2, true, PO>(a, st);
-        }
-    return launch_decode<2, 2, 25, 2, false, PO>(p, a, st);
-}
-
-// The decoder rung of the range calls: the one dispatch_decode picks for maxlen L and table width W, always in the
-// workgroup form (a long range on long channels is the case that matters; the wave-task one-symbol rung has no workgroup
-// form, its plans take the hybrid pair table as long-channel plans do).  f is called with the rung's template arguments
-// <K, M, NR, RL, HY> as a Rung: <4, 4, 17, 1, false> (L <= 2), <2, 2, 25, 2, false> (L == 3), <2, 2, 32, 0, false>
-// (W >= 2L), <2, 2, 31, 2, true> (W < 2L).
-template <int K_, int M_, int NR_, int RL_, bool HY_>
-struct Rung {
-    static constexpr int K = K_, M = M_, NR = NR_, RL = RL_;
-    static constexpr bool HY = HY_;
-};
-
-template <class F>
-static int range_rung(uint32_t L, uint32_t W, F f)
-{
-    if (L <= 2) return f(Rung<4, 4, 17, 1, false>{});
-    if (L != 3) {
-        if (W >= 2 * L) return f(Rung<2, 2, 32, 0, false>{});
-        return f(Rung<2, 2, 31, 2, true>{});
-    }
-    return f(Rung<2, 2, 25, 2, false>{});
-}
-
-static int dispatch_decode_range(const mh_plan *p, const mh::RangeArgs &r, uint32_t nwg, hipStream_t st)
-{
-    return range_rung(p->h.info.maxlen, r.a.W, [&](auto g) {
-        using R = decltype(g);
-        return launch_decode_range<R::K, R::M, R::NR, R::RL, R::HY>(r, nwg, st);
-    });
-}
-
-// the fused decode + re-bin kernel on the same rungs
-static int dispatch_decode_rebin(const mh_plan *p, const mh::RebinArgs &r, bool sat, uint32_t nwg, hipStream_t st)
-{
-    return range_rung(p->h.info.maxlen, r.a.W, [&](auto g) {
-        using R = decltype(g);
-        return launch_decode_rebin<R::K, R::M, R::NR, R::RL, R::HY>(r, sat, nwg, st);
-    });
-}
-
-static int dispatch_decode(const mh_plan *p, uint32_t po, const mh::Dec2Args &a, hipStream_t st)
-{
-    if (po == 2) return dispatch_decode<2>(p, a, st);
-    if (po == 4) return dispatch_decode<4>(p, a, st);
-    return dispatch_decode<0>(p, a, st);
-}
-
-// raise the dynamic-LDS limits of the kernels this plan will launch (once, at plan creation)
-static int prepare_kernels(const mh_plan *p)
-{
-    mh::Enc2Args e{};
-    e.e.stage_dw = enc_stage_dw(p->h.info.maxlen);
-    mh::Dec2Args d{};
-    d.W = p->h.W;
-    g_prepare_only = true;
-    int rc = dispatch_encode(p, e, nullptr);
-    if (rc == MH_OK) rc = dispatch_decode(p, 0, d, nullptr);
-    if (rc == MH_OK && p->h.input_bits == packed_out_bits(p->h.info.S))  // a plan mh_decode_packed accepts
-        rc = dispatch_decode(p, p->h.input_bits, d, nullptr);
-    if (rc == MH_OK && p->h.input_bits == 8) {  // a plan mh_decode_range accepts
-        mh::RangeArgs r{};
-        r.a = d;
-        rc = dispatch_decode_range(p, r, 0, nullptr);
-        mh::RebinArgs b{};
-        b.a = d;
-        if (rc == MH_OK) rc = dispatch_decode_rebin(p, b, true, 0, nullptr);
-    }
-    g_prepare_only = false;
-    return rc;
+    const mh::PlanHost &H = p->h;
+    const uint32_t L = H.info.maxlen, W = H.W;
+    const mh::EncPick e = mh::enc_pick(L, H.info.S, H.input_bits, H.use_wave_tasks);
+    int rc = resolve(&p->k_enc, encoder_instance(e), mh::enc_lds_bytes(e, L, task_args(p).ntask), false);
+    if (rc || (rc = resolve(&p->k_dec, mh::dec_pick(L, W, H.use_wave_tasks, 0), W))) return rc;
+    if (H.input_bits == mh::packed_out_bits(H.info.S))  // a plan mh_decode_packed accepts
+        return resolve(&p->k_dec_packed, mh::dec_pick(L, W, H.use_wave_tasks, H.input_bits), W);
+    if (H.input_bits != 8) return MH_OK;
+    const mh::DecRungId r = mh::dec_pick(L, W, false, 0).rung;  // a plan mh_decode_range / mh_decode_rebin accept
+    if ((rc = resolve(&p->k_range, {r, mh::kDecodeRange, 0}, W)) || (rc = resolve(&p->k_rebin_sat, {r, mh::kDecodeRebinSat, 0}, W)))
+        return rc;
+    return resolve(&p->k_rebin_wide, {r, mh::kDecodeRebinWide, 0}, W);
 }
 
 #pragma GCC visibility push(default)
@@ -691,7 +545,7 @@ int mh_plan_create_packed(mh_plan **plan, const uint64_t *ch_off, const uint64_t
     if (rc == MH_OK && (hipMemset(p->d_hist, 0, (size_t)I.C * mh::kHistStride * sizeof(unsigned long long)) != hipSuccess ||
                         hipMemset(p->d_tile_done, 0, (size_t)I.C * sizeof(uint32_t)) != hipSuccess))
         rc = fail(MH_ERR_HIP, "mh_plan_create: clearing the measure scratch failed");
-    if (rc == MH_OK) rc = prepare_kernels(p);
+    if (rc == MH_OK) rc = resolve_kernels(p);
     if (rc != MH_OK) {
         mh_plan_destroy(p);
         return rc;
@@ -798,22 +652,6 @@ int mh_measure(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_
     return MH_OK;
 }
 
-static mh::TaskArgs task_args(const mh_plan *p)
-{
-    mh::TaskArgs t{};
-    if (p->h.use_wave_tasks) {  // one wave per segment, longest first
-        t.wt = p->d_wave_tasks;
-        t.ntask = (uint32_t)p->h.wave_tasks.size();
-    } else {                    // one workgroup per <= 4 consecutive segments of a channel
-        t.wg = p->d_wg_tasks;
-        t.ntask = (uint32_t)p->h.wg_tasks.size();
-        t.seg_samples = p->h.info.seg_chunks * MH_CHUNK;
-        t.seg_src_stride = p->h.seg_src_stride;
-        t.slot_full = p->h.slot_full;
-    }
-    return t;
-}
-
 // cal_mode: see EncArgs.  Modes 1 and 2 exist for wave-task plans only.
 static int encode_common(mh_plan *p, const uint8_t *data, uint32_t *payload, uint64_t *seg_words,
                          uint64_t *ch_bits, uint32_t cal_mode, const uint8_t *peak_in, const uint8_t *enc_in,
@@ -847,11 +685,11 @@ static int encode_common(mh_plan *p, const uint8_t *data, uint32_t *payload, uin
     a.seg_words = seg_words;
     a.ch_bits = reinterpret_cast<unsigned long long *>(ch_bits);
     a.nseg = (uint32_t)p->h.info.n_segments;
-    a.stage_dw = enc_stage_dw(p->h.info.maxlen);
+    a.stage_dw = mh::enc_stage_dw(p->h.info.maxlen);
     mh::Enc2Args a2;
     a2.e = a;
     a2.t = task_args(p);
-    return dispatch_encode(p, a2, st);
+    return launch_tasks(p, p->k_enc, a2, st);
 }
 
 int mh_encode(mh_plan *p, const uint8_t *data, uint32_t *payload, uint64_t payload_cap_words,
@@ -935,7 +773,7 @@ int mh_decode(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const
         return fail(MH_ERR_ARG, "mh_decode: this plan reads packed pieces (mh_encode_preset only); decode with a byte-layout plan");
     if (int rc_ = check_device(p->device, "mh_decode")) return rc_;
     if (p->h.info.n_segments == 0) return MH_OK;
-    return dispatch_decode(p, 0, decode_args(p, payload, payload_words, seg_off, peak, enc, out), (hipStream_t)stream);
+    return launch_tasks(p, p->k_dec, decode_args(p, payload, payload_words, seg_off, peak, enc, out), (hipStream_t)stream);
 }
 
 int mh_decode_packed(mh_plan *p, const uint32_t *payload, uint64_t payload_words, const uint64_t *seg_off,
@@ -944,13 +782,12 @@ int mh_decode_packed(mh_plan *p, const uint32_t *payload, uint64_t payload_words
     if (!p || !payload || !peak || !enc || !out) return fail(MH_ERR_ARG, "mh_decode_packed: NULL argument");
     if (p->h.input_bits == 8)
         return fail(MH_ERR_ARG, "mh_decode_packed: this plan describes a byte layout; decode it with mh_decode");
-    if (p->h.input_bits != packed_out_bits(p->h.info.S))
+    if (p->h.input_bits != mh::packed_out_bits(p->h.info.S))
         return fail(MH_ERR_ARG, "mh_decode_packed: S=%u decodes to %u-bit pieces, the plan holds %u-bit ones", p->h.info.S,
-                    packed_out_bits(p->h.info.S), p->h.input_bits);
+                    mh::packed_out_bits(p->h.info.S), p->h.input_bits);
     if (int rc_ = check_device(p->device, "mh_decode_packed")) return rc_;
     if (p->h.info.n_segments == 0) return MH_OK;
-    return dispatch_decode(p, p->h.input_bits, decode_args(p, payload, payload_words, seg_off, peak, enc, out),
-                           (hipStream_t)stream);
+    return launch_tasks(p, p->k_dec_packed, decode_args(p, payload, payload_words, seg_off, peak, enc, out), (hipStream_t)stream);
 }
 
 int mh_decode_status(mh_plan *p, uint32_t *flags, void *stream)
@@ -1069,7 +906,7 @@ int mh_decode_range(mh_plan *p, const uint32_t *payload, uint64_t payload_words,
     r.wg = reinterpret_cast<const mh::RangeWg *>(c.wgs());
     r.out = out;
     r.scratch = c.d_aux;
-    return dispatch_decode_range(p, r, (uint32_t)c.w.nwg, st);
+    return launch(p->k_range, (uint32_t)c.w.nwg, &r, st);
 }
 
 // the two output forms of mh_decode_rebin around its decoder: zero fills in front, fix-ups of the shared bins behind
@@ -1083,7 +920,7 @@ static int decode_rebin(const mh_plan *p, const mh::RebinArgs &a, bool sat, hipS
     });
     if (rc || c.w.nwg == 0) return rc;
     if (c.w.naux) MH_HIP(hipMemsetAsync(c.d_aux, 0, c.w.naux * sizeof(uint32_t), st));
-    if ((rc = dispatch_decode_rebin(p, a, sat, (uint32_t)c.w.nwg, st)) || c.w.nfix == 0) return rc;
+    if ((rc = launch(sat ? p->k_rebin_sat : p->k_rebin_wide, (uint32_t)c.w.nwg, &a, st)) || c.w.nfix == 0) return rc;
     hipLaunchKernelGGL(mh::k_rebin_fix<T>, dim3((unsigned)((c.w.nfix + 255) / 256)), dim3(256), 0, st, out,
                        reinterpret_cast<const mh::RebinFix *>(c.fixes()), (uint32_t)c.w.nfix, a.side);
     MH_HIP(hipGetLastError());

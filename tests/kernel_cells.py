@@ -1,21 +1,20 @@
 """The codec kernels the production library ships, one cell per instance (a plain module, not a conftest).
 
 libmuahuff.so compiles a fixed set of k_encode2 / k_encode2w / k_decode2 / k_decode2w template instances, and
-dispatch_encode and dispatch_decode (csrc/muahuff.hip) choose among them from the plan: maxlen L (the longest
-codeword of the plan's SCLV rows), S <= 8 (3-bit pair packing) or not, input_bits (8, or packed 4 / 2), the
-planner's wave-task rule (csrc/mh_planner.hpp) and, for the decoder, the output (bytes for mh_decode, 2- / 4-bit
-pieces for mh_decode_packed: input_bits of the packed cells), the table width W and the staging registers dec_NR.
-decoder_symbol is that decoder choice in Python.  Every CELL names one instance and the plans that land on it:
+enc_pick and dec_pick (csrc/mh_select.hpp) choose among them from the plan: maxlen L (the longest codeword of the
+plan's SCLV rows), S <= 8 (3-bit pair packing) or not, input_bits (8, or packed 4 / 2), the planner's wave-task rule
+(csrc/mh_planner.hpp) and, for the decoder, the output (bytes for mh_decode, 2- / 4-bit pieces for mh_decode_packed:
+input_bits of the packed cells) and the table width W.  Every CELL names one instance and the plans that land on it:
 
   cases    (S, SCLV rows) pairs -- each row Kraft-complete and non-decreasing -- with the maxlen they give; decoder
-           cells also give the planner's W, dec_K and dec_NR for that case
+           cells also give the table width W for that case
   layouts  (channel lengths, seg_chunks): whole-channel windows (MH_WIN_FULL) that put the plan in the cell's task
            form -- wave tasks when the workgroup tasks (<= 4 segments of one channel) would leave more than one
            wave in 16 idle, workgroup tasks otherwise
 
 tests/test_host_kernel_cells.py checks without a GPU that the cells and the shipped symbols are the same set and
-that the host planner puts every case and layout where its cell says; tests/test_gpu_kernel_cells.py (encoders,
-byte decoders) and tests/test_gpu_stream_decode.py (packed decoders) run them against the CPU oracle.
+that the library's own selection puts every case and layout on its cell's instance; tests/test_gpu_kernel_cells.py
+(encoders, byte decoders) and tests/test_gpu_stream_decode.py (packed decoders) run them against the CPU oracle.
 """
 from dataclasses import dataclass
 
@@ -27,9 +26,7 @@ class Case:
     S: int
     rows: tuple          # K rows of S code lengths
     maxlen: int
-    W: int = 0           # decoder cells: index bits of the decode table ...
-    dec_K: int = 0       # ... symbols per lookup ...
-    dec_NR: int = 0      # ... and the planner's staging-register choice (31 only for the hybrid pair table)
+    W: int = 0           # decoder cells: index bits of the decode table
 
 
 @dataclass(frozen=True)
@@ -143,25 +140,24 @@ ENCODER_CELLS = tuple(
 DECODER_CELLS = (
     # byte output; workgroup form: shared tables of up to 10 index bits
     Cell("mh::k_decode2<4, 4, 17, 1, false, 0>", False, 8, 1,
-         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32)), WG_LAYOUTS),
+         (_c(3, 2, W=8), _c(2, 1, W=4)), WG_LAYOUTS),
     Cell("mh::k_decode2<2, 2, 25, 2, false, 0>", False, 8, 0,
-         (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
+         (_c(8, 3, W=6), _c(4, 3, W=6)), WG_LAYOUTS),
     Cell("mh::k_decode2<2, 2, 32, 0, false, 0>", False, 8, 1,      # L = 5 is the last with W = 2L
-         (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32), _c(8, 5, W=10, dec_K=2, dec_NR=32)),
+         (_c(9, 4, W=8), _c(6, 5, W=10), _c(8, 5, W=10)),
          WG_LAYOUTS),
     Cell("mh::k_decode2<2, 2, 31, 2, true, 0>", False, 8, 0,       # L = 6 is the first hybrid one
-         (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31), _c(9, 8, W=10, dec_K=2, dec_NR=31)),
+         (_c(7, 6, W=10), _c(10, 9, W=10), _c(9, 8, W=10)),
          WG_LAYOUTS),
     # wave form: per-wave tables of up to 8 index bits
     Cell("mh::k_decode2w<4, 4, 17, 1, false, false, 0>", True, 8, 0,
-         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)), WAVE_LAYOUTS),
+         (_c(3, 2, W=8), _c(4, 2, W=8)), WAVE_LAYOUTS),
     Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 0>", True, 8, 1,
-         (_c(8, 3, W=6, dec_K=2, dec_NR=32), _c(4, 3, W=6, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+         (_c(8, 3, W=6), _c(4, 3, W=6)), WAVE_LAYOUTS),
     Cell("mh::k_decode2w<2, 2, 32, 0, false, false, 0>", True, 8, 0,      # L = 4 is the last with W = 2L
-         (_c(9, 4, W=8, dec_K=2, dec_NR=32), _c(8, 4, W=8, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+         (_c(9, 4, W=8), _c(8, 4, W=8)), WAVE_LAYOUTS),
     Cell("mh::k_decode2w<1, 2, 36, 2, false, true, 0>", True, 8, 1,       # L = 5 is the first one-symbol one
-         (_c(6, 5, W=8, dec_K=2, dec_NR=31), _c(9, 5, W=8, dec_K=2, dec_NR=31),
-          _c(10, 9, W=9, dec_K=2, dec_NR=31)),                          # (W >= L: an entry holds its first code)
+         (_c(6, 5, W=8), _c(9, 5, W=8), _c(10, 9, W=9)),               # (W >= L: an entry holds its first code)
          WAVE_LAYOUTS),
 )
 
@@ -170,41 +166,28 @@ DECODER_CELLS = (
 PACKED_DECODER_CELLS = (
     # 2-bit pieces (S <= 4): the four-symbol table for L <= 2, the pair table for L = 3
     Cell("mh::k_decode2<4, 4, 17, 1, false, 2>", False, 2, 1,
-         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)),
+         (_c(3, 2, W=8), _c(2, 1, W=4), _c(4, 2, W=8)),
          WG_LAYOUTS),
-    Cell("mh::k_decode2<2, 2, 25, 2, false, 2>", False, 2, 1, (_c(4, 3, W=6, dec_K=2, dec_NR=32),), WG_LAYOUTS),
+    Cell("mh::k_decode2<2, 2, 25, 2, false, 2>", False, 2, 1, (_c(4, 3, W=6),), WG_LAYOUTS),
     Cell("mh::k_decode2w<4, 4, 17, 1, false, false, 2>", True, 2, 1,
-         (_c(3, 2, W=8, dec_K=4, dec_NR=32), _c(2, 1, W=4, dec_K=4, dec_NR=32), _c(4, 2, W=8, dec_K=4, dec_NR=32)),
+         (_c(3, 2, W=8), _c(2, 1, W=4), _c(4, 2, W=8)),
          WAVE_LAYOUTS),
-    Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 2>", True, 2, 1, (_c(4, 3, W=6, dec_K=2, dec_NR=32),), WAVE_LAYOUTS),
+    Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 2>", True, 2, 1, (_c(4, 3, W=6),), WAVE_LAYOUTS),
     # 4-bit pieces (S >= 5)
     Cell("mh::k_decode2<2, 2, 25, 2, false, 4>", False, 4, 1,
-         (_c(5, 3, W=6, dec_K=2, dec_NR=32), _c(8, 3, W=6, dec_K=2, dec_NR=32)), WG_LAYOUTS),
+         (_c(5, 3, W=6), _c(8, 3, W=6)), WG_LAYOUTS),
     Cell("mh::k_decode2<2, 2, 32, 0, false, 4>", False, 4, 1,     # L = 5 is the last with W = 2L
-         (_c(5, 4, W=8, dec_K=2, dec_NR=32), _c(9, 4, W=8, dec_K=2, dec_NR=32), _c(6, 5, W=10, dec_K=2, dec_NR=32)),
+         (_c(5, 4, W=8), _c(9, 4, W=8), _c(6, 5, W=10)),
          WG_LAYOUTS),
     Cell("mh::k_decode2<2, 2, 31, 2, true, 4>", False, 4, 1,      # hybrid pair table from L = 6
-         (_c(7, 6, W=10, dec_K=2, dec_NR=31), _c(10, 9, W=10, dec_K=2, dec_NR=31)), WG_LAYOUTS),
+         (_c(7, 6, W=10), _c(10, 9, W=10)), WG_LAYOUTS),
     Cell("mh::k_decode2w<2, 2, 25, 2, false, false, 4>", True, 4, 1,
-         (_c(5, 3, W=6, dec_K=2, dec_NR=32), _c(8, 3, W=6, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+         (_c(5, 3, W=6), _c(8, 3, W=6)), WAVE_LAYOUTS),
     Cell("mh::k_decode2w<2, 2, 32, 0, false, false, 4>", True, 4, 1,  # L = 4 is the last with W = 2L
-         (_c(5, 4, W=8, dec_K=2, dec_NR=32), _c(10, 4, W=8, dec_K=2, dec_NR=32)), WAVE_LAYOUTS),
+         (_c(5, 4, W=8), _c(10, 4, W=8)), WAVE_LAYOUTS),
     Cell("mh::k_decode2w<1, 2, 36, 2, false, true, 4>", True, 4, 1,   # one-symbol pairs from L = 5
-         (_c(6, 5, W=8, dec_K=2, dec_NR=31), _c(10, 9, W=9, dec_K=2, dec_NR=31)), WAVE_LAYOUTS),
+         (_c(6, 5, W=8), _c(10, 9, W=9)), WAVE_LAYOUTS),
 )
 
 CELLS = ENCODER_CELLS + DECODER_CELLS + PACKED_DECODER_CELLS
 
-
-def decoder_symbol(po, wave, L, W):
-    """dispatch_decode<PO> (csrc/muahuff.hip) in Python: the decoder a plan launches, from the output bits PO (0 =
-    bytes), the task form, maxlen L and the table width W"""
-    if po != 4 and L <= 2:
-        args = "4, 4, 17, 1, false"
-    elif po == 2 or L == 3:
-        args = "2, 2, 25, 2, false"
-    elif W >= 2 * L:
-        args = "2, 2, 32, 0, false"
-    else:
-        return "mh::k_decode2w<1, 2, 36, 2, false, true, %d>" % po if wave else "mh::k_decode2<2, 2, 31, 2, true, %d>" % po
-    return "mh::k_decode2w<%s, false, %d>" % (args, po) if wave else "mh::k_decode2<%s, %d>" % (args, po)

@@ -6,7 +6,10 @@
 // compare with the CPU oracle's:  "nseg cap seg_chunks wave_tasks" then four lines ch / first / n / off.
 // With --cells (tests/kernel_cells.py) each case carries input_bits after seg_chunks,
 //     C S h mode window K seg_chunks input_bits  len[0..C)  sclv[0..K*S)
-// and the program prints only where the kernel dispatch lands:  "maxlen wave_tasks W dec_K dec_NR".
+// and the program prints only where the kernel selection (csrc/mh_select.hpp, what mh_plan_create resolves) lands, fields
+// separated by '|':  "maxlen wave_tasks W", then instance name and dynamic-LDS bytes of the plan's encoder, of its decoder
+// (PO = 0 for a byte plan, PO = input_bits for a packed one; "-" and 0 where mh_decode_packed refuses the plan) and, for
+// byte plans, of its k_decode_range and k_decode_rebin<..., true> instances.
 // With --forms (tests/async_table.py) the same input gives the form of the plan, which decides what each call enqueues:
 // "wave_tasks measure_fused fused_calibration tickets_fit cal_tiles head_segments skipped short_channels".
 // With --worklist (tests/test_host_worklist.py) a case in the first format is followed by a query count and that many
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "mh_planner.hpp"
+#include "mh_select.hpp"
 #include "mh_worklist.hpp"
 
 #define CHECK(cond)                                                    \
@@ -85,7 +89,25 @@ static int cells(bool forms)
                    (int)p.tickets_fit, p.cal_tile_ch.size(), heads, (unsigned long long)p.info.n_skipped, shorter);
             continue;
         }
-        printf("%u %d %u %u %u\n", p.info.maxlen, (int)p.use_wave_tasks, p.W, p.dec_K, p.dec_NR);
+        const uint32_t L = p.info.maxlen, bits = p.input_bits;
+        const bool wave = p.use_wave_tasks;
+        const mh::EncPick e = mh::enc_pick(L, p.info.S, bits, wave);
+        const size_t ntask = wave ? p.wave_tasks.size() : p.wg_tasks.size();
+        printf("%u %d %u|%s|%zu", L, (int)wave, p.W, mh::enc_name(e).c_str(), mh::enc_lds_bytes(e, L, (uint32_t)ntask));
+        if (bits == 8 || bits == mh::packed_out_bits(p.info.S)) {
+            const mh::DecPick d = mh::dec_pick(L, p.W, wave, bits == 8 ? 0 : bits);
+            printf("|%s|%zu", mh::dec_name(d).c_str(), mh::dec_lds_bytes(d, p.W));
+        } else {
+            printf("|-|0");
+        }
+        if (bits == 8) {
+            const mh::DecRungId r = mh::dec_pick(L, p.W, false, 0).rung;
+            for (mh::DecForm f : {mh::kDecodeRange, mh::kDecodeRebinSat}) {
+                const mh::DecPick d{r, f, 0};
+                printf("|%s|%zu", mh::dec_name(d).c_str(), mh::dec_lds_bytes(d, p.W));
+            }
+        }
+        printf("\n");
     }
     return got < 0;
 }
@@ -193,28 +215,26 @@ int main(int argc, char **argv)
             for (uint64_t s = p.ch_seg0[c]; s < p.ch_seg0[c + 1]; ++s) CHECK(p.seg_ch[s] == c);
         }
         if (n) CHECK(p.seg_off[n - 1] + mh::slot_words(p.seg_n[n - 1], maxlen) + 4 == p.info.payload_cap_words);
-        // shared-table tasks: every segment once, <= 4 consecutive ones of one channel
-        size_t covered = 0;
-        for (size_t t = 0; t < p.task_seg0.size(); ++t) {
-            CHECK(p.task_seg0[t] == covered && p.task_n[t] >= 1 && p.task_n[t] <= 4);
-            for (unsigned k = 1; k < p.task_n[t]; ++k) CHECK(p.seg_ch[covered + k] == p.seg_ch[covered]);
-            covered += p.task_n[t];
-        }
-        CHECK(covered == n);
-        // the same tasks as self-contained records: what a wave derives by arithmetic equals the directory
-        CHECK(p.wg_tasks.size() == p.task_seg0.size());
+        // shared-table tasks: every segment once in directory order, 1..4 consecutive ones of one channel, a head segment
+        // alone; what a wave derives from the record by arithmetic equals the directory
         const uint64_t seg_samples = (uint64_t)p.info.seg_chunks * MH_CHUNK;
         CHECK(p.seg_src_stride == seg_samples && p.slot_full == mh::slot_words(seg_samples, maxlen));
+        size_t covered = 0;
         for (size_t t = 0; t < p.wg_tasks.size(); ++t) {
             const mh::WgTask &w = p.wg_tasks[t];
-            CHECK(w.seg0 == p.task_seg0[t] && w.nseg == p.task_n[t] && w.ch == p.seg_ch[w.seg0]);
+            CHECK(w.seg0 == covered && w.nseg >= 1 && w.nseg <= 4 && covered + w.nseg <= n && w.ch == p.seg_ch[w.seg0]);
+            covered += w.nseg;
+            const bool head = p.seg_first[w.seg0] == 0 && mh::head_samples(p.w0[w.ch], p.w1[w.ch], p.info.window) != 0;
+            if (head) CHECK(w.nseg == 1 && w.n_last == mh::head_samples(p.w0[w.ch], p.w1[w.ch], p.info.window));
             for (uint32_t k = 0; k < w.nseg; ++k) {
                 const size_t sg = (size_t)w.seg0 + k;
+                CHECK(p.seg_ch[sg] == w.ch);
                 CHECK(w.src_off + k * p.seg_src_stride == off[w.ch] + p.w0[w.ch] + p.seg_first[sg]);
                 CHECK(w.dst_off + k * p.slot_full == p.seg_off[sg]);
                 CHECK((k + 1 < w.nseg ? seg_samples : (uint64_t)w.n_last) == p.seg_n[sg]);
             }
         }
+        CHECK(covered == n);
         if (p.use_wave_tasks) {  // every segment once, longest first, then one record per channel without segments
             std::vector<uint8_t> seen(n, 0);
             std::vector<uint32_t> per_ch(C, 0), first_ch(C, 0);
@@ -261,7 +281,7 @@ int main(int argc, char **argv)
         if (((uint64_t)1 << h) > mh::kCalDirect)
             for (unsigned c = 0; c < C; ++c) cal_want += len[c] < ((uint64_t)1 << h) ? len[c] : ((uint64_t)1 << h);
         CHECK(cal == cal_want);
-        CHECK(p.W >= maxlen && p.W <= 12 && (p.dec_K == 2 || p.dec_K == 4));
+        CHECK(p.W >= maxlen && p.W <= 12);
         printf("%zu %llu %u %d %d\n", n, (unsigned long long)p.info.payload_cap_words, p.info.seg_chunks, (int)p.use_wave_tasks,
                (int)p.tickets_fit);
         for (size_t s = 0; s < n; ++s) printf("%u ", p.seg_ch[s]);

@@ -4,14 +4,13 @@ decoders themselves are cells of tests/kernel_cells.py (k_decode2 / k_decode2w w
 with the others by tests/test_host_kernel_cells.py.
 
 mh_decode_packed picks the output width from S -- 2 bits for S <= 4, 4 bits for S >= 5 -- and then makes
-mh_decode's choice (dispatch_decode) from maxlen L, the task form and the table width W.  S >= 5 needs a codeword of
+mh_decode's choice (dec_pick, csrc/mh_select.hpp) from maxlen L, the task form and the table width W.  S >= 5 needs a codeword of
 at least 3 bits, S <= 4 has none longer than 3, so ten instances are reachable and nothing else is built."""
 import os
 import re
-import subprocess
 
 from tests import kernel_cells as kc
-from tests.test_host_kernel_cells import code_object_symbols
+from tests.test_host_kernel_cells import code_object_symbols, planned
 from tests.test_planner_sanitized import exe  # noqa: F401  (fixture: planner_check built under the sanitizers)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,8 +42,9 @@ def test_shipped_packed_interleavers(tmp_path):
 
 
 def test_every_reachable_packed_plan_has_a_cell(exe):  # noqa: F811
-    """All SCLV tables of S = 2..10 (every row and the whole table), both task forms: the instance dispatch picks is
-    one of the cells -- a plan that could reach an unbuilt instance fails here."""
+    """All SCLV tables of S = 2..10 (every row and the whole table), both task forms: the instance the library's
+    selection names (planner_check --cells) is one of the cells -- a plan that could reach an unbuilt instance fails
+    here."""
     from tests import helpers
     symbols = {c.symbol for c in kc.PACKED_DECODER_CELLS}
     tabs = helpers.sclv_tables()
@@ -56,12 +56,9 @@ def test_every_reachable_packed_plan_has_a_cell(exe):  # noqa: F811
                 flat = " ".join(str(int(v)) for r in rows for v in r)
                 lines.append("%d %d 0 1 3 %d %d %d  %s  %s" % (len(lens), S, len(rows), sc, po, " ".join(map(str, lens)), flat))
                 meta.append((S, po))
-    r = subprocess.run([exe, "--cells"], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
     seen = set()
-    for g, (S, po) in zip(r.stdout.splitlines(), meta):
-        maxlen, wave, W, _k, _nr = (int(v) for v in g.split())
-        sym = kc.decoder_symbol(po, bool(wave), maxlen, W)
+    for (maxlen, wave, W, picks), (S, po) in zip(planned(exe, lines), meta):
+        sym = picks[1][0]
         assert sym in symbols, (S, maxlen, wave, W)
         seen.add(sym)
     assert len(seen) >= 8

@@ -18,6 +18,7 @@ EXE = os.path.join(ROOT, "tests", "planner_check_asan")
 @pytest.fixture(scope="module")
 def exe():
     deps = [SRC, os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_planner.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_select.hpp"),
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_worklist.hpp"),
             os.path.join(ROOT, "include", "muahuff.h")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
