@@ -217,24 +217,17 @@ class Reader:
         decode that had to abandon a segment raises ValueError.  out: optional tensor of the result's shape and dtype
         with unit stride along its last axis (not with time_major); the rows are written there and nothing else is."""
         import torch
-        start, stop = int(start), int(stop)
-        if not (0 <= start <= stop <= self.T):
-            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, self.T))
-        sel = np.arange(self.C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
-        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
-            raise IndexError("channel index out of range")
-        r = None if bin is None else int(bin)
-        if r is not None:
-            if not 1 <= r <= 4096:
-                raise ValueError("bin factor %d outside 1..4096" % r)
-            if start % r:
-                raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
+
+        from . import codec
+        start, stop, r = int(start), int(stop), None if bin is None else int(bin)
+        sel = codec.query_args(self.T, self.C, start, stop, channels, r)
         n, rows = stop - start, int(sel.size)
         cols = n if r is None else (n + r - 1) // r
         dtype = torch.uint8 if r is None or saturate else torch.int32
-        if out is not None and (time_major or tuple(out.shape) != (rows, cols) or out.dtype != dtype or
-                                (cols > 1 and rows and out.stride(1) != 1)):
-            raise ValueError("out must be a %s [%d, %d] tensor with unit stride along its last axis" % (dtype, rows, cols))
+        if out is not None:
+            if time_major:
+                raise ValueError("out is not taken with time_major")
+            codec.check_out(out, rows, cols, dtype, "its last axis")
         # host side first: every block's words gathered and validated before anything is launched
         jobs = []
         if rows and n:
@@ -248,40 +241,28 @@ class Reader:
         plans = []
         try:
             res = self._decode(torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans)
-        finally:
-            ok = all([p.decode_ok() for p in plans])      # synchronises; every plan's flag is read and cleared
-        if not ok:
-            raise ValueError("corrupt archive: a chunk header points outside the payload (decode abandoned)")
+        except BaseException:
+            codec.check_decoded(plans, unwinding=True)      # every plan's flag is read and cleared all the same
+            raise
+        codec.check_decoded(plans, "archive")               # synchronises
         if not time_major:
             return res
-        if r is not None:
-            return res.t().contiguous()
-        from . import _lib
-        from .codec import _ptr, _stream
-        tm = torch.empty((n, rows), dtype=torch.uint8, device=res.device)
-        in_off = torch.arange(rows, dtype=torch.int64, device=res.device) * (res.stride(0) if rows > 1 else 0)
-        _lib.check(_lib.lib().mh_interleave(_ptr(res), _ptr(in_off), n, rows, _ptr(tm), _stream()))
-        return tm
+        return codec.to_time_major(res) if r is None else res.t().contiguous()
 
     def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans):
         """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride)."""
+        from . import codec
+
         def launch(job, fn):
             bf, a, b, g0, payload, seg_off, peak, enc = job
             plan = self._plan_for(bf)
             if plan not in plans:
                 plans.append(plan)
-            dev = plan.device
-            pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=dev)
-            if payload.size:
-                pay[:payload.size] = torch.from_numpy(payload.view(np.int32)).to(dev)
-            d_off = torch.from_numpy(seg_off.view(np.int64)).to(dev)
-            fn(plan, pay, d_off, torch.from_numpy(peak.copy()).to(dev), torch.from_numpy(enc.copy()).to(dev), a, b, g0)
+            fn(plan, *codec.upload_stream(plan.device, payload, seg_off, peak, enc), a, b, g0)
 
         if r is None:
-            if out is None:     # the first block's local sample t at a byte address congruent to t mod 128 (codec.decode_range)
-                phase = jobs[0][1] % 128
-                pitch = (n + phase + 127) // 128 * 128
-                out = torch.empty(rows * pitch, dtype=torch.uint8, device="cuda").as_strided((rows, n), (pitch, 1), phase)
+            if out is None:     # the first block's local sample t at a byte address congruent to t mod 128
+                out = codec.aligned_rows(rows, n, jobs[0][1], "cuda")
             for job in jobs:
                 launch(job, lambda plan, pay, off, pk, en, a, b, g0:
                        plan.decode_range(pay, off, pk, en, sel, a, b, out=out[:, g0:g0 + b - a]))
@@ -338,22 +319,13 @@ def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None):
     StreamDecoder.decode_block makes, plus the array sizes the directory arithmetic relies on."""
     hd = c.header
     cio._header_fields(hd)
-    if (int(hd["S"]) != S or int(hd["mode"]) != mode or int(hd["window"]) != WIN_FULL or int(hd["seg_chunks"]) != seg_chunks):
-        raise ValueError("block (S, mode, window, seg_chunks) = (%s, %s, %s, %s) is not this archive's (%d, %d, %d, %d)"
-                         % (hd["S"], hd["mode"], hd["window"], hd["seg_chunks"], S, mode, WIN_FULL, seg_chunks))
+    cio.check_block(c, C, S, mode, seg_chunks, sclv, what="block")
     if int(hd.get("format_revision", -1)) != cio.FORMAT_REVISION:
         raise ValueError("an archive block has container format revision %d" % cio.FORMAT_REVISION)
-    if np.asarray(hd["sclv"], np.int64).reshape(-1).tolist() != sclv.astype(np.int64).reshape(-1).tolist():
-        raise ValueError("block SCLV rows are not this archive's")
-    ch_len = np.asarray(c.ch_len, np.uint64)
-    if len(ch_len) != C or int(ch_len[0]) < 1 or (ch_len != ch_len[0]).any():
-        raise ValueError("an archive block holds %d channels of one length" % C)
-    if not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
-        raise ValueError("block arrays disagree about the channel count")
-    nseg = int(cio.segments_per_channel(ch_len, int(hd["h"]), WIN_FULL, seg_chunks).sum())
+    cio.check_consistent(c, what="block")
     words = int(c.payload.size) if payload_words is None else int(payload_words)
-    if len(c.seg_words) != nseg or int(np.asarray(c.seg_words, np.uint64).sum()) != words:
-        raise ValueError("block directory does not match its header and payload")
+    if int(np.asarray(c.seg_words, np.uint64).sum()) != words:
+        raise ValueError("block directory does not match its payload")
 
 
 class Writer:

@@ -27,6 +27,71 @@ def _need_gpu():
         raise _lib.MuaHuffError(_lib.ERR_NO_DEVICE, "no MI355X visible; this package has no CPU fallback")
 
 
+# ---- what every range / re-bin query shares -------------------------------------------------------
+def select_channels(C, channels):
+    """-> int64 channel indices (None = all C; any order, repeats allowed); IndexError outside 0..C-1"""
+    sel = np.arange(C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
+    if sel.size and (sel.min() < 0 or sel.max() >= C):
+        raise IndexError("channel index out of range")
+    return sel
+
+
+def query_args(max_len, C, start, stop, channels, r=None):
+    """The argument rules of every range query: 0 <= start <= stop <= max_len; with a bin factor, 1 <= r <= 4096 and
+    start a multiple of r (ValueError); channel indices inside 0..C-1 (IndexError).  -> sel (select_channels)"""
+    if r is not None and not 1 <= r <= 4096:
+        raise ValueError("bin factor %d outside 1..4096" % r)
+    if not (0 <= start <= stop <= max_len):
+        raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
+    if r is not None and start % r:
+        raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
+    return select_channels(C, channels)
+
+
+def check_out(out, rows, cols, dtype, axis_name):
+    """ValueError unless `out` is a [rows, cols] tensor of `dtype` with unit stride along its last axis"""
+    if tuple(out.shape) != (rows, cols) or out.dtype != dtype or (cols > 1 and rows and out.stride(1) != 1):
+        raise ValueError("out must be a %s [%d, %d] tensor with unit stride along %s" % (dtype, rows, cols, axis_name))
+
+
+def aligned_rows(rows, n, phase, device):
+    """uint8 [rows, n] view of a fresh buffer whose column t sits at a byte address congruent to phase + t mod 128 (the
+    range decoder's interior row stores are then as aligned as mh_decode's)"""
+    phase %= 128
+    pitch = (n + phase + 127) // 128 * 128
+    buf = torch.empty(max(rows * pitch, 1), dtype=torch.uint8, device=device)
+    return buf.as_strided((rows, n), (pitch, 1), phase)
+
+
+def upload_stream(device, payload, seg, peak, enc):
+    """A host stream on the device -> (payload int32 behind four zero words of slack, seg int64, peak, enc uint8).
+    payload: uint32 words; seg: the segments' offsets or sizes, 64-bit."""
+    pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=device)
+    if payload.size:
+        pay[:payload.size] = torch.from_numpy(np.ascontiguousarray(payload).view(np.int32)).to(device)
+    seg = np.ascontiguousarray(seg)
+    seg = seg.view(np.int64) if seg.dtype.itemsize == 8 else seg.astype(np.int64)
+    return (pay, torch.from_numpy(seg).to(device), torch.from_numpy(np.array(peak, np.uint8)).to(device),
+            torch.from_numpy(np.array(enc, np.uint8)).to(device))
+
+
+def check_decoded(plans, what="container", unwinding=False):
+    """Read and clear the status of every plan (synchronises); ValueError when a decode on one of them had to abandon
+    a segment -- unless the caller is `unwinding` from an error of its own."""
+    ok = all([p.decode_ok() for p in plans])
+    if not (ok or unwinding):
+        raise ValueError("corrupt %s: a chunk header points outside the payload (decode abandoned)" % what)
+
+
+def to_time_major(rows):
+    """uint8 [R, n] rows with unit stride along time (any row stride) -> contiguous [n, R] (mh_interleave)"""
+    R, n = int(rows.shape[0]), int(rows.shape[1])
+    tm = torch.empty((n, R), dtype=torch.uint8, device=rows.device)
+    in_off = torch.arange(R, dtype=torch.int64, device=rows.device) * (rows.stride(0) if R > 1 else 0)
+    _lib.check(_lib.lib().mh_interleave(_ptr(rows), _ptr(in_off), n, R, _ptr(tm), _stream()))
+    return tm
+
+
 @dataclass
 class Measured:
     """What the reference computes per validation channel at one (S, h) --
@@ -86,6 +151,7 @@ class Plan:
         self.n_segments = int(info.n_segments)
         self.payload_cap_words = int(info.payload_cap_words)
         self.window_samples = int(info.window_samples)
+        self.max_len = int(self.ch_len.max()) if self.ch_len.size else 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -198,21 +264,13 @@ class Plan:
         stores are then as aligned as mh_decode's) and a strided view is returned.  Not capturable into a graph: the work
         list is built on the host and uploaded (the call synchronises the current stream first)."""
         start, stop = int(start), int(stop)
-        max_len = int(self.ch_len.max()) if self.ch_len.size else 0
-        if not (0 <= start <= stop <= max_len):
-            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
-        sel = np.arange(self.C, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
-        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
-            raise IndexError("channel index out of range")
+        sel = query_args(self.max_len, self.C, start, stop, sel)
         sel32 = np.ascontiguousarray(sel, dtype=np.uint32)
         n, rows = stop - start, int(sel.size)
         if out is None:
-            phase = start % 128
-            pitch = (n + phase + 127) // 128 * 128
-            buf = torch.empty(max(rows * pitch, 1), dtype=torch.uint8, device=self.device)
-            out = buf.as_strided((rows, n), (pitch, 1), phase)
-        elif tuple(out.shape) != (rows, n) or out.dtype != torch.uint8 or (n > 1 and rows and out.stride(1) != 1):
-            raise ValueError("out must be a uint8 [%d, %d] tensor with unit stride along time" % (rows, n))
+            out = aligned_rows(rows, n, start, self.device)
+        else:
+            check_out(out, rows, n, torch.uint8, "time")
         pitch = out.stride(0) if rows > 1 else n
         _lib.check(_lib.lib().mh_decode_range(self._h, _ptr(payload), payload.numel(), _ptr(seg_off),
                                               sel32.ctypes.data if rows else None, rows, start, stop, _ptr(peak),
@@ -226,23 +284,14 @@ class Plan:
         r, 1 <= r <= 4096.  out: optional tensor of that shape and dtype with unit stride along the bins.  Arguments
         otherwise as decode_range; not capturable into a graph."""
         start, stop, r = int(start), int(stop), int(r)
-        if not 1 <= r <= 4096:
-            raise ValueError("bin factor %d outside 1..4096" % r)
-        max_len = int(self.ch_len.max()) if self.ch_len.size else 0
-        if not (0 <= start <= stop <= max_len):
-            raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
-        if start % r:
-            raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
-        sel = np.arange(self.C, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
-        if sel.size and (sel.min() < 0 or sel.max() >= self.C):
-            raise IndexError("channel index out of range")
+        sel = query_args(self.max_len, self.C, start, stop, sel, r)
         sel32 = np.ascontiguousarray(sel, dtype=np.uint32)
         nb, rows = (stop - start + r - 1) // r, int(sel.size)
         dtype = torch.uint8 if saturate else torch.int32
         if out is None:
             out = torch.empty((rows, nb), dtype=dtype, device=self.device)
-        elif tuple(out.shape) != (rows, nb) or out.dtype != dtype or (nb > 1 and rows and out.stride(1) != 1):
-            raise ValueError("out must be a %s [%d, %d] tensor with unit stride along the bins" % (dtype, rows, nb))
+        else:
+            check_out(out, rows, nb, dtype, "the bins")
         pitch = out.stride(0) if rows > 1 else nb
         _lib.check(_lib.lib().mh_decode_rebin(self._h, _ptr(payload), payload.numel(), _ptr(seg_off),
                                               sel32.ctypes.data if rows else None, rows, start, stop, r, 1 if saturate else 0,

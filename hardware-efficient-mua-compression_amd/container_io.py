@@ -53,24 +53,31 @@ class Compressed:
         write(buf, self)
         return buf.getvalue()
 
+    @classmethod
+    def from_device(cls, header, ch_len, enc, n_segments, dense, total):
+        """The host record of an encoded set: enc = the codec.Encoded the plan filled, dense = its compacted words
+        (device int32), total = how many of them are used.  The caller has synchronised."""
+        return cls(header, ch_len.copy(), enc.peak.cpu().numpy(), enc.enc.cpu().numpy(), enc.skipped.cpu().numpy(),
+                   enc.ch_bits.cpu().numpy().astype(np.uint64), enc.seg_words.cpu().numpy().astype(np.uint64)[:n_segments],
+                   dense[:total].cpu().numpy().view(np.uint32).copy())
 
-def _arrays(c):
-    return [("ch_len", c.ch_len, np.uint64), ("peak", c.peak, np.uint8), ("enc", c.enc, np.uint8),
-            ("skipped", c.skipped, np.uint8), ("ch_bits", c.ch_bits, np.uint64),
-            ("seg_words", c.seg_words, np.uint64), ("payload", c.payload, np.uint32)]
+
+# the arrays behind the header, in file order (each padded to 8 bytes); the payload is the last
+ARRAYS = (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skipped", np.uint8), ("ch_bits", np.uint64),
+          ("seg_words", np.uint64), ("payload", np.uint32))
 
 
 def _header_blob(c):
     hdr = dict(c.header)
-    hdr["sizes"] = {name: int(np.asarray(a).size) for name, a, _ in _arrays(c)}
+    hdr["sizes"] = {name: int(np.asarray(getattr(c, name)).size) for name, _ in ARRAYS}
     return json.dumps(hdr, sort_keys=True).encode()
 
 
 def nbytes(c):
     """The number of bytes write() emits for c (archive.py puts it in front of the block)."""
     n = 12 + len(_header_blob(c))
-    for _name, a, dt in _arrays(c):
-        raw = int(np.asarray(a).size) * np.dtype(dt).itemsize
+    for name, dt in ARRAYS:
+        raw = int(np.asarray(getattr(c, name)).size) * np.dtype(dt).itemsize
         n += raw + (-raw % 8)
     return n
 
@@ -80,30 +87,44 @@ def write(f, c):
     f.write(MAGIC)
     f.write(struct.pack("<I", len(blob)))
     f.write(blob)
-    for _name, a, dt in _arrays(c):
-        raw = np.ascontiguousarray(a, dtype=dt).reshape(-1).view(np.uint8)   # written from where it lies: no copy
+    for name, dt in ARRAYS:
+        raw = np.ascontiguousarray(getattr(c, name), dtype=dt).reshape(-1).view(np.uint8)   # written from where it lies: no copy
         f.write(raw)
         f.write(b"\0" * (-raw.size % 8))
 
 
-def read(f):
-    if f.read(8) != MAGIC:
+def _read_array(read, skip, hdr, name, dt):
+    """-> (the array `name` of the container, the bytes it takes in the file with its padding)"""
+    size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
+    raw = read(size)
+    if len(raw) != size:
+        raise ValueError("truncated container (%s)" % name)
+    skip(-size % 8)
+    return np.frombuffer(raw, dtype=dt).copy(), size + (-size % 8)
+
+
+def read_head(read, skip=None):
+    """Everything in front of the payload, through read(n) -> bytes: magic, header length, header, revision check and
+    every array of ARRAYS but the payload.  skip(n) passes over padding (default: read it).
+    -> (header, {name: array}, bytes consumed: the payload starts that far behind the magic)"""
+    skip = read if skip is None else skip
+    if read(8) != MAGIC:
         raise ValueError("not a MUAHUFF1 container")
-    (n,) = struct.unpack("<I", f.read(4))
-    hdr = json.loads(f.read(n).decode())
+    (n,) = struct.unpack("<I", read(4))
+    hdr = json.loads(read(n).decode())
     if hdr.get("format_revision") not in READ_REVISIONS:
         raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
-    out = {}
-    for name, dt in (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skipped", np.uint8),
-                     ("ch_bits", np.uint64), ("seg_words", np.uint64), ("payload", np.uint32)):
-        cnt = hdr["sizes"][name]
-        nbytes = cnt * np.dtype(dt).itemsize
-        raw = f.read(nbytes)
-        if len(raw) != nbytes:
-            raise ValueError("truncated container (%s)" % name)
-        f.read(-nbytes % 8)
-        out[name] = np.frombuffer(raw, dtype=dt).copy()
-    return Compressed(hdr, **out)
+    arrays, pos = {}, 12 + n
+    for name, dt in ARRAYS[:-1]:
+        arrays[name], size = _read_array(read, skip, hdr, name, dt)
+        pos += size
+    return hdr, arrays, pos
+
+
+def read(f):
+    hdr, arrays, _pos = read_head(f.read)
+    arrays["payload"], _size = _read_array(f.read, f.read, hdr, *ARRAYS[-1])
+    return Compressed(hdr, **arrays)
 
 
 def save(path, c):
@@ -136,12 +157,8 @@ def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0):
     enc = plan.encode(cs.data)
     dense, tot = plan.compact(enc)
     torch.cuda.synchronize()
-    total = int(tot.item())
-    c = Compressed(make_header(S, h, mode, window, plan.seg_chunks, sclv), cs.ch_len.copy(),
-                   enc.peak.cpu().numpy(), enc.enc.cpu().numpy(), enc.skipped.cpu().numpy(),
-                   enc.ch_bits.cpu().numpy().astype(np.uint64),
-                   enc.seg_words.cpu().numpy().astype(np.uint64)[:plan.n_segments],
-                   dense.payload[:total].cpu().numpy().view(np.uint32).copy())
+    c = Compressed.from_device(make_header(S, h, mode, window, plan.seg_chunks, sclv), cs.ch_len, enc, plan.n_segments,
+                               dense.payload, int(tot.item()))
     plan.close()
     return c
 
@@ -152,36 +169,40 @@ def plan_window(hd):
     return int(hd["window"]) | (WIN_REV2_SEGMENTS if int(hd.get("format_revision", FORMAT_REVISION)) == 2 else 0)
 
 
-def segments_per_channel(ch_len, h, window, seg_chunks, revision=FORMAT_REVISION):
-    """Number of directory entries of each channel: the window rule of include/muahuff.h applied
-    to the channel length, cut into segments of seg_chunks chunks (the planner's layout) -- from revision 3 on
-    behind a head segment up to the next multiple of 128 samples when the window has at least 16 chunks."""
-    from . import CHUNK
-    seg = int(seg_chunks) * CHUNK
-    n = window_lengths(ch_len, h, window)
-    if int(revision) == 2:
-        return (n + seg - 1) // seg
-    T = np.asarray(ch_len, dtype=np.int64)
-    w0 = np.zeros_like(T) if window == 3 else np.minimum(np.int64(1) << int(h), T)
-    head = np.where((n >= 16 * CHUNK) & (w0 % 128 != 0), 128 - w0 % 128, 0)
-    return (n - head + seg - 1) // seg + (head > 0)
-
-
-def window_lengths(ch_len, h, window):
-    """Samples in the encoded window of each channel (the rules of include/muahuff.h)."""
-    from . import WIN_AFTER_CAL, WIN_FULL, WIN_REF_HALF, WIN_REF_HALF_TRUNC
+def channel_layout(ch_len, h, window, seg_chunks=1, revision=FORMAT_REVISION):
+    """The planner's layout of each channel, by arithmetic (include/muahuff.h) -> int64 arrays (w0, w1, head, nseg): the
+    encoded window [w0, w1) in channel samples by the window rule; the samples of its head segment -- from revision 3 on
+    a window of at least 16 chunks that starts off a multiple of 128 samples opens with a segment up to the next one,
+    else 0 --; its number of directory entries: the head, then segments of seg_chunks chunks."""
+    from . import CHUNK, WIN_AFTER_CAL, WIN_FULL, WIN_REF_HALF, WIN_REF_HALF_TRUNC
     T = np.asarray(ch_len, dtype=np.int64)
     c = np.minimum(np.int64(1) << int(h), T)
     e = c + T // 2
     if window == WIN_REF_HALF:
-        return np.where(e > T, 0, e - c)
-    if window == WIN_REF_HALF_TRUNC:
-        return np.minimum(e, T) - c
-    if window == WIN_AFTER_CAL:
-        return T - c
-    if window == WIN_FULL:
-        return T
-    raise ValueError("unknown window rule %r" % (window,))
+        n = np.where(e > T, 0, e - c)
+    elif window == WIN_REF_HALF_TRUNC:
+        n = np.minimum(e, T) - c
+    elif window == WIN_AFTER_CAL:
+        n = T - c
+    elif window == WIN_FULL:
+        n = T
+    else:
+        raise ValueError("unknown window rule %r" % (window,))
+    w0 = np.zeros_like(T) if window == WIN_FULL else c
+    seg = int(seg_chunks) * CHUNK
+    head = np.zeros_like(T) if int(revision) == 2 else np.where((n >= 16 * CHUNK) & (w0 % 128 != 0), 128 - w0 % 128, 0)
+    return w0, w0 + n, head, (n - head + seg - 1) // seg + (head > 0)
+
+
+def segments_per_channel(ch_len, h, window, seg_chunks, revision=FORMAT_REVISION):
+    """Number of directory entries of each channel (channel_layout)."""
+    return channel_layout(ch_len, h, window, seg_chunks, revision)[3]
+
+
+def window_lengths(ch_len, h, window):
+    """Samples in the encoded window of each channel (the rules of include/muahuff.h)."""
+    w0, w1, _head, _nseg = channel_layout(ch_len, h, window)
+    return w1 - w0
 
 
 def _header_fields(hd):
@@ -201,6 +222,41 @@ def _header_fields(hd):
     return S, K, h, window, seg_chunks, mode, sclv
 
 
+def _stored_words(src):
+    return int(src.payload_words if isinstance(src, ContainerFile) else src.payload.size)
+
+
+def check_consistent(c, arrays=True, what="container"):
+    """ValueError unless the per-channel arrays agree about the channel count (with `arrays`), no channel is empty and
+    the directory has the entries the header's layout gives these lengths.  -> directory entries per channel"""
+    hd = c.header
+    C = len(c.ch_len)
+    if arrays and not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
+        raise ValueError("%s arrays disagree about the channel count" % what)
+    if C and int(np.min(c.ch_len)) == 0:
+        raise ValueError("%s holds an empty channel" % what)
+    nseg = segments_per_channel(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd.get("format_revision", FORMAT_REVISION))
+    if int(nseg.sum()) != len(c.seg_words) or (C == 0 and _stored_words(c)):
+        raise ValueError("%s directory does not match its header" % what)
+    return nseg
+
+
+def check_block(c, C, S, mode, seg_chunks, sclv, what="container"):
+    """ValueError unless c (a Compressed or a ContainerFile) is a block of the stream whose two ends were built with
+    these parameters: (S, mode, seg_chunks), the whole-channel window, the SCLV rows, C channels of one length."""
+    from . import WIN_FULL
+    hd = c.header
+    got = tuple(hd.get(k) for k in ("S", "mode", "window", "seg_chunks"))
+    if tuple(-1 if v is None else int(v) for v in got) != (S, mode, WIN_FULL, seg_chunks):
+        raise ValueError("%s (S, mode, window, seg_chunks) = %s is not the expected %s"
+                         % (what, got, (S, mode, WIN_FULL, seg_chunks)))
+    if np.asarray(hd.get("sclv"), np.int64).reshape(-1).tolist() != np.asarray(sclv, np.int64).reshape(-1).tolist():
+        raise ValueError("%s SCLV rows are not the expected ones" % what)
+    ch_len = np.asarray(c.ch_len, np.uint64)
+    if len(ch_len) != C or ch_len.size == 0 or (ch_len != ch_len[0]).any():
+        raise ValueError("%s does not hold %d channels of one length" % (what, C))
+
+
 def validate(c):
     """Structural check of a container before it goes to the GPU.  The header fields are range-
     checked here; the walk over every chunk header of every segment -- header sizes, sub-stream
@@ -208,27 +264,20 @@ def validate(c):
     payload -- is mh_validate_stream (host-only C, no GPU needed).  mh_decode itself never reads
     outside the payload it is given, so this check is about detecting corruption, not about
     memory safety.  Raises ValueError."""
-    import ctypes as ct
-
     from . import _lib
     hd = c.header
     S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
+    if hd.get("format_revision") not in READ_REVISIONS:
+        raise ValueError("container header: unsupported revision %r" % (hd.get("format_revision"),))
     C = len(c.ch_len)
-    if not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
-        raise ValueError("container arrays disagree about the channel count")
+    check_consistent(c)
     if C == 0:
-        if len(c.seg_words) or c.payload.size:
-            raise ValueError("container directory does not match its header")
         return
-    if int(c.ch_len.min()) == 0:
-        raise ValueError("container holds an empty channel")
     ch_len = np.ascontiguousarray(c.ch_len, np.uint64)
     rows = np.ascontiguousarray(sclv, np.uint8)
     pay = np.ascontiguousarray(c.payload, np.uint32)
     segw = np.ascontiguousarray(c.seg_words, np.uint64)
     peak, enc = np.ascontiguousarray(c.peak, np.uint8), np.ascontiguousarray(c.enc, np.uint8)
-    if hd.get("format_revision") not in READ_REVISIONS:
-        raise ValueError("container header: unsupported revision %r" % (hd.get("format_revision"),))
     rc = _lib.lib().mh_validate_stream(ch_len.ctypes.data, C, S, h, mode, plan_window(hd), rows.ctypes.data, K, seg_chunks,
                                        pay.ctypes.data if pay.size else np.zeros(1, np.uint32).ctypes.data, pay.size,
                                        segw.ctypes.data if segw.size else np.zeros(1, np.uint64).ctypes.data, segw.size,
@@ -250,15 +299,11 @@ def decompress(c, device="cuda", channels=None, check=True):
     if check:
         validate(c)
     hd = c.header
-    nseg_ch = segments_per_channel(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd.get("format_revision", FORMAT_REVISION))
-    if int(nseg_ch.sum()) != len(c.seg_words):
-        raise ValueError("container directory does not match its header")
+    nseg_ch = check_consistent(c, arrays=False)
     seg_words, payload, peak, enc, skipped, ch_bits, ch_len = (c.seg_words, c.payload, c.peak, c.enc, c.skipped,
                                                                 c.ch_bits, c.ch_len)
     if channels is not None:
-        sel = np.asarray(channels, dtype=np.int64)
-        if sel.size and (sel.min() < 0 or sel.max() >= len(c.ch_len)):
-            raise IndexError("channel index out of range")
+        sel = codec.select_channels(len(c.ch_len), channels)
         first = np.concatenate([[0], np.cumsum(nseg_ch)]).astype(np.int64)       # channel -> first segment
         off = np.concatenate([[0], np.cumsum(c.seg_words)]).astype(np.int64)    # segment -> first word
         segs = np.concatenate([np.arange(first[i], first[i + 1]) for i in sel]) if sel.size else np.zeros(0, np.int64)
@@ -271,21 +316,20 @@ def decompress(c, device="cuda", channels=None, check=True):
         return cs
     plan = codec.Plan(cs.ch_off, cs.ch_len, hd["S"], hd["h"], hd["mode"], plan_window(hd),
                       np.array(hd["sclv"], np.uint8), seg_chunks=hd["seg_chunks"])
-    if plan.n_segments != len(seg_words):
-        raise ValueError("container directory does not match its header")
-    dev = cs.data.device
-    pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=dev)
-    pay[:payload.size] = torch.from_numpy(np.ascontiguousarray(payload).view(np.int32)).to(dev)
-    seg_off = np.concatenate([[0], np.cumsum(seg_words)[:-1]]).astype(np.int64) if len(seg_words) else np.zeros(1, np.int64)
-    e = codec.Encoded(pay, torch.from_numpy(seg_words.astype(np.int64)).to(dev),
-                      torch.from_numpy(ch_bits.astype(np.int64)).to(dev), torch.from_numpy(np.ascontiguousarray(peak)).to(dev),
-                      torch.from_numpy(np.ascontiguousarray(enc)).to(dev), torch.from_numpy(np.ascontiguousarray(skipped)).to(dev),
-                      torch.from_numpy(seg_off).to(dev), True)
-    plan.decode(e, cs.data)
-    ok = plan.decode_ok()  # synchronises
-    plan.close()
-    if not ok:
-        raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
+    try:
+        if plan.n_segments != len(seg_words):      # not for a header that validate() accepts: the arithmetic is the planner's
+            raise ValueError("container header: the planner cuts these channels into %d segments, not %d"
+                             % (plan.n_segments, len(seg_words)))
+        dev = cs.data.device
+        seg_off = np.concatenate([[0], np.cumsum(seg_words)[:-1]]).astype(np.int64) if len(seg_words) else np.zeros(1, np.int64)
+        pay, d_off, d_peak, d_enc = codec.upload_stream(dev, payload, seg_off, peak, enc)
+        e = codec.Encoded(pay, torch.from_numpy(seg_words.astype(np.int64)).to(dev),
+                          torch.from_numpy(ch_bits.astype(np.int64)).to(dev), d_peak, d_enc,
+                          torch.from_numpy(np.ascontiguousarray(skipped)).to(dev), d_off, True)
+        plan.decode(e, cs.data)
+        codec.check_decoded([plan])
+    finally:
+        plan.close()
     return cs
 
 
@@ -316,26 +360,12 @@ class ContainerFile:
         return b
 
     def _read_head(self):
-        if self._read(8) != MAGIC:
-            raise ValueError("not a MUAHUFF1 container")
-        (n,) = struct.unpack("<I", self._read(4))
-        hdr = json.loads(self._read(n).decode())
-        if hdr.get("format_revision") not in READ_REVISIONS:
-            raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
-        pos = self.offset + 12 + n
-        for name, dt in (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skipped", np.uint8),
-                         ("ch_bits", np.uint64), ("seg_words", np.uint64)):
-            size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
-            raw = self._read(size)
-            if len(raw) != size:
-                raise ValueError("truncated container (%s)" % name)
-            pos += size + (-size % 8)
-            self._f.seek(pos)
-            setattr(self, name, np.frombuffer(raw, dtype=dt).copy())
-        self.header = hdr
-        self.payload_offset = pos                      # file offset of payload word 0
-        self.payload_words = int(hdr["sizes"]["payload"])
-        self.head_bytes = self.bytes_read              # what open() read
+        self.header, arrays, n = read_head(self._read, lambda pad: self._f.seek(pad, 1))
+        for name, a in arrays.items():
+            setattr(self, name, a)
+        self.payload_offset = self.offset + n           # file offset of payload word 0
+        self.payload_words = int(self.header["sizes"]["payload"])
+        self.head_bytes = self.bytes_read               # what open() read
 
     def read_words(self, first, n):
         """payload words [first, first + n) as uint32 (ValueError past the end of the file)"""
@@ -367,7 +397,6 @@ class ContainerFile:
         self.close()
 
 
-
 def open(path, offset=0):  # noqa: A001  (shadows the builtin in this module only: save / load use builtins.open)
     """-> ContainerFile: header and directory read, payload left on disk."""
     return ContainerFile(path, offset)
@@ -382,11 +411,7 @@ def _range_plan(c):
 
 def window_bounds(ch_len, h, window):
     """(w0, w1): the encoded window [w0, w1) of each channel, in channel samples (include/muahuff.h)."""
-    from . import WIN_FULL
-    T = np.asarray(ch_len, dtype=np.int64)
-    n = window_lengths(T, h, window)
-    w0 = np.zeros_like(T) if window == WIN_FULL else np.minimum(np.int64(1) << int(h), T)
-    return w0, w0 + n
+    return channel_layout(ch_len, h, window)[:2]
 
 
 def range_segments(ch_len, h, window, seg_chunks, start, stop, revision=FORMAT_REVISION):
@@ -394,15 +419,9 @@ def range_segments(ch_len, h, window, seg_chunks, start, stop, revision=FORMAT_R
     (first, end) -- channel c's overlapping segments are entries first[c] .. end[c] - 1 (first == end: none, the range
     misses the channel's window).  A channel's segments are consecutive in the directory and in the payload."""
     from . import CHUNK
-    T = np.asarray(ch_len, dtype=np.int64)
-    w0, w1 = window_bounds(T, h, window)
-    nseg = segments_per_channel(T, h, window, seg_chunks, revision)
-    base = np.concatenate([[0], np.cumsum(nseg)[:-1]]).astype(np.int64) if T.size else np.zeros(0, np.int64)
+    w0, w1, head, nseg = channel_layout(ch_len, h, window, seg_chunks, revision)
+    base = np.cumsum(nseg) - nseg
     seg = int(seg_chunks) * CHUNK
-    if int(revision) == 2:
-        head = np.zeros_like(T)
-    else:
-        head = np.where((w1 - w0 >= 16 * CHUNK) & (w0 % 128 != 0), 128 - w0 % 128, 0)
     a = np.maximum(int(start), w0) - w0                # window samples [a, b)
     b = np.minimum(int(stop), w1) - w0
     hit = a < b
@@ -425,7 +444,7 @@ def gather_range(src, start, stop, sel):
     first, end = range_segments(src.ch_len, h, window, seg_chunks, start, stop, rev)
     seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
     dense = np.concatenate([[0], np.cumsum(seg_words)]).astype(np.int64)  # segment -> first word in the stored payload
-    stored_words = int(src.payload_words if isinstance(src, ContainerFile) else src.payload.size)
+    stored_words = _stored_words(src)
     # one contiguous run of payload words per selected channel (once per channel, whatever the repeats)
     runs, seg_off, idx, base = [], np.zeros(max(len(seg_words), 1), np.uint64), [], 0
     for c in np.unique(sel):
@@ -444,34 +463,23 @@ def gather_range(src, start, stop, sel):
     return payload, seg_off, segs
 
 
-def _range_inputs(src, start, stop, channels, check):
-    """What a range query of a `Compressed` / `ContainerFile` needs on the host: argument checks, the payload of the
-    segments that overlap [start, stop) (gather_range) and, with check, their validation (mh_validate_segments).
-    -> (sel, payload, seg_off, peak, enc); payload is None when the query is empty (no channel or no sample)."""
-    from . import _lib
+def _range_inputs(src, start, stop, channels, check, r=None):
+    """What a range query of a `Compressed` / `ContainerFile` needs on the host: argument checks (codec.query_args), the
+    payload of the segments that overlap [start, stop) (gather_range) and, with check, their validation
+    (mh_validate_segments).  -> (sel, payload, seg_off, peak, enc); payload is None when the query is empty (no channel
+    or no sample)."""
+    from . import _lib, codec
     hd = src.header
     S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
-    rev = int(hd.get("format_revision", FORMAT_REVISION))
     ch_len = np.ascontiguousarray(src.ch_len, np.uint64)
     C = len(ch_len)
-    max_len = int(ch_len.max()) if C else 0
-    if not (0 <= start <= stop <= max_len):
-        raise ValueError("range [%d, %d) is not inside [0, %d)" % (start, stop, max_len))
-    sel = np.arange(C, dtype=np.int64) if channels is None else np.asarray(channels, dtype=np.int64).reshape(-1)
-    if sel.size and (sel.min() < 0 or sel.max() >= C):
-        raise IndexError("channel index out of range")
-    nseg_ch = segments_per_channel(ch_len, h, window, seg_chunks, rev)
-    if int(nseg_ch.sum()) != len(src.seg_words):
-        raise ValueError("container directory does not match its header")
-    if C and int(ch_len.min()) == 0:
-        raise ValueError("container holds an empty channel")
+    sel = codec.query_args(int(ch_len.max()) if C else 0, C, start, stop, channels, r)
+    check_consistent(src, arrays=check)
     if sel.size == 0 or stop == start:
         return sel, None, None, None, None
     payload, seg_off, segs = gather_range(src, start, stop, sel)
     peak, enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
     if check:
-        if not (len(peak) == len(enc) == C):
-            raise ValueError("container arrays disagree about the channel count")
         rows_ = np.ascontiguousarray(sclv, np.uint8)
         seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
         rc = _lib.lib().mh_validate_segments(ch_len.ctypes.data, C, S, h, mode, plan_window(hd), rows_.ctypes.data, K,
@@ -487,23 +495,15 @@ def _range_inputs(src, start, stop, channels, check):
 def _range_decode(src, payload, seg_off, peak, enc, run):
     """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device; ValueError when the decode
     had to abandon a segment."""
-    import torch
+    from . import codec
     own = not isinstance(src, ContainerFile)
     plan = _range_plan(src) if own else src.plan()
     try:
-        dev = plan.device
-        pay = torch.zeros(payload.size + 4, dtype=torch.int32, device=dev)
-        if payload.size:
-            pay[:payload.size] = torch.from_numpy(payload.view(np.int32)).to(dev)
-        d_off = torch.from_numpy(seg_off.view(np.int64)).to(dev)
-        d_peak, d_enc = torch.from_numpy(peak.copy()).to(dev), torch.from_numpy(enc.copy()).to(dev)
-        out = run(plan, pay, d_off, d_peak, d_enc)
-        ok = plan.decode_ok()  # synchronises
+        out = run(plan, *codec.upload_stream(plan.device, payload, seg_off, peak, enc))
+        codec.check_decoded([plan])
     finally:
         if own:
             plan.close()
-    if not ok:
-        raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
     return out
 
 
@@ -517,8 +517,7 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
     had to abandon a segment raises ValueError as decompress() does."""
     import torch
 
-    from . import _lib
-    from .codec import _ptr, _stream
+    from . import codec
     start, stop = int(start), int(stop)
     sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check)
     n, rows = stop - start, int(sel.size)
@@ -527,12 +526,7 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
         return z.t().contiguous() if time_major else z
     out = _range_decode(src, payload, seg_off, peak, enc,
                         lambda plan, pay, off, pk, en: plan.decode_range(pay, off, pk, en, sel, start, stop))
-    if not time_major:
-        return out
-    tm = torch.empty((n, rows), dtype=torch.uint8, device=out.device)
-    in_off = torch.arange(rows, dtype=torch.int64, device=out.device) * (out.stride(0) if rows > 1 else 0)
-    _lib.check(_lib.lib().mh_interleave(_ptr(out), _ptr(in_off), n, rows, _ptr(tm), _stream()))
-    return tm
+    return codec.to_time_major(out) if time_major else out
 
 
 def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, check=True, device="cuda"):
@@ -540,16 +534,12 @@ def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, 
     decompress_range(src, start, stop, channels) re-binned by r gives, decoded in one pass that never stores the
     byte-per-sample rows.  -> device tensor [n_sel, ceil((stop - start) / r)], uint8 = min(sum, 255) (saturate, the form
     ChannelSet.rebin has) or int32 exact sums; the last, partial bin is kept.  stop=None: the longest channel's length.
-    ValueError for r outside 1..4096, start % r != 0 or a bad range, IndexError for a bad channel -- before anything
-    reaches the GPU; check and the status handling as decompress_range."""
+    ValueError for a bad r, start or range, IndexError for a bad channel (codec.query_args) -- before anything reaches
+    the GPU; check and the status handling as decompress_range."""
     import torch
     r, start = int(r), int(start)
     stop = (int(np.max(src.ch_len)) if len(src.ch_len) else 0) if stop is None else int(stop)
-    if not 1 <= r <= 4096:
-        raise ValueError("bin factor %d outside 1..4096" % r)
-    if start % r:
-        raise ValueError("start %d is not a multiple of the bin factor %d" % (start, r))
-    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check)
+    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check, r)
     nb, rows = (stop - start + r - 1) // r, int(sel.size)
     if payload is None:
         return torch.zeros((rows, nb), dtype=torch.uint8 if saturate else torch.int32, device=device)

@@ -22,7 +22,8 @@ so the receive side skips the byte-per-sample intermediate as the send side does
 import numpy as np
 import torch
 
-from . import MODE_APPROX, WIN_FULL, codec, container_io
+from . import MODE_APPROX, WIN_FULL, _lib, codec, container_io
+from .codec import _ptr, _stream
 from .container import ChannelSet
 
 
@@ -58,27 +59,22 @@ class StreamEncoder:
         """block: [T0, C] time-major counts holding at least 2^hist_bits time steps (fewer are
         accepted: the cutoff is min(2^h, T0), as functions_1.py:59-64).  Stores and returns the
         per-channel RAM word (peak, enc) as uint8 device tensors."""
-        cs = ChannelSet.from_time_major(block, device=self.device)
-        plan = codec.Plan(cs.ch_off, cs.ch_len, self.S, self.h, self.mode, WIN_FULL, self.sclv)
-        m = plan.measure(cs.data)
-        torch.cuda.synchronize()
-        self.peak, self.enc = m.peak.clone(), m.enc.clone()
-        plan.close()
-        self.close()  # cached block plans point at the previous RAM word
-        return self.peak, self.enc
+        return self._calibrate(ChannelSet.from_time_major(block, device=self.device))
 
     def calibrate_events(self, ev, origin, period, T):
         """calibrate() on the T bins of `ev` (an events.EventSet) from `origin` at `period` ticks per bin: the counts
         are binned on the GPU (ChannelSet.from_events), no time-major block is built."""
         if ev.C != self.C:
             raise ValueError("event set has %d channels, encoder was built for %d" % (ev.C, self.C))
-        cs = ChannelSet.from_events(ev, origin, period, T)
+        return self._calibrate(ChannelSet.from_events(ev, origin, period, T))
+
+    def _calibrate(self, cs):
         plan = codec.Plan(cs.ch_off, cs.ch_len, self.S, self.h, self.mode, WIN_FULL, self.sclv)
         m = plan.measure(cs.data)
         torch.cuda.synchronize()
         self.peak, self.enc = m.peak.clone(), m.enc.clone()
         plan.close()
-        self.close()
+        self.close()  # cached block plans point at the previous RAM word
         return self.peak, self.enc
 
     def _slot(self, Tb):
@@ -127,9 +123,6 @@ class StreamEncoder:
         the same shape: a consumer that keeps a block in flight while the next one is enqueued
         (dist.gather_payload_pipelined) must copy them out -- or read the total and record an
         event -- before asking for the next block."""
-        import ctypes as ct
-
-        from . import _lib
         if self.peak is None:
             raise RuntimeError("calibrate() first")
         t = block if isinstance(block, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(block, np.uint8))
@@ -139,10 +132,8 @@ class StreamEncoder:
             raise ValueError("block has %d channels, encoder was built for %d" % (C, self.C))
         slot = self._slot(Tb)
         cs, plan = slot["cs"], slot["plan"]
-        _lib.check(_lib.lib().mh_deinterleave_packed(ct.c_void_p(t.data_ptr()), Tb, C, plan.input_bits,
-                                                     ct.c_void_p(cs.data.data_ptr()),
-                                                     ct.c_void_p(slot["d_off"].data_ptr()), plan.chunk_stride,
-                                                     ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().mh_deinterleave_packed(_ptr(t), Tb, C, plan.input_bits, _ptr(cs.data), _ptr(slot["d_off"]),
+                                                     plan.chunk_stride, _stream()))
         return self._encode_slot(slot, track)
 
     def encode_events_device(self, ev, origin, period, T, track=False):
@@ -165,18 +156,12 @@ class StreamEncoder:
 
     def _encode_slot(self, slot, track):
         """The block path behind the slot's packed pieces: optional drift measure, preset encode, compaction."""
-        import ctypes as ct
-
-        from . import _lib
         cs, plan = slot["cs"], slot["plan"]
         if track:
             self._monitor(slot).measure(cs.data, out=slot["fresh"])
         enc = slot["enc"]
-        _lib.check(_lib.lib().mh_encode_preset(plan._h, ct.c_void_p(cs.data.data_ptr()), ct.c_void_p(self.peak.data_ptr()),
-                                               ct.c_void_p(self.enc.data_ptr()), ct.c_void_p(enc.payload.data_ptr()),
-                                               enc.payload.numel(), ct.c_void_p(enc.seg_words.data_ptr()),
-                                               ct.c_void_p(enc.ch_bits.data_ptr()),
-                                               ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().mh_encode_preset(plan._h, _ptr(cs.data), _ptr(self.peak), _ptr(self.enc), _ptr(enc.payload),
+                                               enc.payload.numel(), _ptr(enc.seg_words), _ptr(enc.ch_bits), _stream()))
         dense, tot = plan.compact(enc, dense=slot["dense"], off=slot["off"], tot=slot["tot"])
         return dense, tot, slot
 
@@ -186,15 +171,12 @@ class StreamEncoder:
         return self._finish_block(*self.encode_block_device(block))
 
     def _finish_block(self, dense, tot, slot):
-        plan, cs, enc = slot["plan"], slot["cs"], slot["enc"]
+        plan = slot["plan"]
         torch.cuda.synchronize()
-        total = int(tot.item())
         hdr = container_io.make_header(self.S, 0, self.mode, WIN_FULL, plan.seg_chunks, self.sclv)
         hdr["preset"] = True
-        return container_io.Compressed(hdr, cs.ch_len.copy(), enc.peak.cpu().numpy(), enc.enc.cpu().numpy(),
-                                       enc.skipped.cpu().numpy(), enc.ch_bits.cpu().numpy().astype(np.uint64),
-                                       enc.seg_words.cpu().numpy().astype(np.uint64)[:plan.n_segments],
-                                       dense.payload[:total].cpu().numpy().view(np.uint32).copy())
+        return container_io.Compressed.from_device(hdr, slot["cs"].ch_len, slot["enc"], plan.n_segments, dense.payload,
+                                                   int(tot.item()))
 
     def encode_events(self, ev, origin, period, T):
         """encode_block for the T bins that `ev` fills from `origin` at `period` ticks per bin."""
@@ -273,9 +255,6 @@ class StreamDecoder:
         word; seg_off: optional int64 device segment offsets (else scanned from seg_words here).  The stream is not
         validated (the decoder never reads outside `payload`; ok() tells whether it had to abandon a segment).
         The returned tensor belongs to the shape's slot and is OVERWRITTEN by the next block of the same shape."""
-        import ctypes as ct
-
-        from . import _lib
         Tb = int(Tb)
         slot = self._slot(Tb)
         plan = slot["plan"]
@@ -284,18 +263,16 @@ class StreamDecoder:
             raise ValueError("a block of %d steps has %d segments" % (Tb, n))
         if peak.numel() < self.C or enc.numel() < self.C:
             raise ValueError("the RAM word needs %d channels" % self.C)
-        st = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _stream()
         if seg_off is None:
             seg_off = slot["seg_off"]
             if n > 1:  # exclusive scan: seg_off[0] stays 0
                 torch.cumsum(seg_words[:n - 1], 0, out=seg_off[1:n])
-        _lib.check(_lib.lib().mh_decode_packed(plan._h, ct.c_void_p(payload.data_ptr()), payload.numel(),
-                                               ct.c_void_p(seg_off.data_ptr()), ct.c_void_p(peak.data_ptr()),
-                                               ct.c_void_p(enc.data_ptr()), ct.c_void_p(slot["pieces"].data_ptr()), st))
+        _lib.check(_lib.lib().mh_decode_packed(plan._h, _ptr(payload), payload.numel(), _ptr(seg_off), _ptr(peak), _ptr(enc),
+                                               _ptr(slot["pieces"]), st))
         out = slot["out"]
-        _lib.check(_lib.lib().mh_interleave_packed(ct.c_void_p(slot["pieces"].data_ptr()),
-                                                   ct.c_void_p(slot["d_off"].data_ptr()), Tb, self.C, plan.input_bits,
-                                                   plan.chunk_stride, ct.c_void_p(out.data_ptr()), st))
+        _lib.check(_lib.lib().mh_interleave_packed(_ptr(slot["pieces"]), _ptr(slot["d_off"]), Tb, self.C, plan.input_bits,
+                                                   plan.chunk_stride, _ptr(out), st))
         return out
 
     def ok(self):
@@ -310,29 +287,11 @@ class StreamDecoder:
         """Checked host form: c = container_io.Compressed of one block as StreamEncoder.encode_block writes it ->
         [Tb, C] numpy array of min(x, S-1).  Raises ValueError when the container does not belong to this decoder or
         its stream is corrupt (mh_validate_stream, as container_io.decompress)."""
-        hd = c.header
-        ch_len = np.asarray(c.ch_len, np.uint64)
-        if (int(hd.get("S", -1)) != self.S or int(hd.get("mode", -1)) != self.mode or
-                int(hd.get("window", -1)) != WIN_FULL or int(hd.get("seg_chunks", -1)) != self.seg_chunks):
-            raise ValueError("container (S, mode, window, seg_chunks) = (%s, %s, %s, %s) is not this decoder's (%d, %d, %d, %d)"
-                             % (hd.get("S"), hd.get("mode"), hd.get("window"), hd.get("seg_chunks"), self.S, self.mode,
-                                WIN_FULL, self.seg_chunks))
-        if np.asarray(hd.get("sclv"), np.int64).reshape(-1).tolist() != self.sclv.astype(np.int64).reshape(-1).tolist():
-            raise ValueError("container SCLV rows are not this decoder's")
-        if len(ch_len) != self.C or ch_len.size == 0 or (ch_len != ch_len[0]).any():
-            raise ValueError("a stream block holds %d channels of one length" % self.C)
+        container_io.check_block(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv)
         container_io.validate(c)
-        Tb = int(ch_len[0])
-        dev = self.device
-        pay = torch.zeros(c.payload.size + 4, dtype=torch.int32, device=dev)
-        if c.payload.size:
-            pay[:c.payload.size] = torch.from_numpy(np.ascontiguousarray(c.payload).view(np.int32)).to(dev)
-        segw = torch.from_numpy(np.ascontiguousarray(c.seg_words).astype(np.int64)).to(dev)
-        peak = torch.from_numpy(np.ascontiguousarray(c.peak, np.uint8)).to(dev)
-        enc = torch.from_numpy(np.ascontiguousarray(c.enc, np.uint8)).to(dev)
-        out = self.decode_block_device(pay, segw, peak, enc, Tb)
-        if not self.ok():  # synchronises
-            raise ValueError("corrupt container: a chunk header points outside the payload (decode abandoned)")
+        out = self.decode_block_device(*codec.upload_stream(self.device, c.payload, c.seg_words, c.peak, c.enc),
+                                       int(c.ch_len[0]))
+        codec.check_decoded([slot["plan"] for slot in self._slots.values()])  # synchronises
         return out.cpu().numpy()
 
     def close(self):

@@ -83,11 +83,28 @@ def _boundaries(lens, h, window, sc):
 def test_range_segments_follow_the_planner_directory(rev, window):
     rng = np.random.RandomState(10 * rev + window)
     tab = helpers.sclv_tables()[3]
+    heads = 0
     for h, sc, lens in ((2, 1, [16 * CH + 1000, 50000, 20 * CH + 3, 5]), (3, 2, [40 * CH + 7, 16 * CH, 3, 70001]),
                         (6, 3, [33 * CH + 100, 64, 65, 16 * CH + 64 + 5])):
         wflag = window | (_lib.WIN_REV2_SEGMENTS if rev == 2 else 0)
         rc, info, seg = _plan_query(lens, 3, h, 1, wflag, tab, sc)
         assert rc == 0
+        # the one layout function against the planner: entries per channel, the head segment, the window they tile
+        w0, w1, head, nseg = cio.channel_layout(lens, h, window, sc, rev)
+        assert np.array_equal(nseg, np.bincount(seg["ch"], minlength=len(lens))) and int(nseg.sum()) == info.n_segments
+        for c in range(len(lens)):
+            ids = np.nonzero(seg["ch"] == c)[0]
+            assert int(seg["n"][ids].sum()) == int(w1[c] - w0[c])
+            assert np.array_equal(seg["first"][ids], np.cumsum(seg["n"][ids]) - seg["n"][ids])    # back to back from w0
+            if head[c]:
+                assert rev == 3 and int(seg["n"][ids[0]]) == int(head[c]) and (int(w0[c]) + int(head[c])) % 128 == 0
+            elif ids.size:
+                assert int(seg["n"][ids[0]]) == min(sc * CH, int(w1[c] - w0[c]))
+        heads += int((head > 0).sum())
+        # and its thin callers give the same
+        assert all(np.array_equal(x, y) for x, y in zip(cio.window_bounds(lens, h, window), (w0, w1)))
+        assert np.array_equal(cio.window_lengths(lens, h, window), w1 - w0)
+        assert np.array_equal(cio.segments_per_channel(lens, h, window, sc, rev), nseg)
         pts = _boundaries(lens, h, window, sc)
         pairs = [(a, b) for a in pts[::3] for b in pts[::5] if a <= b] + [(0, max(lens))]
         pairs += [tuple(sorted(rng.randint(0, max(lens) + 1, size=2))) for _ in range(30)]
@@ -95,6 +112,7 @@ def test_range_segments_follow_the_planner_directory(rev, window):
             got = cio.range_segments(lens, h, window, sc, a, b, rev)
             want = _expected_runs(seg, lens, h, window, a, b)
             assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (h, sc, a, b)
+    assert (heads > 0) == (rev == 3 and window != 3)        # the layouts do have head segments where the format has them
 
 
 def _oracle_container(lens, S, h, window, sc, rev=3, seed=0):
@@ -214,3 +232,78 @@ def test_range_argument_errors_come_before_any_device_work(tmp_path):
     # the C entry point rejects a NULL plan with a code and a message
     assert _lib.lib().mh_decode_range(None, None, 0, None, None, 0, 0, 0, None, None, None, 0, None) == _lib.ERR_ARG
     assert b"mh_decode_range" in _lib.lib().mh_last_error()
+
+
+QUERY_OK = [  # (max_len, C, start, stop, channels, r) -> sel
+    ((50000, 3, 0, 50000, None, None), [0, 1, 2]),
+    ((50000, 3, 7, 7, None, None), [0, 1, 2]),                 # an empty range is a range
+    ((50000, 3, 0, 10, [2, 0, 0], None), [2, 0, 0]),           # order and repeats are kept
+    ((50000, 3, 0, 10, [], None), []),
+    ((50000, 3, 0, 10, np.array([[1], [2]]), None), [1, 2]),   # any shape, flattened
+    ((0, 0, 0, 0, None, None), []),                            # no channels at all
+    ((50000, 3, 0, 9, None, 1), [0, 1, 2]),
+    ((50000, 3, 4096, 50000, [1], 4096), [1]),
+    ((50000, 3, 10, 90, None, 5), [0, 1, 2]),
+    ((50000, 3, 0, 90, [], 7), []),
+]
+QUERY_BAD = [  # the cases of test_range_argument_errors_... here and test_read_checks_its_arguments_... of the archive
+    ((50000, 3, 10, 5, None, None), ValueError), ((50000, 3, 0, 50001, None, None), ValueError),
+    ((50000, 3, -1, 5, None, None), ValueError), ((50000, 3, 0, 10, [0, 3], None), IndexError),
+    ((50000, 3, 0, 10, [-1], None), IndexError), ((50000, 3, 7, 3, None, None), ValueError),
+    ((50000, 3, 0, 3, [5], None), IndexError),
+    ((900, 5, 5, 4, None, None), ValueError), ((900, 5, 0, 901, None, None), ValueError), ((900, 5, -1, 3, None, None), ValueError),
+    ((900, 5, 0, 9, None, 0), ValueError), ((900, 5, 0, 9, None, 4097), ValueError), ((900, 5, 7, 90, None, 5), ValueError),
+    ((900, 5, 0, 10, [5], None), IndexError), ((900, 5, 0, 10, [-1], None), IndexError),
+    # each rule of r on its own, and a bad argument next to a bad channel
+    ((900, 5, 0, 9, None, -1), ValueError), ((900, 5, 1, 9, None, 2), ValueError), ((900, 5, 0, 9, [5], 0), ValueError),
+    ((900, 5, 10, 5, [9], None), ValueError), ((0, 0, 0, 1, None, None), ValueError), ((0, 0, 0, 0, [0], None), IndexError),
+]
+
+
+def test_query_args_table():
+    from muahuff import codec
+    for args, want in QUERY_OK:
+        sel = codec.query_args(*args)
+        assert sel.dtype == np.int64 and sel.ndim == 1 and sel.tolist() == want, args
+    for args, exc in QUERY_BAD:
+        with pytest.raises(exc):
+            codec.query_args(*args)
+
+
+def test_head_parser_reads_what_container_file_reads(tmp_path):
+    import io
+    c, _ = _oracle_container([20000, 50000, 3000, 17 * CH + 5, 9], 3, 6, 2, 1)
+    raw = c.tobytes()
+    hdr, arrays, used = cio.read_head(io.BytesIO(raw).read)
+    names = [name for name, _dt in cio.ARRAYS]
+    assert names[-1] == "payload" and list(arrays) == names[:-1]
+    assert used == len(raw) - 4 * c.payload.size - (-4 * c.payload.size % 8)
+    for offset in (0, 32):
+        fn = str(tmp_path / ("c%d.muahuff" % offset))
+        with open(fn, "wb") as f:
+            f.write(b"\xee" * offset + raw)
+        with cio.ContainerFile(fn, offset) as cf:
+            assert cf.header == hdr and cf.payload_offset == offset + used and cf.payload_words == c.payload.size
+            for name in names[:-1]:
+                a = arrays[name]
+                assert a.dtype == getattr(c, name).dtype and np.array_equal(a, getattr(c, name)), name
+                assert np.array_equal(getattr(cf, name), a), name
+            # padding is passed over, not read: ContainerFile counts fewer bytes than the parser consumed
+            pads = sum(-a.nbytes % 8 for a in arrays.values())
+            assert cf.head_bytes == cf.bytes_read == used - pads and pads > 0
+            assert np.array_equal(cf.read_words(0, c.payload.size), c.payload)
+    # read() is the same parse followed by the payload
+    back = cio.read(io.BytesIO(raw))
+    assert back.header == hdr and np.array_equal(back.payload, c.payload)
+    # a cut inside each array is named
+    pos = 12 + int.from_bytes(raw[8:12], "little")
+    for name, dt in cio.ARRAYS:
+        size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
+        assert size > 0
+        for cut in (pos, pos + size // 2, pos + size - 1):
+            src = io.BytesIO(raw[:cut])
+            with pytest.raises(ValueError) as e:
+                cio.read(src) if name == "payload" else cio.read_head(src.read)
+            assert str(e.value) == "truncated container (%s)" % name, (name, cut)
+        pos += size + (-size % 8)
+    assert pos == len(raw)
