@@ -1,5 +1,5 @@
-"""ctypes binding of libmuahuff_ingest.so (include/muahuff_ingest.h), the front-end companion of libmuahuff.so: spike time
-stamps -> binned counts.  Fails loudly: there is no CPU path."""
+"""ctypes binding of libmuahuff_ingest.so (include/muahuff_ingest.h), the companion of libmuahuff.so: spike time stamps ->
+binned counts in front of the codec, per-segment payload checksums behind it.  Fails loudly: there is no CPU path."""
 import ctypes as ct
 import os
 
@@ -17,6 +17,7 @@ PROTOTYPES = {
     "mhi_bin_events": (_int, [_vp, _vp, _u32, _u64, _u64, _u64, _u32, _vp, _vp, _u64, _vp]),
     "mhi_aer_scratch_bytes": (_int, [_u64, _u32, ct.POINTER(_u64)]),
     "mhi_aer_to_csr": (_int, [_vp, _vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "mhi_seg_crc32": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
 }
 AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
 
@@ -71,3 +72,21 @@ def aer_to_csr(ticks, channels, C, out_ticks, ev_off, dropped, scratch):
                                int(ticks.numel()), int(C), _vp(out_ticks.data_ptr()), _vp(ev_off.data_ptr()),
                                _vp(dropped.data_ptr()), _vp(scratch.data_ptr()), int(scratch.numel()),
                                _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def seg_crc32(payload, seg_off, seg_words, n_segments, seg_idx=None, crc=None, expect=None, bad=None, payload_words=None):
+    """Enqueue mhi_seg_crc32 on the current stream.  payload: int32 device words (payload_words of them: default all);
+    seg_off / seg_words: 64-bit device tensors of n_segments entries; seg_idx: optional 64-bit device list of directory
+    indices; crc: int32 / uint32 device tensor [n_segments] to fill; expect: the stored values in the same form and bad: a
+    64-bit device tensor [2] the caller set to {0, -1} (verify_state) -- the verify form."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    check(lib().mhi_seg_crc32(p(payload), int(payload.numel() if payload_words is None else payload_words), p(seg_off),
+                              p(seg_words), int(n_segments), p(seg_idx), int(seg_idx.numel()) if seg_idx is not None else 0,
+                              p(crc), p(expect), p(bad), _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def verify_state(device):
+    """-> the `bad` tensor of one checked block or query: int64 [2] = {0 mismatches, -1 = no index yet}"""
+    import torch
+    return torch.tensor([0, -1], dtype=torch.int64, device=device)

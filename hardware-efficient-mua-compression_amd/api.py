@@ -30,14 +30,15 @@ def bit_rates(channels, S=3, hist_bits=6, approx=True, sclv_rows=None, BP=50):
     return out
 
 
-def compress(channels, S=3, hist_bits=6, approx=True, sclv_rows=None, path=None):
+def compress(channels, S=3, hist_bits=6, approx=True, sclv_rows=None, path=None, checksum=False):
     """Encode everything after the calibration window of every channel.  Returns a
-    container_io.Compressed (and writes it to `path` when given)."""
+    container_io.Compressed (and writes it to `path` when given).  checksum=True: a revision-4 container that carries
+    the CRC-32 of every segment, taken on the device and verified there whenever the container is read."""
     from . import MODE_APPROX, MODE_NOSORT, container_io, sclv
     from .container import ChannelSet
     cs = channels if isinstance(channels, ChannelSet) else ChannelSet.from_channels(channels)
     rows = sclv.table(S) if sclv_rows is None else np.asarray(sclv_rows, dtype=np.uint8).reshape(-1, S)
-    c = container_io.compress(cs, S, hist_bits, MODE_APPROX if approx else MODE_NOSORT, rows)
+    c = container_io.compress(cs, S, hist_bits, MODE_APPROX if approx else MODE_NOSORT, rows, checksum=checksum)
     if path is not None:
         container_io.save(path, c)
     return c

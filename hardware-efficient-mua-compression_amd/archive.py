@@ -16,6 +16,10 @@ reads it lazily) coded with the word it carries, so a reader needs nothing but t
 -- the writer crashed, or the last record is cut short -- opens by walking the record prefixes; what follows the last
 complete record is ignored and `truncated` is set.  open(path, "a") cuts that tail (and an old trailer) off and goes on
 appending with the word of the last complete block.
+
+Archive revision 2 (create(..., checksum=True)) is revision 1 with "checksum": "crc32" in the header and every block a
+revision-4 container: the CRC-32 of each of its segments, taken on the device as the block is coded, verified there by
+read() on exactly the segments a query uploads, and by verify() over the whole file.
 """
 import builtins
 import json
@@ -29,7 +33,8 @@ from . import MODE_APPROX, MODE_NOSORT, WIN_FULL
 from . import container_io as cio
 
 MAGIC, BLOCK_MAGIC, INDEX_MAGIC, END_MAGIC = b"MUAHARC1", b"MUAHBLK1", b"MUAHIDX1", b"MUAHEND1"
-ARCHIVE_REVISION = 1
+ARCHIVE_REVISION = 1                  # written by default
+CHECKSUM_REVISION = 2                 # revision 1 whose blocks are revision-4 containers (checksum=True)
 PREFIX = struct.Struct("<8sQQQ")      # block magic, record_len, t_first, Tb
 ENTRY = struct.Struct("<QQQQ")        # offset, nbytes, t_first, Tb
 OPEN_BLOCK_FILES = 16                 # block files a reader keeps open at once (one descriptor each)
@@ -68,8 +73,10 @@ def _load(f, size):
     if len(blob) != n:
         raise ValueError("truncated archive header")
     hdr = json.loads(blob.decode())
-    if hdr.get("archive_revision") != ARCHIVE_REVISION:
+    if hdr.get("archive_revision") not in (ARCHIVE_REVISION, CHECKSUM_REVISION):
         raise ValueError("unsupported archive revision %r" % (hdr.get("archive_revision"),))
+    if (hdr["archive_revision"] == CHECKSUM_REVISION) != (hdr.get("checksum") == "crc32") or hdr.get("checksum", "crc32") != "crc32":
+        raise ValueError("archive revision %d with checksum %r" % (hdr["archive_revision"], hdr.get("checksum")))
     data0, nread = 12 + n, 12 + n
     # the trailer, when the back pointer leads to one whose entries chain from the header to itself
     if size >= data0 + 32:
@@ -134,7 +141,8 @@ class _BlockFile(cio.ContainerFile):
 
 
 class Reader:
-    """archive.open(path): C, S, T (total steps), meta, truncated, blocks (Block tuples), block(i), words(), read()."""
+    """archive.open(path): C, S, T (total steps), meta, truncated, checksum, blocks (Block tuples), block(i), words(),
+    read(), verify()."""
 
     def __init__(self, path):
         self.path = str(path)
@@ -148,6 +156,7 @@ class Reader:
             self._f.close()
             raise
         self.meta = self.header.get("meta", {})
+        self.checksum = self.header.get("checksum") == "crc32"
         self.T = int(sum(b.Tb for b in self.blocks))
         self._t_first = np.array([b.t_first for b in self.blocks], np.int64)
         self._Tb = np.array([b.Tb for b in self.blocks], np.int64)
@@ -200,7 +209,8 @@ class Reader:
     def _checked_block_file(self, i):
         bf = self.block_file(i)
         b = self.blocks[i]
-        _check_member(bf, self.C, self.S, self.mode, self.seg_chunks, self.sclv, payload_words=bf.payload_words)
+        _check_member(bf, self.C, self.S, self.mode, self.seg_chunks, self.sclv, payload_words=bf.payload_words,
+                      checksum=self.checksum)
         if int(bf.ch_len[0]) != b.Tb:
             raise ValueError("corrupt archive: block %d holds %d steps, its record says %d" % (i, int(bf.ch_len[0]), b.Tb))
         return bf
@@ -213,8 +223,10 @@ class Reader:
         b*r + r, stop)) -- uint8 = min(sum, 255) (saturate) or int32 exact sums, [n_sel, ceil((stop - start) / r)]; a
         bin that straddles a block boundary is summed over both blocks and saturated after that.
         Only the blocks that overlap the range are opened, and of those only the segments of the selected channels that
-        overlap it are read.  check=True validates those segments (mh_validate_segments) before anything is launched; a
-        decode that had to abandon a segment raises ValueError.  out: optional tensor of the result's shape and dtype
+        overlap it are read.  check=True validates those segments (mh_validate_segments) before anything is launched and,
+        in an archive with checksums, verifies them on the device next to each block's upload (one counter per block,
+        read where the decode status is read): ValueError names the block and the segment whose checksum does not match;
+        a decode that had to abandon a segment raises ValueError.  out: optional tensor of the result's shape and dtype
         with unit stride along its last axis (not with time_major); the rows are written there and nothing else is."""
         import torch
 
@@ -233,32 +245,40 @@ class Reader:
         if rows and n:
             for i, a, b in block_ranges(self._t_first, self._Tb, start, stop):
                 bf = self._checked_block_file(i)
-                _sel, payload, seg_off, peak, enc = cio._range_inputs(bf, a, b, sel, check)
-                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc))
+                _sel, payload, seg_off, segs, peak, enc = cio._range_inputs(bf, a, b, sel, check)
+                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc, i, segs))
         if not jobs:
             z = torch.zeros((rows, cols), dtype=dtype, device="cuda") if out is None else out.zero_()
             return z.t().contiguous() if time_major else z
-        plans = []
+        plans, bads = [], []
         try:
-            res = self._decode(torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans)
+            res = self._decode(torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads if check else None)
         except BaseException:
             codec.check_decoded(plans, unwinding=True)      # every plan's flag is read and cleared all the same
             raise
-        codec.check_decoded(plans, "archive")               # synchronises
+        for i, bad in bads:                                 # synchronises
+            cio.check_verified(bad, plans, "archive", " of block %d" % i)
+        codec.check_decoded(plans, "archive")
         if not time_major:
             return res
         return codec.to_time_major(res) if r is None else res.t().contiguous()
 
-    def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans):
-        """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride)."""
+    def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads):
+        """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride); with
+        `bads` a list, the verification of each block's uploaded segments next to its upload: (block, counter) pairs."""
         from . import codec
 
         def launch(job, fn):
-            bf, a, b, g0, payload, seg_off, peak, enc = job
+            bf, a, b, g0, payload, seg_off, peak, enc, i, segs = job
             plan = self._plan_for(bf)
             if plan not in plans:
                 plans.append(plan)
-            fn(plan, *codec.upload_stream(plan.device, payload, seg_off, peak, enc), a, b, g0)
+            up = codec.upload_stream(plan.device, payload, seg_off, peak, enc)
+            if bads is not None:
+                bad = cio.enqueue_verify(bf, up[0], up[1], bf.seg_words, segs, True)
+                if bad is not None:
+                    bads.append((i, bad))
+            fn(plan, *up, a, b, g0)
 
         if r is None:
             if out is None:     # the first block's local sample t at a byte address congruent to t mod 128
@@ -296,6 +316,35 @@ class Reader:
         res = acc.clamp_(max=255).to(torch.uint8) if saturate else acc
         return res if out is None else out.copy_(res)
 
+    def verify(self, device=True):
+        """Every segment of every block against its stored CRC-32, one block's payload at a time -> [(block, segment)]
+        of the mismatches, in order; empty when the file is clean.  device=True: the payload is uploaded and
+        mhi_seg_crc32 takes the checksums; device=False: zlib on the host, no GPU.  The arrays in front of each payload
+        are checked as every read of a block's head checks them (ValueError).  ValueError on an archive without
+        checksums."""
+        if not self.checksum:
+            raise ValueError("this archive carries no checksums (create(..., checksum=True) writes them)")
+        bad = []
+        for i in range(len(self.blocks)):
+            c = self.block(i)
+            _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=True)
+            if device:
+                import torch
+
+                from . import _ingest, codec
+                n = len(c.seg_words)
+                off = np.concatenate([[0], np.cumsum(c.seg_words)[:-1]]).astype(np.int64) if n else np.zeros(1, np.int64)
+                pay, d_off, _pk, _en = codec.upload_stream(torch.device("cuda", torch.cuda.current_device()), c.payload,
+                                                           off, c.peak, c.enc)
+                words = torch.from_numpy(np.ascontiguousarray(c.seg_words, np.uint64).view(np.int64)).to(pay.device)
+                crc = torch.zeros(max(n, 1), dtype=torch.int32, device=pay.device)
+                _ingest.seg_crc32(pay, d_off, words, n, crc=crc, payload_words=pay.numel() - 4)
+                got = crc[:n].cpu().numpy().view(np.uint32)
+            else:
+                got = cio.seg_crc_host(c)
+            bad += [(i, int(s)) for s in np.nonzero(got != np.asarray(c.seg_crc, np.uint32))[0]]
+        return bad
+
     def close(self):
         for p in self._plans.values():
             p.close()
@@ -314,14 +363,18 @@ class Reader:
 
 
 # ---- writer --------------------------------------------------------------------------------------
-def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None):
+def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None, checksum=False):
     """ValueError unless c (a Compressed or a ContainerFile) is a block of an archive with these parameters: the check
-    StreamDecoder.decode_block makes, plus the array sizes the directory arithmetic relies on."""
+    StreamDecoder.decode_block makes, plus the array sizes the directory arithmetic relies on.  checksum: the archive's
+    blocks are revision-4 containers, each with one checksum per segment."""
     hd = c.header
     cio._header_fields(hd)
     cio.check_block(c, C, S, mode, seg_chunks, sclv, what="block")
-    if int(hd.get("format_revision", -1)) != cio.FORMAT_REVISION:
-        raise ValueError("an archive block has container format revision %d" % cio.FORMAT_REVISION)
+    revision = cio.CHECKSUM_REVISION if checksum else cio.FORMAT_REVISION
+    if int(hd.get("format_revision", -1)) != revision:
+        raise ValueError("an archive block has container format revision %d" % revision)
+    if checksum != (getattr(c, "seg_crc", None) is not None) or (checksum and len(c.seg_crc) != len(c.seg_words)):
+        raise ValueError("a block of an archive %s checksums carries %s" % (("with", "none") if checksum else ("without", "them")))
     cio.check_consistent(c, what="block")
     words = int(c.payload.size) if payload_words is None else int(payload_words)
     if int(np.asarray(c.seg_words, np.uint64).sum()) != words:
@@ -341,11 +394,12 @@ class Writer:
             raise ValueError("recalibrate is None or an excess of at least 1 bit")
         self.recalibrate = None if recalibrate is None else int(recalibrate)
         self.pipeline = bool(pipeline)
+        self.checksum = header.get("checksum") == "crc32"
         self._word = word                  # (peak, enc) host arrays to go on with, or None: calibrate on the next block
         self._gpu = None
         self._pending = None
         self._n = 0
-        self._block_header = cio.make_header(self.S, 0, self.mode, WIN_FULL, self.seg_chunks, self.sclv)
+        self._block_header = cio.make_header(self.S, 0, self.mode, WIN_FULL, self.seg_chunks, self.sclv, self.checksum)
         self._block_header["preset"] = True    # what StreamEncoder.encode_block writes
 
     # -- records
@@ -361,8 +415,13 @@ class Writer:
     def append_compressed(self, c):
         """Append a block that is already encoded (StreamEncoder.encode_block, or one received over a link).  Needs no
         GPU.  ValueError when the block is not this archive's (S, mode, seg_chunks, SCLV rows, WIN_FULL, C channels of
-        one length)."""
-        _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv)
+        one length).  An archive with checksums stores the block's own seg_crc or, for a block without, takes the
+        values on the host with zlib (container_io.seg_crc_host); a block with checksums does not go into an archive
+        without them (ValueError)."""
+        if self.checksum and getattr(c, "seg_crc", None) is None:
+            hdr = dict(c.header, format_revision=cio.CHECKSUM_REVISION)
+            c = cio.Compressed(hdr, c.ch_len, c.peak, c.enc, c.skipped, c.ch_bits, c.seg_words, c.payload, cio.seg_crc_host(c))
+        _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=self.checksum)
         self._drain()
         self._write_record(c, int(c.ch_len[0]))
         self._word = (np.array(c.peak, np.uint8), np.array(c.enc, np.uint8))
@@ -401,7 +460,7 @@ class Writer:
             raise ValueError("a block is a uint8 [Tb >= 1, %d] array" % self.C)
         t = t.to(dev).contiguous()
         self._append(int(t.shape[0]), lambda se: se.calibrate(t),
-                     lambda se, track: se.encode_block_device(t, track=track))
+                     lambda se, track: se.encode_block_device(t, track=track, checksum=self.checksum))
 
     def append_events(self, ev, origin, period, T):
         """append() for the block of T bins that `ev` (an events.EventSet of C channels) fills from tick `origin` at
@@ -412,7 +471,7 @@ class Writer:
         if ev.C != self.C or T < 1:
             raise ValueError("a block of events has %d channels and at least 1 bin" % self.C)
         self._append(T, lambda se: se.calibrate_events(ev, origin, period, T),
-                     lambda se, track: se.encode_events_device(ev, origin, period, T, track=track))
+                     lambda se, track: se.encode_events_device(ev, origin, period, T, track=track, checksum=self.checksum))
 
     def append_aer(self, ticks, channels, origin, period, T):
         """append_events() for one merged, time-ordered list of (tick, channel) pairs on the device
@@ -449,16 +508,19 @@ class Writer:
         plan, e = slot["plan"], slot["enc"]
         if Tb not in st["small"]:
             st["small"][Tb] = (torch.empty(plan.n_segments, dtype=torch.int64).pin_memory(),
-                               torch.empty(self.C, dtype=torch.int64).pin_memory())
-        segw, bits = st["small"][Tb]
+                               torch.empty(self.C, dtype=torch.int64).pin_memory(),
+                               torch.empty(plan.n_segments, dtype=torch.int32).pin_memory() if self.checksum else None)
+        segw, bits, crc = st["small"][Tb]
         sizes = torch.cuda.Event()
         with torch.cuda.stream(g["copy"]):
             g["copy"].wait_event(coded)
             st["tot"].copy_(slot["tot"], non_blocking=True)
             segw.copy_(e.seg_words[:plan.n_segments], non_blocking=True)
             bits.copy_(e.ch_bits, non_blocking=True)
+            if crc is not None:        # taken behind the compaction, in front of `coded`
+                crc.copy_(slot["crc"][:plan.n_segments], non_blocking=True)
             sizes.record(g["copy"])
-        job = dict(st=st, Tb=Tb, dense=dense.payload, segw=segw, bits=bits, sizes=sizes)
+        job = dict(st=st, Tb=Tb, dense=dense.payload, segw=segw, bits=bits, crc=crc, sizes=sizes)
         self._n += 1
         self._drain()                  # block k - 1 goes to the file while block k runs
         self._pending = job
@@ -484,7 +546,8 @@ class Writer:
         st["done"] = done
         c = cio.Compressed(self._block_header, np.full(self.C, job["Tb"], np.uint64), st["peak"].numpy(), st["enc"].numpy(),
                            np.zeros(self.C, np.uint8), job["bits"].numpy().astype(np.uint64),
-                           job["segw"].numpy().astype(np.uint64), st["dense"][:total].numpy().view(np.uint32))
+                           job["segw"].numpy().astype(np.uint64), st["dense"][:total].numpy().view(np.uint32),
+                           None if job["crc"] is None else job["crc"].numpy().view(np.uint32))
         self._write_record(c, job["Tb"])
         self._word = (st["peak"].numpy().copy(), st["enc"].numpy().copy())
 
@@ -518,13 +581,17 @@ class Writer:
         self.close()
 
 
-def create(path, C, S=3, hist_bits=6, sclv_rows=None, approx=True, seg_chunks=2, recalibrate=None, pipeline=True, meta=None):
-    """Start a new archive (an existing file is replaced) -> Writer, a context manager."""
+def create(path, C, S=3, hist_bits=6, sclv_rows=None, approx=True, seg_chunks=2, recalibrate=None, pipeline=True, meta=None,
+           checksum=False):
+    """Start a new archive (an existing file is replaced) -> Writer, a context manager.  checksum=True: archive
+    revision 2 -- every block carries the CRC-32 of each of its segments (module docstring)."""
     from . import sclv
     rows = np.asarray(sclv.table(S) if sclv_rows is None else sclv_rows, dtype=np.uint8).reshape(-1, int(S))
     header = {"archive_revision": ARCHIVE_REVISION, "C": int(C), "S": int(S), "mode": MODE_APPROX if approx else MODE_NOSORT,
               "seg_chunks": int(seg_chunks), "hist_bits": int(hist_bits), "K": int(rows.shape[0]),
               "sclv": [[int(v) for v in r] for r in rows], "meta": dict(meta or {})}
+    if checksum:
+        header.update(archive_revision=CHECKSUM_REVISION, checksum="crc32")
     cio._header_fields(cio.make_header(S, hist_bits, header["mode"], WIN_FULL, seg_chunks, rows))   # range checks
     _archive_fields(header)
     blob = json.dumps(header, sort_keys=True).encode()

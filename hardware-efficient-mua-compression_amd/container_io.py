@@ -1,5 +1,5 @@
-"""Wire / file format of a compressed channel set (format revision 3; revision 2 is still read), and the two calls that
-make the codec usable end to end: compress() and decompress().
+"""Wire / file format of a compressed channel set (format revision 3; revision 2 is still read; revision 4 = revision 3
+plus checksums, written on request), and the two calls that make the codec usable end to end: compress() and decompress().
 
 The reference never serialises a bitstream; this container is the
 build's own.  File layout (little-endian):
@@ -7,6 +7,10 @@ build's own.  File layout (little-endian):
     b"MUAHUFF1" | u32 header_len | header (UTF-8 JSON) | arrays, each padded to 8 bytes:
         ch_len u64[C] | peak u8[C] | enc u8[C] | skipped u8[C] | ch_bits u64[C]
         | seg_words u64[n_segments] | payload u32[total_words]
+    revision 4 (checksum=True) puts seg_crc u32[n_segments] between seg_words and payload: zlib's CRC-32 of each segment's
+    stored words as little-endian bytes (0 for a segment of 0 words), taken on the device (mhi_seg_crc32) and checked there
+    on read; its header also carries "checksum": "crc32" and "arrays_crc32", the CRC-32 of the bytes of ch_len .. seg_crc
+    as written (padding included), checked on the host when the head is read.  The header JSON itself is not covered.
 
 The header carries everything a decoder needs to rebuild the plan: format revision, chunk
 geometry, S, h, mapper, window rule, seg_chunks and the K SCLV rows (the static codebooks).
@@ -19,13 +23,15 @@ import builtins
 import io
 import json
 import struct
+import zlib
 from dataclasses import dataclass
 
 import numpy as np
 
 MAGIC = b"MUAHUFF1"
 FORMAT_REVISION = 3          # written; revision 2 (no head segments, include/muahuff.h MH_WIN_REV2_SEGMENTS) is still read
-READ_REVISIONS = (2, 3)
+CHECKSUM_REVISION = 4        # revision 3 with seg_crc and arrays_crc32; written only with checksum=True
+READ_REVISIONS = (2, 3, 4)
 WIN_REV2_SEGMENTS = 0x100
 
 
@@ -39,6 +45,7 @@ class Compressed:
     ch_bits: np.ndarray    # uint64 [C]  exact code bits (== reference histogram . SCLV)
     seg_words: np.ndarray  # uint64 [n_segments]
     payload: np.ndarray    # uint32 [sum(seg_words)]
+    seg_crc: np.ndarray = None  # uint32 [n_segments], revision 4 only: CRC-32 of each segment's stored words
 
     @property
     def payload_bits(self):
@@ -54,12 +61,14 @@ class Compressed:
         return buf.getvalue()
 
     @classmethod
-    def from_device(cls, header, ch_len, enc, n_segments, dense, total):
+    def from_device(cls, header, ch_len, enc, n_segments, dense, total, seg_crc=None):
         """The host record of an encoded set: enc = the codec.Encoded the plan filled, dense = its compacted words
-        (device int32), total = how many of them are used.  The caller has synchronised."""
+        (device int32), total = how many of them are used, seg_crc = their checksums (device int32 [n_segments], for a
+        revision-4 header).  The caller has synchronised."""
         return cls(header, ch_len.copy(), enc.peak.cpu().numpy(), enc.enc.cpu().numpy(), enc.skipped.cpu().numpy(),
                    enc.ch_bits.cpu().numpy().astype(np.uint64), enc.seg_words.cpu().numpy().astype(np.uint64)[:n_segments],
-                   dense[:total].cpu().numpy().view(np.uint32).copy())
+                   dense[:total].cpu().numpy().view(np.uint32).copy(),
+                   None if seg_crc is None else seg_crc[:n_segments].cpu().numpy().view(np.uint32).copy())
 
 
 # the arrays behind the header, in file order (each padded to 8 bytes); the payload is the last
@@ -67,16 +76,38 @@ ARRAYS = (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skippe
           ("seg_words", np.uint64), ("payload", np.uint32))
 
 
+SEG_CRC = ("seg_crc", np.uint32)   # revision 4: between seg_words and payload (ARRAYS stays what revision 3 holds)
+
+
+def _file_arrays(c):
+    """(name, dtype) of the arrays c has in a file, in file order.  ValueError unless checksums and revision agree."""
+    has = getattr(c, "seg_crc", None) is not None
+    if has != (c.header.get("format_revision") == CHECKSUM_REVISION):
+        raise ValueError("container revision %r %s seg_crc" % (c.header.get("format_revision"), "with" if has else "without"))
+    return ARRAYS[:-1] + (SEG_CRC,) + ARRAYS[-1:] if has else ARRAYS
+
+
+def _raw(c, name, dt):
+    return np.ascontiguousarray(getattr(c, name), dtype=dt).reshape(-1).view(np.uint8)   # from where it lies: no copy
+
+
 def _header_blob(c):
     hdr = dict(c.header)
-    hdr["sizes"] = {name: int(np.asarray(getattr(c, name)).size) for name, _ in ARRAYS}
+    arrays = _file_arrays(c)
+    hdr["sizes"] = {name: int(np.asarray(getattr(c, name)).size) for name, _ in arrays}
+    if len(arrays) > len(ARRAYS):
+        crc = 0
+        for name, dt in arrays[:-1]:
+            raw = _raw(c, name, dt)
+            crc = zlib.crc32(b"\0" * (-raw.size % 8), zlib.crc32(raw, crc))
+        hdr["checksum"], hdr["arrays_crc32"] = "crc32", crc
     return json.dumps(hdr, sort_keys=True).encode()
 
 
 def nbytes(c):
     """The number of bytes write() emits for c (archive.py puts it in front of the block)."""
     n = 12 + len(_header_blob(c))
-    for name, dt in ARRAYS:
+    for name, dt in _file_arrays(c):
         raw = int(np.asarray(getattr(c, name)).size) * np.dtype(dt).itemsize
         n += raw + (-raw % 8)
     return n
@@ -87,10 +118,21 @@ def write(f, c):
     f.write(MAGIC)
     f.write(struct.pack("<I", len(blob)))
     f.write(blob)
-    for name, dt in ARRAYS:
-        raw = np.ascontiguousarray(getattr(c, name), dtype=dt).reshape(-1).view(np.uint8)   # written from where it lies: no copy
+    for name, dt in _file_arrays(c):
+        raw = _raw(c, name, dt)
         f.write(raw)
         f.write(b"\0" * (-raw.size % 8))
+
+
+def seg_crc_host(c):
+    """The checksums of c's segments (a `Compressed` or a `ContainerFile`) with zlib, no GPU: uint32 [n_segments],
+    zlib.crc32 of each segment's stored words as little-endian bytes, 0 for a segment of 0 words."""
+    words = np.asarray(c.seg_words, np.uint64)
+    off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
+    if off[-1] > _stored_words(c):
+        raise ValueError("corrupt container: the directory points past the payload")
+    pay = c.read_words(0, int(off[-1])) if isinstance(c, ContainerFile) else np.ascontiguousarray(c.payload, "<u4")
+    return np.array([zlib.crc32(pay[off[s]:off[s + 1]].tobytes()) if words[s] else 0 for s in range(len(words))], np.uint32)
 
 
 def _read_array(read, skip, hdr, name, dt):
@@ -114,10 +156,20 @@ def read_head(read, skip=None):
     hdr = json.loads(read(n).decode())
     if hdr.get("format_revision") not in READ_REVISIONS:
         raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
-    arrays, pos = {}, 12 + n
-    for name, dt in ARRAYS[:-1]:
-        arrays[name], size = _read_array(read, skip, hdr, name, dt)
+    has = isinstance(hdr.get("sizes"), dict) and SEG_CRC[0] in hdr["sizes"]
+    if has != (hdr["format_revision"] == CHECKSUM_REVISION):
+        raise ValueError("container revision %d %s seg_crc" % (hdr["format_revision"], "with" if has else "without"))
+    arrays, pos, crc = {}, 12 + n, 0
+    for name, dt in ARRAYS[:-1] + ((SEG_CRC,) if has else ()):
+        if has:     # arrays_crc32 covers the padding as written: read, not skipped
+            arrays[name], size = _read_array(read, lambda pad: None, hdr, name, dt)
+            pad = read(size - arrays[name].nbytes)
+            crc = zlib.crc32(pad, zlib.crc32(arrays[name].view(np.uint8), crc))
+        else:
+            arrays[name], size = _read_array(read, skip, hdr, name, dt)
         pos += size
+    if has and (hdr.get("checksum") != "crc32" or hdr.get("arrays_crc32") != crc):
+        raise ValueError("corrupt container: checksum of the arrays in front of the payload does not match")
     return hdr, arrays, pos
 
 
@@ -137,18 +189,20 @@ def load(path):
         return read(f)
 
 
-def make_header(S, h, mode, window, seg_chunks, sclv):
+def make_header(S, h, mode, window, seg_chunks, sclv, checksum=False):
     from . import _lib
     sclv = np.asarray(sclv, dtype=np.uint8).reshape(-1, int(S))
-    return {"format_revision": FORMAT_REVISION, "piece": _lib.PIECE, "lanes": _lib.LANES, "rows": _lib.ROWS,
+    return {"format_revision": CHECKSUM_REVISION if checksum else FORMAT_REVISION, "piece": _lib.PIECE, "lanes": _lib.LANES, "rows": _lib.ROWS,
             "S": int(S), "h": int(h), "mode": int(mode), "window": int(window), "seg_chunks": int(seg_chunks),
             "K": int(sclv.shape[0]), "sclv": [[int(v) for v in r] for r in sclv]}
 
 
 # ---- GPU end-to-end ----------------------------------------------------------------------------
-def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0):
+def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0, checksum=False):
     """Calibrate + encode every channel of a ChannelSet on the GPU and bring the dense stream to
-    the host as a `Compressed`.  seg_chunks = 0: the planner's choice; the header records it."""
+    the host as a `Compressed`.  seg_chunks = 0: the planner's choice; the header records it.
+    checksum=True: a revision-4 container -- the CRC-32 of every segment of the compacted payload is taken on the
+    device (mhi_seg_crc32) and comes to the host with the other small arrays."""
     import torch
 
     from . import WIN_AFTER_CAL, codec
@@ -156,11 +210,69 @@ def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0):
     plan = codec.Plan(cs.ch_off, cs.ch_len, S, h, mode, window, sclv, seg_chunks=seg_chunks)
     enc = plan.encode(cs.data)
     dense, tot = plan.compact(enc)
+    crc = enqueue_seg_crc(plan, dense) if checksum else None
     torch.cuda.synchronize()
-    c = Compressed.from_device(make_header(S, h, mode, window, plan.seg_chunks, sclv), cs.ch_len, enc, plan.n_segments,
-                               dense.payload, int(tot.item()))
+    c = Compressed.from_device(make_header(S, h, mode, window, plan.seg_chunks, sclv, checksum), cs.ch_len, enc,
+                               plan.n_segments, dense.payload, int(tot.item()), crc)
     plan.close()
     return c
+
+
+def enqueue_seg_crc(plan, dense, out=None):
+    """mhi_seg_crc32 over every segment of a compacted stream (dense: the codec.Encoded that Plan.compact returns, with
+    its device offsets and sizes), on the current stream -> int32 device tensor [n_segments] holding the uint32 values."""
+    import torch
+
+    from . import _ingest
+    crc = torch.zeros(max(plan.n_segments, 1), dtype=torch.int32, device=plan.device) if out is None else out
+    if plan.n_segments:
+        _ingest.seg_crc32(dense.payload, dense.seg_off, dense.seg_words, plan.n_segments, crc=crc)
+    return crc
+
+
+def enqueue_verify(src, pay, d_off, seg_words, segs, check, expect=None):
+    """The read side of the checksums, next to an upload: with `check` and a source that carries seg_crc, mhi_seg_crc32 in
+    verify form over the uploaded segments -- pay (codec.upload_stream: four words of slack behind the payload), d_off
+    and seg_words indexed by segment, segs: the uint64 directory entries that were uploaded (None: all) -- against the
+    stored values (expect: those in the order of seg_words when it is not the source's).  On the current stream, no
+    synchronisation.  -> the call's own `bad` tensor for check_verified, or None when nothing is verified."""
+    import torch
+
+    from . import _ingest
+    stored = getattr(src, "seg_crc", None) if expect is None else expect
+    if not check or stored is None:
+        return None
+    if len(stored) != len(seg_words):
+        raise ValueError("corrupt container: %d checksums for %d segments" % (len(stored), len(seg_words)))
+    if len(seg_words) == 0:
+        return None
+    dev = pay.device
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int64 if dt == np.uint64 else np.int32)).to(dev)  # noqa: E731
+    cached = getattr(src, "_dev_dir", None) if expect is None else None     # a ContainerFile keeps its directory there
+    if cached is None or cached[0].device != dev:
+        cached = (up(seg_words, np.uint64), up(stored, np.uint32))
+        if expect is None and isinstance(src, ContainerFile):
+            src._dev_dir = cached
+    bad = _ingest.verify_state(dev)
+    _ingest.seg_crc32(pay, d_off, cached[0], len(seg_words), seg_idx=None if segs is None else up(segs, np.uint64),
+                      expect=cached[1], bad=bad, payload_words=pay.numel() - 4)
+    return bad
+
+
+def check_verified(bad, plans=(), what="container", where="", index=None):
+    """Read one call's `bad` (synchronises; None: nothing was verified) where the decode status is read: ValueError
+    naming the lowest mismatching segment (index: local -> directory entry, for a re-gathered selection); the plans'
+    status words are read and cleared first, so that the error leaves none behind."""
+    if bad is None:
+        return
+    n, first = (int(v) for v in bad.tolist())
+    if n:
+        from . import codec
+        codec.check_decoded(plans, unwinding=True)
+        if index is not None and 0 <= first < len(index):
+            first = int(index[first])
+        raise ValueError("corrupt %s: checksum of segment %d%s does not match its payload (%d of the segments read)"
+                         % (what, first, where, n))
 
 
 def plan_window(hd):
@@ -291,7 +403,8 @@ def decompress(c, device="cuda", channels=None, check=True):
     encoded windows are zero).  channels: optional list of channel indices -- only their segments
     are uploaded and decoded (the directory gives random access per channel); the returned set
     holds them in the order given.  check=True runs validate() first (containers from disk are
-    untrusted input for a kernel that follows their headers)."""
+    untrusted input for a kernel that follows their headers) and, when the container carries checksums, verifies every
+    uploaded segment on the device (mhi_seg_crc32): ValueError names the first that does not match."""
     import torch
 
     from . import codec
@@ -302,6 +415,7 @@ def decompress(c, device="cuda", channels=None, check=True):
     nseg_ch = check_consistent(c, arrays=False)
     seg_words, payload, peak, enc, skipped, ch_bits, ch_len = (c.seg_words, c.payload, c.peak, c.enc, c.skipped,
                                                                 c.ch_bits, c.ch_len)
+    stored_crc, segs = getattr(c, "seg_crc", None), None
     if channels is not None:
         sel = codec.select_channels(len(c.ch_len), channels)
         first = np.concatenate([[0], np.cumsum(nseg_ch)]).astype(np.int64)       # channel -> first segment
@@ -310,6 +424,8 @@ def decompress(c, device="cuda", channels=None, check=True):
         payload = (np.concatenate([c.payload[off[s]:off[s + 1]] for s in segs]) if segs.size
                    else np.zeros(0, np.uint32))
         seg_words = c.seg_words[segs]
+        if stored_crc is not None and len(stored_crc) == len(c.seg_words):
+            stored_crc = stored_crc[segs]
         peak, enc, skipped, ch_bits, ch_len = c.peak[sel], c.enc[sel], c.skipped[sel], c.ch_bits[sel], c.ch_len[sel]
     cs = ChannelSet.empty([int(n) for n in ch_len], device=device)
     if len(ch_len) == 0:
@@ -326,7 +442,9 @@ def decompress(c, device="cuda", channels=None, check=True):
         e = codec.Encoded(pay, torch.from_numpy(seg_words.astype(np.int64)).to(dev),
                           torch.from_numpy(ch_bits.astype(np.int64)).to(dev), d_peak, d_enc,
                           torch.from_numpy(np.ascontiguousarray(skipped)).to(dev), d_off, True)
+        bad = enqueue_verify(c, pay, d_off, seg_words, None, check, expect=stored_crc)
         plan.decode(e, cs.data)
+        check_verified(bad, [plan], index=segs)
         codec.check_decoded([plan])
     finally:
         plan.close()
@@ -336,7 +454,7 @@ def decompress(c, device="cuda", channels=None, check=True):
 # ---- random access in time -----------------------------------------------------------------------
 class ContainerFile:
     """A container on disk with its payload left there: open() reads the magic, the header and the per-channel and
-    directory arrays, and remembers where the payload starts.  Same fields as `Compressed` but `payload`;
+    directory arrays, and remembers where the payload starts.  Same fields as `Compressed` but `payload` (seg_crc: None without checksums);
     read_words() fetches a run of payload words (seek + readinto).  `bytes_read` counts every byte read from the file,
     so that "a range query reads only what it needs" can be checked.  Caches one decode plan of the container's layout
     (decompress_range).  offset: the byte of the file where the container starts (a block inside an archive, archive.py)."""
@@ -346,6 +464,8 @@ class ContainerFile:
         self.offset = int(offset)
         self.bytes_read = 0
         self._plan = None
+        self.seg_crc = None     # revision 4: the stored checksums
+        self._dev_dir = None    # (seg_words, seg_crc) on the device once a query has verified against them
         self._f = builtins.open(self.path, "rb")
         try:
             self._f.seek(self.offset)
@@ -466,8 +586,8 @@ def gather_range(src, start, stop, sel):
 def _range_inputs(src, start, stop, channels, check, r=None):
     """What a range query of a `Compressed` / `ContainerFile` needs on the host: argument checks (codec.query_args), the
     payload of the segments that overlap [start, stop) (gather_range) and, with check, their validation
-    (mh_validate_segments).  -> (sel, payload, seg_off, peak, enc); payload is None when the query is empty (no channel
-    or no sample)."""
+    (mh_validate_segments).  -> (sel, payload, seg_off, segs, peak, enc); segs: the directory entries whose words
+    `payload` holds; payload is None when the query is empty (no channel or no sample)."""
     from . import _lib, codec
     hd = src.header
     S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
@@ -476,7 +596,7 @@ def _range_inputs(src, start, stop, channels, check, r=None):
     sel = codec.query_args(int(ch_len.max()) if C else 0, C, start, stop, channels, r)
     check_consistent(src, arrays=check)
     if sel.size == 0 or stop == start:
-        return sel, None, None, None, None
+        return sel, None, None, None, None, None
     payload, seg_off, segs = gather_range(src, start, stop, sel)
     peak, enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
     if check:
@@ -489,17 +609,21 @@ def _range_inputs(src, start, stop, channels, check, r=None):
                                              peak.ctypes.data, enc.ctypes.data)
         if rc != 0:
             raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
-    return sel, payload, seg_off, peak, enc
+    return sel, payload, seg_off, segs, peak, enc
 
 
-def _range_decode(src, payload, seg_off, peak, enc, run):
-    """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device; ValueError when the decode
-    had to abandon a segment."""
+def _range_decode(src, payload, seg_off, segs, peak, enc, check, run):
+    """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device, its segments verified
+    next to the upload when the source carries checksums (enqueue_verify); ValueError when one does not match or the
+    decode had to abandon a segment."""
     from . import codec
     own = not isinstance(src, ContainerFile)
     plan = _range_plan(src) if own else src.plan()
     try:
-        out = run(plan, *codec.upload_stream(plan.device, payload, seg_off, peak, enc))
+        up = codec.upload_stream(plan.device, payload, seg_off, peak, enc)
+        bad = enqueue_verify(src, up[0], up[1], src.seg_words, segs, check)
+        out = run(plan, *up)
+        check_verified(bad, [plan])
         codec.check_decoded([plan])
     finally:
         if own:
@@ -513,18 +637,19 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
     channels[i]: min(x, S-1) inside the channel's encoded window, 0 outside it and past its length -- exactly
     decompress(src, channels).to_channels()[i][start:stop], zero-extended), or [stop - start, n_sel] with
     time_major=True.  channels: None = all, else indices (rows in that order, repeats allowed).  check=True validates the
-    header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU; a decode that
-    had to abandon a segment raises ValueError as decompress() does."""
+    header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU and, when the
+    source carries checksums, verifies exactly those segments on the device next to their upload; a segment whose
+    checksum does not match, or a decode that had to abandon one, raises ValueError as decompress() does."""
     import torch
 
     from . import codec
     start, stop = int(start), int(stop)
-    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check)
+    sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check)
     n, rows = stop - start, int(sel.size)
     if payload is None:
         z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
         return z.t().contiguous() if time_major else z
-    out = _range_decode(src, payload, seg_off, peak, enc,
+    out = _range_decode(src, payload, seg_off, segs, peak, enc, check,
                         lambda plan, pay, off, pk, en: plan.decode_range(pay, off, pk, en, sel, start, stop))
     return codec.to_time_major(out) if time_major else out
 
@@ -539,9 +664,9 @@ def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, 
     import torch
     r, start = int(r), int(start)
     stop = (int(np.max(src.ch_len)) if len(src.ch_len) else 0) if stop is None else int(stop)
-    sel, payload, seg_off, peak, enc = _range_inputs(src, start, stop, channels, check, r)
+    sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check, r)
     nb, rows = (stop - start + r - 1) // r, int(sel.size)
     if payload is None:
         return torch.zeros((rows, nb), dtype=torch.uint8 if saturate else torch.int32, device=device)
-    return _range_decode(src, payload, seg_off, peak, enc,
+    return _range_decode(src, payload, seg_off, segs, peak, enc, check,
                          lambda plan, pay, off, pk, en: plan.decode_rebin(pay, off, pk, en, sel, start, stop, r, saturate))

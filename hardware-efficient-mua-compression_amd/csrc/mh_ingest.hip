@@ -1,5 +1,5 @@
-// mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp and the pair-list partition
-// in mh_aer.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
+// mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
+// in mh_aer.hpp and the segment checksum in mh_crc.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
 // fallback here either.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 
 #include "mh_aer.hpp"
 #include "mh_aer_layout.hpp"
+#include "mh_crc.hpp"
 #include "mh_ingest.hpp"
 // built with -fvisibility=hidden: the mhi_* functions of the header are ALL the library exports
 #pragma GCC visibility push(default)
@@ -160,6 +161,26 @@ int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits
         aer_launch<uint32_t>(ticks, channels, n, C, L, (uint8_t *)scratch, out_ticks, ev_off, dropped, st);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_aer_to_csr: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *seg_off, const uint64_t *seg_words,
+                  uint64_t n_segments, const uint64_t *seg_idx, uint64_t n_idx, uint32_t *crc, const uint32_t *expect,
+                  uint64_t *bad, void *stream)
+{
+    if (!payload || !seg_off || !seg_words) return fail(MH_ERR_ARG, "mhi_seg_crc32: NULL pointer");
+    if (!crc && !expect) return fail(MH_ERR_ARG, "mhi_seg_crc32: neither crc nor expect is given");
+    if (expect && !bad) return fail(MH_ERR_ARG, "mhi_seg_crc32: expect is given without bad");
+    if ((uintptr_t)payload % 4) return fail(MH_ERR_ARG, "mhi_seg_crc32: payload is not 4-byte aligned");
+    const uint64_t n_list = seg_idx ? n_idx : n_segments;
+    if (n_list == 0) return MH_OK;
+    const uint64_t groups = (n_list + mh::kCrcWaves - 1) / mh::kCrcWaves;
+    const dim3 grid((unsigned)(groups < mh::kCrcMaxGroups ? groups : mh::kCrcMaxGroups)), block(64u * mh::kCrcWaves);
+    hipLaunchKernelGGL(mh::k_seg_crc32, grid, block, 0, (hipStream_t)stream, static_cast<const uint32_t *>(payload),
+                       payload_words, seg_off, seg_words, n_segments, seg_idx, n_list, crc, expect,
+                       reinterpret_cast<unsigned long long *>(bad));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_seg_crc32: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

@@ -111,10 +111,12 @@ class StreamEncoder:
                                            z(self.C, torch.uint8))
         return slot["monitor"]
 
-    def encode_block_device(self, block, track=False):
+    def encode_block_device(self, block, track=False, checksum=False):
         """block: [Tb, C] time-major counts (device tensor or host array).  Enqueues
         de-interleave + preset encode + compaction on the current stream and returns
         (dense Encoded, total_words tensor, slot) without synchronising.
+        checksum=True also enqueues, behind the compaction, the CRC-32 of every segment of the dense words
+        (mhi_seg_crc32) into slot["crc"] (int32 [n_segments] holding the uint32 values), a slot buffer like the others.
         track=True also enqueues, behind the de-interleave and on the same stream, a measure of the block's packed
         pieces with a FRESH calibration (on the block's own first 2^hist_bits steps): slot["fresh"] is the
         codec.Measured of this block, overwritten per block like the other slot buffers -- see drift() and adopt().
@@ -134,9 +136,9 @@ class StreamEncoder:
         cs, plan = slot["cs"], slot["plan"]
         _lib.check(_lib.lib().mh_deinterleave_packed(_ptr(t), Tb, C, plan.input_bits, _ptr(cs.data), _ptr(slot["d_off"]),
                                                      plan.chunk_stride, _stream()))
-        return self._encode_slot(slot, track)
+        return self._encode_slot(slot, track, checksum)
 
-    def encode_events_device(self, ev, origin, period, T, track=False):
+    def encode_events_device(self, ev, origin, period, T, track=False, checksum=False):
         """encode_block_device for the block of T bins that `ev` (an events.EventSet) fills from `origin` at `period`
         ticks per bin: the slot's packed chunk-blocked pieces are written by the binner (mhi_bin_events, min(count, 3)
         in 2 bits for S <= 4, min(count, 15) in 4 bits for S >= 5) -- no time-major block, no de-interleave.  Everything
@@ -152,10 +154,11 @@ class StreamEncoder:
         slot = self._slot(T)
         cs, plan = slot["cs"], slot["plan"]
         _ingest.bin_events(ev, origin, period, T, plan.input_bits, cs.data, slot["d_off"], plan.chunk_stride)
-        return self._encode_slot(slot, track)
+        return self._encode_slot(slot, track, checksum)
 
-    def _encode_slot(self, slot, track):
-        """The block path behind the slot's packed pieces: optional drift measure, preset encode, compaction."""
+    def _encode_slot(self, slot, track, checksum=False):
+        """The block path behind the slot's packed pieces: optional drift measure, preset encode, compaction, optional
+        segment checksums."""
         cs, plan = slot["cs"], slot["plan"]
         if track:
             self._monitor(slot).measure(cs.data, out=slot["fresh"])
@@ -163,24 +166,27 @@ class StreamEncoder:
         _lib.check(_lib.lib().mh_encode_preset(plan._h, _ptr(cs.data), _ptr(self.peak), _ptr(self.enc), _ptr(enc.payload),
                                                enc.payload.numel(), _ptr(enc.seg_words), _ptr(enc.ch_bits), _stream()))
         dense, tot = plan.compact(enc, dense=slot["dense"], off=slot["off"], tot=slot["tot"])
+        if checksum:
+            slot["crc"] = container_io.enqueue_seg_crc(plan, dense, out=slot.get("crc"))
         return dense, tot, slot
 
-    def encode_block(self, block):
+    def encode_block(self, block, checksum=False):
         """block: [Tb, C] time-major counts -> container_io.Compressed covering all Tb bins of
-        every channel, coded with the stored RAM word."""
-        return self._finish_block(*self.encode_block_device(block))
+        every channel, coded with the stored RAM word.  checksum=True: a revision-4 container with the segments'
+        CRC-32 (taken on the device)."""
+        return self._finish_block(*self.encode_block_device(block, checksum=checksum), checksum=checksum)
 
-    def _finish_block(self, dense, tot, slot):
+    def _finish_block(self, dense, tot, slot, checksum=False):
         plan = slot["plan"]
         torch.cuda.synchronize()
-        hdr = container_io.make_header(self.S, 0, self.mode, WIN_FULL, plan.seg_chunks, self.sclv)
+        hdr = container_io.make_header(self.S, 0, self.mode, WIN_FULL, plan.seg_chunks, self.sclv, checksum)
         hdr["preset"] = True
         return container_io.Compressed.from_device(hdr, slot["cs"].ch_len, slot["enc"], plan.n_segments, dense.payload,
-                                                   int(tot.item()))
+                                                   int(tot.item()), slot["crc"] if checksum else None)
 
-    def encode_events(self, ev, origin, period, T):
+    def encode_events(self, ev, origin, period, T, checksum=False):
         """encode_block for the T bins that `ev` fills from `origin` at `period` ticks per bin."""
-        return self._finish_block(*self.encode_events_device(ev, origin, period, T))
+        return self._finish_block(*self.encode_events_device(ev, origin, period, T, checksum=checksum), checksum=checksum)
 
     def drift(self, slot):
         """int64 device tensor [C]: the code bits the slot's last tracked block spent under the word it was coded with,
@@ -283,15 +289,22 @@ class StreamDecoder:
             good = slot["plan"].decode_ok() and good
         return good
 
-    def decode_block(self, c):
+    def decode_block(self, c, check=True):
         """Checked host form: c = container_io.Compressed of one block as StreamEncoder.encode_block writes it ->
-        [Tb, C] numpy array of min(x, S-1).  Raises ValueError when the container does not belong to this decoder or
-        its stream is corrupt (mh_validate_stream, as container_io.decompress)."""
+        [Tb, C] numpy array of min(x, S-1).  Raises ValueError when the container does not belong to this decoder or,
+        with check, its stream is corrupt (mh_validate_stream, as container_io.decompress) or -- for a block that
+        carries checksums -- a segment does not match its CRC-32 (verified on the device next to the upload)."""
         container_io.check_block(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv)
-        container_io.validate(c)
-        out = self.decode_block_device(*codec.upload_stream(self.device, c.payload, c.seg_words, c.peak, c.enc),
-                                       int(c.ch_len[0]))
-        codec.check_decoded([slot["plan"] for slot in self._slots.values()])  # synchronises
+        if check:
+            container_io.validate(c)
+        Tb = int(c.ch_len[0])
+        up = codec.upload_stream(self.device, c.payload, c.seg_words, c.peak, c.enc)
+        out = self.decode_block_device(*up, Tb)
+        plans = [slot["plan"] for slot in self._slots.values()]
+        # the block's offsets are the slot's, scanned by decode_block_device in front of this on the same stream
+        container_io.check_verified(container_io.enqueue_verify(c, up[0], self._slots[Tb]["seg_off"], c.seg_words, None,
+                                                                check), plans)
+        codec.check_decoded(plans)  # synchronises
         return out.cpu().numpy()
 
     def close(self):

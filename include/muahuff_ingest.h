@@ -1,6 +1,8 @@
 /*
- * muahuff_ingest.h -- C ABI of libmuahuff_ingest.so, the front-end companion of libmuahuff.so: stage L0 of the
- * reference's pipeline, spike time stamps -> binned counts, on the MI355X (gfx950).
+ * muahuff_ingest.h -- C ABI of libmuahuff_ingest.so, the companion of libmuahuff.so: what stands around the codec.
+ * In front of it, stage L0 of the reference's pipeline, spike time stamps -> binned counts; behind it, storage: the
+ * per-segment CRC-32 of a compacted payload (mhi_seg_crc32), taken when a container is written and checked when it is
+ * read.  All on the MI355X (gfx950).
  *
  * The reference bins per-channel spike times with histogram2 and uint8() (Data/Load_and_bin_Sabes_store_as_mat_file.m:
  * 30-54); its RTL counts detections per BIN_PERIOD clock ticks and holds at SPIKE_RATE_CLIP-1 (FPGA implementation/
@@ -12,7 +14,7 @@
  * mhi_aer_to_csr brings such a list, resident on the device, into the per-channel form mhi_bin_events reads -- a stable
  * partition by channel (count, scan, scatter), not a sort -- so that no stage in front of the codec runs on the host.
  *
- * A binner is not a codec operation, so it is not part of muahuff.h: that ABI is closed.  The conventions are the
+ * Neither a binner nor a checksum is a codec operation, so they are not part of muahuff.h: that ABI is closed.  The conventions are the
  * same: every function returns MH_OK or a negative MH_ERR_* code of muahuff.h and never throws, mhi_last_error()
  * returns a thread-local message for the last failure on this thread, every argument check comes before any device
  * work, `stream` is a hipStream_t passed as void* (NULL = the default stream), the caller owns every buffer.  There
@@ -80,6 +82,26 @@ int mhi_aer_scratch_bytes(uint64_t n, uint32_t C, uint64_t *bytes);
 int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits, uint64_t n, uint32_t C,
                    uint64_t *out_ticks, uint64_t *ev_off, uint64_t *dropped, void *scratch, uint64_t scratch_bytes,
                    void *stream);
+
+/* CRC-32 of directory segments of a payload, one value per segment: the zlib / IEEE 802.3 one (reflected polynomial
+ * 0xEDB88320, initial value and final xor 0xFFFFFFFF, "123456789" -> 0xCBF43926) over the segment's stored words as
+ * little-endian bytes -- zlib.crc32(payload[off : off + n].tobytes()).  A segment of 0 words has CRC 0.
+ * payload: device, payload_words 32-bit words, 4-byte aligned -- segments may start at ANY word (mh_compact packs them
+ * back to back).  seg_off / seg_words: device, n_segments entries, words.  seg_idx: device, n_idx directory indices
+ * (the segments a range query uploaded; any order), or NULL: all n_segments.
+ * crc: device, n_segments entries, written at the listed segments only; may be NULL when expect is given.
+ * expect: NULL, or device, n_segments stored values -- the verify form: bad[0] += the number of listed segments whose
+ * CRC differs from expect[segment], bad[1] = min(bad[1], index of each such segment).  The caller initialises bad
+ * (device, 2 entries) to {0, UINT64_MAX}; several calls may share it.
+ * No value read from device memory is trusted: a segment with seg_off + seg_words > payload_words (tested so that a
+ * sum that wraps 64 bits fails too) is never read, counts as a mismatch and has 0 written to crc; a seg_idx entry
+ * >= n_segments is skipped, counted in bad[0] and entered into bad[1] as it stands.
+ * MH_ERR_ARG, before any device work: payload, seg_off or seg_words NULL; payload not 4-byte aligned; crc and expect
+ * both NULL; expect without bad.  n_segments == 0 (or seg_idx with n_idx == 0) enqueues nothing.
+ * Only enqueues on `stream`: no synchronisation, allocation or free, so it can be captured into a hipGraph. */
+int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *seg_off, const uint64_t *seg_words,
+                  uint64_t n_segments, const uint64_t *seg_idx, uint64_t n_idx, uint32_t *crc, const uint32_t *expect,
+                  uint64_t *bad, void *stream);
 
 #ifdef __cplusplus
 }
