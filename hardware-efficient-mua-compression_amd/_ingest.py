@@ -1,5 +1,5 @@
 """ctypes binding of libmuahuff_ingest.so (include/muahuff_ingest.h), the companion of libmuahuff.so: spike time stamps ->
-binned counts in front of the codec, per-segment payload checksums behind it.  Fails loudly: there is no CPU path."""
+binned counts in front of the codec, per-segment payload checksums and the way back from counts to events behind it.  Fails loudly: there is no CPU path."""
 import ctypes as ct
 import os
 
@@ -18,7 +18,11 @@ PROTOTYPES = {
     "mhi_aer_scratch_bytes": (_int, [_u64, _u32, ct.POINTER(_u64)]),
     "mhi_aer_to_csr": (_int, [_vp, _vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "mhi_seg_crc32": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "mhi_unbin_scratch_bytes": (_int, [_u32, _u64, _u64, ct.POINTER(_u64)]),
+    "mhi_unbin_count": (_int, [_u32, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "mhi_unbin_emit": (_int, [_u32, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _u64, _vp]),
 }
+UNBIN_CSR, UNBIN_AER = 0, 1       # MHI_UNBIN_CSR, MHI_UNBIN_AER
 AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
 
 _lib = None
@@ -72,6 +76,36 @@ def aer_to_csr(ticks, channels, C, out_ticks, ev_off, dropped, scratch):
                                int(ticks.numel()), int(C), _vp(out_ticks.data_ptr()), _vp(ev_off.data_ptr()),
                                _vp(dropped.data_ptr()), _vp(scratch.data_ptr()), int(scratch.numel()),
                                _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def unbin_scratch_bytes(form, rows, cols):
+    """mhi_unbin_scratch_bytes: host arithmetic, no device."""
+    b = _u64(0)
+    check(lib().mhi_unbin_scratch_bytes(int(form), int(rows), int(cols), ct.byref(b)))
+    return int(b.value)
+
+
+def unbin_count(form, x, row_off, rows, cols, ev_off, total, scratch):
+    """Enqueue mhi_unbin_count on the current stream.  x: uint8 device tensor whose data_ptr() is the matrix's first byte;
+    row_off: 64-bit device tensor of `rows` byte offsets (UNBIN_CSR) or None (UNBIN_AER, a contiguous [rows, cols] block);
+    ev_off: 64-bit device tensor [rows + 1] (CSR) or None; total: 64-bit device tensor [1]; scratch: uint8 device tensor of
+    at least unbin_scratch_bytes(form, rows, cols) bytes."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    check(lib().mhi_unbin_count(int(form), p(x), p(row_off), int(rows), int(cols), p(ev_off), p(total), p(scratch),
+                                int(scratch.numel()), _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def unbin_emit(form, x, row_off, rows, cols, origin, period, phase, out_ticks, out_ch, over, scratch, capacity=None):
+    """Enqueue mhi_unbin_emit on the current stream, after unbin_count on the same (form, x, row_off, rows, cols, scratch).
+    out_ticks: 64-bit device tensor; out_ch: 16- or 32-bit device tensor of as many entries (AER) or None; capacity: the
+    entries they hold (default: all of out_ticks); over: 64-bit device tensor [1], zeroed by the caller."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    cap = int(out_ticks.numel()) if capacity is None else int(capacity)
+    check(lib().mhi_unbin_emit(int(form), p(x), p(row_off), int(rows), int(cols), int(origin), int(period), int(phase),
+                               p(out_ticks), p(out_ch), 8 * out_ch.element_size() if out_ch is not None else 0, cap, p(over),
+                               p(scratch), int(scratch.numel()), _vp(torch.cuda.current_stream().cuda_stream)))
 
 
 def seg_crc32(payload, seg_off, seg_words, n_segments, seg_idx=None, crc=None, expect=None, bad=None, payload_words=None):

@@ -263,6 +263,39 @@ class Reader:
             return res
         return codec.to_time_major(res) if r is None else res.t().contiguous()
 
+    def read_events(self, start, stop, channels=None, origin=0, period=1, phase=0, check=True, aer=False,  # noqa: A002
+                    ch_dtype=None):
+        """Global samples [start, stop) of the selected channels as spike events on the recording's clock: sample t of a
+        channel with count k gives k events at the tick origin + t*period + phase -- read(start, stop, channels,
+        check=check) followed by events.EventSet.from_counts with the origin moved to origin + start*period, expanded on
+        the device (mhi_unbin_count / mhi_unbin_emit).  What the archive holds is min(count, S-1) per bin, and all of a
+        bin's events get the bin's start + phase.
+        -> events.EventSet whose channel k is channels[k] (None = all; any order, repeats allowed).
+        aer=True: read(time_major=True) and events.aer_from_counts -> (ticks int64, channels): one merged list in time
+        order; the channel numbers are the archive's (mapped through `channels` when a subset was selected; within a
+        tick the pairs follow the order of `channels`).  ch_dtype: torch.int32 (default) or a 16-bit type."""
+        import torch
+
+        from . import codec, events
+        start, stop = int(start), int(stop)
+        sel = codec.query_args(self.T, self.C, start, stop, channels, None)
+        origin, period, phase = events._tick_args(origin, period, phase, max(stop, 1))
+        ch_dtype = torch.int32 if ch_dtype is None else ch_dtype
+        if sel.size == 0:
+            raise ValueError("read_events needs at least one channel")
+        if stop == start:       # an empty range: no events
+            none = torch.zeros(0, dtype=torch.int64, device="cuda")
+            if aer:
+                return none, torch.zeros(0, dtype=ch_dtype, device="cuda")
+            return events.EventSet(none, np.zeros(int(sel.size) + 1, np.uint64), check=False)
+        x = self.read(start, stop, channels, time_major=aer, check=check)
+        if not aer:
+            return events.EventSet.from_counts(x, origin + start * period, period, phase)
+        ticks, ch = events.aer_from_counts(x.contiguous(), origin + start * period, period, phase, ch_dtype=ch_dtype)
+        if channels is not None:
+            ch = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int64)).to(ch.device)[ch.long()].to(ch_dtype)
+        return ticks, ch
+
     def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads):
         """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride); with
         `bads` a list, the verification of each block's uploaded segments next to its upload: (block, counter) pairs."""

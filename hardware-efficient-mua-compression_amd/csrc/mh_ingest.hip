@@ -1,5 +1,5 @@
 // mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
-// in mh_aer.hpp and the segment checksum in mh_crc.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
+// in mh_aer.hpp, the segment checksum in mh_crc.hpp and the way back from counts to events in mh_unbin.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
 // fallback here either.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,8 @@
 #include "mh_aer_layout.hpp"
 #include "mh_crc.hpp"
 #include "mh_ingest.hpp"
+#include "mh_unbin.hpp"
+#include "mh_unbin_layout.hpp"
 // built with -fvisibility=hidden: the mhi_* functions of the header are ALL the library exports
 #pragma GCC visibility push(default)
 #include "muahuff_ingest.h"
@@ -64,6 +66,39 @@ void aer_launch(const uint64_t *ticks, const void *channels, uint64_t n, uint32_
         hipLaunchKernelGGL(mh::k_aer_scatter<CH>, tiles, waves, L.lds_bytes, st, ticks, ch, n, C, L.nbits, L.run, L.rows, matrix,
                            out_ticks);
     }
+}
+
+// What mhi_unbin_count and mhi_unbin_emit share: the form, the shape and the scratch.  `fn` names the caller.
+int unbin_args(const char *fn, uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
+               const void *scratch, uint64_t scratch_bytes, mh::UnbinLayout *L)
+{
+    if (form != mh::kUnbinCsr && form != mh::kUnbinAer)
+        return fail(MH_ERR_ARG, "%s: form=%u (MHI_UNBIN_CSR or MHI_UNBIN_AER)", fn, form);
+    if (!in || !scratch) return fail(MH_ERR_ARG, "%s: NULL pointer", fn);
+    if (form == mh::kUnbinCsr && !row_off) return fail(MH_ERR_ARG, "%s: the CSR form needs row_off", fn);
+    if (form == mh::kUnbinAer && row_off) return fail(MH_ERR_ARG, "%s: the AER form is one contiguous block: row_off must be NULL", fn);
+    const int rc = mh::unbin_layout(form, rows, cols, L);
+    if (rc == -1)
+        return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu (each at least 1; AER form: cols <= 2^32)", fn,
+                    (unsigned long long)rows, (unsigned long long)cols);
+    if (rc) return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu make more than 2^32 - 1 tiles", fn, (unsigned long long)rows,
+                        (unsigned long long)cols);
+    if (scratch_bytes < L->bytes)
+        return fail(MH_ERR_ARG, "%s: scratch_bytes=%llu, mhi_unbin_scratch_bytes asks for %llu", fn,
+                    (unsigned long long)scratch_bytes, (unsigned long long)L->bytes);
+    if ((uintptr_t)scratch % 16) return fail(MH_ERR_ARG, "%s: scratch is not 16-byte aligned", fn);
+    return MH_OK;
+}
+
+template <uint32_t FORM, typename CH>
+void unbin_emit_launch(const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols, const mh::UnbinLayout &L,
+                       uint64_t first_tick, uint64_t period, const uint64_t *base, uint64_t *out_ticks, void *out_ch,
+                       uint64_t capacity, uint64_t *over, hipStream_t st)
+{
+    const dim3 grid((unsigned)((L.tiles + mh::kUnbinWaves - 1) / mh::kUnbinWaves)), block(64u * mh::kUnbinWaves);
+    hipLaunchKernelGGL((mh::k_unbin_emit<FORM, CH>), grid, block, 0, st, in, row_off, cols, (uint32_t)L.tiles_per_row,
+                       rows * cols, (uint32_t)L.tiles, first_tick, period, base, out_ticks, static_cast<CH *>(out_ch), capacity,
+                       reinterpret_cast<unsigned long long *>(over));
 }
 
 }  // namespace
@@ -181,6 +216,97 @@ int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *s
                        reinterpret_cast<unsigned long long *>(bad));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_seg_crc32: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_unbin_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes)
+{
+    static_assert(mh::kUnbinCsr == MHI_UNBIN_CSR && mh::kUnbinAer == MHI_UNBIN_AER, "the header publishes the forms");
+    if (!bytes) return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: NULL pointer");
+    mh::UnbinLayout L;
+    const int rc = mh::unbin_layout(form, rows, cols, &L);
+    if (rc == -1)
+        return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: form=%u, rows=%llu, cols=%llu (a known form, each at least 1; AER form: cols <= 2^32)",
+                    form, (unsigned long long)rows, (unsigned long long)cols);
+    if (rc)
+        return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: rows=%llu, cols=%llu make more than 2^32 - 1 tiles",
+                    (unsigned long long)rows, (unsigned long long)cols);
+    *bytes = L.bytes;
+    return MH_OK;
+}
+
+int mhi_unbin_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
+                    uint64_t *ev_off, uint64_t *total, void *scratch, uint64_t scratch_bytes, void *stream)
+{
+    mh::UnbinLayout L;
+    const int rc = unbin_args("mhi_unbin_count", form, in, row_off, rows, cols, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (!total) return fail(MH_ERR_ARG, "mhi_unbin_count: NULL pointer");
+    if (form == mh::kUnbinCsr && !ev_off) return fail(MH_ERR_ARG, "mhi_unbin_count: the CSR form needs ev_off");
+    uint8_t *const s8 = static_cast<uint8_t *>(scratch);
+    uint32_t *const sums = reinterpret_cast<uint32_t *>(s8 + L.off_sum);
+    uint64_t *const base = reinterpret_cast<uint64_t *>(s8 + L.off_base);
+    uint64_t *const partial = reinterpret_cast<uint64_t *>(s8 + L.off_partial);
+    const uint32_t tiles = (uint32_t)L.tiles, tpr = (uint32_t)L.tiles_per_row;
+    const dim3 grid((unsigned)((L.tiles + mh::kUnbinWaves - 1) / mh::kUnbinWaves)), block(64u * mh::kUnbinWaves);
+    const dim3 groups((unsigned)L.groups), per_group(mh::kUnbinBaseThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (form == mh::kUnbinCsr)
+        hipLaunchKernelGGL(mh::k_unbin_count<mh::kUnbinCsr>, grid, block, 0, st, in, row_off, cols, tpr, rows * cols, tiles, sums);
+    else
+        hipLaunchKernelGGL(mh::k_unbin_count<mh::kUnbinAer>, grid, block, 0, st, in, row_off, cols, tpr, rows * cols, tiles, sums);
+    hipLaunchKernelGGL(mh::k_unbin_group_sum, groups, per_group, 0, st, sums, tiles, partial);
+    uint64_t *const offs = form == mh::kUnbinCsr ? ev_off : nullptr;
+    hipLaunchKernelGGL(mh::k_unbin_scan, dim3(1), dim3(mh::kUnbinScanThreads), 0, st, partial, L.groups, total, offs, rows);
+    hipLaunchKernelGGL(mh::k_unbin_bases, groups, per_group, 0, st, sums, tiles, partial, base, tpr, offs);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_unbin_count: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
+                   uint64_t origin, uint64_t period, uint64_t phase, uint64_t *out_ticks, void *out_ch, uint32_t ch_bits,
+                   uint64_t capacity, uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream)
+{
+    mh::UnbinLayout L;
+    const int rc = unbin_args("mhi_unbin_emit", form, in, row_off, rows, cols, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (!out_ticks || !over) return fail(MH_ERR_ARG, "mhi_unbin_emit: NULL pointer");
+    if (period == 0 || phase >= period)
+        return fail(MH_ERR_ARG, "mhi_unbin_emit: period=%llu, phase=%llu (period at least 1, phase below it)",
+                    (unsigned long long)period, (unsigned long long)phase);
+    const uint64_t steps = form == mh::kUnbinCsr ? cols : rows;
+    const unsigned __int128 last = (unsigned __int128)origin + (unsigned __int128)(steps - 1) * period + phase;
+    if (last >= ((unsigned __int128)1 << 63))
+        return fail(MH_ERR_ARG, "mhi_unbin_emit: the largest tick reaches 2^63 (origin=%llu, period=%llu, phase=%llu, %llu steps)",
+                    (unsigned long long)origin, (unsigned long long)period, (unsigned long long)phase,
+                    (unsigned long long)steps);
+    if (form == mh::kUnbinAer) {
+        if (!out_ch) return fail(MH_ERR_ARG, "mhi_unbin_emit: the AER form needs out_ch");
+        if (ch_bits != 16 && ch_bits != 32) return fail(MH_ERR_ARG, "mhi_unbin_emit: ch_bits=%u (16 or 32)", ch_bits);
+        if (ch_bits == 16 && cols > 65536)
+            return fail(MH_ERR_ARG, "mhi_unbin_emit: cols=%llu does not fit 16-bit channels", (unsigned long long)cols);
+    }
+    {   // out_ticks[0 .. capacity) against the input: the whole block in the AER form, where its extent is known here
+        const unsigned __int128 a = (uintptr_t)in, b = (uintptr_t)out_ticks;
+        const unsigned __int128 na = form == mh::kUnbinAer ? (unsigned __int128)rows * cols : 1, nb = (unsigned __int128)capacity * 8;
+        if (nb && a < b + nb && b < a + na) return fail(MH_ERR_ARG, "mhi_unbin_emit: out_ticks overlaps the input");
+    }
+    const uint8_t *const s8 = static_cast<const uint8_t *>(scratch);
+    const uint64_t *const base = reinterpret_cast<const uint64_t *>(s8 + L.off_base);
+    const uint64_t first_tick = origin + phase;
+    hipStream_t st = (hipStream_t)stream;
+    if (form == mh::kUnbinCsr)
+        unbin_emit_launch<mh::kUnbinCsr, uint32_t>(in, row_off, rows, cols, L, first_tick, period, base, out_ticks, nullptr, capacity,
+                                                   over, st);
+    else if (ch_bits == 16)
+        unbin_emit_launch<mh::kUnbinAer, uint16_t>(in, row_off, rows, cols, L, first_tick, period, base, out_ticks, out_ch, capacity,
+                                                   over, st);
+    else
+        unbin_emit_launch<mh::kUnbinAer, uint32_t>(in, row_off, rows, cols, L, first_tick, period, base, out_ticks, out_ch, capacity,
+                                                   over, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_unbin_emit: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

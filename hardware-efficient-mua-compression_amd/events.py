@@ -124,6 +124,85 @@ class EventSet:
             raise ValueError("channel index outside 0..%d" % (C - 1))
         return cls(out, meta[:C + 1].view(np.uint64), check=check, device=dev)
 
+    @classmethod
+    def from_counts(cls, x, origin=0, period=1, phase=0):
+        """The inverse of ChannelSet.from_events: every bin b of channel c with count k gives k events at the tick
+        origin + b*period + phase, expanded on the device (mhi_unbin_count / mhi_unbin_emit).  x: a container.ChannelSet whose
+        channels have one length (ValueError otherwise, as matrix() raises), or a 2-D uint8 device tensor [channels, bins]
+        with unit stride along its last axis and any row pitch or offset -- what decompress(..., start=, stop=) and
+        archive.Reader.read return.  Host arrays are not taken: there is no CPU path.  -> EventSet (host offsets; the ticks
+        are ordered by construction and are not checked again).  One synchronisation, for the number of events."""
+        from . import _ingest
+        if hasattr(x, "matrix") and hasattr(x, "ch_off"):
+            x = x.matrix()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("from_counts takes a ChannelSet or a device tensor: there is no CPU path")
+        if x.dtype != torch.uint8 or x.dim() != 2:
+            raise ValueError("counts are a 2-D uint8 tensor [channels, bins]")
+        rows, cols = int(x.shape[0]), int(x.shape[1])
+        if rows < 1 or cols < 1:
+            raise ValueError("at least one channel and one bin")
+        if cols > 1 and x.stride(1) != 1:
+            raise ValueError("the bins of a channel lie back to back (unit stride along the last axis)")
+        if rows > 1 and x.stride(0) < 0:
+            raise ValueError("the row pitch is not negative")
+        origin, period, phase = _tick_args(origin, period, phase, cols)
+        row_off = torch.arange(rows, dtype=torch.int64, device=x.device) * (int(x.stride(0)) if rows > 1 else 0)
+        ticks, _ch, off = _unbin(_ingest.UNBIN_CSR, x, row_off, rows, cols, origin, period, phase)
+        return cls(ticks, off, check=False, device=x.device)
+
+
+def _tick_args(origin, period, phase, steps):
+    origin, period, phase = int(origin), int(period), int(phase)
+    if origin < 0 or period < 1 or not 0 <= phase < period:
+        raise ValueError("origin >= 0, period >= 1 and 0 <= phase < period")
+    if origin + (int(steps) - 1) * period + phase >= 1 << 63:
+        raise ValueError("the largest tick reaches 2^63")
+    return origin, period, phase
+
+
+def _unbin(form, x, row_off, rows, cols, origin, period, phase, ch_dtype=None):
+    """count, ONE read of the total, emit -> (ticks int64 [total], channels or None, ev_off host uint64 [rows + 1] or None)"""
+    from . import _ingest
+    dev = x.device
+    with torch.cuda.device(dev):
+        csr = form == _ingest.UNBIN_CSR
+        meta = torch.zeros(rows + 3 if csr else 2, dtype=torch.int64, device=dev)   # [ev_off[0..rows],] total, over
+        ev_off, total, over = (meta[:rows + 1] if csr else None), meta[-2:-1], meta[-1:]
+        scratch = torch.empty(_ingest.unbin_scratch_bytes(form, rows, cols), dtype=torch.uint8, device=dev)
+        _ingest.unbin_count(form, x, row_off, rows, cols, ev_off, total, scratch)
+        host = meta.cpu().numpy()              # the one synchronisation: the output is sized by the total
+        n = int(host[-2])
+        ticks = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]      # a pointer also for an empty result
+        ch = None if csr else torch.empty(max(n, 1), dtype=ch_dtype, device=dev)[:n]
+        _ingest.unbin_emit(form, x, row_off, rows, cols, origin, period, phase, ticks, ch, over, scratch, capacity=n)
+        lost = int(over.item())
+        if lost:
+            raise RuntimeError("the counts changed between the two passes: %d events had no place" % lost)
+    return ticks, ch, (host[:rows + 1].view(np.uint64).copy() if csr else None)
+
+
+def aer_from_counts(block, origin=0, period=1, phase=0, ch_dtype=torch.int32):
+    """A time-major block of counts as one merged list of (tick, channel) pairs: element (t, c) with count k gives k pairs
+    (origin + t*period + phase, c), in time order and in channel order within a tick -- input for EventSet.from_aer and
+    archive.Writer.append_aer.  block: contiguous [T, C] uint8 device tensor.  ch_dtype: a 16- or 32-bit integer type
+    (16 bits hold C <= 65536).  -> (ticks int64, channels).  One synchronisation, for the number of pairs."""
+    from . import _ingest
+    if not (isinstance(block, torch.Tensor) and block.is_cuda):
+        raise ValueError("aer_from_counts takes a device tensor: there is no CPU path")
+    if block.dtype != torch.uint8 or block.dim() != 2 or not block.is_contiguous():
+        raise ValueError("counts are a contiguous 2-D uint8 tensor [time steps, channels]")
+    if ch_dtype not in (torch.int16, torch.uint16, torch.int32, torch.uint32):
+        raise ValueError("channels are 16- or 32-bit integers")
+    rows, cols = int(block.shape[0]), int(block.shape[1])
+    if rows < 1 or cols < 1:
+        raise ValueError("at least one time step and one channel")
+    if cols > (1 << 16) and ch_dtype in (torch.int16, torch.uint16):
+        raise ValueError("%d channels do not fit 16 bits" % cols)
+    origin, period, phase = _tick_args(origin, period, phase, rows)
+    ticks, ch, _off = _unbin(_ingest.UNBIN_AER, block, None, rows, cols, origin, period, phase, ch_dtype)
+    return ticks, ch
+
 
 def aer_time_slice(ticks, t0, t1):
     """(i0, i1): the pairs of a time-ordered 64-bit tick tensor with t0 <= tick < t1 are ticks[i0:i1] -- how a long

@@ -14,6 +14,9 @@
  * mhi_aer_to_csr brings such a list, resident on the device, into the per-channel form mhi_bin_events reads -- a stable
  * partition by channel (count, scan, scatter), not a sort -- so that no stage in front of the codec runs on the host.
  *
+ * And the way back: mhi_unbin_count / mhi_unbin_emit expand a matrix of counts -- a decoded recording -- into spike events
+ * again, per channel (the input of mhi_bin_events) or as one merged pair list (the input of mhi_aer_to_csr).
+ *
  * Neither a binner nor a checksum is a codec operation, so they are not part of muahuff.h: that ABI is closed.  The conventions are the
  * same: every function returns MH_OK or a negative MH_ERR_* code of muahuff.h and never throws, mhi_last_error()
  * returns a thread-local message for the last failure on this thread, every argument check comes before any device
@@ -102,6 +105,48 @@ int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits
 int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *seg_off, const uint64_t *seg_words,
                   uint64_t n_segments, const uint64_t *seg_idx, uint64_t n_idx, uint32_t *crc, const uint32_t *expect,
                   uint64_t *bad, void *stream);
+
+/* ---- counts back to events: the inverse of mhi_bin_events ------------------------------------------------------------
+ * A matrix of uint8 counts is walked in row-major order and element (i, j) with count k emits k entries, in two passes
+ * with ONE read of a number between them: mhi_unbin_count writes total[0], the caller sizes the output from it, and
+ * mhi_unbin_emit stores the events.  Any count up to 255 is expanded.
+ * MHI_UNBIN_CSR: rows are channels, columns are bins.  Row i is the cols bytes at in + row_off[i] (row_off: device,
+ *   rows entries, bytes; rows may start at ANY byte address and no byte outside a row is read).  An event of element
+ *   (i, j) is the tick origin + j*period + phase; ev_off[0 .. rows] receives the rows' offsets, and (out_ticks, ev_off)
+ *   is the input of mhi_bin_events.  out_ch and ch_bits are not used.
+ * MHI_UNBIN_AER: rows are time steps, columns are channels, in = one contiguous [rows, cols] block, row_off = NULL.
+ *   An event of element (i, j) is the pair (origin + i*period + phase, j): the tick goes to out_ticks, the channel to
+ *   out_ch in ch_bits = 16 or 32 bits (16 needs cols <= 65536).  The list is in time order and in channel order within
+ *   a tick: input for mhi_aer_to_csr.  ev_off is not used and may be NULL.
+ * period >= 1, phase < period, rows >= 1, cols >= 1 (AER: cols <= 2^32), and the largest tick -- origin + (cols - 1) *
+ * period + phase, with rows - 1 in the AER form -- is below 2^63.  The input is cut into tiles of 16 KiB (a CSR row
+ * into ceil(cols / 16384) of them); more than 2^32 - 1 tiles are refused.
+ * scratch: device, 16-byte aligned, at least mhi_unbin_scratch_bytes(form, rows, cols) bytes; it need not be zeroed,
+ * and every cell of it that is read was written by the same mhi_unbin_count, so that calls chain on one scratch.
+ * All three return MH_ERR_ARG, before any device work, for a NULL pointer that is used, an unknown form, a row_off that
+ * does not fit the form, and any breach of the rules above.
+ * count and emit only enqueue on `stream`: no synchronisation, allocation or free, so they can be captured into a
+ * hipGraph. */
+#define MHI_UNBIN_CSR 0u
+#define MHI_UNBIN_AER 1u
+
+/* Bytes of scratch for (form, rows, cols).  Host arithmetic only: no device is needed or touched.  Never 0. */
+int mhi_unbin_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes);
+
+/* First pass: total[0] = the number of events (device, 1 entry); CSR form: ev_off[0 .. rows] (device) as well.
+ * Leaves the 64-bit output base of every tile in the scratch for mhi_unbin_emit. */
+int mhi_unbin_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
+                    uint64_t *ev_off, uint64_t *total, void *scratch, uint64_t scratch_bytes, void *stream);
+
+/* Second pass, on the SAME (form, in, row_off, rows, cols, scratch) as the count before it: out_ticks[0 .. total) and,
+ * in the AER form, out_ch[0 .. total).  capacity: the entries out_ticks (and out_ch) hold.  Nothing is ever stored at or
+ * behind index capacity, whatever the input holds by then: the events that could not be stored are added to over[0]
+ * (device, 1 entry, zeroed by the caller) -- with capacity >= total and an unchanged input over stays 0, every entry
+ * below total is written and nothing else.  With total == 0 nothing is written.  out_ticks[0 .. capacity) must not
+ * overlap the input. */
+int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
+                   uint64_t origin, uint64_t period, uint64_t phase, uint64_t *out_ticks, void *out_ch, uint32_t ch_bits,
+                   uint64_t capacity, uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
