@@ -16,6 +16,7 @@
 #include "mh_codec2.hpp"
 #include "mh_layout.hpp"
 #include "mh_packed_measure.hpp"
+#include "mh_plan_arena.hpp"
 #include "mh_planner.hpp"
 #include "mh_range.hpp"
 #include "mh_rebin_decode.hpp"
@@ -48,21 +49,34 @@ int fail(int code, const char *fmt, ...)
                         __FILE__, __LINE__);                                                 \
     } while (0)
 
-template <typename T>
-int upload(T **dst, const std::vector<T> &src)
-{
-    const size_t bytes = (src.size() ? src.size() : 1) * sizeof(T);
-    MH_HIP(hipMalloc(reinterpret_cast<void **>(dst), bytes));
-    if (src.size()) MH_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MH_OK;
-}
+static_assert(mh::kArenaHistSlots == mh::kHistStride && mh::kArenaLutEntries == mh::kLut && sizeof(uint2) == 8 &&
+                  mh::kArenaScanBlock == mh::kScanBlock,
+              "mh_plan_arena.hpp sizes the scratch regions by the kernels' constants");
 
-template <typename T>
-int alloc(T **dst, size_t n)
-{
-    MH_HIP(hipMalloc(reinterpret_cast<void **>(dst), (n ? n : 1) * sizeof(T)));
-    return MH_OK;
-}
+// The one device allocation of a plan or a sweep handle, laid out by mh_plan_arena.hpp: the tables part uploaded in
+// one copy, the scratch part behind it zeroed.  Synchronises.  Freed with the handle, a half-created one included.
+struct DeviceArena {
+    uint8_t *base = nullptr;
+
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena &) = delete;
+    DeviceArena &operator=(const DeviceArena &) = delete;
+    ~DeviceArena() { (void)hipFree(base); }
+    int create(const mh::Arena &a)
+    {
+        MH_HIP(hipMalloc(reinterpret_cast<void **>(&base), a.bytes()));
+        MH_HIP(hipMemcpy(base, a.tables.get(), a.tables_bytes, hipMemcpyHostToDevice));
+        MH_HIP(hipMemset(base + a.tables_bytes, 0, a.scratch_bytes));
+        MH_HIP(hipStreamSynchronize(nullptr));
+        return MH_OK;
+    }
+    // the typed view of a region (null where the layout leaves it out)
+    template <class T>
+    void view(T *&d, const mh::Region &r) const
+    {
+        d = r.present ? reinterpret_cast<T *>(base + r.off) : nullptr;
+    }
+};
 
 }  // namespace
 
@@ -76,6 +90,10 @@ struct ListCache {
     uint8_t *d_list = nullptr, *d_aux = nullptr;  // w.blob; the list's w.naux scratch slots / side words
     size_t cap = 0, aux_cap = 0;
 
+    ListCache() = default;
+    ListCache(const ListCache &) = delete;
+    ListCache &operator=(const ListCache &) = delete;
+    ~ListCache() { (void)hipFree(d_list), (void)hipFree(d_aux); }
     bool same_query(const uint32_t *s, uint32_t n, uint64_t a, uint64_t b, uint32_t r_, uint64_t pitch_) const
     {
         return t0 == a && t1 == b && r == r_ && pitch == pitch_ && sel.size() == n && std::equal(s, s + n, sel.begin());
@@ -95,6 +113,7 @@ struct Kernel {
 struct mh_plan {
     int device = 0;
     mh::PlanHost h;  // everything the planner computed (host copies)
+    DeviceArena arena;  // ALL the plan owns on the device but the two work lists; the d_* below are views into it (plan_upload)
     // device tables
     uint64_t *d_ch_off = nullptr, *d_ch_len = nullptr, *d_w0 = nullptr, *d_w1 = nullptr;
     uint8_t *d_skip = nullptr, *d_sclv = nullptr;
@@ -130,10 +149,18 @@ struct mh_sweep {
     uint32_t C = 0, nh = 0, ni = 0;
     std::vector<uint64_t> bounds;  // C * (ni + 1), sorted per channel
     uint64_t n_tiles = 0, n_slots = 0;
+    // views into the arena
     uint64_t *d_ch_off = nullptr, *d_tile_start = nullptr, *d_slot_len = nullptr;
     uint32_t *d_tile_ch = nullptr, *d_tile_n = nullptr, *d_tile_slot = nullptr;
     unsigned long long *d_scratch = nullptr;
+    DeviceArena arena;  // what the d_* above point into
 };
+
+// chunk_stride of `bits`-bit pieces: 0 (contiguous), or packed input only, a multiple of 16, at least one chunk
+static bool chunk_stride_ok(uint64_t chunk_stride, uint32_t bits)
+{
+    return !chunk_stride || (bits != 8 && chunk_stride % 16 == 0 && chunk_stride >= (uint64_t)MH_CHUNK * bits / 8);
+}
 
 // device operations run on the plan's device: its tables live there
 static int check_device(int device, const char *who)
@@ -175,6 +202,20 @@ static mh::CalArgs calibrate_args(const mh_plan *p, const uint8_t *data, uint64_
     return a;
 }
 
+static mh::HistArgs hist_args(const uint8_t *data, const uint64_t *ch_off, const uint32_t *tile_ch, const uint64_t *tile_start,
+                              const uint32_t *tile_n, unsigned long long *hist, const uint32_t *tile_slot)
+{
+    mh::HistArgs a{};
+    a.data = data;
+    a.ch_off = ch_off;
+    a.tile_ch = tile_ch;
+    a.tile_start = tile_start;
+    a.tile_n = tile_n;
+    a.hist = hist;
+    a.tile_slot = tile_slot;
+    return a;
+}
+
 static int launch_calibrate(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_hist,
                             uint8_t *peak, uint8_t *enc, hipStream_t st, unsigned long long *zero_hist,
                             unsigned long long *zero_bits, uint8_t *skip_dst)
@@ -183,14 +224,7 @@ static int launch_calibrate(mh_plan *p, const uint8_t *data, uint64_t *cutoff, u
     mh::CalArgs a = calibrate_args(p, data, cutoff, cal_hist, peak, enc, zero_hist, zero_bits, skip_dst);
     if (!p->h.cal_tile_ch.empty()) {  // long calibration windows (2^h > kCalDirect): tiled histogram first
         MH_HIP(hipMemsetAsync(p->d_calhist, 0, (size_t)a.C * mh::kHistStride * sizeof(unsigned long long), st));
-        mh::HistArgs ha{};
-        ha.data = data;
-        ha.ch_off = p->d_ch_off;
-        ha.tile_ch = p->d_cal_tile_ch;
-        ha.tile_start = p->d_cal_tile_start;
-        ha.tile_n = p->d_cal_tile_n;
-        ha.hist = p->d_calhist;
-        ha.tile_slot = nullptr;
+        const mh::HistArgs ha = hist_args(data, p->d_ch_off, p->d_cal_tile_ch, p->d_cal_tile_start, p->d_cal_tile_n, p->d_calhist, nullptr);
         hipLaunchKernelGGL(mh::k_hist2<4>, dim3((unsigned)p->h.cal_tile_ch.size()), dim3(256), 0, st, ha, I.S);
         a.pre_hist = p->d_calhist;
     }
@@ -399,67 +433,25 @@ int mh_approx_sort_perm(int S, int peak, uint8_t *idx)
 
 int mh_plan_destroy(mh_plan *p)
 {
-    if (!p) return MH_OK;
-    void *ptrs[] = {p->d_ch_off, p->d_ch_len, p->d_w0, p->d_w1, p->d_skip, p->d_sclv, p->d_sclv16, p->d_tile_cnt,
-                    p->d_tile_done, p->d_codes,
-                    p->d_seg_ch, p->d_seg_first, p->d_seg_n, p->d_seg_off, p->d_tile_ch,
-                    p->d_tile_n, p->d_tile_start, p->d_hist, p->d_peak, p->d_enc,
-                    p->d_lut, p->d_wg_tasks, p->d_wave_tasks, p->d_scan,
-                    p->d_cal_tile_ch, p->d_cal_tile_n, p->d_cal_tile_start, p->d_calhist, p->d_err, p->d_acc,
-                    p->range.d_list, p->range.d_aux, p->rebin.d_list, p->rebin.d_aux};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    delete p;
+    delete p;  // (the arena and the work-list caches free what they hold)
     return MH_OK;
 }
 
-// device side of plan creation: upload the planner's tables, allocate the per-channel scratch
+// device side of plan creation: the arena (mh_plan_arena.hpp) and the views into it
 static int plan_upload(mh_plan *p)
 {
-    const mh::PlanHost &H = p->h;
-    const uint32_t C = H.info.C;
-    const bool cal = !H.cal_tile_ch.empty();
-    int rc;
-    std::vector<uint32_t> rows16((size_t)H.info.K * 4, 0u);
-    for (uint32_t k = 0; k < H.info.K; ++k)
-        for (uint32_t r = 0; r < H.info.S; ++r)
-            rows16[(size_t)k * 4 + (r >> 2)] |= (uint32_t)H.sclv[(size_t)k * H.info.S + r] << (8 * (r & 3));
-    if ((rc = upload(&p->d_sclv16, rows16)) || (rc = upload(&p->d_tile_cnt, H.tile_cnt)) || (rc = alloc(&p->d_tile_done, C))) return rc;
-    if ((rc = upload(&p->d_ch_off, H.ch_off)) || (rc = upload(&p->d_ch_len, H.ch_len)) ||
-        (rc = upload(&p->d_w0, H.w0)) || (rc = upload(&p->d_w1, H.w1)) || (rc = upload(&p->d_skip, H.skip)) ||
-        (rc = upload(&p->d_sclv, H.sclv)) || (rc = upload(&p->d_codes, H.codes)) ||
-        (rc = upload(&p->d_seg_ch, H.seg_ch)) || (rc = upload(&p->d_seg_first, H.seg_first)) ||
-        (rc = upload(&p->d_seg_n, H.seg_n)) || (rc = upload(&p->d_seg_off, H.seg_off)) ||
-        (rc = upload(&p->d_tile_ch, H.tile_ch)) || (rc = upload(&p->d_tile_n, H.tile_n)) ||
-        (rc = upload(&p->d_tile_start, H.tile_start)) ||
-        (rc = alloc(&p->d_hist, (size_t)C * mh::kHistStride)) || (rc = alloc(&p->d_peak, C)) ||
-        (rc = alloc(&p->d_enc, C)) || (rc = alloc(&p->d_lut, (size_t)C * mh::kLut)) ||
-        (rc = upload(&p->d_wg_tasks, H.wg_tasks)) ||
-        (H.use_wave_tasks && (rc = upload(&p->d_wave_tasks, H.wave_tasks))) ||
-        (rc = alloc(&p->d_scan, H.seg_ch.size() / mh::kScanBlock + 2)) || (rc = upload(&p->d_err, std::vector<uint32_t>(1, 0u))) ||
-        (H.use_wave_tasks && (rc = upload(&p->d_acc, std::vector<unsigned long long>(C, 0ull)))) ||
-        (cal && ((rc = upload(&p->d_cal_tile_ch, H.cal_tile_ch)) || (rc = upload(&p->d_cal_tile_n, H.cal_tile_n)) ||
-                 (rc = upload(&p->d_cal_tile_start, H.cal_tile_start)) ||
-                 (rc = alloc(&p->d_calhist, (size_t)C * mh::kHistStride)))))
-        return rc;
-    if (H.input_bits != 8) {
-        // mh_measure on packed pieces histograms EVERY calibration window with the tiled kernel: the planner's tiles
-        // above kCalDirect samples, else one tile per channel, built here (the planner's lists stay what byte plans use)
-        p->packed_cal_tiles = H.cal_tile_ch.size();
-        if (!cal) {
-            std::vector<uint32_t> tch(C), tn(C);
-            const std::vector<uint64_t> tstart(C, 0);
-            const uint64_t lim = (uint64_t)1 << H.info.h;
-            for (uint32_t c = 0; c < C; ++c) {
-                tch[c] = c;
-                tn[c] = (uint32_t)(H.ch_len[c] < lim ? H.ch_len[c] : lim);
-            }
-            if ((rc = upload(&p->d_cal_tile_ch, tch)) || (rc = upload(&p->d_cal_tile_n, tn)) ||
-                (rc = upload(&p->d_cal_tile_start, tstart)) || (rc = alloc(&p->d_calhist, (size_t)C * mh::kHistStride)))
-                return rc;
-            p->packed_cal_tiles = C;
-        }
-    }
+    const mh::PlanArena a = mh::plan_arena(p->h);
+    if (int rc = p->arena.create(a)) return rc;
+    const DeviceArena &d = p->arena;
+    d.view(p->d_sclv16, a.sclv16), d.view(p->d_tile_cnt, a.tile_cnt), d.view(p->d_ch_off, a.ch_off), d.view(p->d_ch_len, a.ch_len);
+    d.view(p->d_w0, a.w0), d.view(p->d_w1, a.w1), d.view(p->d_skip, a.skip), d.view(p->d_sclv, a.sclv), d.view(p->d_codes, a.codes);
+    d.view(p->d_seg_ch, a.seg_ch), d.view(p->d_seg_first, a.seg_first), d.view(p->d_seg_n, a.seg_n), d.view(p->d_seg_off, a.seg_off);
+    d.view(p->d_tile_ch, a.tile_ch), d.view(p->d_tile_n, a.tile_n), d.view(p->d_tile_start, a.tile_start);
+    d.view(p->d_wg_tasks, a.wg_tasks), d.view(p->d_wave_tasks, a.wave_tasks);
+    d.view(p->d_cal_tile_ch, a.cal_tile_ch), d.view(p->d_cal_tile_n, a.cal_tile_n), d.view(p->d_cal_tile_start, a.cal_tile_start);
+    d.view(p->d_tile_done, a.tile_done), d.view(p->d_hist, a.hist), d.view(p->d_peak, a.peak), d.view(p->d_enc, a.enc);
+    d.view(p->d_lut, a.lut), d.view(p->d_scan, a.scan), d.view(p->d_err, a.err), d.view(p->d_acc, a.acc), d.view(p->d_calhist, a.calhist);
+    if (p->h.input_bits != 8) p->packed_cal_tiles = a.n_cal_tiles;
     return MH_OK;
 }
 
@@ -484,6 +476,15 @@ static int plan_args(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h,
     return MH_OK;
 }
 
+// the first n entries of the directory, into those of the four arrays the caller asked for
+static void copy_segments(const mh::PlanHost &H, size_t n, uint32_t *seg_ch, uint64_t *seg_first, uint64_t *seg_n, uint64_t *seg_off)
+{
+    if (seg_ch && n) memcpy(seg_ch, H.seg_ch.data(), n * sizeof(uint32_t));
+    if (seg_first && n) memcpy(seg_first, H.seg_first.data(), n * sizeof(uint64_t));
+    if (seg_n && n) memcpy(seg_n, H.seg_n.data(), n * sizeof(uint64_t));
+    if (seg_off && n) memcpy(seg_off, H.seg_off.data(), n * sizeof(uint64_t));
+}
+
 int mh_plan_query(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
                   const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, mh_plan_info_t *info, uint32_t *seg_ch,
                   uint64_t *seg_first, uint64_t *seg_n, uint64_t *seg_off, uint64_t seg_cap)
@@ -494,11 +495,7 @@ int mh_plan_query(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, ui
     std::vector<uint64_t> off(C, 0);  // offsets do not enter the directory
     mh::plan_host_build(H, off.data(), ch_len, sclv);
     *info = H.info;
-    const size_t n = H.seg_ch.size() < seg_cap ? H.seg_ch.size() : (size_t)seg_cap;
-    if (seg_ch && n) memcpy(seg_ch, H.seg_ch.data(), n * sizeof(uint32_t));
-    if (seg_first && n) memcpy(seg_first, H.seg_first.data(), n * sizeof(uint64_t));
-    if (seg_n && n) memcpy(seg_n, H.seg_n.data(), n * sizeof(uint64_t));
-    if (seg_off && n) memcpy(seg_off, H.seg_off.data(), n * sizeof(uint64_t));
+    copy_segments(H, H.seg_ch.size() < seg_cap ? H.seg_ch.size() : (size_t)seg_cap, seg_ch, seg_first, seg_n, seg_off);
     return MH_OK;
 }
 
@@ -520,7 +517,7 @@ int mh_plan_create_packed(mh_plan **plan, const uint64_t *ch_off, const uint64_t
     if (input_bits != 8 && (window & ~MH_WIN_REV2_SEGMENTS) != MH_WIN_FULL)
         return fail(MH_ERR_ARG, "packed input needs the whole-channel window (MH_WIN_FULL)");
     if (input_bits == 2 && S > 4) return fail(MH_ERR_ARG, "2-bit input holds symbols 0..3: S=%u is above 4", S);
-    if (chunk_stride && (input_bits == 8 || chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * input_bits / 8))
+    if (!chunk_stride_ok(chunk_stride, input_bits))
         return fail(MH_ERR_ARG, "chunk_stride=%llu: packed input only, a multiple of 16, at least one chunk",
                     (unsigned long long)chunk_stride);
     mh_plan_info_t I;
@@ -542,9 +539,6 @@ int mh_plan_create_packed(mh_plan **plan, const uint64_t *ch_off, const uint64_t
         return fail(MH_ERR_ARG, "mh_plan_create: %zu segments exceed the 32-bit directory", nseg);
     }
     int rc = plan_upload(p);
-    if (rc == MH_OK && (hipMemset(p->d_hist, 0, (size_t)I.C * mh::kHistStride * sizeof(unsigned long long)) != hipSuccess ||
-                        hipMemset(p->d_tile_done, 0, (size_t)I.C * sizeof(uint32_t)) != hipSuccess))
-        rc = fail(MH_ERR_HIP, "mh_plan_create: clearing the measure scratch failed");
     if (rc == MH_OK) rc = resolve_kernels(p);
     if (rc != MH_OK) {
         mh_plan_destroy(p);
@@ -565,11 +559,7 @@ int mh_plan_segments(const mh_plan *plan, uint32_t *seg_ch, uint64_t *seg_first,
                      uint64_t *seg_off)
 {
     if (!plan) return fail(MH_ERR_ARG, "mh_plan_segments: NULL plan");
-    const size_t n = plan->h.seg_ch.size();
-    if (seg_ch && n) memcpy(seg_ch, plan->h.seg_ch.data(), n * sizeof(uint32_t));
-    if (seg_first && n) memcpy(seg_first, plan->h.seg_first.data(), n * sizeof(uint64_t));
-    if (seg_n && n) memcpy(seg_n, plan->h.seg_n.data(), n * sizeof(uint64_t));
-    if (seg_off && n) memcpy(seg_off, plan->h.seg_off.data(), n * sizeof(uint64_t));
+    copy_segments(plan->h, plan->h.seg_ch.size(), seg_ch, seg_first, seg_n, seg_off);
     return MH_OK;
 }
 
@@ -620,14 +610,7 @@ int mh_measure(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_
         if (rc) return rc;
     }
     if (!p->h.tile_ch.empty()) {
-        mh::HistArgs a{};
-        a.data = data;
-        a.ch_off = p->d_ch_off;
-        a.tile_ch = p->d_tile_ch;
-        a.tile_start = p->d_tile_start;
-        a.tile_n = p->d_tile_n;
-        a.hist = p->d_hist;
-        a.tile_slot = nullptr;
+        mh::HistArgs a = hist_args(data, p->d_ch_off, p->d_tile_ch, p->d_tile_start, p->d_tile_n, p->d_hist, nullptr);
         if (fused) {
             a.tile_cnt = p->d_tile_cnt;
             a.tile_done = p->d_tile_done;
@@ -649,6 +632,15 @@ int mh_measure(mh_plan *p, const uint8_t *data, uint64_t *cutoff, uint32_t *cal_
     if (fused) return MH_OK;
     hipLaunchKernelGGL(mh::k_finalize, dim3((f.C + 255) / 256), dim3(256), 0, st, f);
     MH_HIP(hipGetLastError());
+    return MH_OK;
+}
+
+static int check_payload_cap(const mh_plan *p, uint64_t payload_cap_words)
+{
+    if (payload_cap_words < p->h.info.payload_cap_words)
+        return fail(MH_ERR_CAPACITY, "payload buffer holds %llu words, plan needs %llu",
+                    (unsigned long long)payload_cap_words,
+                    (unsigned long long)p->h.info.payload_cap_words);
     return MH_OK;
 }
 
@@ -700,10 +692,7 @@ int mh_encode(mh_plan *p, const uint8_t *data, uint32_t *payload, uint64_t paylo
         return fail(MH_ERR_ARG, "mh_encode: NULL argument");
     if (p->h.input_bits != 8) return fail(MH_ERR_ARG, "mh_encode: this plan reads packed pieces (mh_encode_preset only)");
     if (int rc_ = check_device(p->device, "mh_encode")) return rc_;
-    if (payload_cap_words < p->h.info.payload_cap_words)
-        return fail(MH_ERR_CAPACITY, "payload buffer holds %llu words, plan needs %llu",
-                    (unsigned long long)payload_cap_words,
-                    (unsigned long long)p->h.info.payload_cap_words);
+    if (int rc_ = check_payload_cap(p, payload_cap_words)) return rc_;
     hipStream_t st = (hipStream_t)stream;
     if (p->h.fused_calibration && p->h.tickets_fit)  // short channels: every wave calibrates its own channel, one launch in all
         return encode_common(p, data, payload, seg_words, ch_bits, 1u, nullptr, nullptr, peak, enc, skipped, st);
@@ -721,10 +710,7 @@ int mh_encode_preset(mh_plan *p, const uint8_t *data, const uint8_t *peak, const
     if (!p || !data || !peak || !enc || !payload || !seg_words || !ch_bits)
         return fail(MH_ERR_ARG, "mh_encode_preset: NULL argument");
     if (int rc_ = check_device(p->device, "mh_encode_preset")) return rc_;
-    if (payload_cap_words < p->h.info.payload_cap_words)
-        return fail(MH_ERR_CAPACITY, "payload buffer holds %llu words, plan needs %llu",
-                    (unsigned long long)payload_cap_words,
-                    (unsigned long long)p->h.info.payload_cap_words);
+    if (int rc_ = check_payload_cap(p, payload_cap_words)) return rc_;
     hipStream_t st = (hipStream_t)stream;
     if (p->h.use_wave_tasks && p->h.tickets_fit)  // the waves build their tables from the preset word themselves: one launch
         return encode_common(p, data, payload, seg_words, ch_bits, 2u, peak, enc, nullptr, nullptr, nullptr, st);
@@ -1154,17 +1140,27 @@ int mh_rebin(const uint8_t *data, const uint64_t *in_off, const uint64_t *in_len
     return MH_OK;
 }
 
+// The grid of the transposing kernels over T x C with tpw tiles of a strip per workgroup visit: strips of kTr2C
+// channels times visits, in one grid dimension (strip fastest), the visits capped so that the product fits 31 bits.
+static int transposed_grid(const char *who, uint64_t T, uint32_t C, uint32_t tpw, unsigned *grid)
+{
+    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
+    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
+    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;
+    if (by > 65535) return fail(MH_ERR_ARG, "%s: C=%u too large", who, C);
+    *grid = (unsigned)(bx * by);
+    return MH_OK;
+}
+
 int mh_deinterleave(const uint8_t *in, uint64_t T, uint32_t C, uint8_t *out, const uint64_t *out_off,
                     void *stream)
 {
     if (!in || !out || !out_off || C == 0) return fail(MH_ERR_ARG, "mh_deinterleave: bad argument");
     if (T == 0) return MH_OK;
     const uint32_t tpw = 4;
-    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
-    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
-    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
-    if (by > 65535) return fail(MH_ERR_ARG, "mh_deinterleave: C=%u too large", C);
-    hipLaunchKernelGGL(mh::k_deinterleave2, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
+    unsigned grid;
+    if (int rc_ = transposed_grid("mh_deinterleave", T, C, tpw, &grid)) return rc_;
+    hipLaunchKernelGGL(mh::k_deinterleave2, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
                        out, out_off);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1175,21 +1171,19 @@ int mh_deinterleave_packed(const uint8_t *in, uint64_t T, uint32_t C, uint32_t b
 {
     if (!in || !out || !out_off || C == 0) return fail(MH_ERR_ARG, "mh_deinterleave_packed: bad argument");
     if (bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mh_deinterleave_packed: bits=%u (4 or 2)", bits);
-    if (chunk_stride && (chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * bits / 8))
+    if (!chunk_stride_ok(chunk_stride, bits))
         return fail(MH_ERR_ARG, "mh_deinterleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
     if (T == 0) return MH_OK;
     const uint32_t tpw = bits == 2 ? (uint32_t)mh::P2<2>::kTpw : (uint32_t)mh::P2<4>::kTpw;  // tiles of a visit held in LDS
-    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
-    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
-    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
-    if (by > 65535) return fail(MH_ERR_ARG, "mh_deinterleave_packed: C=%u too large", C);
+    unsigned grid;
+    if (int rc_ = transposed_grid("mh_deinterleave_packed", T, C, tpw, &grid)) return rc_;
     // pieces that fit the Infinity Cache (256 MiB) stay cacheable for the encoder that reads them next
     const uint32_t cached = (double)T * C * bits / 8.0 <= 192.0 * 1048576.0 ? 1u : 0u;
     if (bits == 4)
-        hipLaunchKernelGGL(mh::k_deinterleave_p<4>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
+        hipLaunchKernelGGL(mh::k_deinterleave_p<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
                            out, out_off, chunk_stride, cached);
     else
-        hipLaunchKernelGGL(mh::k_deinterleave_p<2>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
+        hipLaunchKernelGGL(mh::k_deinterleave_p<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, T, C, tpw,
                            out, out_off, chunk_stride, cached);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1200,11 +1194,9 @@ int mh_interleave(const uint8_t *in, const uint64_t *in_off, uint64_t T, uint32_
     if (!in || !in_off || !out || C == 0) return fail(MH_ERR_ARG, "mh_interleave: bad argument");
     if (T == 0) return MH_OK;
     const uint32_t tpw = 4;
-    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
-    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
-    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
-    if (by > 65535) return fail(MH_ERR_ARG, "mh_interleave: C=%u too large", C);
-    hipLaunchKernelGGL(mh::k_interleave, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T, C,
+    unsigned grid;
+    if (int rc_ = transposed_grid("mh_interleave", T, C, tpw, &grid)) return rc_;
+    hipLaunchKernelGGL(mh::k_interleave, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, in_off, T, C,
                        tpw, out);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1215,20 +1207,18 @@ int mh_interleave_packed(const uint8_t *in, const uint64_t *in_off, uint64_t T, 
 {
     if (!in || !in_off || !out || C == 0) return fail(MH_ERR_ARG, "mh_interleave_packed: bad argument");
     if (bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mh_interleave_packed: bits=%u (4 or 2)", bits);
-    if (chunk_stride && (chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * bits / 8))
+    if (!chunk_stride_ok(chunk_stride, bits))
         return fail(MH_ERR_ARG, "mh_interleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
     if (T == 0) return MH_OK;
     const uint32_t tpw = 4;
-    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
-    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
-    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;  // one grid dimension: strip fastest
-    if (by > 65535) return fail(MH_ERR_ARG, "mh_interleave_packed: C=%u too large", C);
+    unsigned grid;
+    if (int rc_ = transposed_grid("mh_interleave_packed", T, C, tpw, &grid)) return rc_;
     const uint32_t nt = 1u;  // non-temporal row stores, as k_interleave (profiles/r04_stream_decode.txt)
     if (bits == 4)
-        hipLaunchKernelGGL(mh::k_interleave_p<4>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
+        hipLaunchKernelGGL(mh::k_interleave_p<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
                            C, tpw, chunk_stride, nt, out);
     else
-        hipLaunchKernelGGL(mh::k_interleave_p<2>, dim3((unsigned)(bx * by)), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
+        hipLaunchKernelGGL(mh::k_interleave_p<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, in_off, T,
                            C, tpw, chunk_stride, nt, out);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1236,11 +1226,6 @@ int mh_interleave_packed(const uint8_t *in, const uint64_t *in_off, uint64_t T, 
 
 int mh_sweep_destroy(mh_sweep *w)
 {
-    if (!w) return MH_OK;
-    void *ptrs[] = {w->d_ch_off, w->d_tile_start, w->d_slot_len, w->d_tile_ch, w->d_tile_n, w->d_tile_slot,
-                    w->d_scratch};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
     delete w;
     return MH_OK;
 }
@@ -1303,14 +1288,14 @@ int mh_sweep_create(mh_sweep **sweep, const uint64_t *ch_off, const uint64_t *ch
     }
     w->n_tiles = tile_ch.size();
     w->n_slots = (uint64_t)C * w->ni;
-    int rc;
-    if ((rc = upload(&w->d_ch_off, off)) || (rc = upload(&w->d_tile_ch, tile_ch)) ||
-        (rc = upload(&w->d_tile_n, tile_n)) || (rc = upload(&w->d_tile_slot, tile_slot)) ||
-        (rc = upload(&w->d_tile_start, tile_start)) || (rc = upload(&w->d_slot_len, slot_len)) ||
-        (rc = alloc(&w->d_scratch, (size_t)w->n_slots * mh::kHistStride))) {
+    const mh::SweepArena a = mh::sweep_arena(off, tile_ch, tile_n, tile_slot, tile_start, slot_len);
+    if (int rc = w->arena.create(a)) {
         mh_sweep_destroy(w);
         return rc;
     }
+    const DeviceArena &d = w->arena;
+    d.view(w->d_ch_off, a.ch_off), d.view(w->d_tile_ch, a.tile_ch), d.view(w->d_tile_n, a.tile_n), d.view(w->d_tile_slot, a.tile_slot);
+    d.view(w->d_tile_start, a.tile_start), d.view(w->d_slot_len, a.slot_len), d.view(w->d_scratch, a.hist);
     *sweep = w;
     return MH_OK;
 }
@@ -1330,14 +1315,7 @@ int mh_sweep_run(mh_sweep *w, const uint8_t *data, uint64_t *hist, void *stream)
     hipStream_t st = (hipStream_t)stream;
     MH_HIP(hipMemsetAsync(w->d_scratch, 0, (size_t)w->n_slots * mh::kHistStride * sizeof(unsigned long long), st));
     if (w->n_tiles) {
-        mh::HistArgs a{};
-        a.data = data;
-        a.ch_off = w->d_ch_off;
-        a.tile_ch = w->d_tile_ch;
-        a.tile_start = w->d_tile_start;
-        a.tile_n = w->d_tile_n;
-        a.hist = w->d_scratch;
-        a.tile_slot = w->d_tile_slot;
+        const mh::HistArgs a = hist_args(data, w->d_ch_off, w->d_tile_ch, w->d_tile_start, w->d_tile_n, w->d_scratch, w->d_tile_slot);
         hipLaunchKernelGGL(mh::k_hist2<4>, dim3((unsigned)w->n_tiles), dim3(256), 0, st, a, (uint32_t)MH_SWEEP_BINS);
         MH_HIP(hipGetLastError());
     }

@@ -17,11 +17,18 @@
 // csrc/mh_worklist.hpp as the library builds them.  Output: "D nseg" and the directory's ch / first / n lines, then per
 // query "L ntask nwg nfix nfill naux max_fill" + the blob offsets of the workgroup, fix and fill sections + its size,
 // and one line per record: T (task fields in struct order, without padding), W task0 ntask ch, X off slot, F off n.
+// With --arena (tests/test_planner_sanitized.py) the --cells input gives the device layout of the plan (csrc/mh_plan_arena.hpp,
+// what mh_plan_create allocates and uploads): "A tables_bytes scratch_bytes nregions", one line "R name part present off
+// bytes elems elem_size" per region (part T or S; elems: what PlanHost and the plan's form say the region holds, counted
+// here and not by the header), "K" + the staged 16-byte SCLV rows as words, and "P n" + n lines "ch start n" of the
+// staged calibration tiles where the header builds them (a packed plan without planner tiles; n = 0 otherwise).  The
+// staged blob is compared with the planner's vectors byte for byte here.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "mh_plan_arena.hpp"
 #include "mh_planner.hpp"
 #include "mh_select.hpp"
 #include "mh_worklist.hpp"
@@ -183,8 +190,81 @@ static int worklist()
     return got < 0;
 }
 
+// the staged bytes of a table equal the vector it was laid out from
+template <class T>
+static bool staged(const mh::Arena &a, const mh::Region &r, const std::vector<T> &v)
+{
+    return r.present && r.bytes == v.size() * sizeof(T) && r.off + r.bytes <= a.tables_bytes &&
+           (v.empty() || !memcmp(a.tables.get() + r.off, v.data(), r.bytes));
+}
+
+static int arena()
+{
+    mh::PlanHost p;
+    int got;
+    while ((got = read_plan(true, p)) > 0) {
+        if (got == 2) continue;
+        const mh::PlanArena a = mh::plan_arena(p);
+        const size_t C = p.info.C, nseg = p.seg_ch.size(), ntile = p.tile_ch.size();
+        const bool wave = p.use_wave_tasks, built = p.input_bits != 8 && p.cal_tile_ch.empty();
+        const bool cal = built || !p.cal_tile_ch.empty();
+        const size_t ncal = built ? C : p.cal_tile_ch.size();
+        CHECK(staged(a, a.tile_cnt, p.tile_cnt) && staged(a, a.ch_off, p.ch_off) && staged(a, a.ch_len, p.ch_len));
+        CHECK(staged(a, a.w0, p.w0) && staged(a, a.w1, p.w1) && staged(a, a.skip, p.skip) && staged(a, a.sclv, p.sclv));
+        CHECK(staged(a, a.codes, p.codes) && staged(a, a.seg_ch, p.seg_ch) && staged(a, a.seg_first, p.seg_first));
+        CHECK(staged(a, a.seg_n, p.seg_n) && staged(a, a.seg_off, p.seg_off) && staged(a, a.tile_ch, p.tile_ch));
+        CHECK(staged(a, a.tile_n, p.tile_n) && staged(a, a.tile_start, p.tile_start) && staged(a, a.wg_tasks, p.wg_tasks));
+        CHECK(wave ? staged(a, a.wave_tasks, p.wave_tasks) : !a.wave_tasks.present);
+        if (!p.cal_tile_ch.empty())
+            CHECK(staged(a, a.cal_tile_ch, p.cal_tile_ch) && staged(a, a.cal_tile_n, p.cal_tile_n) &&
+                  staged(a, a.cal_tile_start, p.cal_tile_start));
+        CHECK(a.n_cal_tiles == ncal);
+        // what each region holds, in the header's layout order: elements (-1: absent) and their size
+        const struct { const char *name; long long elems; size_t size; } want[] = {
+            {"sclv16", (long long)p.info.K * 4, 4}, {"tile_cnt", (long long)C, 4}, {"ch_off", (long long)C, 8},
+            {"ch_len", (long long)C, 8}, {"w0", (long long)C, 8}, {"w1", (long long)C, 8}, {"skip", (long long)C, 1},
+            {"sclv", (long long)p.info.K * p.info.S, 1}, {"codes", (long long)p.info.K * 16, 4}, {"seg_ch", (long long)nseg, 4},
+            {"seg_first", (long long)nseg, 8}, {"seg_n", (long long)nseg, 8}, {"seg_off", (long long)nseg, 8},
+            {"tile_ch", (long long)ntile, 4}, {"tile_n", (long long)ntile, 4}, {"tile_start", (long long)ntile, 8},
+            {"wg_tasks", (long long)p.wg_tasks.size(), sizeof(mh::WgTask)},
+            {"wave_tasks", wave ? (long long)p.wave_tasks.size() : -1, sizeof(mh::WaveTask)},
+            {"cal_tile_ch", cal ? (long long)ncal : -1, 4}, {"cal_tile_n", cal ? (long long)ncal : -1, 4},
+            {"cal_tile_start", cal ? (long long)ncal : -1, 8},
+            {"tile_done", (long long)C, 4}, {"hist", (long long)C * 16, 8}, {"peak", (long long)C, 1}, {"enc", (long long)C, 1},
+            {"lut", (long long)C * 16, 8}, {"scan", (long long)(nseg / 2048 + 2), 8}, {"err", 1, 4},
+            {"acc", wave ? (long long)C : -1, 8}, {"calhist", cal ? (long long)C * 16 : -1, 8}};
+        const size_t nwant = sizeof(want) / sizeof(want[0]);
+        CHECK(a.regions.size() == nwant);
+        printf("A %zu %zu %zu\n", a.tables_bytes, a.scratch_bytes, nwant);
+        for (size_t i = 0; i < nwant; ++i) {
+            const mh::Arena::Named &g = a.regions[i];
+            CHECK(!strcmp(g.name, want[i].name));
+            printf("R %s %c %d %zu %zu %lld %zu\n", g.name, g.scratch ? 'S' : 'T', (int)g.r.present, g.r.off, g.r.bytes,
+                   want[i].elems, want[i].size);
+        }
+        CHECK(a.sclv16.present && a.sclv16.bytes == (size_t)p.info.K * 16);
+        printf("K");
+        for (size_t i = 0; i < (size_t)p.info.K * 4; ++i) {
+            uint32_t w;
+            memcpy(&w, a.tables.get() + a.sclv16.off + 4 * i, 4);
+            printf(" %u", w);
+        }
+        printf("\nP %zu\n", built ? C : (size_t)0);
+        for (size_t c = 0; built && c < C; ++c) {
+            uint32_t ch, n;
+            uint64_t start;
+            memcpy(&ch, a.tables.get() + a.cal_tile_ch.off + 4 * c, 4);
+            memcpy(&n, a.tables.get() + a.cal_tile_n.off + 4 * c, 4);
+            memcpy(&start, a.tables.get() + a.cal_tile_start.off + 8 * c, 8);
+            printf("%u %llu %u\n", ch, (unsigned long long)start, n);
+        }
+    }
+    return got < 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--arena")) return arena();
     if (argc > 1 && !strcmp(argv[1], "--cells")) return cells(false);
     if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);
     if (argc > 1 && !strcmp(argv[1], "--worklist")) return worklist();

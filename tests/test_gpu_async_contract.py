@@ -610,10 +610,10 @@ class Transpose(Case):
 class Sweep(Case):
     name = "mh_sweep_run"
 
-    def __init__(self):
+    def __init__(self, lens=(3, 100, 5000, 3 * CH + 5, 300000)):
         super().__init__()
         rng = np.random.RandomState(5)
-        self.lens = [3, 100, 5000, 3 * CH + 5, 300000]
+        self.lens = list(lens)
         self.hb = np.array([2, 6, 10, 14], np.uint32)
         self.sets = [[np.minimum(rng.poisson(lam, size=T), 255).astype(np.uint8) for T in self.lens] for lam in (0.1, 4.0, 12.0)]
         flat = [OC.flatten(s) for s in self.sets]
@@ -1057,6 +1057,96 @@ def test_plan_state_across_a_mixed_sequence(mh, layout):
     pairs = set(zip(seq[:-1], seq[1:]))
     assert pairs == {(a, b) for a in KINDS for b in KINDS if a != b}, "the sequence was thinned out"
     _run_sequence(mh, layout, seq, seed=11)
+
+
+class PackedMeasure(Case):
+    """mh_measure of a packed plan (contiguous `bits`-bit pieces, S symbols) over the lengths of world w, on w's datasets
+    clipped to the piece width; the oracle measures the clipped bytes with the whole-channel window"""
+
+    def __init__(self, mh, w, bits, S):
+        super().__init__()
+        l, self.C, self.S, self.name = w.l, w.C, S, "measure_packed[%s,%d]" % (w.l.name, bits)
+        rows = helpers.sclv_tables()[S]
+        sets = [[np.minimum(d[int(o):int(o) + T], (1 << bits) - 1) for o, T in zip(w.off, l.lens)] for d in w.data]
+        size = [((T + 15) // 16 * 2 * bits + 15) // 16 * 16 + 16 for T in l.lens]
+        off = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint64)
+        images = []
+        for chans in sets:
+            buf = np.full(sum(size), CANARY, np.uint8)
+            for x, o in zip(chans, off):
+                pk = _pieces(x, bits).reshape(-1)
+                buf[int(o):int(o) + len(pk)] = pk
+            images.append(buf)
+        p = OC.Params(S, l.h, l.mode, OC.WIN_FULL, rows)
+        self.om = [OC.measure(*OC.flatten(chans), p, nthreads=NT) for chans in sets]
+        self.plan = mh.codec.Plan(off, np.array(l.lens, np.uint64), S, l.h, l.mode, mh.WIN_FULL, rows, seg_chunks=1,
+                                  input_bits=bits)
+        self.data = self.inp(images)
+        C = self.C
+        self.o = [self.out(n) for n in (8 * C, 4 * C * S, C, C, 8 * C * S, 8 * C, C)]
+
+    def call(self, st):
+        cut, cal, pk, en, post, bits, sk = (g.ptr for g in self.o)
+        _ok(_lib().mh_measure(self.plan._h, self.data.ptr, cut, cal, pk, en, post, bits, sk, st))
+
+    def verify(self, k):
+        for g, key, dt in zip(self.o, ("cutoff", "cal_sorted", "peak", "enc", "post_mapped", "bits", "skipped"),
+                              (np.uint64, np.uint32, np.uint8, np.uint8, np.uint64, np.uint64, np.uint8)):
+            assert np.array_equal(g.host(dt), self.om[k][key].reshape(-1)), (self.name, k, key)
+
+    def close(self):
+        self.plan.close()
+
+
+def test_six_handles_alive_at_once(mh):
+    """Every plan and sweep handle keeps its device tables and scratch in one allocation of its own
+    (csrc/mh_plan_arena.hpp).  Byte plans of layouts a, c and d, a 4-bit and a 2-bit packed plan and a sweep handle over
+    layout a's lengths, all alive: measure, encode and decode on the byte plans in an interleaved order, measure on the
+    packed pieces, the sweep; three handles destroyed in another order than they were made, the rest run once more.
+    Arenas that alias, a region sized short or a view taken before its arena exists show as a result that differs from
+    the oracle (or as a write outside an output)."""
+    side = torch.cuda.Stream()
+    st = ct.c_void_p(side.cuda_stream)
+
+    def run(case, k):
+        with torch.cuda.stream(side):
+            case.load(k)
+            case.reset()
+            case.call(st)
+            case.fetch()
+        side.synchronize()
+        case.verify(k)
+
+    alive = []
+    try:
+        benches = {}
+        for name in ("a", "c", "d"):
+            benches[name] = Bench(mh, _world(name))
+            alive.append(benches[name])
+        p4, p2 = PackedMeasure(mh, _world("a"), 4, 5), PackedMeasure(mh, _world("a"), 2, 3)
+        alive += [p4, p2]
+        sweep = Sweep(at.BY_NAME["a"].lens)
+        alive.append(sweep)
+        ops = {n: [b.case("measure", 0), b.case("encode", 0), b.case("decode", 0)] for n, b in benches.items()}
+        for i in range(3):                                  # a measures while c encodes and d decodes, then they rotate
+            for j, name in enumerate(("a", "c", "d")):
+                run(ops[name][(i + j) % 3], (i + 2 * j) % 3)
+        run(p4, 1)
+        run(p2, 2)
+        run(sweep, 0)
+        for b in benches.values():
+            assert b.status(st) == 0
+        for gone in (sweep, benches["c"], p4):              # made third from last, second and fourth
+            gone.close()
+            alive.remove(gone)
+        for i, name in enumerate(("d", "a")):
+            for j in (1, 2, 0):                             # encode, decode, measure on another dataset
+                run(ops[name][j], (i + j + 1) % 3)
+            assert benches[name].status(st) == 0
+        run(p2, 0)
+    finally:
+        for h in alive:
+            h.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

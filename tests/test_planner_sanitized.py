@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
-from tests import helpers
+from tests import async_table, helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "planner_check.cpp")
@@ -18,6 +18,7 @@ EXE = os.path.join(ROOT, "tests", "planner_check_asan")
 @pytest.fixture(scope="module")
 def exe():
     deps = [SRC, os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_planner.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_plan_arena.hpp"),
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_select.hpp"),
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_worklist.hpp"),
             os.path.join(ROOT, "include", "muahuff.h")]
@@ -114,3 +115,87 @@ def test_planner_rejects_bad_arguments_under_sanitizers(exe):
     r = subprocess.run([exe], input="\n".join(bad) + "\n", capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.split() == ["error", "-2", "error", "-1", "error", "-1", "error", "-3", "error", "-1"]
+
+
+def _arena_cases():
+    """(S, h, mode, window, table, seg_chunks, input_bits, lens)"""
+    tabs = helpers.sclv_tables()
+    cases = [(l.S, l.h, l.mode, l.window, tabs[l.S], l.seg_chunks, 8, list(l.lens)) for l in async_table.LAYOUTS]
+    for l in async_table.LAYOUTS:       # the same lengths as packed pieces (whole-channel windows only)
+        cases.append((5, l.h, l.mode, 3, tabs[5], l.seg_chunks, 4, list(l.lens)))
+        cases.append((3, l.h, l.mode, 3, tabs[3], l.seg_chunks, 2, list(l.lens)))
+    cases.append((3, 6, 1, 2, tabs[3], 0, 8, [1]))                     # one channel of one sample
+    cases.append((3, 6, 1, 0, tabs[3], 0, 8, [5, 40, 63]))             # MH_WIN_REF_HALF skips every channel: no segments
+    cases.append((5, 13, 1, 3, tabs[5], 0, 4, [100, 8192, 8193, 200_000, 3 * 131072 + 1]))  # long calibration, packed
+    cases.append((3, 6, 1, 2, tabs[3], 2, 8, [10_000_000] * 1024))     # (the bench shape of _cases())
+    return cases
+
+
+def test_plan_arena_layout_under_sanitizers(exe):
+    """csrc/mh_plan_arena.hpp: every device region of a plan in one byte range.  The program compares the staged blob
+    with the planner's vectors byte for byte (its exit status); the printed layout is checked here."""
+    cases = _arena_cases()
+    text = "\n".join("%d %d %d %d %d %d %d %d  %s  %s" % (len(lens), S, h, mode, window, len(tab), sc, bits, " ".join(map(str, lens)),
+                                                          " ".join(str(int(v)) for v in tab.ravel()))
+                     for S, h, mode, window, tab, sc, bits, lens in cases) + "\n"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "--arena"], input=text, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    f = subprocess.run([exe, "--forms"], input=text, capture_output=True, text=True, timeout=600, env=env)
+    assert f.returncode == 0, f.stderr[-3000:]
+    forms = [[int(v) for v in ln.split()] for ln in f.stdout.splitlines()]
+    assert len(forms) == len(cases)
+    for l, form in zip(async_table.LAYOUTS, forms):
+        assert bool(form[0]) == l.wave and bool(form[4]) == l.cal_tiled
+    tables = ["sclv16", "tile_cnt", "ch_off", "ch_len", "w0", "w1", "skip", "sclv", "codes", "seg_ch", "seg_first", "seg_n",
+              "seg_off", "tile_ch", "tile_n", "tile_start", "wg_tasks", "wave_tasks", "cal_tile_ch", "cal_tile_n", "cal_tile_start"]
+    scratch = ["tile_done", "hist", "peak", "enc", "lut", "scan", "err", "acc", "calhist"]
+    lines = iter(r.stdout.splitlines())
+    for (S, h, mode, window, tab, sc, bits, lens), form in zip(cases, forms):
+        C, K, wave = len(lens), len(tab), bool(form[0])
+        head = next(lines).split()
+        assert head[0] == "A"
+        t_bytes, s_bytes, n = int(head[1]), int(head[2]), int(head[3])
+        assert t_bytes % 256 == 0 and s_bytes % 256 == 0 and n == len(tables) + len(scratch)
+        regs = {}
+        end = 0           # regions come in address order: disjoint, each with an address of its own, tables before scratch
+        for name in tables + scratch:
+            tag, nm, part, present, off, nbytes, elems, size = next(lines).split()
+            assert tag == "R" and nm == name and part == ("T" if name in tables else "S")
+            present, off, nbytes, elems, size = int(present), int(off), int(nbytes), int(elems), int(size)
+            regs[name] = (present, off, nbytes, elems)
+            assert present == (elems >= 0), name
+            if not present:
+                continue
+            assert off % 256 == 0 and nbytes == elems * size, name
+            lo, hi = (0, t_bytes) if part == "T" else (t_bytes, t_bytes + s_bytes)
+            assert lo <= off and off >= end and off + max(nbytes, 1) <= hi, name
+            end = off + max(nbytes, 1)
+        # exactly these are absent, and only for these forms
+        absent = set() if wave else {"wave_tasks", "acc"}
+        if bits == 8 and 2 ** h <= async_table.K_CAL_DIRECT:
+            absent |= {"cal_tile_ch", "cal_tile_n", "cal_tile_start", "calhist"}
+        assert {nm for nm, v in regs.items() if not v[0]} == absent
+        # sizes that follow from the case alone
+        for name, want in (("sclv16", 4 * K), ("ch_off", C), ("ch_len", C), ("w0", C), ("w1", C), ("skip", C), ("tile_cnt", C),
+                           ("sclv", K * S), ("codes", 16 * K), ("tile_done", C), ("hist", 16 * C), ("peak", C), ("enc", C),
+                           ("lut", 16 * C), ("err", 1)):
+            assert regs[name][3] == want, name
+        assert regs["seg_ch"][3] == regs["seg_first"][3] == regs["seg_n"][3] == regs["seg_off"][3]
+        if window == 0 and max(lens) < 2 ** h:
+            assert regs["seg_ch"][0] and regs["seg_ch"][2] == 0 and form[6] == C   # no segments: present, empty
+        # the 16-byte rows
+        words = [int(v) for v in next(lines).split()[1:]]
+        rows = np.zeros((K, 16), np.uint8)
+        rows[:, :S] = tab
+        assert words == [int(v) for v in rows.view("<u4").ravel()]
+        # calibration tiles built for packed plans without planner tiles: one per channel over min(len, 2^h) samples
+        tag, npk = next(lines).split()
+        assert tag == "P"
+        recs = [[int(v) for v in next(lines).split()] for _ in range(int(npk))]
+        if bits != 8 and 2 ** h <= async_table.K_CAL_DIRECT:
+            assert recs == [[c, 0, min(lens[c], 2 ** h)] for c in range(C)]
+            assert regs["cal_tile_ch"][3] == regs["cal_tile_n"][3] == regs["cal_tile_start"][3] == C
+        else:
+            assert recs == []
+    assert next(lines, None) is None

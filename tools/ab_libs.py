@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-box A/B of two builds of libmuahuff.so: encode / decode of the roofline set (1024 channels x
 1e7 bins) per S and of the short-channel set, each library in its own child process, alternating.
-env: PROBE=1 (placement-probed input copy / payload / output buffers)  SS=3,5,8,10  REPS=2  RATES=lo,hi  H=6 (calibration bits: the window starts at sample 2^H)  SMALL_ONLY=1  BIG_ONLY=1  SEG=0 (chunks per segment, 0 = the planner's choice)
+env: PLAN=1 (instead: plan creation + destruction, host clock around the pair, median of PLAN_N=20 per shape)  PROBE=1 (placement-probed input copy / payload / output buffers)  SS=3,5,8,10  REPS=2  RATES=lo,hi  H=6 (calibration bits: the window starts at sample 2^H)  SMALL_ONLY=1  BIG_ONLY=1  SEG=0 (chunks per segment, 0 = the planner's choice)
 usage: ab_libs.py A.so B.so ...      (children: ab_libs.py --one X.so)"""
 import os
 import subprocess
@@ -29,6 +29,22 @@ def one(path):
         torch.cuda.synchronize()
         return float(np.median([a.elapsed_time(b) for a, b in ev])) * 1e3
 
+    if os.environ.get("PLAN") == "1":  # both calls synchronise; the bench set, the short-channel set, one stream block
+        import time
+        for C, T, window, sc, bits in ((1024, 10_000_000, muahuff.WIN_AFTER_CAL, 0, 8), (2400, 72_000, muahuff.WIN_AFTER_CAL, 0, 8),
+                                       (1024, 147_456, muahuff.WIN_FULL, 2, 2)):
+            cb = 16384 * bits // 8   # stream.py's chunk-blocked pieces
+            off = np.arange(C, dtype=np.uint64) * np.uint64(cb if bits != 8 else (T + 15) // 16 * 16)
+            ts = []
+            for _ in range(3 + int(os.environ.get("PLAN_N", "20"))):
+                t0 = time.perf_counter()
+                codec.Plan(off, np.full(C, T, np.uint64), 3, 6 if bits == 8 else 0, 1, window, sclv.table(3), seg_chunks=sc,
+                           input_bits=bits, chunk_stride=C * cb if bits != 8 else 0).close()
+                ts.append(1e6 * (time.perf_counter() - t0))
+            ts = ts[3:]
+            print("%-28s %5d x %8d %d-bit : plan create + destroy %9.1f us median (%.1f .. %.1f)"
+                  % (os.path.basename(path), C, T, bits, float(np.median(ts)), min(ts), max(ts)), flush=True)
+        return
     Ss = [int(v) for v in os.environ.get("SS", "3,5,8,10").split(",")]
     shapes = ((1024, 10_000_000, 30), (2400, 72_000, 50), (96, 72_000, 50), (10_000, 20_000, 50), (96, 3_600_000, 50))
     if os.environ.get("SMALL_ONLY") == "1":
