@@ -11,14 +11,15 @@ ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "libmuahuff.so")
 SOURCES = ["csrc/muahuff.hip"]
 HEADERS = ["csrc/exports.map", "csrc/mh_kernels.hpp", "csrc/mh_device.hpp", "csrc/mh_codec2.hpp", "csrc/mh_range.hpp", "csrc/mh_rebin_decode.hpp", "csrc/mh_layout.hpp", "csrc/mh_packed_measure.hpp",
-           "csrc/mh_planner.hpp", "csrc/mh_plan_arena.hpp", "csrc/mh_select.hpp", "csrc/mh_worklist.hpp", "csrc/mh_analysis.hpp", "../include/muahuff.h"]
+           "csrc/mh_planner.hpp", "csrc/mh_plan_arena.hpp", "csrc/mh_select.hpp", "csrc/mh_worklist.hpp", "csrc/mh_analysis.hpp",
+           "csrc/mh_msg.hpp", "csrc/mh_validate.hpp", "csrc/mh_sweep_planner.hpp", "csrc/mh_launch.hpp", "../include/muahuff.h"]
 # the companion (include/muahuff_ingest.h), what stands around the codec: spike time stamps -> binned counts in front,
 # payload checksums behind
 INGEST_SO = os.path.join(HERE, "libmuahuff_ingest.so")
 INGEST_SOURCES = ["csrc/mh_ingest.hip"]
 INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_aer.hpp", "csrc/mh_aer_layout.hpp",
                   "csrc/mh_crc.hpp", "csrc/mh_crc_tables.hpp", "csrc/mh_unbin.hpp", "csrc/mh_unbin_layout.hpp",
-                  "csrc/mh_device.hpp", "../include/muahuff.h",
+                  "csrc/mh_device.hpp", "csrc/mh_msg.hpp", "csrc/mh_launch.hpp", "../include/muahuff.h",
                   "../include/muahuff_ingest.h"]
 
 

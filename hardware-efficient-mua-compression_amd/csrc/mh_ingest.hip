@@ -10,6 +10,7 @@
 #include "mh_aer_layout.hpp"
 #include "mh_crc.hpp"
 #include "mh_ingest.hpp"
+#include "mh_launch.hpp"
 #include "mh_unbin.hpp"
 #include "mh_unbin_layout.hpp"
 // built with -fvisibility=hidden: the mhi_* functions of the header are ALL the library exports
@@ -29,6 +30,8 @@ int fail(int code, const char *fmt, ...)
     va_end(ap);
     return code;
 }
+
+static_assert(mh::kGeoCrcWaves == mh::kCrcWaves && mh::kCrcMaxX == mh::kCrcMaxGroups, "mh_launch.hpp sizes the grid by mh_crc.hpp's constants");
 
 // Where does a table live?  Only a query of the runtime's allocation records: nothing is enqueued, nothing waits.
 enum class Where { kDevice, kBoth, kHostOnly };
@@ -118,7 +121,7 @@ int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, ui
         return fail(MH_ERR_ARG, "mhi_bin_events: C=%u, T=%llu, period=%llu (each at least 1)", C, (unsigned long long)T,
                     (unsigned long long)period);
     if (bits != 8 && bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mhi_bin_events: bits=%u (8, 4 or 2)", bits);
-    if (chunk_stride && (bits == 8 || chunk_stride % 16 || chunk_stride < (uint64_t)MH_CHUNK * bits / 8))
+    if (!mh::chunk_stride_ok(chunk_stride, bits))
         return fail(MH_ERR_ARG, "mhi_bin_events: chunk_stride=%llu (packed output only, a multiple of 16, at least one chunk)",
                     (unsigned long long)chunk_stride);
     const unsigned __int128 end = (unsigned __int128)origin + (unsigned __int128)T * period;
@@ -134,25 +137,20 @@ int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, ui
                                 (unsigned long long)out_off[c]);
         if (w == Where::kHostOnly) return fail(MH_ERR_ARG, "mhi_bin_events: out_off is host memory the device cannot read");
     }
-    const uint64_t nchunks = (T + MH_CHUNK - 1) / MH_CHUNK;
-    // chunks per workgroup: 8 amortise the start search and keep the event list streaming; fewer when that would leave
-    // the device short of workgroups, more when the grid would not fit one dimension
-    uint64_t span = 8;
-    while (span > 1 && (unsigned __int128)C * ((nchunks + span - 1) / span) < 4096) span >>= 1;
-    while ((unsigned __int128)C * ((nchunks + span - 1) / span) > 0x7FFFFFFFull) span <<= 1;
-    const uint64_t nspans = (nchunks + span - 1) / span;
-    const uint32_t div_mode = period == 1 ? 0u : period < (1ull << 18) ? 1u : 2u;
-    const dim3 grid((unsigned)(C * nspans)), block(mh::kBinThreads);
+    mh::Msg m;
+    mh::BinLaunch l;  // chunks per workgroup and the grid (mh_launch.hpp)
+    if (int rc = mh::bin_events_launch(m, C, T, period, &l)) return fail(rc, "%s", m.text);
+    const dim3 grid(l.grid), block(mh::kBinThreads);
     hipStream_t st = (hipStream_t)stream;
     if (bits == 8)
-        hipLaunchKernelGGL(mh::k_bin_events<8>, grid, block, 0, st, ticks, ev_off, origin, period, T, nchunks, span, nspans,
-                           div_mode, out, out_off, chunk_stride);
+        hipLaunchKernelGGL(mh::k_bin_events<8>, grid, block, 0, st, ticks, ev_off, origin, period, T, l.nchunks, l.span, l.nspans,
+                           l.div_mode, out, out_off, chunk_stride);
     else if (bits == 4)
-        hipLaunchKernelGGL(mh::k_bin_events<4>, grid, block, 0, st, ticks, ev_off, origin, period, T, nchunks, span, nspans,
-                           div_mode, out, out_off, chunk_stride);
+        hipLaunchKernelGGL(mh::k_bin_events<4>, grid, block, 0, st, ticks, ev_off, origin, period, T, l.nchunks, l.span, l.nspans,
+                           l.div_mode, out, out_off, chunk_stride);
     else
-        hipLaunchKernelGGL(mh::k_bin_events<2>, grid, block, 0, st, ticks, ev_off, origin, period, T, nchunks, span, nspans,
-                           div_mode, out, out_off, chunk_stride);
+        hipLaunchKernelGGL(mh::k_bin_events<2>, grid, block, 0, st, ticks, ev_off, origin, period, T, l.nchunks, l.span, l.nspans,
+                           l.div_mode, out, out_off, chunk_stride);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_bin_events: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
@@ -209,8 +207,7 @@ int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *s
     if ((uintptr_t)payload % 4) return fail(MH_ERR_ARG, "mhi_seg_crc32: payload is not 4-byte aligned");
     const uint64_t n_list = seg_idx ? n_idx : n_segments;
     if (n_list == 0) return MH_OK;
-    const uint64_t groups = (n_list + mh::kCrcWaves - 1) / mh::kCrcWaves;
-    const dim3 grid((unsigned)(groups < mh::kCrcMaxGroups ? groups : mh::kCrcMaxGroups)), block(64u * mh::kCrcWaves);
+    const dim3 grid(mh::seg_crc_grid(n_list)), block(64u * mh::kCrcWaves);
     hipLaunchKernelGGL(mh::k_seg_crc32, grid, block, 0, (hipStream_t)stream, static_cast<const uint32_t *>(payload),
                        payload_words, seg_off, seg_words, n_segments, seg_idx, n_list, crc, expect,
                        reinterpret_cast<unsigned long long *>(bad));

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "mh_planner.hpp"
+#include "mh_sweep_planner.hpp"
 
 namespace mh {
 
@@ -163,25 +164,23 @@ inline PlanArena plan_arena(const PlanHost &H)
     return a;
 }
 
-// mh_sweep: the tiles of every (channel, interval) slot and one histogram per slot
+// mh_sweep (mh_sweep_planner.hpp): the tiles of every (channel, interval) slot and one histogram per slot
 struct SweepArena : Arena {
     Region ch_off, tile_ch, tile_n, tile_slot, tile_start, slot_len;  // tables
     Region hist;                                                      // scratch
 };
 
-inline SweepArena sweep_arena(const std::vector<uint64_t> &ch_off, const std::vector<uint32_t> &tile_ch,
-                              const std::vector<uint32_t> &tile_n, const std::vector<uint32_t> &tile_slot,
-                              const std::vector<uint64_t> &tile_start, const std::vector<uint64_t> &slot_len)
+inline SweepArena sweep_arena(const SweepHost &w)
 {
     SweepArena a;
-    a.ch_off = a.table("ch_off", ch_off);
-    a.tile_ch = a.table("tile_ch", tile_ch);
-    a.tile_n = a.table("tile_n", tile_n);
-    a.tile_slot = a.table("tile_slot", tile_slot);
-    a.tile_start = a.table("tile_start", tile_start);
-    a.slot_len = a.table("slot_len", slot_len);
+    a.ch_off = a.table("ch_off", w.ch_off);
+    a.tile_ch = a.table("tile_ch", w.tile_ch);
+    a.tile_n = a.table("tile_n", w.tile_n);
+    a.tile_slot = a.table("tile_slot", w.tile_slot);
+    a.tile_start = a.table("tile_start", w.tile_start);
+    a.slot_len = a.table("slot_len", w.slot_len);
     a.stage();
-    a.hist = a.scratch("hist", slot_len.size() * kArenaHistSlots * sizeof(uint64_t));
+    a.hist = a.scratch("hist", w.slot_len.size() * kArenaHistSlots * sizeof(uint64_t));
     return a;
 }
 

@@ -9,6 +9,7 @@
 #include <numeric>
 #include <vector>
 
+#include "mh_msg.hpp"
 #include "mh_select.hpp"
 #include "muahuff.h"
 
@@ -27,6 +28,11 @@ constexpr uint64_t kFusedMeasureTiles = 16384;
 // 300 x 72 000 (900 two-chunk segments) 29 / 35, 600 x 72 000 (1800) 37 / 42, 1344 x 72 000 (4032) 60 / 58,
 // 2400 x 72 000 (7200) 91 / 91, 10 000 x 20 000 (10 000) 130 / 120, 96 x 3.6e6 (10 560) 209 / 169.
 constexpr uint64_t kAutoSegLimit = 3072;
+
+// Histogram tiles cut a range into pieces of kHistTileBytes samples, the last one shorter: the samples of the tile in
+// front of which `left` samples remain.  (Shared by the three loops that cut: window and calibration tiles here, a
+// sweep's slots in mh_sweep_planner.hpp.)
+inline uint32_t tile_samples(uint64_t left) { return (uint32_t)(left < kHistTileBytes ? left : kHistTileBytes); }
 
 inline uint32_t bitrev(uint32_t v, int n)
 {
@@ -196,6 +202,32 @@ inline int plan_check_args(const uint64_t *ch_len, uint32_t C, uint32_t S, uint3
     return MH_OK;
 }
 
+// The checked arguments of a plan as the `info` plan_host_build starts from (seg_chunks = 0: the planner chooses), or
+// the error code with its message in m.
+inline int plan_args(Msg &m, const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
+                     const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, mh_plan_info_t *I)
+{
+    const char *msg = "";
+    uint32_t arg = 0, maxlen = 0;
+    const int rc = plan_check_args(ch_len, C, S, h, mode, window, sclv, K, &maxlen, &msg, &arg);
+    if (rc != MH_OK) {
+        snprintf(m.text, sizeof(m.text), msg, arg);  // (one of plan_check_args's strings: at most one %u)
+        return rc;
+    }
+    if (seg_chunks > kMaxSegChunks)  // a wave task counts its samples in 32 bits
+        return m.set(MH_ERR_ARG, "seg_chunks=%u above %u", seg_chunks, kMaxSegChunks);
+    *I = mh_plan_info_t{};
+    I->C = C;
+    I->S = S;
+    I->h = h;
+    I->mode = mode;
+    I->window = window;
+    I->K = K;
+    I->seg_chunks = seg_chunks;
+    I->maxlen = maxlen;
+    return MH_OK;
+}
+
 // Everything mh_plan_create uploads, computed on the host.  `info` must hold C, S, h, mode, window,
 // K, seg_chunks (0 = choose) and maxlen; arguments are already checked.
 inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t *ch_len, const uint8_t *sclv)
@@ -277,7 +309,7 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
         for (uint64_t first = 0; first < n; first += kHistTileBytes) {
             p.tile_ch.push_back(c);
             p.tile_start.push_back(p.w0[c] + first);
-            p.tile_n.push_back((uint32_t)(n - first < kHistTileBytes ? n - first : kHistTileBytes));
+            p.tile_n.push_back(tile_samples(n - first));
         }
         // every channel has at least one tile (an empty one for an empty window): the workgroup of a channel's
         // last tile finishes the channel when mh_measure runs as one launch
@@ -342,7 +374,7 @@ inline void plan_host_build(PlanHost &p, const uint64_t *ch_off, const uint64_t 
             for (uint64_t first = 0; first < n; first += kHistTileBytes) {
                 p.cal_tile_ch.push_back(c);
                 p.cal_tile_start.push_back(first);
-                p.cal_tile_n.push_back((uint32_t)(n - first < kHistTileBytes ? n - first : kHistTileBytes));
+                p.cal_tile_n.push_back(tile_samples(n - first));
             }
         }
     p.W = dec_table_bits(I.maxlen, p.use_wave_tasks);

@@ -1,5 +1,7 @@
 // muahuff.hip -- C ABI (include/muahuff.h) over the gfx950 kernels in mh_kernels.hpp.
-// Host side: argument checking, the segment/tile planner, table upload, kernel launches.
+// Host side: the ABI's NULL checks, HIP calls and kernel launches.  What decides WHAT the device does is computed in
+// host-only headers (mh_planner.hpp, mh_sweep_planner.hpp, mh_plan_arena.hpp, mh_select.hpp, mh_worklist.hpp,
+// mh_launch.hpp) and so is the walk over stored streams (mh_validate.hpp).
 // There is no CPU fallback anywhere in this library.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +16,7 @@
 
 #include "mh_analysis.hpp"
 #include "mh_codec2.hpp"
+#include "mh_launch.hpp"
 #include "mh_layout.hpp"
 #include "mh_packed_measure.hpp"
 #include "mh_plan_arena.hpp"
@@ -21,6 +24,8 @@
 #include "mh_range.hpp"
 #include "mh_rebin_decode.hpp"
 #include "mh_select.hpp"
+#include "mh_sweep_planner.hpp"
+#include "mh_validate.hpp"
 #include "mh_worklist.hpp"
 // The library is built with -fvisibility=hidden: the C ABI of include/muahuff.h is ALL it exports
 // (tests/test_host.py compares the dynamic symbol table with the header's prototypes).
@@ -41,6 +46,9 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+// the error a host-only header reported (mh_msg.hpp)
+int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
+
 #define MH_HIP(call)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
@@ -52,6 +60,9 @@ int fail(int code, const char *fmt, ...)
 static_assert(mh::kArenaHistSlots == mh::kHistStride && mh::kArenaLutEntries == mh::kLut && sizeof(uint2) == 8 &&
                   mh::kArenaScanBlock == mh::kScanBlock,
               "mh_plan_arena.hpp sizes the scratch regions by the kernels' constants");
+static_assert(mh::kGeoRebinTileBytes == mh::kRebinTileBytes && mh::kGeoTr2T == mh::kTr2T && mh::kGeoTr2C == mh::kTr2C &&
+                  mh::kGeoScanBlock == mh::kScanBlock && mh::kGeoCompactSegs == mh::kCompactSegs,
+              "mh_launch.hpp sizes the grids by the kernels' constants");
 
 // The one device allocation of a plan or a sweep handle, laid out by mh_plan_arena.hpp: the tables part uploaded in
 // one copy, the scratch part behind it zeroed.  Synchronises.  Freed with the handle, a half-created one included.
@@ -146,8 +157,8 @@ struct mh_plan {
 
 struct mh_sweep {
     int device = 0;
-    uint32_t C = 0, nh = 0, ni = 0;
-    std::vector<uint64_t> bounds;  // C * (ni + 1), sorted per channel
+    uint32_t ni = 0;
+    std::vector<uint64_t> bounds;  // C * (ni + 1), sorted per channel (mh_sweep_planner.hpp)
     uint64_t n_tiles = 0, n_slots = 0;
     // views into the arena
     uint64_t *d_ch_off = nullptr, *d_tile_start = nullptr, *d_slot_len = nullptr;
@@ -155,12 +166,6 @@ struct mh_sweep {
     unsigned long long *d_scratch = nullptr;
     DeviceArena arena;  // what the d_* above point into
 };
-
-// chunk_stride of `bits`-bit pieces: 0 (contiguous), or packed input only, a multiple of 16, at least one chunk
-static bool chunk_stride_ok(uint64_t chunk_stride, uint32_t bits)
-{
-    return !chunk_stride || (bits != 8 && chunk_stride % 16 == 0 && chunk_stride >= (uint64_t)MH_CHUNK * bits / 8);
-}
 
 // device operations run on the plan's device: its tables live there
 static int check_device(int device, const char *who)
@@ -455,27 +460,6 @@ static int plan_upload(mh_plan *p)
     return MH_OK;
 }
 
-static int plan_args(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
-                     const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, mh_plan_info_t *I)
-{
-    const char *msg = "";
-    uint32_t arg = 0, maxlen = 0;
-    const int rc = mh::plan_check_args(ch_len, C, S, h, mode, window, sclv, K, &maxlen, &msg, &arg);
-    if (rc != MH_OK) return fail(rc, msg, arg);
-    if (seg_chunks > mh::kMaxSegChunks)  // a wave task counts its samples in 32 bits
-        return fail(MH_ERR_ARG, "seg_chunks=%u above %u", seg_chunks, mh::kMaxSegChunks);
-    *I = mh_plan_info_t{};
-    I->C = C;
-    I->S = S;
-    I->h = h;
-    I->mode = mode;
-    I->window = window;
-    I->K = K;
-    I->seg_chunks = seg_chunks;  // 0 = the planner chooses
-    I->maxlen = maxlen;
-    return MH_OK;
-}
-
 // the first n entries of the directory, into those of the four arrays the caller asked for
 static void copy_segments(const mh::PlanHost &H, size_t n, uint32_t *seg_ch, uint64_t *seg_first, uint64_t *seg_n, uint64_t *seg_off)
 {
@@ -491,9 +475,8 @@ int mh_plan_query(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, ui
 {
     if (!ch_len || !sclv || !info) return fail(MH_ERR_ARG, "mh_plan_query: NULL argument");
     mh::PlanHost H;
-    if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &H.info)) return rc;
-    std::vector<uint64_t> off(C, 0);  // offsets do not enter the directory
-    mh::plan_host_build(H, off.data(), ch_len, sclv);
+    mh::Msg m;
+    if (int rc = mh::plan_host_of_args(m, ch_len, C, S, h, mode, window, sclv, K, seg_chunks, H)) return fail(rc, m);
     *info = H.info;
     copy_segments(H, H.seg_ch.size() < seg_cap ? H.seg_ch.size() : (size_t)seg_cap, seg_ch, seg_first, seg_n, seg_off);
     return MH_OK;
@@ -517,11 +500,12 @@ int mh_plan_create_packed(mh_plan **plan, const uint64_t *ch_off, const uint64_t
     if (input_bits != 8 && (window & ~MH_WIN_REV2_SEGMENTS) != MH_WIN_FULL)
         return fail(MH_ERR_ARG, "packed input needs the whole-channel window (MH_WIN_FULL)");
     if (input_bits == 2 && S > 4) return fail(MH_ERR_ARG, "2-bit input holds symbols 0..3: S=%u is above 4", S);
-    if (!chunk_stride_ok(chunk_stride, input_bits))
+    if (!mh::chunk_stride_ok(chunk_stride, input_bits))
         return fail(MH_ERR_ARG, "chunk_stride=%llu: packed input only, a multiple of 16, at least one chunk",
                     (unsigned long long)chunk_stride);
     mh_plan_info_t I;
-    if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &I)) return rc;
+    mh::Msg m;
+    if (int rc = mh::plan_args(m, ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &I)) return fail(rc, m);
     int ndev = 0, dev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(MH_ERR_NO_DEVICE, "no HIP device visible (libmuahuff has no CPU fallback)");
@@ -854,17 +838,15 @@ static int check_range_call(const char *who, const mh_plan *p, const uint32_t *p
     return check_device(p->device, who);
 }
 
-// The cache's fill records, launch(grid, first record): y = up to 65535 records per launch, the workgroups of x stride
-// over the longest one (per_block elements per workgroup and pass).
+// The cache's fill records, launch(grid, first record), in the grids of mh_launch.hpp (per_block elements per workgroup
+// and pass).
 extern "C++" template <class Launch>
 static int launch_fills(const ListCache &c, uint64_t per_block, Launch launch)
 {
-    const uint64_t nb = (c.w.max_fill + per_block - 1) / per_block;
-    const unsigned nx = (unsigned)(nb < 1 ? 1 : nb < 1024 ? nb : 1024);
+    const unsigned nx = mh::fill_grid_x(c.w.max_fill, per_block);
     const auto *d_fill = reinterpret_cast<const mh::RangeFill *>(c.fills());
-    for (size_t f = 0; f < c.w.nfill; f += 65535) {
-        const unsigned ny = (unsigned)(c.w.nfill - f < 65535 ? c.w.nfill - f : 65535);
-        launch(dim3(nx, ny), d_fill + f);
+    for (size_t f = 0; f < c.w.nfill; f += mh::kFillMaxRecords) {
+        launch(dim3(nx, mh::fill_grid_y(c.w.nfill, f)), d_fill + f);
         MH_HIP(hipGetLastError());
     }
     return MH_OK;
@@ -937,45 +919,6 @@ int mh_decode_rebin(mh_plan *p, const uint32_t *payload, uint64_t payload_words,
     return saturate ? decode_rebin<uint8_t>(p, a, true, st) : decode_rebin<uint32_t>(p, a, false, st);
 }
 
-// The chunk walk of one stored segment s (directory entry of H) whose words are payload[pos, end): header sizes,
-// sub-stream lengths possible for the channel's code (row = its SCLV row), chunk sizes adding up exactly to end.
-static int validate_segment(const mh::PlanHost &H, size_t s, const uint8_t *row, uint32_t S, const uint32_t *payload,
-                            uint64_t pos, uint64_t words)
-{
-    const uint64_t end = pos + words;
-    const uint64_t maxlen = row[S - 1];
-    uint64_t left = H.seg_n[s];
-    while (left) {
-        const uint64_t m = left < MH_CHUNK ? left : MH_CHUNK;
-        if (pos >= end) return fail(MH_ERR_STREAM, "segment %zu is shorter than its chunk headers say", s);
-        const uint32_t w0 = payload[pos];
-        const uint32_t mn = w0 & 0xFFFu, w = (w0 >> 12) & 15u;
-        if (w > 12) return fail(MH_ERR_STREAM, "segment %zu: chunk header field width %u above 12", s, w);
-        const uint64_t hw = (16u + 64u * w + 31u) >> 5;
-        if (pos + hw > end) return fail(MH_ERR_STREAM, "segment %zu: chunk header runs past the segment", s);
-        uint64_t sum = 0, longest = 0;
-        for (uint32_t l = 0; l < 64; ++l) {
-            uint64_t f = 0;
-            if (w) {
-                const uint32_t fb = 16u + l * w;
-                uint64_t v = payload[pos + (fb >> 5)];
-                if ((fb & 31) + w > 32) v |= (uint64_t)payload[pos + (fb >> 5) + 1] << 32;
-                f = (v >> (fb & 31)) & ((1u << w) - 1u);
-            }
-            sum += mn + f;
-            if (mn + f > longest) longest = mn + f;
-        }
-        // every codeword has 1..maxlen bits; a sub-stream holds <= 256 samples
-        if (longest > 256 * maxlen || sum > m * maxlen || sum < m)
-            return fail(MH_ERR_STREAM, "segment %zu: sub-stream lengths impossible for this code", s);
-        pos += hw + ((sum + 31) >> 5);
-        left -= m;
-    }
-    if (pos != end)
-        return fail(MH_ERR_STREAM, "segment %zu: chunk sizes do not add up to its %llu words", s, (unsigned long long)words);
-    return MH_OK;
-}
-
 int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
                        const uint8_t *sclv, uint32_t K, uint32_t seg_chunks, const uint32_t *payload,
                        uint64_t payload_words, const uint64_t *seg_words, uint64_t n_segments,
@@ -983,30 +926,11 @@ int mh_validate_stream(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t 
 {
     if (!ch_len || !sclv || !payload || !seg_words || !peak || !enc)
         return fail(MH_ERR_ARG, "mh_validate_stream: NULL argument");
-    if (seg_chunks == 0) return fail(MH_ERR_ARG, "mh_validate_stream: a stored stream names its seg_chunks");
     mh::PlanHost H;
-    if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &H.info)) return rc;
-    std::vector<uint64_t> off(C, 0);
-    mh::plan_host_build(H, off.data(), ch_len, sclv);
-    if (H.seg_ch.size() != n_segments)
-        return fail(MH_ERR_STREAM, "directory has %llu segments, the layout implies %zu",
-                    (unsigned long long)n_segments, H.seg_ch.size());
-    for (uint32_t c = 0; c < C; ++c)
-        if (peak[c] >= S || enc[c] >= K)
-            return fail(MH_ERR_STREAM, "channel %u: (peak %u, encoder %u) outside (S=%u, K=%u)", c, peak[c], enc[c], S, K);
-    uint64_t pos = 0;
-    for (size_t s = 0; s < H.seg_ch.size(); ++s) {
-        const uint64_t end = pos + seg_words[s];
-        if (end < pos || end > payload_words)
-            return fail(MH_ERR_STREAM, "segment %zu ends at word %llu, the payload has %llu", s,
-                        (unsigned long long)end, (unsigned long long)payload_words);
-        if (int rc = validate_segment(H, s, sclv + (size_t)enc[H.seg_ch[s]] * S, S, payload, pos, seg_words[s])) return rc;
-        pos = end;
-    }
-    if (pos != payload_words)
-        return fail(MH_ERR_STREAM, "payload has %llu words, the directory accounts for %llu",
-                    (unsigned long long)payload_words, (unsigned long long)pos);
-    return MH_OK;
+    mh::Msg m;
+    int rc = mh::stored_plan_host(m, "mh_validate_stream", ch_len, C, S, h, mode, window, sclv, K, seg_chunks, n_segments, H);
+    if (!rc) rc = mh::validate_stream(m, H, payload, payload_words, seg_words, peak, enc);
+    return rc ? fail(rc, m) : MH_OK;
 }
 
 int mh_validate_segments(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_t h, uint32_t mode, uint32_t window,
@@ -1016,29 +940,11 @@ int mh_validate_segments(const uint64_t *ch_len, uint32_t C, uint32_t S, uint32_
 {
     if (!ch_len || !sclv || !seg_off || !seg_words || !peak || !enc || (n_idx && (!payload || !seg_idx)))
         return fail(MH_ERR_ARG, "mh_validate_segments: NULL argument");
-    if (seg_chunks == 0) return fail(MH_ERR_ARG, "mh_validate_segments: a stored stream names its seg_chunks");
     mh::PlanHost H;
-    if (int rc = plan_args(ch_len, C, S, h, mode, window, sclv, K, seg_chunks, &H.info)) return rc;
-    std::vector<uint64_t> off(C, 0);
-    mh::plan_host_build(H, off.data(), ch_len, sclv);
-    if (H.seg_ch.size() != n_segments)
-        return fail(MH_ERR_STREAM, "directory has %llu segments, the layout implies %zu",
-                    (unsigned long long)n_segments, H.seg_ch.size());
-    for (uint64_t j = 0; j < n_idx; ++j) {
-        const uint64_t s = seg_idx[j];
-        if (s >= n_segments)
-            return fail(MH_ERR_ARG, "mh_validate_segments: seg_idx[%llu] = %llu, the directory has %llu entries",
-                        (unsigned long long)j, (unsigned long long)s, (unsigned long long)n_segments);
-        const uint32_t c = H.seg_ch[s];
-        if (peak[c] >= S || enc[c] >= K)
-            return fail(MH_ERR_STREAM, "channel %u: (peak %u, encoder %u) outside (S=%u, K=%u)", c, peak[c], enc[c], S, K);
-        const uint64_t pos = seg_off[s], end = pos + seg_words[s];
-        if (end < pos || end > payload_words)
-            return fail(MH_ERR_STREAM, "segment %llu ends at word %llu, the payload has %llu", (unsigned long long)s,
-                        (unsigned long long)end, (unsigned long long)payload_words);
-        if (int rc = validate_segment(H, (size_t)s, sclv + (size_t)enc[c] * S, S, payload, pos, seg_words[s])) return rc;
-    }
-    return MH_OK;
+    mh::Msg m;
+    int rc = mh::stored_plan_host(m, "mh_validate_segments", ch_len, C, S, h, mode, window, sclv, K, seg_chunks, n_segments, H);
+    if (!rc) rc = mh::validate_segments(m, "mh_validate_segments", H, payload, payload_words, seg_off, seg_words, seg_idx, n_idx, peak, enc);
+    return rc ? fail(rc, m) : MH_OK;
 }
 
 int mh_compact(mh_plan *p, const uint32_t *payload, const uint64_t *seg_words, uint32_t *dense,
@@ -1049,21 +955,19 @@ int mh_compact(mh_plan *p, const uint32_t *payload, const uint64_t *seg_words, u
     if (int rc_ = check_device(p->device, "mh_compact")) return rc_;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t nseg = p->h.info.n_segments;
-    const uint64_t nblocks = (nseg + mh::kScanBlock - 1) / mh::kScanBlock;
-    if (nblocks <= 1) {  // one launch: every wave scans for itself
-        const uint64_t nwg = nseg ? (nseg + mh::kCompactSegs - 1) / mh::kCompactSegs : 1;
-        hipLaunchKernelGGL(mh::k_compact<true>, dim3((unsigned)nwg), dim3(256), 0, st, payload,
+    const unsigned scan_blocks = mh::compact_scan_blocks(nseg), groups = mh::compact_groups(nseg);
+    if (scan_blocks <= 1) {  // one launch: every wave scans for itself
+        hipLaunchKernelGGL(mh::k_compact<true>, dim3(groups), dim3(256), 0, st, payload,
                            (const uint64_t *)p->d_seg_off, seg_words, dense_off, dense, dense_cap_words, nseg, total_words);
         MH_HIP(hipGetLastError());
         return MH_OK;
     }
-    hipLaunchKernelGGL(mh::k_scan_block_sums, dim3((unsigned)nblocks), dim3(256), 0, st, seg_words, nseg, p->d_scan);
-    hipLaunchKernelGGL(mh::k_scan_top, dim3(1), dim3(1024), 0, st, p->d_scan, nblocks, total_words);
-    hipLaunchKernelGGL(mh::k_scan_apply, dim3((unsigned)nblocks), dim3(256), 0, st, seg_words, nseg,
+    hipLaunchKernelGGL(mh::k_scan_block_sums, dim3(scan_blocks), dim3(256), 0, st, seg_words, nseg, p->d_scan);
+    hipLaunchKernelGGL(mh::k_scan_top, dim3(1), dim3(1024), 0, st, p->d_scan, (uint64_t)scan_blocks, total_words);
+    hipLaunchKernelGGL(mh::k_scan_apply, dim3(scan_blocks), dim3(256), 0, st, seg_words, nseg,
                        (const uint64_t *)p->d_scan, dense_off);
     MH_HIP(hipGetLastError());
-    const uint64_t nwg = (nseg + mh::kCompactSegs - 1) / mh::kCompactSegs;
-    hipLaunchKernelGGL(mh::k_compact<false>, dim3((unsigned)nwg), dim3(256), 0, st, payload,
+    hipLaunchKernelGGL(mh::k_compact<false>, dim3(groups), dim3(256), 0, st, payload,
                        (const uint64_t *)p->d_seg_off, seg_words, dense_off, dense, dense_cap_words, nseg, total_words);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1073,11 +977,8 @@ int mh_synth_poisson(uint8_t *data, const uint64_t *ch_off, const uint64_t *ch_l
                      uint64_t max_len, const uint32_t *thr, uint64_t seed, void *stream)
 {
     if (!data || !ch_off || !ch_len || !thr || C == 0) return fail(MH_ERR_ARG, "mh_synth_poisson: bad argument");
-    uint64_t bx = (max_len + 256 * 16 - 1) / (256 * 16);
-    if (bx == 0) bx = 1;
-    if (bx > 4096) bx = 4096;
-    const uint32_t by = C > 65535 ? 65535 : C;
-    hipLaunchKernelGGL(mh::k_synth, dim3((unsigned)bx, by), dim3(256), 0, (hipStream_t)stream, data,
+    const mh::GridXY g = mh::synth_grid(max_len, C);
+    hipLaunchKernelGGL(mh::k_synth, dim3(g.x, g.y), dim3(256), 0, (hipStream_t)stream, data,
                        ch_off, ch_len, C, thr, seed);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1090,22 +991,11 @@ int mh_rebin(const uint8_t *data, const uint64_t *in_off, const uint64_t *in_len
     if (!data || !in_off || !in_len || !out || !out_off || C == 0 || r == 0)
         return fail(MH_ERR_ARG, "mh_rebin: bad argument");
     if (r > 4096) return fail(MH_ERR_ARG, "mh_rebin: r=%u above 4096", r);
-    const uint32_t by = C > 65535 ? 65535 : C;
     if (r >= 4) {
-        // unit = g bins = u whole dwords; tile = upt units (<= 32 KiB, whole passes of 256 threads
-        // when there are that many); a workgroup walks 4 consecutive tiles of a channel
-        const uint32_t g = r % 4 == 0 ? 1u : r % 2 == 0 ? 2u : 4u;
-        const uint32_t u = g * r / 4;
-        uint32_t upt = mh::kRebinTileBytes / 4 / u;
-        if (upt >= 256) upt -= upt % 256;
-        const uint32_t tpw = 4;
-        const uint64_t tile_bytes = (uint64_t)upt * u * 4;
-        uint64_t bx = ((max_len + tile_bytes - 1) / tile_bytes + tpw - 1) / tpw;
-        if (bx == 0) bx = 1;
-        if (bx > 65535) bx = 65535;
-#define MH_REBIN3(SAT_, R_)                                                                              \
-    hipLaunchKernelGGL((mh::k_rebin3<SAT_, R_>), dim3((unsigned)bx, by), dim3(256), 0, (hipStream_t)stream, \
-                       data, in_off, in_len, C, r, g, u, upt, tpw, out, out_off)
+        const mh::Rebin3Launch l = mh::rebin3_launch(max_len, C, r);
+#define MH_REBIN3(SAT_, R_)                                                                                      \
+    hipLaunchKernelGGL((mh::k_rebin3<SAT_, R_>), dim3(l.grid.x, l.grid.y), dim3(256), 0, (hipStream_t)stream, \
+                       data, in_off, in_len, C, r, l.g, l.u, l.upt, l.tpw, out, out_off)
 #define MH_REBIN3_R(R_)               \
     do {                              \
         if (saturate)                 \
@@ -1126,30 +1016,23 @@ int mh_rebin(const uint8_t *data, const uint64_t *in_off, const uint64_t *in_len
         MH_HIP(hipGetLastError());
         return MH_OK;
     }
-    const uint64_t bins_per_tile = mh::kRebinTileBytes / r;
-    uint64_t bx = ((max_len + r - 1) / r + bins_per_tile - 1) / bins_per_tile;
-    if (bx == 0) bx = 1;
-    if (bx > 4096) bx = 4096;
+    const mh::GridXY g = mh::rebin2_grid(max_len, C, r);
     if (saturate)
-        hipLaunchKernelGGL(mh::k_rebin2<true>, dim3((unsigned)bx, by), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(mh::k_rebin2<true>, dim3(g.x, g.y), dim3(256), 0, (hipStream_t)stream,
                            data, in_off, in_len, C, r, out, out_off);
     else
-        hipLaunchKernelGGL(mh::k_rebin2<false>, dim3((unsigned)bx, by), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(mh::k_rebin2<false>, dim3(g.x, g.y), dim3(256), 0, (hipStream_t)stream,
                            data, in_off, in_len, C, r, out, out_off);
     MH_HIP(hipGetLastError());
     return MH_OK;
 }
 
-// The grid of the transposing kernels over T x C with tpw tiles of a strip per workgroup visit: strips of kTr2C
-// channels times visits, in one grid dimension (strip fastest), the visits capped so that the product fits 31 bits.
+// the one-dimensional grid of the transposing kernels (mh_launch.hpp)
 static int transposed_grid(const char *who, uint64_t T, uint32_t C, uint32_t tpw, unsigned *grid)
 {
-    uint64_t bx = ((T + mh::kTr2T - 1) / mh::kTr2T + tpw - 1) / tpw;
-    const uint32_t by = (C + mh::kTr2C - 1) / mh::kTr2C;
-    if (bx > 0x7FFFFFFFull / by) bx = 0x7FFFFFFFull / by;
-    if (by > 65535) return fail(MH_ERR_ARG, "%s: C=%u too large", who, C);
-    *grid = (unsigned)(bx * by);
-    return MH_OK;
+    mh::Msg m;
+    const int rc = mh::transposed_grid(m, who, T, C, tpw, grid);
+    return rc ? fail(rc, m) : MH_OK;
 }
 
 int mh_deinterleave(const uint8_t *in, uint64_t T, uint32_t C, uint8_t *out, const uint64_t *out_off,
@@ -1171,7 +1054,7 @@ int mh_deinterleave_packed(const uint8_t *in, uint64_t T, uint32_t C, uint32_t b
 {
     if (!in || !out || !out_off || C == 0) return fail(MH_ERR_ARG, "mh_deinterleave_packed: bad argument");
     if (bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mh_deinterleave_packed: bits=%u (4 or 2)", bits);
-    if (!chunk_stride_ok(chunk_stride, bits))
+    if (!mh::chunk_stride_ok(chunk_stride, bits))
         return fail(MH_ERR_ARG, "mh_deinterleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
     if (T == 0) return MH_OK;
     const uint32_t tpw = bits == 2 ? (uint32_t)mh::P2<2>::kTpw : (uint32_t)mh::P2<4>::kTpw;  // tiles of a visit held in LDS
@@ -1207,7 +1090,7 @@ int mh_interleave_packed(const uint8_t *in, const uint64_t *in_off, uint64_t T, 
 {
     if (!in || !in_off || !out || C == 0) return fail(MH_ERR_ARG, "mh_interleave_packed: bad argument");
     if (bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mh_interleave_packed: bits=%u (4 or 2)", bits);
-    if (!chunk_stride_ok(chunk_stride, bits))
+    if (!mh::chunk_stride_ok(chunk_stride, bits))
         return fail(MH_ERR_ARG, "mh_interleave_packed: chunk_stride=%llu", (unsigned long long)chunk_stride);
     if (T == 0) return MH_OK;
     const uint32_t tpw = 4;
@@ -1235,12 +1118,8 @@ int mh_sweep_create(mh_sweep **sweep, const uint64_t *ch_off, const uint64_t *ch
 {
     if (!sweep || !ch_off || !ch_len || !hist_bits) return fail(MH_ERR_ARG, "mh_sweep_create: NULL argument");
     *sweep = nullptr;
-    if (C == 0 || nh == 0 || nh > 16) return fail(MH_ERR_ARG, "mh_sweep_create: C=%u nh=%u", C, nh);
-    for (uint32_t i = 0; i < nh; ++i)
-        if (hist_bits[i] > 30) return fail(MH_ERR_ARG, "hist_bits[%u]=%u outside 0..30", i, hist_bits[i]);
-    for (uint32_t c = 0; c < C; ++c)
-        if (ch_len[c] == 0)
-            return fail(MH_ERR_EMPTY_CHANNEL, "channel %u has no bins (the reference raises IndexError)", c);
+    mh::Msg m;
+    if (int rc = mh::sweep_check_args(m, ch_len, C, hist_bits, nh)) return fail(rc, m);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(MH_ERR_NO_DEVICE, "no HIP device visible (libmuahuff has no CPU fallback)");
@@ -1249,46 +1128,13 @@ int mh_sweep_create(mh_sweep **sweep, const uint64_t *ch_off, const uint64_t *ch
     mh_sweep *w = new (std::nothrow) mh_sweep;
     if (!w) return fail(MH_ERR_ARG, "out of host memory");
     w->device = dev;
-    w->C = C;
-    w->nh = nh;
-    w->ni = 2 * nh + 1;
-    const uint32_t np = w->ni + 1;
-    w->bounds.resize((size_t)C * np);
-    std::vector<uint32_t> tile_ch, tile_n, tile_slot;
-    std::vector<uint64_t> tile_start, slot_len((size_t)C * w->ni), off(ch_off, ch_off + C);
-    for (uint32_t c = 0; c < C; ++c) {
-        const uint64_t T = ch_len[c];
-        uint64_t *b = &w->bounds[(size_t)c * np];
-        uint32_t k = 0;
-        b[k++] = 0;
-        for (uint32_t i = 0; i < nh; ++i) {
-            const uint64_t lim = (uint64_t)1 << hist_bits[i];
-            const uint64_t cut = T < lim ? T : lim;  // functions_1.py:59-64
-            const uint64_t e = cut + T / 2;          // get_BR_with_approx_sort.py:180
-            b[k++] = cut;
-            b[k++] = e > T ? T : e;
-        }
-        b[k++] = T;
-        for (uint32_t i = 1; i < np; ++i)  // insertion sort, np <= 34
-            for (uint32_t j = i; j > 0 && b[j] < b[j - 1]; --j) {
-                const uint64_t t = b[j];
-                b[j] = b[j - 1];
-                b[j - 1] = t;
-            }
-        for (uint32_t j = 0; j < w->ni; ++j) {
-            const uint64_t lo = b[j], hi = b[j + 1], slot = (uint64_t)c * w->ni + j;
-            slot_len[slot] = hi - lo;
-            for (uint64_t first = lo; first < hi; first += mh::kHistTileBytes) {
-                tile_ch.push_back(c);
-                tile_slot.push_back((uint32_t)slot);
-                tile_start.push_back(first);
-                tile_n.push_back((uint32_t)(hi - first < mh::kHistTileBytes ? hi - first : mh::kHistTileBytes));
-            }
-        }
-    }
-    w->n_tiles = tile_ch.size();
-    w->n_slots = (uint64_t)C * w->ni;
-    const mh::SweepArena a = mh::sweep_arena(off, tile_ch, tile_n, tile_slot, tile_start, slot_len);
+    mh::SweepHost h;
+    mh::sweep_host_build(h, ch_off, ch_len, C, hist_bits, nh);
+    w->ni = h.ni;
+    w->n_tiles = h.tile_ch.size();
+    w->n_slots = h.slot_len.size();
+    const mh::SweepArena a = mh::sweep_arena(h);
+    w->bounds = std::move(h.bounds);  // (not a table: what mh_sweep_info reports)
     if (int rc = w->arena.create(a)) {
         mh_sweep_destroy(w);
         return rc;
@@ -1332,8 +1178,10 @@ int mh_power_draws(const double *br, uint32_t n_br, const int32_t *idx, uint32_t
 {
     if (!br || !idx || !x || n_br == 0 || x_stride == 0) return fail(MH_ERR_ARG, "mh_power_draws: bad argument");
     if (n_draws == 0) return MH_OK;
-    if (n_draws > 0x7FFFFFFFull * 256) return fail(MH_ERR_ARG, "mh_power_draws: too many draws for one launch");
-    hipLaunchKernelGGL(mh::k_power_draws, dim3((unsigned)((n_draws + 255) / 256)), dim3(256), 0, (hipStream_t)stream, br,
+    mh::Msg m;
+    unsigned grid;
+    if (int rc = mh::per_item_grid(m, "mh_power_draws", "draws", n_draws, &grid)) return fail(rc, m);
+    hipLaunchKernelGGL(mh::k_power_draws, dim3(grid), dim3(256), 0, (hipStream_t)stream, br,
                        idx, Z, n_draws, comm_energy, per_channels, static_power, x, x_stride);
     MH_HIP(hipGetLastError());
     return MH_OK;
@@ -1343,8 +1191,10 @@ int mh_reduce_rows(const double *vals, const uint64_t *row_off, uint64_t n_rows,
 {
     if (!vals || !row_off || !sum || !mx) return fail(MH_ERR_ARG, "mh_reduce_rows: NULL argument");
     if (n_rows == 0) return MH_OK;
-    if (n_rows > 0x7FFFFFFFull * 256) return fail(MH_ERR_ARG, "mh_reduce_rows: too many rows for one launch");
-    hipLaunchKernelGGL(mh::k_reduce_rows, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vals,
+    mh::Msg m;
+    unsigned grid;
+    if (int rc = mh::per_item_grid(m, "mh_reduce_rows", "rows", n_rows, &grid)) return fail(rc, m);
+    hipLaunchKernelGGL(mh::k_reduce_rows, dim3(grid), dim3(256), 0, (hipStream_t)stream, vals,
                        row_off, n_rows, sum, mx);
     MH_HIP(hipGetLastError());
     return MH_OK;

@@ -38,7 +38,7 @@ const char *mhi_last_error(void);
 /* ticks: device, all channels' event time stamps back to back; channel c owns ticks[ev_off[c] .. ev_off[c+1]),
  * non-decreasing within the channel (duplicates allowed).  ev_off: device, C + 1 entries.
  * Bin b of a channel counts its events with origin + b*period <= tick < origin + (b+1)*period, b < T.
- * Events before origin or at/after origin + T*period are ignored.  period >= 1, T >= 1, C >= 1, ticks < 2^63;
+ * Events before origin or at/after origin + T*period are ignored.  period >= 1, T >= 1, 1 <= C < 2^31, ticks < 2^63;
  * origin + T*period must not exceed 2^63 (else MH_ERR_ARG: no tick could lie beyond it, and the bounds of every bin
  * then fit 64 bits without a wrap).
  * bits = 8: out + out_off[c] receives T bytes min(count, 255)                (MATLAB uint8(), Sabes loader :54)

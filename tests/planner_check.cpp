@@ -23,14 +23,34 @@
 // here and not by the header), "K" + the staged 16-byte SCLV rows as words, and "P n" + n lines "ch start n" of the
 // staged calibration tiles where the header builds them (a packed plan without planner tiles; n = 0 otherwise).  The
 // staged blob is compared with the planner's vectors byte for byte here.
+// With --validate (tests/test_host_validate.py) the walk of a stored stream (csrc/mh_validate.hpp, what mh_validate_stream
+// and mh_validate_segments run behind their NULL checks).  A case is a plan line in the first format, then
+//     n_segments seg_words[0..n_segments)  peak[0..C) enc[0..C)  payload_words <payload>  n_walks <walk>...
+// <payload>: the words in decimal ("-" for none), or @FILE, a raw little-endian file of them; <walk>: null n_idx seg_idx[0..n_idx)
+// seg_off[0..n_segments), null = 1 passing a NULL payload.  The payload sits in a heap block of EXACTLY payload_words
+// words, so a read of one word behind it stops the program.  Output: "S rc message" for the stream walk, then
+// "G rc message" per segment walk (rc and message: what the ABI call returns and leaves in mh_last_error).
+// With --sweep (tests/test_host_sweep_planner.py) the planner of mh_sweep_create (csrc/mh_sweep_planner.hpp), cases
+//     C nh hist_bits[0..nh) len[0..C)
+// Output: "error rc" for refused arguments, else "W ni ntiles tables_bytes scratch_bytes", "B" + the C * (ni + 1)
+// bounds, "L" + the C * ni slot lengths and one line "T ch slot start n" per tile; sweep_arena's staged blob is compared
+// with the vectors here, as --arena does.
+// With --geometry (tests/test_host_launch_geometry.py) the capped launch grids of csrc/mh_launch.hpp, one launch per
+// line: synth max_len C | rebin max_len C r | fills max_fill per_block nfill | transposed T C tpw | items n |
+// compact nseg | bin_events C T period | seg_crc32 n_list | chunk_stride stride bits.  Output per line: the name, the
+// grid and the derived kernel arguments, or "name error rc message".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
+#include "mh_launch.hpp"
 #include "mh_plan_arena.hpp"
 #include "mh_planner.hpp"
 #include "mh_select.hpp"
+#include "mh_sweep_planner.hpp"
+#include "mh_validate.hpp"
 #include "mh_worklist.hpp"
 
 #define CHECK(cond)                                                    \
@@ -41,40 +61,54 @@
         }                                                              \
     } while (0)
 
-// One plan case from stdin (with_bits: input_bits after seg_chunks) -> p.  1: built; 2: the arguments were rejected
-// ("error <code>" printed); 0: end of input; -1: a malformed case.
-static int read_plan(bool with_bits, mh::PlanHost &p)
-{
+// The arguments of one plan case from stdin (with_bits: input_bits after seg_chunks).  1: read; 0: end of input; -1: malformed.
+struct PlanArgs {
     unsigned C, S, h, mode, window, K, sc, bits = 8;
-    if (scanf("%u %u %u %u %u %u %u", &C, &S, &h, &mode, &window, &K, &sc) != 7) return 0;
-    if (with_bits && scanf("%u", &bits) != 1) return -1;
-    std::vector<uint64_t> len(C), off(C);
-    std::vector<uint8_t> sclv((size_t)K * S);
+    std::vector<uint64_t> len, off;
+    std::vector<uint8_t> sclv;
+};
+
+static int read_plan_args(bool with_bits, PlanArgs &a)
+{
+    if (scanf("%u %u %u %u %u %u %u", &a.C, &a.S, &a.h, &a.mode, &a.window, &a.K, &a.sc) != 7) return 0;
+    a.bits = 8;
+    if (with_bits && scanf("%u", &a.bits) != 1) return -1;
+    a.len.assign(a.C, 0), a.off.assign(a.C, 0);
+    a.sclv.assign((size_t)a.K * a.S, 0);
     uint64_t o = 0;
-    for (unsigned c = 0; c < C; ++c) {
+    for (unsigned c = 0; c < a.C; ++c) {
         unsigned long long v;
         if (scanf("%llu", &v) != 1) return -1;
-        len[c] = v;
-        off[c] = o;
+        a.len[c] = v;
+        a.off[c] = o;
         o += (v + 15) & ~15ull;
     }
-    for (auto &b : sclv) {
+    for (auto &b : a.sclv) {
         unsigned v;
         if (scanf("%u", &v) != 1) return -1;
         b = (uint8_t)v;
     }
+    return 1;
+}
+
+// One plan case from stdin -> p.  1: built; 2: the arguments were rejected ("error <code>" printed); 0: end of input;
+// -1: a malformed case.
+static int read_plan(bool with_bits, mh::PlanHost &p)
+{
+    PlanArgs a;
+    if (const int got = read_plan_args(with_bits, a); got <= 0) return got;
     const char *msg = "";
     uint32_t arg = 0, maxlen = 0;
-    const int rc = mh::plan_check_args(len.data(), C, S, h, mode, window, sclv.data(), K, &maxlen, &msg, &arg);
+    const int rc = mh::plan_check_args(a.len.data(), a.C, a.S, a.h, a.mode, a.window, a.sclv.data(), a.K, &maxlen, &msg, &arg);
     if (rc != MH_OK) {
         printf("error %d\n", rc);
         return 2;
     }
     p = mh::PlanHost();
-    p.info.C = C; p.info.S = S; p.info.h = h; p.info.mode = mode; p.info.window = window;
-    p.info.K = K; p.info.seg_chunks = sc; p.info.maxlen = maxlen;
-    p.input_bits = bits;
-    mh::plan_host_build(p, off.data(), len.data(), sclv.data());
+    p.info.C = a.C; p.info.S = a.S; p.info.h = a.h; p.info.mode = a.mode; p.info.window = a.window;
+    p.info.K = a.K; p.info.seg_chunks = a.sc; p.info.maxlen = maxlen;
+    p.input_bits = a.bits;
+    mh::plan_host_build(p, a.off.data(), a.len.data(), a.sclv.data());
     return 1;
 }
 
@@ -262,8 +296,186 @@ static int arena()
     return got < 0;
 }
 
+static bool read_u64s(std::vector<uint64_t> &v)
+{
+    for (auto &x : v) {
+        unsigned long long t;
+        if (scanf("%llu", &t) != 1) return false;
+        x = t;
+    }
+    return true;
+}
+
+static bool read_u8s(std::vector<uint8_t> &v)
+{
+    for (auto &x : v) {
+        unsigned t;
+        if (scanf("%u", &t) != 1) return false;
+        x = (uint8_t)t;
+    }
+    return true;
+}
+
+static int validate()
+{
+    PlanArgs a;
+    int got;
+    while ((got = read_plan_args(false, a)) > 0) {
+        unsigned long long nseg, nwords, nwalks;
+        if (scanf("%llu", &nseg) != 1) return 1;
+        std::vector<uint64_t> seg_words(nseg);
+        std::vector<uint8_t> peak(a.C), enc(a.C);
+        if (!read_u64s(seg_words) || !read_u8s(peak) || !read_u8s(enc) || scanf("%llu", &nwords) != 1) return 1;
+        const std::unique_ptr<uint32_t[]> payload(new uint32_t[nwords]);  // exactly the words: nothing behind them is readable
+        char tok[4096];
+        for (unsigned long long i = 0; i < nwords || i == 0; ++i) {
+            if (scanf("%4095s", tok) != 1) return 1;
+            if (i == 0 && tok[0] == '@') {
+                FILE *f = fopen(tok + 1, "rb");
+                if (!f) return 1;
+                const size_t n = fread(payload.get(), 4, nwords, f);
+                const bool whole = n == nwords && fgetc(f) == EOF;
+                fclose(f);
+                if (!whole) return 1;
+                break;
+            }
+            if (i >= nwords) {  // no words: "-"
+                if (strcmp(tok, "-")) return 1;
+                break;
+            }
+            payload[i] = (uint32_t)strtoul(tok, nullptr, 10);
+        }
+        {   // mh_validate_stream
+            mh::PlanHost H;
+            mh::Msg m;
+            int rc = mh::stored_plan_host(m, "mh_validate_stream", a.len.data(), a.C, a.S, a.h, a.mode, a.window, a.sclv.data(),
+                                           a.K, a.sc, nseg, H);
+            if (!rc) rc = mh::validate_stream(m, H, payload.get(), nwords, seg_words.data(), peak.data(), enc.data());
+            printf("S %d %s\n", rc, m.text);
+        }
+        if (scanf("%llu", &nwalks) != 1) return 1;
+        for (unsigned long long k = 0; k < nwalks; ++k) {  // mh_validate_segments
+            unsigned null;
+            unsigned long long n_idx;
+            if (scanf("%u %llu", &null, &n_idx) != 2 || (null && n_idx)) return 1;
+            std::vector<uint64_t> seg_idx(n_idx), seg_off(nseg);
+            if (!read_u64s(seg_idx) || !read_u64s(seg_off)) return 1;
+            mh::PlanHost H;
+            mh::Msg m;
+            int rc = mh::stored_plan_host(m, "mh_validate_segments", a.len.data(), a.C, a.S, a.h, a.mode, a.window,
+                                           a.sclv.data(), a.K, a.sc, nseg, H);
+            if (!rc)
+                rc = mh::validate_segments(m, "mh_validate_segments", H, null ? nullptr : payload.get(), nwords, seg_off.data(),
+                                           seg_words.data(), seg_idx.data(), n_idx, peak.data(), enc.data());
+            printf("G %d %s\n", rc, m.text);
+        }
+    }
+    return got < 0;
+}
+
+static int sweep()
+{
+    unsigned C, nh;
+    while (scanf("%u %u", &C, &nh) == 2) {
+        if (C > (1u << 20) || nh > 64) return 1;
+        std::vector<uint32_t> bits(nh);
+        for (auto &b : bits)
+            if (scanf("%u", &b) != 1) return 1;
+        std::vector<uint64_t> len(C), off(C);
+        if (!read_u64s(len)) return 1;
+        uint64_t o = 0;
+        for (unsigned c = 0; c < C; ++c) {
+            off[c] = o;
+            o += (len[c] + 15) & ~15ull;
+        }
+        mh::Msg m;
+        if (const int rc = mh::sweep_check_args(m, len.data(), C, bits.data(), nh)) {
+            printf("error %d\n", rc);
+            continue;
+        }
+        mh::SweepHost w;
+        mh::sweep_host_build(w, off.data(), len.data(), C, bits.data(), nh);
+        const size_t nt = w.tile_ch.size();
+        CHECK(w.C == C && w.nh == nh && w.ni == 2 * nh + 1 && w.ch_off == off);
+        CHECK(w.bounds.size() == (size_t)C * (w.ni + 1) && w.slot_len.size() == (size_t)C * w.ni);
+        CHECK(w.tile_n.size() == nt && w.tile_slot.size() == nt && w.tile_start.size() == nt);
+        const mh::SweepArena a = mh::sweep_arena(w);
+        CHECK(staged(a, a.ch_off, w.ch_off) && staged(a, a.tile_ch, w.tile_ch) && staged(a, a.tile_n, w.tile_n));
+        CHECK(staged(a, a.tile_slot, w.tile_slot) && staged(a, a.tile_start, w.tile_start) && staged(a, a.slot_len, w.slot_len));
+        CHECK(a.regions.size() == 7 && a.hist.present && a.hist.off >= a.tables_bytes && a.hist.bytes == w.slot_len.size() * 16 * 8);
+        CHECK(a.hist.off + a.hist.bytes <= a.bytes() && a.tables_bytes % mh::kArenaAlign == 0 && a.scratch_bytes % mh::kArenaAlign == 0);
+        printf("W %u %zu %zu %zu\nB", w.ni, nt, a.tables_bytes, a.scratch_bytes);
+        for (uint64_t b : w.bounds) printf(" %llu", (unsigned long long)b);
+        printf("\nL");
+        for (uint64_t l : w.slot_len) printf(" %llu", (unsigned long long)l);
+        printf("\n");
+        for (size_t t = 0; t < nt; ++t)
+            printf("T %u %u %llu %u\n", w.tile_ch[t], w.tile_slot[t], (unsigned long long)w.tile_start[t], w.tile_n[t]);
+    }
+    return !feof(stdin);
+}
+
+static int geometry()
+{
+    char name[32];
+    while (scanf("%31s", name) == 1) {
+        unsigned long long v[3] = {0, 0, 0};
+        const bool two = !strcmp(name, "synth") || !strcmp(name, "chunk_stride");
+        const bool one = !strcmp(name, "items") || !strcmp(name, "compact") || !strcmp(name, "seg_crc32");
+        for (int i = 0; i < (one ? 1 : two ? 2 : 3); ++i)
+            if (scanf("%llu", &v[i]) != 1) return 1;
+        mh::Msg m;
+        int rc = MH_OK;
+        if (!strcmp(name, "synth")) {
+            const mh::GridXY g = mh::synth_grid(v[0], (uint32_t)v[1]);
+            printf("synth %u %u\n", g.x, g.y);
+        } else if (!strcmp(name, "rebin")) {
+            if (v[2] < 1 || v[2] > 4096) return 1;  // (what mh_rebin refuses before it looks at a grid)
+            if (v[2] < 4) {
+                const mh::GridXY g = mh::rebin2_grid(v[0], (uint32_t)v[1], (uint32_t)v[2]);
+                printf("rebin %u %u\n", g.x, g.y);
+            } else {
+                const mh::Rebin3Launch l = mh::rebin3_launch(v[0], (uint32_t)v[1], (uint32_t)v[2]);
+                printf("rebin %u %u %u %u %u %u\n", l.grid.x, l.grid.y, l.g, l.u, l.upt, l.tpw);
+            }
+        } else if (!strcmp(name, "fills")) {
+            if (v[1] == 0) return 1;
+            printf("fills %u", mh::fill_grid_x(v[0], v[1]));
+            for (uint64_t f = 0; f < v[2]; f += mh::kFillMaxRecords) printf(" %u", mh::fill_grid_y(v[2], f));
+            printf("\n");
+        } else if (!strcmp(name, "transposed")) {
+            if (v[1] == 0 || v[2] == 0) return 1;
+            uint32_t grid = 0;
+            if (!(rc = mh::transposed_grid(m, "transposed", v[0], (uint32_t)v[1], (uint32_t)v[2], &grid))) printf("transposed %u\n", grid);
+        } else if (!strcmp(name, "items")) {
+            uint32_t grid = 0;
+            if (!(rc = mh::per_item_grid(m, "items", "items", v[0], &grid))) printf("items %u\n", grid);
+        } else if (!strcmp(name, "compact")) {
+            const uint32_t blocks = mh::compact_scan_blocks(v[0]);
+            printf("compact %d %u %u\n", (int)(blocks <= 1), blocks, mh::compact_groups(v[0]));
+        } else if (!strcmp(name, "bin_events")) {
+            if (v[0] == 0 || v[1] == 0 || v[2] == 0) return 1;
+            mh::BinLaunch l;
+            if (!(rc = mh::bin_events_launch(m, (uint32_t)v[0], v[1], v[2], &l)))
+                printf("bin_events %u %llu %llu %llu %u\n", l.grid, (unsigned long long)l.nchunks, (unsigned long long)l.span,
+                       (unsigned long long)l.nspans, l.div_mode);
+        } else if (!strcmp(name, "seg_crc32")) {
+            printf("seg_crc32 %u\n", mh::seg_crc_grid(v[0]));
+        } else if (!strcmp(name, "chunk_stride")) {
+            printf("chunk_stride %d\n", (int)mh::chunk_stride_ok(v[0], (uint32_t)v[1]));
+        } else {
+            return 1;
+        }
+        if (rc) printf("%s error %d %s\n", name, rc, m.text);
+    }
+    return !feof(stdin);
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--validate")) return validate();
+    if (argc > 1 && !strcmp(argv[1], "--sweep")) return sweep();
+    if (argc > 1 && !strcmp(argv[1], "--geometry")) return geometry();
     if (argc > 1 && !strcmp(argv[1], "--arena")) return arena();
     if (argc > 1 && !strcmp(argv[1], "--cells")) return cells(false);
     if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);

@@ -1,16 +1,18 @@
 """The launches of libmuahuff.so whose grid is capped, at shapes that cross the cap: the stride loop, the second launch
-or the refusal that covers what the capped grid does not (csrc/muahuff.hip; DESIGN.md lists every capped launch).
+or the refusal that covers what the capped grid does not (the grids: csrc/mh_launch.hpp; DESIGN.md lists every capped launch).
 
-    mh_rebin           more channels than 65535 grid rows (k_rebin2, k_rebin3);  a channel of more than 4096 tiles (k_rebin2)
-    mh_synth_poisson   more channels than 65535 grid rows;  a channel of more than 4096 workgroups' samples (k_synth)
-    mh_decode_range /  more than 65535 fill records: several launches (launch_fills);  one fill longer than what 1024
-    mh_decode_rebin    workgroups zero in a pass (k_range_fill, k_rebin_fill)
+    mh_rebin           more channels than 65535 grid rows (channel_rows; k_rebin2, k_rebin3);  a channel of more than 4096
+                       tiles (rebin2_grid; k_rebin2)
+    mh_synth_poisson   more channels than 65535 grid rows;  a channel of more than 4096 workgroups' samples (synth_grid; k_synth)
+    mh_decode_range /  more than 65535 fill records: several launches (fill_grid_y);  one fill longer than what 1024
+    mh_decode_rebin    workgroups zero in a pass (fill_grid_x; k_range_fill, k_rebin_fill)
     mh_deinterleave, mh_deinterleave_packed, mh_interleave, mh_interleave_packed   more than 65535 strips of 128 channels
-                       are refused; 65535 strips are not
+                       are refused; 65535 strips are not (transposed_grid)
 
-The launched grid cannot be read back, so every test restates the rule it targets (the host function is named next to
-it) and asserts that its shape crosses it: a coverage guard, never an expectation.  When the rule changes in the
-library, that assertion is the reminder to move the shape.
+The grid a call launched cannot be read back from the device, so every test restates the rule it targets (its function
+in csrc/mh_launch.hpp is named next to it) and asserts that its shape crosses it: a coverage guard, never an
+expectation.  The functions themselves are read back off-device, at these shapes too, by
+tests/test_host_launch_geometry.py.  When a rule changes in the header, the assertion here is the reminder to move the shape.
 
 Every output lies in a buffer filled with a non-zero canary in front of, between and behind the channels or rows; the
 WHOLE buffer is compared with the CPU reference, exactly.  A bin that no workgroup wrote shows as the canary.
@@ -99,7 +101,7 @@ R_MANY = (2, 3, 5, 7, 100)        # k_rebin2, k_rebin2, k_rebin3<., 5>, k_rebin3
 @pytest.mark.parametrize("r", R_MANY)
 def test_rebin_more_channels_than_grid_rows(mh, r):
     C = C_BIG
-    by = min(C, YMAX)                                   # mh_rebin: by = C > 65535 ? 65535 : C
+    by = min(C, YMAX)                                   # channel_rows (mh_rebin): y = min(C, 65535)
     assert -(-C // by) == 3 and C - 2 * by == 3         # ch += gridDim.y: three trips, the last one of three workgroups
     rng = np.random.RandomState(100 + r)
     lens = rng.randint(1, 301, size=C).astype(np.int64)
@@ -161,7 +163,7 @@ def test_rebin_one_channel_behind_the_tile_clamp(mh, long_channel, r, sat):
     lens = np.array((_long_len(r),) + SHORT, np.int64)
     in_off = np.array((0,) + short_off, np.int64)
     assert in_off[1] >= lens[0]
-    bins_per_tile = TILE // r                            # mh_rebin, r < 4: bx = ceil(ceil(max_len / r) / bins_per_tile)
+    bins_per_tile = TILE // r                            # rebin2_grid (r < 4): x = ceil(ceil(max_len / r) / bins_per_tile)
     bx = -(-(-(-int(lens.max()) // r)) // bins_per_tile)
     assert bx == 4096 + 2 > 4096                         # ... clamped to 4096: b0 += gridDim.x * bins_per_tile, two tiles
     assert (-(-int(lens[0]) // r)) % bins_per_tile not in (0, bins_per_tile - 1) and lens[0] % 16   # the last tile is cut
@@ -208,7 +210,7 @@ def _synth(mh, lens, thr, seed):
 
 def test_synth_one_channel_behind_the_workgroup_clamp(mh):
     lens = [4096 * 4096 + 5 * 4096 + 7, 1, 15, 16, 17, 4097]
-    bx = -(-max(lens) // (256 * 16))                     # mh_synth_poisson: bx = ceil(max_len / 4096) ...
+    bx = -(-max(lens) // (256 * 16))                     # synth_grid: x = ceil(max_len / 4096) ...
     assert bx == 4096 + 6 > 4096                         # ... clamped to 4096: pc += gridDim.x * 256, six workgroups, a cut piece
     thr = mh.synth.thresholds(mh.synth.channel_rates(len(lens), 0.3, 3.0))
     x = _synth(mh, lens, thr, 11)
@@ -217,7 +219,7 @@ def test_synth_one_channel_behind_the_workgroup_clamp(mh):
 
 def test_synth_more_channels_than_grid_rows(mh):
     C = C_BIG
-    by = min(C, YMAX)                                    # mh_synth_poisson: by = C > 65535 ? 65535 : C
+    by = min(C, YMAX)                                    # channel_rows (mh_synth_poisson): y = min(C, 65535)
     assert -(-C // by) == 3 and C - 2 * by == 3          # ch += gridDim.y
     lens = np.random.RandomState(8).randint(1, 41, size=C)
     lens[list(EDGE_CH)] = (1, 15, 16, 17, 40, 33, 1)
@@ -309,7 +311,7 @@ def _many_lens():
 def test_fill_records_in_more_than_one_launch(mh, S, a, b):
     plan, d, flat, lens = _stream(mh, ("many", S), _many_lens(), S, 1.2 if S == 3 else 5.0)
     # walk_query (csrc/mh_worklist.hpp): one record for a row wholly behind its channel's end, one behind the data of a
-    # row that ends inside the range; launch_fills: 65535 records per launch
+    # row that ends inside the range; fill_grid_y: 65535 records per launch
     nfill = int((lens <= a).sum() + ((lens > a) & (lens < b)).sum())
     assert nfill == 2 * YMAX + 2 and -(-nfill // YMAX) == 3          # launches of 65535, 65535 and 2 records
     assert (lens <= a).sum() > (YMAX if a else -1) and (lens[YMAX:] > a).any()
@@ -326,7 +328,7 @@ def test_one_range_fill_behind_the_workgroup_clamp(mh):
     plan, d, flat, lens = _stream(mh, "one", ONE_FILL_LENS, 3, 1.2)
     a, b = 0, RANGE_STOP
     max_fill = b - int(lens.min())
-    nx = -(-max_fill // (256 * 16 * 4))                  # launch_fills(c, 256 * 16 * 4, ...) of mh_decode_range
+    nx = -(-max_fill // (256 * 16 * 4))                  # fill_grid_x(max_fill, 256 * 16 * 4) of mh_decode_range
     assert nx > 1024                                     # ... clamped to 1024: i += gridDim.x * 256 in k_range_fill
     assert 0 < -(-max_fill // 16) % (1024 * 256) <= 4 * 256      # the last pass is taken by a few workgroups only
     rows = _rows(flat, lens, 3, a, b)
@@ -343,7 +345,7 @@ def test_one_rebin_fill_behind_the_workgroup_clamp(mh, sat):
     a, b, r = 0, REBIN_STOP, REBIN_R
     nb = (b - a) // r
     max_fill = nb - -(-int(lens.min()) // r)
-    nx = -(-max_fill // (256 * 16))                      # launch_fills(c, 256 * 16, ...) of decode_rebin
+    nx = -(-max_fill // (256 * 16))                      # fill_grid_x(max_fill, 256 * 16) of mh_decode_rebin
     assert nx > 1024                                     # ... clamped to 1024: i += gridDim.x * 256 in k_rebin_fill
     assert 0 < max_fill % (1024 * 256) <= 4 * 256
     rows = _sums(_rows(flat, lens, 3, a, b).ravel(), r, sat).reshape(len(lens), nb)
@@ -360,7 +362,7 @@ STRIP = 128                       # kTr2C: channels of a strip
 def test_layout_calls_refuse_more_than_65535_strips(mh):
     lib, L = mh._lib.lib(), mh._lib
     T, C = 1, YMAX * STRIP + 1
-    assert -(-C // STRIP) == YMAX + 1                    # by = ceil(C / kTr2C); by > 65535: MH_ERR_ARG (all four calls)
+    assert -(-C // STRIP) == YMAX + 1                    # transposed_grid: strips = ceil(C / 128); above 65535: MH_ERR_ARG (all four calls)
     # real buffers and offsets: a call that wrongly went ahead would stay inside them
     rng = np.random.RandomState(6)
     src = torch.from_numpy(rng.randint(0, 256, size=16 * C + PAD, dtype=np.uint8)).cuda()

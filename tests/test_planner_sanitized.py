@@ -21,6 +21,10 @@ def exe():
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_plan_arena.hpp"),
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_select.hpp"),
             os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_worklist.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_msg.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_validate.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_sweep_planner.hpp"),
+            os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc", "mh_launch.hpp"),
             os.path.join(ROOT, "include", "muahuff.h")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",

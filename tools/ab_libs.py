@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-box A/B of two builds of libmuahuff.so: encode / decode of the roofline set (1024 channels x
 1e7 bins) per S and of the short-channel set, each library in its own child process, alternating.
-env: PLAN=1 (instead: plan creation + destruction, host clock around the pair, median of PLAN_N=20 per shape)  PROBE=1 (placement-probed input copy / payload / output buffers)  SS=3,5,8,10  REPS=2  RATES=lo,hi  H=6 (calibration bits: the window starts at sample 2^H)  SMALL_ONLY=1  BIG_ONLY=1  SEG=0 (chunks per segment, 0 = the planner's choice)
+env: PLAN=1 (instead: plan creation + destruction, host clock around the pair, median of PLAN_N=20 per shape)  SWEEP=1 (instead: the same for mh_sweep_create + mh_sweep_destroy)  PROBE=1 (placement-probed input copy / payload / output buffers)  SS=3,5,8,10  REPS=2  RATES=lo,hi  H=6 (calibration bits: the window starts at sample 2^H)  SMALL_ONLY=1  BIG_ONLY=1  SEG=0 (chunks per segment, 0 = the planner's choice)
 usage: ab_libs.py A.so B.so ...      (children: ab_libs.py --one X.so)"""
 import os
 import subprocess
@@ -44,6 +44,25 @@ def one(path):
             ts = ts[3:]
             print("%-28s %5d x %8d %d-bit : plan create + destroy %9.1f us median (%.1f .. %.1f)"
                   % (os.path.basename(path), C, T, bits, float(np.median(ts)), min(ts), max(ts)), flush=True)
+        return
+    if os.environ.get("SWEEP") == "1":  # mh_sweep_create + mh_sweep_destroy (both synchronise), nine hist_bits: the long and the short recording
+        import ctypes as ct
+        import time
+        L = muahuff._lib.lib()
+        torch.cuda.synchronize()
+        hb = np.arange(2, 11, dtype=np.uint32)
+        for C, T in ((96, 3_600_000), (2400, 72_000)):
+            off, ln = np.arange(C, dtype=np.uint64) * np.uint64((T + 15) // 16 * 16), np.full(C, T, np.uint64)
+            ts = []
+            for _ in range(3 + int(os.environ.get("PLAN_N", "20"))):
+                h = ct.c_void_p()
+                t0 = time.perf_counter()
+                muahuff._lib.check(L.mh_sweep_create(ct.byref(h), off.ctypes.data, ln.ctypes.data, C, hb.ctypes.data, len(hb)))
+                L.mh_sweep_destroy(h)
+                ts.append(1e6 * (time.perf_counter() - t0))
+            ts = ts[3:]
+            print("%-28s %5d x %8d %d hist_bits : sweep create + destroy %9.1f us median (%.1f .. %.1f)"
+                  % (os.path.basename(path), C, T, len(hb), float(np.median(ts)), min(ts), max(ts)), flush=True)
         return
     Ss = [int(v) for v in os.environ.get("SS", "3,5,8,10").split(",")]
     shapes = ((1024, 10_000_000, 30), (2400, 72_000, 50), (96, 72_000, 50), (10_000, 20_000, 50), (96, 3_600_000, 50))
