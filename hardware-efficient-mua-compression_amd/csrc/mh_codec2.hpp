@@ -1551,9 +1551,10 @@ __device__ __forceinline__ void decode_segment_dual(const DecArgs &d, uint64_t p
 // NR payload registers per lane: the next chunk's payload (up to NR*64 words) is fetched into
 // registers while the current chunk decodes, and lands in LDS at the top of the next iteration.
 // All those loads are issued BEFORE the current chunk's 16 output stores, so waiting for them
-// (in-order vmcnt) never waits for a store.  A chunk whose payload exceeds NR*64 words (more
-// than 3 bits/sample when NR = 24; impossible when NR = 17 and maxlen <= 2) takes the
-// per-symbol routine that reads the stream straight from global memory.
+// (in-order vmcnt) never waits for a store.  A chunk whose payload and 3 words of read-ahead exceed
+// NR*64 words takes the per-symbol routine that reads the stream straight from global memory.  The
+// rungs are NR = 17 / 25 / 31 / 32 / 36 (mh_select.hpp): about 3.9 / 4 / 4.5 bits per sample at NR =
+// 31 / 32 / 36; impossible at NR = 17 with maxlen <= 2 and at NR = 25 with maxlen 3.
 constexpr int kDecMinBlocks = 1;  // launch-bounds minimum of the decoders
 // Long channels: up to 4 consecutive segments of ONE channel per workgroup, tables shared at LDS
 // address 0 (the kernel has no static LDS; mh_plan_create verifies that from the code object).

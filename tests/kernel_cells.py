@@ -15,6 +15,10 @@ input_bits of the packed cells) and the table width W.  Every CELL names one ins
 tests/test_host_kernel_cells.py checks without a GPU that the cells and the shipped symbols are the same set and
 that the library's own selection puts every case and layout on its cell's instance; tests/test_gpu_kernel_cells.py
 (encoders, byte decoders) and tests/test_gpu_stream_decode.py (packed decoders) run them against the CPU oracle.
+
+  mixed    the layouts here keep every channel on ONE route per chunk (all staged or all oversize); transitions within
+           a segment -- staged and oversize chunks side by side -- are tests/mixed_chunks.py, run by
+           tests/test_host_mixed_chunks.py and tests/test_gpu_mixed_chunks.py
 """
 from dataclasses import dataclass
 

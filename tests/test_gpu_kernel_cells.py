@@ -11,6 +11,8 @@ multiples of 16, whole chunks and one past), NOSORT and APPROX in turn:
            decode as (0, 0) -- in the in-wave table build (wave form) and in k_lut_preset (workgroup form)
   lanes    alternate 16-sample pieces of the longest and the shortest code: the widest chunk headers
   clip     counts far above 15 (and 3): clipped by the encoder, for packed input first by the intermediate
+  mixed    not here: every pattern above keeps a channel's chunks on one route (all staged or all slow); segments
+           that switch between the routes are tests/test_gpu_mixed_chunks.py (scenarios: tests/mixed_chunks.py)
 
 Packed cells read pieces built on the host (the documented bit layout, _bitpack) or by mh_deinterleave_packed
 (equal-length layouts), contiguous and chunk-blocked.  Every run checks the segment sizes, every used payload word
