@@ -21,7 +21,12 @@ PROTOTYPES = {
     "mhi_unbin_scratch_bytes": (_int, [_u32, _u64, _u64, ct.POINTER(_u64)]),
     "mhi_unbin_count": (_int, [_u32, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
     "mhi_unbin_emit": (_int, [_u32, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _u64, _vp]),
+    "mhi_excess_scratch_bytes": (_int, [_u32, _u64, _u64, ct.POINTER(_u64)]),
+    "mhi_excess_count": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "mhi_excess_emit": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "mhi_excess_apply": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u32, _u64, _u64, _vp]),
 }
+EXCESS_ROWS, EXCESS_COLS = 0, 1   # MHI_EXCESS_ROWS, MHI_EXCESS_COLS
 UNBIN_CSR, UNBIN_AER = 0, 1       # MHI_UNBIN_CSR, MHI_UNBIN_AER
 AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
 
@@ -106,6 +111,47 @@ def unbin_emit(form, x, row_off, rows, cols, origin, period, phase, out_ticks, o
     check(lib().mhi_unbin_emit(int(form), p(x), p(row_off), int(rows), int(cols), int(origin), int(period), int(phase),
                                p(out_ticks), p(out_ch), 8 * out_ch.element_size() if out_ch is not None else 0, cap, p(over),
                                p(scratch), int(scratch.numel()), _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def excess_scratch_bytes(form, rows, cols):
+    """mhi_excess_scratch_bytes: host arithmetic, no device."""
+    b = _u64(0)
+    check(lib().mhi_excess_scratch_bytes(int(form), int(rows), int(cols), ct.byref(b)))
+    return int(b.value)
+
+
+def excess_count(form, x, row_off, lo, hi, rows, cols, threshold, exc_off, total, scratch):
+    """Enqueue mhi_excess_count on the current stream.  x: uint8 device tensor whose data_ptr() is the matrix's first byte;
+    row_off / lo / hi: 64-bit device tensors of `rows` entries (EXCESS_ROWS; lo and hi may be None) or None (EXCESS_COLS, a
+    contiguous time-major [rows, cols] block); exc_off: 64-bit device tensor [channels + 1]; total: 64-bit device tensor
+    [1]; scratch: uint8 device tensor of at least excess_scratch_bytes(form, rows, cols) bytes."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    check(lib().mhi_excess_count(int(form), p(x), p(row_off), p(lo), p(hi), int(rows), int(cols), int(threshold), p(exc_off),
+                                 p(total), p(scratch), int(scratch.numel()), _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def excess_emit(form, x, row_off, lo, hi, rows, cols, threshold, pos, val, over, scratch, capacity=None):
+    """Enqueue mhi_excess_emit on the current stream, after excess_count on the same arguments and scratch.  pos: int32 /
+    uint32 device tensor, val: uint8 device tensor of as many entries; capacity: the entries they hold (default: all of
+    pos); over: 64-bit device tensor [1], zeroed by the caller."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    cap = int(pos.numel()) if capacity is None else int(capacity)
+    check(lib().mhi_excess_emit(int(form), p(x), p(row_off), p(lo), p(hi), int(rows), int(cols), int(threshold), p(pos), p(val),
+                                cap, p(over), p(scratch), int(scratch.numel()), _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def excess_apply(pos, val, first, last, start, stop, r, lead, out_ptr, out_bits, row_stride, col_stride, n_entries=None):
+    """Enqueue mhi_excess_apply on the current stream.  pos (int32 / uint32) and val (uint8): the list, device tensors;
+    first / last: 64-bit device tensors of one entry per output row; out_ptr: the address of element (0, 0); the strides
+    are in bytes."""
+    import torch
+    n = int(pos.numel()) if n_entries is None else int(n_entries)
+    check(lib().mhi_excess_apply(_vp(pos.data_ptr()) if n else None, _vp(val.data_ptr()) if n else None, n,
+                                 _vp(first.data_ptr()), _vp(last.data_ptr()), int(first.numel()), int(start), int(stop), int(r),
+                                 int(lead), _vp(int(out_ptr)), int(out_bits), int(row_stride), int(col_stride),
+                                 _vp(torch.cuda.current_stream().cuda_stream)))
 
 
 def seg_crc32(payload, seg_off, seg_words, n_segments, seg_idx=None, crc=None, expect=None, bad=None, payload_words=None):

@@ -20,6 +20,10 @@ appending with the word of the last complete block.
 Archive revision 2 (create(..., checksum=True)) is revision 1 with "checksum": "crc32" in the header and every block a
 revision-4 container: the CRC-32 of each of its segments, taken on the device as the block is coded, verified there by
 read() on exactly the segments a query uploads, and by verify() over the whole file.
+
+create(..., exact=True) puts "exact": true into the header (the revision stays what it is) and makes every block an
+exact container (container_io: exc_seg / exc_pos / exc_val behind the payload, the sparse list of the counts above S-1),
+so that read() returns the counts themselves.  Plain blocks and exact blocks do not mix.
 """
 import builtins
 import json
@@ -157,6 +161,7 @@ class Reader:
             raise
         self.meta = self.header.get("meta", {})
         self.checksum = self.header.get("checksum") == "crc32"
+        self.exact = self.header.get("exact") is True
         self.T = int(sum(b.Tb for b in self.blocks))
         self._t_first = np.array([b.t_first for b in self.blocks], np.int64)
         self._Tb = np.array([b.Tb for b in self.blocks], np.int64)
@@ -210,12 +215,13 @@ class Reader:
         bf = self.block_file(i)
         b = self.blocks[i]
         _check_member(bf, self.C, self.S, self.mode, self.seg_chunks, self.sclv, payload_words=bf.payload_words,
-                      checksum=self.checksum)
+                      checksum=self.checksum, exact=self.exact)
         if int(bf.ch_len[0]) != b.Tb:
             raise ValueError("corrupt archive: block %d holds %d steps, its record says %d" % (i, int(bf.ch_len[0]), b.Tb))
         return bf
 
-    def read(self, start, stop, channels=None, bin=None, saturate=True, time_major=False, check=True, out=None):  # noqa: A002
+    def read(self, start, stop, channels=None, bin=None, saturate=True, time_major=False, check=True, out=None,  # noqa: A002
+             exact=None):
         """Global samples [start, stop) of the selected channels -> device tensor.
         bin=None: uint8 [n_sel, stop - start], row i = min(x, S-1) of channel channels[i] (None = all; any order,
         repeats allowed), or [stop - start, n_sel] with time_major.
@@ -227,10 +233,16 @@ class Reader:
         in an archive with checksums, verifies them on the device next to each block's upload (one counter per block,
         read where the decode status is read): ValueError names the block and the segment whose checksum does not match;
         a decode that had to abandon a segment raises ValueError.  out: optional tensor of the result's shape and dtype
-        with unit stride along its last axis (not with time_major); the rows are written there and nothing else is."""
+        with unit stride along its last axis (not with time_major); the rows are written there and nothing else is.
+        exact: None = in an archive written with exact=True every block's excess list is added back onto its columns of
+        the result (mhi_excess_apply behind each block's decode, on the same stream), so that x stands where min(x, S-1)
+        stood -- only the entries of the segments that are read are fetched, range-checked on the host with `check` (not
+        CRC'd: excess_crc32 covers a block's lists whole, verify() checks it); False = the lists are not read; True =
+        ValueError in an archive without them."""
         import torch
 
         from . import codec
+        use = cio.wants_excess(self, exact, "archive")
         start, stop, r = int(start), int(stop), None if bin is None else int(bin)
         sel = codec.query_args(self.T, self.C, start, stop, channels, r)
         n, rows = stop - start, int(sel.size)
@@ -246,7 +258,8 @@ class Reader:
             for i, a, b in block_ranges(self._t_first, self._Tb, start, stop):
                 bf = self._checked_block_file(i)
                 _sel, payload, seg_off, segs, peak, enc = cio._range_inputs(bf, a, b, sel, check)
-                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc, i, segs))
+                lists = cio.gather_excess(bf, a, b, sel, check, "archive block %d" % i) if use and payload is not None else None
+                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc, i, segs, lists))
         if not jobs:
             z = torch.zeros((rows, cols), dtype=dtype, device="cuda") if out is None else out.zero_()
             return z.t().contiguous() if time_major else z
@@ -264,12 +277,13 @@ class Reader:
         return codec.to_time_major(res) if r is None else res.t().contiguous()
 
     def read_events(self, start, stop, channels=None, origin=0, period=1, phase=0, check=True, aer=False,  # noqa: A002
-                    ch_dtype=None):
+                    ch_dtype=None, exact=None):
         """Global samples [start, stop) of the selected channels as spike events on the recording's clock: sample t of a
         channel with count k gives k events at the tick origin + t*period + phase -- read(start, stop, channels,
         check=check) followed by events.EventSet.from_counts with the origin moved to origin + start*period, expanded on
-        the device (mhi_unbin_count / mhi_unbin_emit).  What the archive holds is min(count, S-1) per bin, and all of a
-        bin's events get the bin's start + phase.
+        the device (mhi_unbin_count / mhi_unbin_emit).  An archive written with exact=True gives every event that went in
+        (exact as read()); any other holds min(count, S-1) per bin and gives that many.  All of a bin's events get the
+        bin's start + phase.
         -> events.EventSet whose channel k is channels[k] (None = all; any order, repeats allowed).
         aer=True: read(time_major=True) and events.aer_from_counts -> (ticks int64, channels): one merged list in time
         order; the channel numbers are the archive's (mapped through `channels` when a subset was selected; within a
@@ -288,7 +302,7 @@ class Reader:
             if aer:
                 return none, torch.zeros(0, dtype=ch_dtype, device="cuda")
             return events.EventSet(none, np.zeros(int(sel.size) + 1, np.uint64), check=False)
-        x = self.read(start, stop, channels, time_major=aer, check=check)
+        x = self.read(start, stop, channels, time_major=aer, check=check, exact=exact)
         if not aer:
             return events.EventSet.from_counts(x, origin + start * period, period, phase)
         ticks, ch = events.aer_from_counts(x.contiguous(), origin + start * period, period, phase, ch_dtype=ch_dtype)
@@ -299,10 +313,10 @@ class Reader:
     def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads):
         """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride); with
         `bads` a list, the verification of each block's uploaded segments next to its upload: (block, counter) pairs."""
-        from . import codec
+        from . import codec, excess
 
-        def launch(job, fn):
-            bf, a, b, g0, payload, seg_off, peak, enc, i, segs = job
+        def launch(job, fn, lead=0):
+            bf, a, b, g0, payload, seg_off, peak, enc, i, segs, lists = job
             plan = self._plan_for(bf)
             if plan not in plans:
                 plans.append(plan)
@@ -311,7 +325,10 @@ class Reader:
                 bad = cio.enqueue_verify(bf, up[0], up[1], bf.seg_words, segs, True)
                 if bad is not None:
                     bads.append((i, bad))
-            fn(plan, *up, a, b, g0)
+            target = fn(plan, *up, a, b, g0)
+            if lists is not None and len(lists[0]):      # behind the block's decode, into the block's columns
+                excess.apply(*excess.upload(lists[0], lists[1], plan.device), lists[2], lists[3], a, b, 1 if r is None else r,
+                             lead, target)
 
         if r is None:
             if out is None:     # the first block's local sample t at a byte address congruent to t mod 128
@@ -345,7 +362,8 @@ class Reader:
                     tmp = torch.zeros((rows, k * r), dtype=torch.uint8, device=plan.device)
                     plan.decode_range(pay, off, pk, en, sel, a, b, out=tmp[:, lead:lead + b - a])
                     acc[:, g0 // r:g0 // r + k] += tmp.view(rows, k, r).sum(dim=2, dtype=torch.int32)
-                launch(job, edge)
+                    return acc[:, g0 // r:g0 // r + k]
+                launch(job, edge, job[3] % r)
         res = acc.clamp_(max=255).to(torch.uint8) if saturate else acc
         return res if out is None else out.copy_(res)
 
@@ -359,8 +377,8 @@ class Reader:
             raise ValueError("this archive carries no checksums (create(..., checksum=True) writes them)")
         bad = []
         for i in range(len(self.blocks)):
-            c = self.block(i)
-            _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=True)
+            c = self.block(i)      # read whole: an exact block's lists against excess_crc32 and the directory (ValueError)
+            _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=True, exact=self.exact)
             if device:
                 import torch
 
@@ -396,11 +414,14 @@ class Reader:
 
 
 # ---- writer --------------------------------------------------------------------------------------
-def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None, checksum=False):
+def _check_member(c, C, S, mode, seg_chunks, sclv, payload_words=None, checksum=False, exact=False):
     """ValueError unless c (a Compressed or a ContainerFile) is a block of an archive with these parameters: the check
     StreamDecoder.decode_block makes, plus the array sizes the directory arithmetic relies on.  checksum: the archive's
-    blocks are revision-4 containers, each with one checksum per segment."""
+    blocks are revision-4 containers, each with one checksum per segment.  exact: the archive's blocks carry the excess
+    lists -- plain blocks and exact blocks do not mix."""
     hd = c.header
+    if (hd.get("exact") is True) != bool(exact):
+        raise ValueError("a block of an archive %s the excess lists carries %s" % (("with", "none") if exact else ("without", "them")))
     cio._header_fields(hd)
     cio.check_block(c, C, S, mode, seg_chunks, sclv, what="block")
     revision = cio.CHECKSUM_REVISION if checksum else cio.FORMAT_REVISION
@@ -428,11 +449,12 @@ class Writer:
         self.recalibrate = None if recalibrate is None else int(recalibrate)
         self.pipeline = bool(pipeline)
         self.checksum = header.get("checksum") == "crc32"
+        self.exact = header.get("exact") is True
         self._word = word                  # (peak, enc) host arrays to go on with, or None: calibrate on the next block
         self._gpu = None
         self._pending = None
         self._n = 0
-        self._block_header = cio.make_header(self.S, 0, self.mode, WIN_FULL, self.seg_chunks, self.sclv, self.checksum)
+        self._block_header = cio.make_header(self.S, 0, self.mode, WIN_FULL, self.seg_chunks, self.sclv, self.checksum, self.exact)
         self._block_header["preset"] = True    # what StreamEncoder.encode_block writes
 
     # -- records
@@ -453,8 +475,9 @@ class Writer:
         without them (ValueError)."""
         if self.checksum and getattr(c, "seg_crc", None) is None:
             hdr = dict(c.header, format_revision=cio.CHECKSUM_REVISION)
-            c = cio.Compressed(hdr, c.ch_len, c.peak, c.enc, c.skipped, c.ch_bits, c.seg_words, c.payload, cio.seg_crc_host(c))
-        _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=self.checksum)
+            c = cio.Compressed(hdr, c.ch_len, c.peak, c.enc, c.skipped, c.ch_bits, c.seg_words, c.payload, cio.seg_crc_host(c),
+                               getattr(c, "exc_seg", None), getattr(c, "exc_pos", None), getattr(c, "exc_val", None))
+        _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=self.checksum, exact=self.exact)
         self._drain()
         self._write_record(c, int(c.ch_len[0]))
         self._word = (np.array(c.peak, np.uint8), np.array(c.enc, np.uint8))
@@ -484,7 +507,11 @@ class Writer:
         de-interleave, preset encode (with the drift measure when recalibrate is set) and compaction on the current
         stream, then the copies of the block's sizes to pinned memory on the archive's copy stream.  pipeline=True:
         returns then, after writing the PREVIOUS block to the file while this one runs; pipeline=False: waits for this
-        block and writes it."""
+        block and writes it.
+        In an archive created with exact=True the block's excess list is made on the time-major block itself (the COLS
+        form of mhi_excess_count / mhi_excess_emit: the packed intermediate has already lost the counts above S-1), and
+        the list's length is read between the two passes: ONE synchronisation of the current stream per block, behind
+        the block's encode.  The file is the same with pipeline on and off."""
         g = self._device()
         torch = g["torch"]
         dev = g["enc"][0].device
@@ -492,14 +519,22 @@ class Writer:
         if t.dim() != 2 or int(t.shape[1]) != self.C or int(t.shape[0]) < 1 or t.dtype != torch.uint8:
             raise ValueError("a block is a uint8 [Tb >= 1, %d] array" % self.C)
         t = t.to(dev).contiguous()
+        lists = None
+        if self.exact:
+            def lists():
+                from . import excess
+                return excess.from_time_major(t, self.S - 1)
         self._append(int(t.shape[0]), lambda se: se.calibrate(t),
-                     lambda se, track: se.encode_block_device(t, track=track, checksum=self.checksum))
+                     lambda se, track: se.encode_block_device(t, track=track, checksum=self.checksum), lists)
 
     def append_events(self, ev, origin, period, T):
         """append() for the block of T bins that `ev` (an events.EventSet of C channels) fills from tick `origin` at
         `period` ticks per bin: binned on the GPU straight into the encoder's packed pieces
         (StreamEncoder.encode_events_device; a first block calibrates with calibrate_events), then the same pipeline.
-        The archive's time axis counts bins as before: this block is its next T steps."""
+        The archive's time axis counts bins as before: this block is its next T steps.  ValueError in an archive created
+        with exact=True: the binner writes packed pieces, which have lost the counts above S-1."""
+        from .stream import _no_exact_events
+        _no_exact_events(self.exact)
         T = int(T)
         if ev.C != self.C or T < 1:
             raise ValueError("a block of events has %d channels and at least 1 bin" % self.C)
@@ -510,11 +545,13 @@ class Writer:
         """append_events() for one merged, time-ordered list of (tick, channel) pairs on the device
         (events.EventSet.from_aer: partitioned by channel there).  The same file as from the host-sorted EventSet."""
         from . import events
+        from .stream import _no_exact_events
+        _no_exact_events(self.exact)
         self.append_events(events.EventSet.from_aer(ticks, channels, self.C), origin, period, T)
 
-    def _append(self, Tb, calibrate, encode):
+    def _append(self, Tb, calibrate, encode, lists=None):
         """The pipeline of one block: calibrate(encoder) on a first block, encode(encoder, track) -> what
-        encode_block_device returns."""
+        encode_block_device returns; lists() -> the block's excess list on the device (synchronises the current stream)."""
         g = self._device()
         torch = g["torch"]
         dev = g["enc"][0].device
@@ -553,7 +590,12 @@ class Writer:
             if crc is not None:        # taken behind the compaction, in front of `coded`
                 crc.copy_(slot["crc"][:plan.n_segments], non_blocking=True)
             sizes.record(g["copy"])
-        job = dict(st=st, Tb=Tb, dense=dense.payload, segw=segw, bits=bits, crc=crc, sizes=sizes)
+        job = dict(st=st, Tb=Tb, dense=dense.payload, segw=segw, bits=bits, crc=crc, sizes=sizes, exc=None)
+        if lists is not None:
+            made = torch.cuda.Event()
+            job["exc"] = lists()
+            made.record(cur)
+            job["made"] = made
         self._n += 1
         self._drain()                  # block k - 1 goes to the file while block k runs
         self._pending = job
@@ -581,6 +623,10 @@ class Writer:
                            np.zeros(self.C, np.uint8), job["bits"].numpy().astype(np.uint64),
                            job["segw"].numpy().astype(np.uint64), st["dense"][:total].numpy().view(np.uint32),
                            None if job["crc"] is None else job["crc"].numpy().view(np.uint32))
+        if job["exc"] is not None:
+            job["made"].synchronize()
+            exc_off, pos, val = job["exc"]
+            cio.attach_excess(c, exc_off.cpu().numpy(), pos.cpu().numpy().view(np.uint32), val.cpu().numpy())
         self._write_record(c, job["Tb"])
         self._word = (st["peak"].numpy().copy(), st["enc"].numpy().copy())
 
@@ -615,9 +661,11 @@ class Writer:
 
 
 def create(path, C, S=3, hist_bits=6, sclv_rows=None, approx=True, seg_chunks=2, recalibrate=None, pipeline=True, meta=None,
-           checksum=False):
+           checksum=False, exact=False):
     """Start a new archive (an existing file is replaced) -> Writer, a context manager.  checksum=True: archive
-    revision 2 -- every block carries the CRC-32 of each of its segments (module docstring)."""
+    revision 2 -- every block carries the CRC-32 of each of its segments (module docstring).  exact=True: every block
+    also carries the sparse list of its counts above S-1, and read() returns the counts themselves; the header says
+    "exact": true, the revision stays, and open(path, "a") goes on in the file's mode."""
     from . import sclv
     rows = np.asarray(sclv.table(S) if sclv_rows is None else sclv_rows, dtype=np.uint8).reshape(-1, int(S))
     header = {"archive_revision": ARCHIVE_REVISION, "C": int(C), "S": int(S), "mode": MODE_APPROX if approx else MODE_NOSORT,
@@ -625,6 +673,8 @@ def create(path, C, S=3, hist_bits=6, sclv_rows=None, approx=True, seg_chunks=2,
               "sclv": [[int(v) for v in r] for r in rows], "meta": dict(meta or {})}
     if checksum:
         header.update(archive_revision=CHECKSUM_REVISION, checksum="crc32")
+    if exact:
+        header["exact"] = True
     cio._header_fields(cio.make_header(S, hist_bits, header["mode"], WIN_FULL, seg_chunks, rows))   # range checks
     _archive_fields(header)
     blob = json.dumps(header, sort_keys=True).encode()

@@ -11,6 +11,12 @@ build's own.  File layout (little-endian):
     stored words as little-endian bytes (0 for a segment of 0 words), taken on the device (mhi_seg_crc32) and checked there
     on read; its header also carries "checksum": "crc32" and "arrays_crc32", the CRC-32 of the bytes of ch_len .. seg_crc
     as written (padding included), checked on the host when the head is read.  The header JSON itself is not covered.
+    exact=True (any revision; the header then carries "exact": true) puts three arrays BEHIND the payload:
+        exc_seg u64[n_segments + 1] | exc_pos u32[n] | exc_val u8[n]
+    the sparse list of what the clip at S-1 dropped (excess.py): entry e says sample exc_pos[e] of its channel held
+    S-1 + exc_val[e]; channel-major, ascending in exc_pos, and exc_seg[s] is the first entry of directory segment s.
+    Everything from ch_len through payload is byte for byte what the container without the option holds.  With
+    checksums the header also carries "excess_crc32", the CRC-32 of the three arrays as written.
 
 The header carries everything a decoder needs to rebuild the plan: format revision, chunk
 geometry, S, h, mapper, window rule, seg_chunks and the K SCLV rows (the static codebooks).
@@ -27,6 +33,8 @@ import zlib
 from dataclasses import dataclass
 
 import numpy as np
+
+from . import excess
 
 MAGIC = b"MUAHUFF1"
 FORMAT_REVISION = 3          # written; revision 2 (no head segments, include/muahuff.h MH_WIN_REV2_SEGMENTS) is still read
@@ -46,6 +54,9 @@ class Compressed:
     seg_words: np.ndarray  # uint64 [n_segments]
     payload: np.ndarray    # uint32 [sum(seg_words)]
     seg_crc: np.ndarray = None  # uint32 [n_segments], revision 4 only: CRC-32 of each segment's stored words
+    exc_seg: np.ndarray = None  # uint64 [n_segments + 1]  exact=True only: first list entry of each segment
+    exc_pos: np.ndarray = None  # uint32 [n]               sample index inside the channel
+    exc_val: np.ndarray = None  # uint8  [n]               x - (S-1)
 
     @property
     def payload_bits(self):
@@ -54,6 +65,11 @@ class Compressed:
     @property
     def container_bits(self):
         return int(self.payload.size) * 32
+
+    @property
+    def excess_bits(self):
+        """What exact=True costs: 40 bits per entry plus the segment index; 0 without the lists."""
+        return 0 if self.exc_pos is None else excess.ENTRY_BITS * int(len(self.exc_pos)) + 64 * int(len(self.exc_seg))
 
     def tobytes(self):
         buf = io.BytesIO()
@@ -77,14 +93,24 @@ ARRAYS = (("ch_len", np.uint64), ("peak", np.uint8), ("enc", np.uint8), ("skippe
 
 
 SEG_CRC = ("seg_crc", np.uint32)   # revision 4: between seg_words and payload (ARRAYS stays what revision 3 holds)
+EXCESS = excess.NAMES              # exact=True: exc_seg, exc_pos, exc_val behind the payload
+
+
+def _has_excess(c):
+    """Does c carry the lists?  ValueError unless the header's "exact" and the three arrays agree."""
+    have = [getattr(c, name, None) is not None for name, _ in EXCESS]
+    if any(have) != all(have) or all(have) != (c.header.get("exact") is True):
+        raise ValueError("container header says exact=%r %s the excess lists" % (c.header.get("exact"), "with" if any(have) else "without"))
+    return all(have)
 
 
 def _file_arrays(c):
-    """(name, dtype) of the arrays c has in a file, in file order.  ValueError unless checksums and revision agree."""
+    """(name, dtype) of the arrays c has in a file, in file order.  ValueError unless checksums and revision, and the
+    header's "exact" and the lists, agree."""
     has = getattr(c, "seg_crc", None) is not None
     if has != (c.header.get("format_revision") == CHECKSUM_REVISION):
         raise ValueError("container revision %r %s seg_crc" % (c.header.get("format_revision"), "with" if has else "without"))
-    return ARRAYS[:-1] + (SEG_CRC,) + ARRAYS[-1:] if has else ARRAYS
+    return (ARRAYS[:-1] + (SEG_CRC,) + ARRAYS[-1:] if has else ARRAYS) + (EXCESS if _has_excess(c) else ())
 
 
 def _raw(c, name, dt):
@@ -95,12 +121,14 @@ def _header_blob(c):
     hdr = dict(c.header)
     arrays = _file_arrays(c)
     hdr["sizes"] = {name: int(np.asarray(getattr(c, name)).size) for name, _ in arrays}
-    if len(arrays) > len(ARRAYS):
+    if SEG_CRC in arrays:
         crc = 0
-        for name, dt in arrays[:-1]:
+        for name, dt in arrays[:arrays.index(ARRAYS[-1])]:
             raw = _raw(c, name, dt)
             crc = zlib.crc32(b"\0" * (-raw.size % 8), zlib.crc32(raw, crc))
         hdr["checksum"], hdr["arrays_crc32"] = "crc32", crc
+        if EXCESS[0] in arrays:
+            hdr["excess_crc32"] = excess.crc32(c.exc_seg, c.exc_pos, c.exc_val)
     return json.dumps(hdr, sort_keys=True).encode()
 
 
@@ -159,6 +187,11 @@ def read_head(read, skip=None):
     has = isinstance(hdr.get("sizes"), dict) and SEG_CRC[0] in hdr["sizes"]
     if has != (hdr["format_revision"] == CHECKSUM_REVISION):
         raise ValueError("container revision %d %s seg_crc" % (hdr["format_revision"], "with" if has else "without"))
+    listed = [name in hdr["sizes"] for name, _ in EXCESS] if isinstance(hdr.get("sizes"), dict) else [False]
+    if any(listed) != all(listed) or all(listed) != (hdr.get("exact") is True) or ("exact" in hdr and hdr["exact"] is not True):
+        raise ValueError("container header says exact=%r %s the excess lists" % (hdr.get("exact"), "with" if any(listed) else "without"))
+    if all(listed) and has and not isinstance(hdr.get("excess_crc32"), int):
+        raise ValueError("corrupt container: checksums without excess_crc32")
     arrays, pos, crc = {}, 12 + n, 0
     for name, dt in ARRAYS[:-1] + ((SEG_CRC,) if has else ()):
         if has:     # arrays_crc32 covers the padding as written: read, not skipped
@@ -173,9 +206,32 @@ def read_head(read, skip=None):
     return hdr, arrays, pos
 
 
+def read_excess(read, hdr):
+    """The three arrays behind the payload, through read(n) -> bytes, with excess_crc32 checked when the header has one.
+    -> {name: array}"""
+    out, crc = {}, 0
+    for name, dt in EXCESS:
+        out[name], size = _read_array(read, lambda pad: None, hdr, name, dt)
+        pad = read(size - out[name].nbytes)
+        if len(pad) != size - out[name].nbytes:
+            raise ValueError("truncated container (%s)" % name)
+        crc = zlib.crc32(pad, zlib.crc32(out[name].view(np.uint8), crc))
+    if "excess_crc32" in hdr and hdr["excess_crc32"] != crc:
+        raise ValueError("corrupt container: checksum of the excess lists does not match")
+    return out
+
+
 def read(f):
     hdr, arrays, _pos = read_head(f.read)
     arrays["payload"], _size = _read_array(f.read, f.read, hdr, *ARRAYS[-1])
+    if hdr.get("exact"):
+        arrays.update(read_excess(f.read, hdr))
+        c = Compressed(hdr, **arrays)
+        if len(c.exc_pos) != len(c.exc_val):
+            raise ValueError("corrupt container: exc_pos and exc_val differ in length")
+        check_consistent(c, arrays=False)
+        excess.check_container(c)
+        return c
     return Compressed(hdr, **arrays)
 
 
@@ -189,20 +245,35 @@ def load(path):
         return read(f)
 
 
-def make_header(S, h, mode, window, seg_chunks, sclv, checksum=False):
+def make_header(S, h, mode, window, seg_chunks, sclv, checksum=False, exact=False):
     from . import _lib
     sclv = np.asarray(sclv, dtype=np.uint8).reshape(-1, int(S))
-    return {"format_revision": CHECKSUM_REVISION if checksum else FORMAT_REVISION, "piece": _lib.PIECE, "lanes": _lib.LANES, "rows": _lib.ROWS,
+    return {**({"exact": True} if exact else {}), "format_revision": CHECKSUM_REVISION if checksum else FORMAT_REVISION, "piece": _lib.PIECE, "lanes": _lib.LANES, "rows": _lib.ROWS,
             "S": int(S), "h": int(h), "mode": int(mode), "window": int(window), "seg_chunks": int(seg_chunks),
             "K": int(sclv.shape[0]), "sclv": [[int(v) for v in r] for r in sclv]}
 
 
 # ---- GPU end-to-end ----------------------------------------------------------------------------
-def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0, checksum=False):
+def attach_excess(c, exc_off, pos, val):
+    """Give the `Compressed` c (header with "exact": true) its lists: (exc_off [C + 1], pos, val) is the channel-major list
+    of its channels (host arrays); the segment index is made here from the directory."""
+    hd = c.header
+    ch, lo, _hi = excess.segment_bounds(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd["format_revision"])
+    c.exc_pos = np.ascontiguousarray(pos, np.uint32)
+    c.exc_val = np.ascontiguousarray(val, np.uint8)
+    c.exc_seg = excess.segment_index(exc_off, c.exc_pos, ch, lo)
+    return c
+
+
+def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0, checksum=False, exact=False):
     """Calibrate + encode every channel of a ChannelSet on the GPU and bring the dense stream to
     the host as a `Compressed`.  seg_chunks = 0: the planner's choice; the header records it.
     checksum=True: a revision-4 container -- the CRC-32 of every segment of the compacted payload is taken on the
-    device (mhi_seg_crc32) and comes to the host with the other small arrays."""
+    device (mhi_seg_crc32) and comes to the host with the other small arrays.
+    exact=True: the container also keeps what the clip at S-1 drops -- every sample above S-1 inside a channel's encoded
+    window, as a sparse list made on the device (mhi_excess_count / mhi_excess_emit, one more read of a count) -- so that
+    decompress() returns the counts themselves.  Skipped channels get no entries.  The stream is unchanged; `excess_bits`
+    is the price."""
     import torch
 
     from . import WIN_AFTER_CAL, codec
@@ -212,9 +283,15 @@ def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0, checksum=False):
     dense, tot = plan.compact(enc)
     crc = enqueue_seg_crc(plan, dense) if checksum else None
     torch.cuda.synchronize()
-    c = Compressed.from_device(make_header(S, h, mode, window, plan.seg_chunks, sclv, checksum), cs.ch_len, enc,
+    c = Compressed.from_device(make_header(S, h, mode, window, plan.seg_chunks, sclv, checksum, exact), cs.ch_len, enc,
                                plan.n_segments, dense.payload, int(tot.item()), crc)
     plan.close()
+    if exact:
+        w0, w1, _head, _nseg = channel_layout(cs.ch_len, h, window)
+        w1 = np.where(c.skipped != 0, w0, w1)
+        exc_off, pos, val = excess.from_rows(cs.data, cs.ch_off, w0, w1, int(cs.ch_len.max()) if cs.C else 1, int(S) - 1) \
+            if cs.C else (torch.zeros(1, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.uint8))
+        attach_excess(c, exc_off.cpu().numpy(), pos.cpu().numpy().view(np.uint32), val.cpu().numpy())
     return c
 
 
@@ -398,19 +475,48 @@ def validate(c):
         raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
 
 
-def decompress(c, device="cuda", channels=None, check=True):
+def wants_excess(src, exact, what="container"):
+    """The exact= rule of every reader: None -> apply the lists when the source has them, False -> never, True ->
+    ValueError when it has none.  -> bool: apply them"""
+    has = src.header.get("exact") is True
+    if exact is True and not has:
+        raise ValueError("exact=True: this %s was written without the excess lists" % what)
+    return has and exact is not False
+
+
+def _apply_channel_set(cs, pos, val, fe, le):
+    """mhi_excess_apply onto the rows of a ChannelSet: one call when the channels are equally spaced, else one per channel
+    that has entries."""
+    off, ln = cs.ch_off.astype(np.int64), cs.ch_len.astype(np.int64)
+    pitch = np.diff(off)
+    if len(off) == 1 or (pitch == pitch[0]).all():
+        excess.apply(pos, val, fe, le, 0, int(ln.max()), 1, 0, cs.data, int(pitch[0]) if len(off) > 1 else 0, 1,
+                     ptr=cs.data.data_ptr() + int(off[0]))
+        return
+    fd, ld = excess._i64(fe, pos.device), excess._i64(le, pos.device)
+    for i in np.nonzero(np.asarray(le) > np.asarray(fe))[0]:
+        excess.apply(pos, val, fd[i:i + 1], ld[i:i + 1], 0, int(ln[i]), 1, 0, cs.data, 0, 1, ptr=cs.data.data_ptr() + int(off[i]))
+
+
+def decompress(c, device="cuda", channels=None, check=True, exact=None):
     """Inverse of compress(): a ChannelSet whose windows hold min(x, S-1) (bytes outside the
     encoded windows are zero).  channels: optional list of channel indices -- only their segments
     are uploaded and decoded (the directory gives random access per channel); the returned set
     holds them in the order given.  check=True runs validate() first (containers from disk are
     untrusted input for a kernel that follows their headers) and, when the container carries checksums, verifies every
-    uploaded segment on the device (mhi_seg_crc32): ValueError names the first that does not match."""
+    uploaded segment on the device (mhi_seg_crc32): ValueError names the first that does not match.
+    exact: None = add the excess lists back when the container has them (then the windows hold x itself), False = do not
+    read them (min(x, S-1), what the container without the lists gives), True = ValueError when it has none.  The lists
+    are range-checked on the host with `check` and applied on the decode's stream, right behind it."""
     import torch
 
     from . import codec
     from .container import ChannelSet
+    use = wants_excess(c, exact)
     if check:
         validate(c)
+        if use:
+            excess.check_container(c)
     hd = c.header
     nseg_ch = check_consistent(c, arrays=False)
     seg_words, payload, peak, enc, skipped, ch_bits, ch_len = (c.seg_words, c.payload, c.peak, c.enc, c.skipped,
@@ -444,6 +550,11 @@ def decompress(c, device="cuda", channels=None, check=True):
                           torch.from_numpy(np.ascontiguousarray(skipped)).to(dev), d_off, True)
         bad = enqueue_verify(c, pay, d_off, seg_words, None, check, expect=stored_crc)
         plan.decode(e, cs.data)
+        if use and len(c.exc_pos):
+            first = np.concatenate([[0], np.cumsum(nseg_ch)]).astype(np.int64)
+            ch = np.arange(len(c.ch_len)) if channels is None else sel
+            seg_e = np.asarray(c.exc_seg, np.uint64).astype(np.int64)
+            _apply_channel_set(cs, *excess.upload(c.exc_pos, c.exc_val, dev), seg_e[first[ch]], seg_e[first[ch + 1]])
         check_verified(bad, [plan], index=segs)
         codec.check_decoded([plan])
     finally:
@@ -486,6 +597,51 @@ class ContainerFile:
         self.payload_offset = self.offset + n           # file offset of payload word 0
         self.payload_words = int(self.header["sizes"]["payload"])
         self.head_bytes = self.bytes_read               # what open() read
+        self._exc_seg = None
+        if self.header.get("exact"):                    # the lists stay on disk: only where they lie is worked out
+            pad8 = lambda b: b + (-b % 8)  # noqa: E731
+            sizes = self.header["sizes"]
+            self.excess_entries = int(sizes["exc_pos"])
+            if int(sizes["exc_val"]) != self.excess_entries:
+                raise ValueError("corrupt container: exc_pos and exc_val differ in length")
+            self._off_exc_seg = self.payload_offset + pad8(4 * self.payload_words)
+            self._off_exc_pos = self._off_exc_seg + pad8(8 * int(sizes["exc_seg"]))
+            self._off_exc_val = self._off_exc_pos + pad8(4 * self.excess_entries)
+
+    def _read_at(self, at, count, dt, name):
+        out = np.empty(int(count), dtype=dt)
+        if count:
+            self._f.seek(at)
+            got = self._f.readinto(memoryview(out).cast("B"))
+            self.bytes_read += got
+            if got != out.nbytes:
+                raise ValueError("truncated container (%s)" % name)
+        return out
+
+    @property
+    def exc_seg(self):
+        """The segment index of the excess lists (read on first use, checked: monotone, within the entries)."""
+        if self._exc_seg is None:
+            seg = self._read_at(self._off_exc_seg, int(self.header["sizes"]["exc_seg"]), np.uint64, "exc_seg")
+            excess.check_index(seg, len(self.seg_words), self.excess_entries)
+            self._exc_seg = seg
+        return self._exc_seg
+
+    def read_excess(self, first, n):
+        """list entries [first, first + n) -> (exc_pos uint32, exc_val uint8) (ValueError past the end of the file)"""
+        return (self._read_at(self._off_exc_pos + 4 * int(first), n, np.uint32, "exc_pos"),
+                self._read_at(self._off_exc_val + int(first), n, np.uint8, "exc_val"))
+
+    def verify_excess(self):
+        """Read the three arrays whole and compare them with the header's excess_crc32 (a no-op without one) and with
+        the directory (excess.check_container).  ValueError."""
+        if not self.header.get("exact"):
+            return
+        self._f.seek(self._off_exc_seg)
+        arrays = read_excess(self._read, self.header)
+        c = Compressed(self.header, self.ch_len, self.peak, self.enc, self.skipped, self.ch_bits, self.seg_words, None,
+                       self.seg_crc, **arrays)
+        excess.check_container(c)
 
     def read_words(self, first, n):
         """payload words [first, first + n) as uint32 (ValueError past the end of the file)"""
@@ -612,6 +768,41 @@ def _range_inputs(src, start, stop, channels, check, r=None):
     return sel, payload, seg_off, segs, peak, enc
 
 
+def gather_excess(src, start, stop, sel, check, what="container"):
+    """The list entries a range query reads: for each distinct channel of `sel`, the one slice of entries of its segments
+    that overlap [start, stop), back to back, next to the payload words gather_range reads.  With check the slices are
+    range-checked on the host (excess.check_index / check_entries) -- they are not CRC'd: excess_crc32 covers the arrays
+    whole.  -> (pos uint32, val uint8, first, last): row i of the query takes entries [first[i], last[i]) of (pos, val)."""
+    hd = src.header
+    h, window, seg_chunks = int(hd["h"]), int(hd["window"]), int(hd["seg_chunks"])
+    rev = int(hd.get("format_revision", FORMAT_REVISION))
+    s_first, s_end = range_segments(src.ch_len, h, window, seg_chunks, start, stop, rev)
+    seg_e = np.asarray(src.exc_seg, np.uint64).astype(np.int64)
+    n = int(src.excess_entries if isinstance(src, ContainerFile) else len(src.exc_pos))
+    if not isinstance(src, ContainerFile) and check:
+        excess.check_index(seg_e, len(src.seg_words), n, what)
+    e0, e1 = np.minimum(seg_e[s_first], n), np.minimum(seg_e[s_end], n)
+    base = np.zeros(len(src.ch_len), np.int64)
+    ps, vs, counts, segs, at = [], [], [], [], 0
+    for c in np.unique(sel):
+        a, b = int(e0[c]), int(e1[c])
+        if b <= a:
+            continue
+        p, v = src.read_excess(a, b - a) if isinstance(src, ContainerFile) else (src.exc_pos[a:b], src.exc_val[a:b])
+        ps.append(p), vs.append(v)
+        base[c] = at - a
+        at += b - a
+        counts.append(np.diff(seg_e[int(s_first[c]):int(s_end[c]) + 1])), segs.append(np.arange(int(s_first[c]), int(s_end[c])))
+    pos = np.concatenate(ps) if ps else np.zeros(0, np.uint32)
+    val = np.concatenate(vs) if vs else np.zeros(0, np.uint8)
+    if check and ps:
+        _ch, lo, hi = excess.segment_bounds(src.ch_len, h, window, seg_chunks, rev)
+        segs = np.concatenate(segs)
+        excess.check_entries(pos, val, np.concatenate(counts), lo[segs], hi[segs], int(hd["S"]) - 1, what)
+    first, last = e0[sel] + base[sel], e1[sel] + base[sel]
+    return pos, val, first, np.maximum(last, first)
+
+
 def _range_decode(src, payload, seg_off, segs, peak, enc, check, run):
     """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device, its segments verified
     next to the upload when the source carries checksums (enqueue_verify); ValueError when one does not match or the
@@ -631,7 +822,7 @@ def _range_decode(src, payload, seg_off, segs, peak, enc, check, run):
     return out
 
 
-def decompress_range(src, start, stop, channels=None, device="cuda", check=True, time_major=False):
+def decompress_range(src, start, stop, channels=None, device="cuda", check=True, time_major=False, exact=None):
     """Samples [start, stop) of the selected channels of a `Compressed` or a `ContainerFile` (open()), reading and
     decoding only the segments that overlap the range.  -> uint8 device tensor [n_sel, stop - start] (row i = channel
     channels[i]: min(x, S-1) inside the channel's encoded window, 0 outside it and past its length -- exactly
@@ -639,34 +830,52 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
     time_major=True.  channels: None = all, else indices (rows in that order, repeats allowed).  check=True validates the
     header fields and the segments the query reads (mh_validate_segments) before anything reaches the GPU and, when the
     source carries checksums, verifies exactly those segments on the device next to their upload; a segment whose
-    checksum does not match, or a decode that had to abandon one, raises ValueError as decompress() does."""
+    checksum does not match, or a decode that had to abandon one, raises ValueError as decompress() does.
+    exact (None / False / True as decompress): with the lists the rows hold x itself; only the entries of the segments
+    that are read are fetched (gather_excess), range-checked on the host with `check` and added on the decode's stream."""
     import torch
 
     from . import codec
     start, stop = int(start), int(stop)
+    use = wants_excess(src, exact)
     sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check)
     n, rows = stop - start, int(sel.size)
     if payload is None:
         z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
         return z.t().contiguous() if time_major else z
-    out = _range_decode(src, payload, seg_off, segs, peak, enc, check,
-                        lambda plan, pay, off, pk, en: plan.decode_range(pay, off, pk, en, sel, start, stop))
+    lists = gather_excess(src, start, stop, sel, check) if use else None
+
+    def run(plan, pay, off, pk, en):
+        out = plan.decode_range(pay, off, pk, en, sel, start, stop)
+        if lists is not None and len(lists[0]):
+            excess.apply(*excess.upload(lists[0], lists[1], out.device), lists[2], lists[3], start, stop, 1, 0, out)
+        return out
+    out = _range_decode(src, payload, seg_off, segs, peak, enc, check, run)
     return codec.to_time_major(out) if time_major else out
 
 
-def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, check=True, device="cuda"):
+def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, check=True, device="cuda", exact=None):
     """Samples [start, stop) of the selected channels summed in bins of r samples (mh_decode_rebin): what
     decompress_range(src, start, stop, channels) re-binned by r gives, decoded in one pass that never stores the
     byte-per-sample rows.  -> device tensor [n_sel, ceil((stop - start) / r)], uint8 = min(sum, 255) (saturate, the form
     ChannelSet.rebin has) or int32 exact sums; the last, partial bin is kept.  stop=None: the longest channel's length.
     ValueError for a bad r, start or range, IndexError for a bad channel (codec.query_args) -- before anything reaches
-    the GPU; check and the status handling as decompress_range."""
+    the GPU; check and the status handling as decompress_range.  exact as decompress_range: with the lists the bins
+    hold the sums of x itself (uint8: min(sum, 255), which is what adding the list with saturation to the clipped,
+    saturated sum gives)."""
     import torch
     r, start = int(r), int(start)
     stop = (int(np.max(src.ch_len)) if len(src.ch_len) else 0) if stop is None else int(stop)
+    use = wants_excess(src, exact)
     sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check, r)
     nb, rows = (stop - start + r - 1) // r, int(sel.size)
     if payload is None:
         return torch.zeros((rows, nb), dtype=torch.uint8 if saturate else torch.int32, device=device)
-    return _range_decode(src, payload, seg_off, segs, peak, enc, check,
-                         lambda plan, pay, off, pk, en: plan.decode_rebin(pay, off, pk, en, sel, start, stop, r, saturate))
+    lists = gather_excess(src, start, stop, sel, check) if use else None
+
+    def run(plan, pay, off, pk, en):
+        out = plan.decode_rebin(pay, off, pk, en, sel, start, stop, r, saturate)
+        if lists is not None and len(lists[0]):
+            excess.apply(*excess.upload(lists[0], lists[1], out.device), lists[2], lists[3], start, stop, r, 0, out)
+        return out
+    return _range_decode(src, payload, seg_off, segs, peak, enc, check, run)

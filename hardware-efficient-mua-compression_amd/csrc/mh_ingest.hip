@@ -1,6 +1,7 @@
 // mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
-// in mh_aer.hpp, the segment checksum in mh_crc.hpp and the way back from counts to events in mh_unbin.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
-// fallback here either.
+// in mh_aer.hpp, the segment checksum in mh_crc.hpp, the way back from counts to events in mh_unbin.hpp and the side
+// list of what the clip at S-1 drops in mh_excess.hpp: argument checks and the launches.  A companion of libmuahuff.so,
+// not part of it; there is no CPU fallback here either.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -9,6 +10,8 @@
 #include "mh_aer.hpp"
 #include "mh_aer_layout.hpp"
 #include "mh_crc.hpp"
+#include "mh_excess.hpp"
+#include "mh_excess_layout.hpp"
 #include "mh_ingest.hpp"
 #include "mh_launch.hpp"
 #include "mh_unbin.hpp"
@@ -102,6 +105,31 @@ void unbin_emit_launch(const uint8_t *in, const uint64_t *row_off, uint64_t rows
     hipLaunchKernelGGL((mh::k_unbin_emit<FORM, CH>), grid, block, 0, st, in, row_off, cols, (uint32_t)L.tiles_per_row,
                        rows * cols, (uint32_t)L.tiles, first_tick, period, base, out_ticks, static_cast<CH *>(out_ch), capacity,
                        reinterpret_cast<unsigned long long *>(over));
+}
+
+// What mhi_excess_count and mhi_excess_emit share: the form, the shape, the threshold and the scratch.
+int excess_args(const char *fn, uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo,
+                const uint64_t *hi, uint64_t rows, uint64_t cols, uint32_t threshold, const void *scratch,
+                uint64_t scratch_bytes, mh::ExcessLayout *L)
+{
+    if (form != mh::kExcessRows && form != mh::kExcessCols)
+        return fail(MH_ERR_ARG, "%s: form=%u (MHI_EXCESS_ROWS or MHI_EXCESS_COLS)", fn, form);
+    if (!in || !scratch) return fail(MH_ERR_ARG, "%s: NULL pointer", fn);
+    if (form == mh::kExcessRows && !row_off) return fail(MH_ERR_ARG, "%s: the ROWS form needs row_off", fn);
+    if (form == mh::kExcessCols && (row_off || lo || hi))
+        return fail(MH_ERR_ARG, "%s: the COLS form is one contiguous block, every column whole: row_off, lo and hi must be NULL", fn);
+    if (threshold < 1 || threshold > 254) return fail(MH_ERR_ARG, "%s: threshold=%u (1 .. 254)", fn, threshold);
+    const int rc = mh::excess_layout(form, rows, cols, L);
+    if (rc == -1)
+        return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu (each at least 1, cols below 2^32; COLS form: rows below 2^32)", fn,
+                    (unsigned long long)rows, (unsigned long long)cols);
+    if (rc) return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu make more than 2^32 - 1 pieces", fn, (unsigned long long)rows,
+                        (unsigned long long)cols);
+    if (scratch_bytes < L->bytes)
+        return fail(MH_ERR_ARG, "%s: scratch_bytes=%llu, mhi_excess_scratch_bytes asks for %llu", fn,
+                    (unsigned long long)scratch_bytes, (unsigned long long)L->bytes);
+    if ((uintptr_t)scratch % 16) return fail(MH_ERR_ARG, "%s: scratch is not 16-byte aligned", fn);
+    return MH_OK;
 }
 
 }  // namespace
@@ -304,6 +332,131 @@ int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, ui
                                                    over, st);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_unbin_emit: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_excess_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes)
+{
+    static_assert(mh::kExcessRows == MHI_EXCESS_ROWS && mh::kExcessCols == MHI_EXCESS_COLS, "the header publishes the forms");
+    if (!bytes) return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: NULL pointer");
+    mh::ExcessLayout L;
+    const int rc = mh::excess_layout(form, rows, cols, &L);
+    if (rc == -1)
+        return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: form=%u, rows=%llu, cols=%llu (a known form, each at least 1, cols below 2^32; COLS form: rows below 2^32)",
+                    form, (unsigned long long)rows, (unsigned long long)cols);
+    if (rc)
+        return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: rows=%llu, cols=%llu make more than 2^32 - 1 pieces",
+                    (unsigned long long)rows, (unsigned long long)cols);
+    *bytes = L.bytes;
+    return MH_OK;
+}
+
+int mhi_excess_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo, const uint64_t *hi,
+                     uint64_t rows, uint64_t cols, uint32_t threshold, uint64_t *exc_off, uint64_t *total, void *scratch,
+                     uint64_t scratch_bytes, void *stream)
+{
+    mh::ExcessLayout L;
+    const int rc = excess_args("mhi_excess_count", form, in, row_off, lo, hi, rows, cols, threshold, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (!exc_off || !total) return fail(MH_ERR_ARG, "mhi_excess_count: NULL pointer");
+    uint8_t *const s8 = static_cast<uint8_t *>(scratch);
+    uint32_t *const sums = reinterpret_cast<uint32_t *>(s8 + L.off_sum);
+    uint64_t *const base = reinterpret_cast<uint64_t *>(s8 + L.off_base);
+    uint64_t *const partial = reinterpret_cast<uint64_t *>(s8 + L.off_partial);
+    const uint32_t pieces = (uint32_t)L.pieces, per = (uint32_t)L.per_channel, k = (255u - threshold) * 0x01010101u;
+    const dim3 block(64u * mh::kExcessWaves), groups((unsigned)L.groups), per_group(mh::kUnbinBaseThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (form == mh::kExcessRows) {
+        const dim3 grid((unsigned)((L.pieces + mh::kExcessWaves - 1) / mh::kExcessWaves));
+        hipLaunchKernelGGL(mh::k_excess_rows_count, grid, block, 0, st, in, row_off, lo, hi, cols, per, pieces, k, sums);
+    } else {
+        const uint64_t waves = L.strips * L.per_channel;
+        const dim3 grid((unsigned)((waves + mh::kExcessWaves - 1) / mh::kExcessWaves));
+        hipLaunchKernelGGL(mh::k_excess_cols_count, grid, block, 0, st, in, rows, cols, per, waves, k, sums);
+    }
+    hipLaunchKernelGGL(mh::k_unbin_group_sum, groups, per_group, 0, st, sums, pieces, partial);
+    hipLaunchKernelGGL(mh::k_unbin_scan, dim3(1), dim3(mh::kUnbinScanThreads), 0, st, partial, L.groups, total, exc_off, L.channels);
+    hipLaunchKernelGGL(mh::k_unbin_bases, groups, per_group, 0, st, sums, pieces, partial, base, per, exc_off);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_count: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_excess_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo, const uint64_t *hi,
+                    uint64_t rows, uint64_t cols, uint32_t threshold, uint32_t *pos, uint8_t *val, uint64_t capacity,
+                    uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream)
+{
+    mh::ExcessLayout L;
+    const int rc = excess_args("mhi_excess_emit", form, in, row_off, lo, hi, rows, cols, threshold, scratch, scratch_bytes, &L);
+    if (rc) return rc;
+    if (!pos || !val || !over) return fail(MH_ERR_ARG, "mhi_excess_emit: NULL pointer");
+    if ((uintptr_t)pos % 4) return fail(MH_ERR_ARG, "mhi_excess_emit: pos is not 4-byte aligned");
+    const uint8_t *const s8 = static_cast<const uint8_t *>(scratch);
+    const uint64_t *const base = reinterpret_cast<const uint64_t *>(s8 + L.off_base);
+    const uint32_t pieces = (uint32_t)L.pieces, per = (uint32_t)L.per_channel, k = (255u - threshold) * 0x01010101u;
+    const dim3 block(64u * mh::kExcessWaves);
+    unsigned long long *const ov = reinterpret_cast<unsigned long long *>(over);
+    hipStream_t st = (hipStream_t)stream;
+    if (form == mh::kExcessRows) {
+        const dim3 grid((unsigned)((L.pieces + mh::kExcessWaves - 1) / mh::kExcessWaves));
+        hipLaunchKernelGGL(mh::k_excess_rows_emit, grid, block, 0, st, in, row_off, lo, hi, cols, per, pieces, k, threshold, base,
+                           pos, val, capacity, ov);
+    } else {
+        const uint64_t waves = L.strips * L.per_channel;
+        const dim3 grid((unsigned)((waves + mh::kExcessWaves - 1) / mh::kExcessWaves));
+        hipLaunchKernelGGL(mh::k_excess_cols_emit, grid, block, 0, st, in, rows, cols, per, waves, k, threshold, base, pos, val,
+                           capacity, ov);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_emit: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries, const uint64_t *first, const uint64_t *last,
+                     uint64_t n_rows, uint64_t start, uint64_t stop, uint64_t r, uint64_t lead, void *out, uint32_t out_bits,
+                     uint64_t row_stride, uint64_t col_stride, void *stream)
+{
+    if (!first || !last || !out || (n_entries && (!pos || !val))) return fail(MH_ERR_ARG, "mhi_excess_apply: NULL pointer");
+    if (out_bits != 8 && out_bits != 32) return fail(MH_ERR_ARG, "mhi_excess_apply: out_bits=%u (8 or 32)", out_bits);
+    if (r == 0 || r > mh::kExcessMaxLen || lead >= mh::kExcessMaxLen)
+        return fail(MH_ERR_ARG, "mhi_excess_apply: r=%llu, lead=%llu (r 1 .. 2^32, lead below 2^32)", (unsigned long long)r,
+                    (unsigned long long)lead);
+    if (start > stop || stop > mh::kExcessMaxLen)
+        return fail(MH_ERR_ARG, "mhi_excess_apply: start=%llu, stop=%llu (start <= stop <= 2^32)", (unsigned long long)start,
+                    (unsigned long long)stop);
+    if (out_bits == 32 && ((uintptr_t)out % 4 || row_stride % 4 || col_stride % 4))
+        return fail(MH_ERR_ARG, "mhi_excess_apply: out_bits=32 needs out and both strides to be multiples of 4");
+    if ((uintptr_t)pos % 4) return fail(MH_ERR_ARG, "mhi_excess_apply: pos is not 4-byte aligned");
+    if (n_rows == 0 || n_entries == 0 || start == stop) return MH_OK;  // nothing to add
+    const uint64_t elements = mh::apply_elements(start, stop, r, lead);
+    const uint64_t runs = (elements + mh::kApplyRun - 1) / mh::kApplyRun;
+    if ((unsigned __int128)n_rows * runs >= ((unsigned __int128)1 << 63))
+        return fail(MH_ERR_ARG, "mhi_excess_apply: n_rows=%llu is too large", (unsigned long long)n_rows);
+    uint8_t *const o8 = static_cast<uint8_t *>(out);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(mh::kApplyThreads);
+    if (r == 1) {
+        // a row's entries are few against its samples: 64 blocks stride them, one grid row per output row
+        const uint64_t per_row = (n_entries + mh::kApplyThreads - 1) / mh::kApplyThreads;
+        const dim3 grid((unsigned)(per_row < 64 ? per_row : 64), (unsigned)(n_rows < 65535 ? n_rows : 65535));
+        if (out_bits == 8)
+            hipLaunchKernelGGL(mh::k_excess_apply1<uint8_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
+                               stop, lead, o8, row_stride, col_stride);
+        else
+            hipLaunchKernelGGL(mh::k_excess_apply1<uint32_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
+                               stop, lead, o8, row_stride, col_stride);
+    } else {
+        const uint64_t jobs = n_rows * runs, blocks = (jobs + mh::kApplyThreads - 1) / mh::kApplyThreads;
+        const dim3 grid((unsigned)(blocks < mh::kApplyMaxBlocks ? blocks : mh::kApplyMaxBlocks));
+        if (out_bits == 8)
+            hipLaunchKernelGGL(mh::k_excess_apply<uint8_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
+                               stop, r, lead, elements, runs, o8, row_stride, col_stride);
+        else
+            hipLaunchKernelGGL(mh::k_excess_apply<uint32_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
+                               stop, r, lead, elements, runs, o8, row_stride, col_stride);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_apply: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

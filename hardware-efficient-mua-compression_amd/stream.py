@@ -46,6 +46,12 @@ def _packed_block(owner, Tb, slack=0):
     return buf, ch_off, plan
 
 
+def _no_exact_events(exact):
+    if exact:
+        raise ValueError("exact=True is not available for blocks binned from events: the binner writes packed pieces of "
+                         "min(count, S-1); bin to a time-major uint8 block and append that")
+
+
 class StreamEncoder:
     def __init__(self, C, S, hist_bits, sclv, mode=MODE_APPROX, seg_chunks=2, device="cuda"):
         self.C, self.S, self.h, self.mode = int(C), int(S), int(hist_bits), int(mode)
@@ -138,12 +144,13 @@ class StreamEncoder:
                                                      plan.chunk_stride, _stream()))
         return self._encode_slot(slot, track, checksum)
 
-    def encode_events_device(self, ev, origin, period, T, track=False, checksum=False):
+    def encode_events_device(self, ev, origin, period, T, track=False, checksum=False, exact=False):
         """encode_block_device for the block of T bins that `ev` (an events.EventSet) fills from `origin` at `period`
         ticks per bin: the slot's packed chunk-blocked pieces are written by the binner (mhi_bin_events, min(count, 3)
         in 2 bits for S <= 4, min(count, 15) in 4 bits for S >= 5) -- no time-major block, no de-interleave.  Everything
         behind the pieces is the block path's, and so is the stream, byte for byte."""
         from . import _ingest
+        _no_exact_events(exact)
         if self.peak is None:
             raise RuntimeError("calibrate() first")
         if ev.C != self.C:
@@ -170,22 +177,33 @@ class StreamEncoder:
             slot["crc"] = container_io.enqueue_seg_crc(plan, dense, out=slot.get("crc"))
         return dense, tot, slot
 
-    def encode_block(self, block, checksum=False):
+    def encode_block(self, block, checksum=False, exact=False):
         """block: [Tb, C] time-major counts -> container_io.Compressed covering all Tb bins of
         every channel, coded with the stored RAM word.  checksum=True: a revision-4 container with the segments'
-        CRC-32 (taken on the device)."""
-        return self._finish_block(*self.encode_block_device(block, checksum=checksum), checksum=checksum)
+        CRC-32 (taken on the device).  exact=True: the block also carries, as a sparse list, every count above S-1
+        (excess.from_time_major: the COLS form of mhi_excess_count / mhi_excess_emit on the time-major block itself --
+        the packed intermediate has already lost them -- with one read of the list's length between the two)."""
+        t = block if isinstance(block, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(block, np.uint8))
+        t = t.to(self.device).contiguous()
+        c = self._finish_block(*self.encode_block_device(t, checksum=checksum), checksum=checksum, exact=exact)
+        if exact:
+            from . import excess
+            exc_off, pos, val = excess.from_time_major(t, self.S - 1)
+            container_io.attach_excess(c, exc_off.cpu().numpy(), pos.cpu().numpy().view(np.uint32), val.cpu().numpy())
+        return c
 
-    def _finish_block(self, dense, tot, slot, checksum=False):
+    def _finish_block(self, dense, tot, slot, checksum=False, exact=False):
         plan = slot["plan"]
         torch.cuda.synchronize()
-        hdr = container_io.make_header(self.S, 0, self.mode, WIN_FULL, plan.seg_chunks, self.sclv, checksum)
+        hdr = container_io.make_header(self.S, 0, self.mode, WIN_FULL, plan.seg_chunks, self.sclv, checksum, exact)
         hdr["preset"] = True
         return container_io.Compressed.from_device(hdr, slot["cs"].ch_len, slot["enc"], plan.n_segments, dense.payload,
                                                    int(tot.item()), slot["crc"] if checksum else None)
 
-    def encode_events(self, ev, origin, period, T, checksum=False):
-        """encode_block for the T bins that `ev` fills from `origin` at `period` ticks per bin."""
+    def encode_events(self, ev, origin, period, T, checksum=False, exact=False):
+        """encode_block for the T bins that `ev` fills from `origin` at `period` ticks per bin.  exact=True raises
+        ValueError: the binner writes packed pieces, which have lost the counts above S-1."""
+        _no_exact_events(exact)
         return self._finish_block(*self.encode_events_device(ev, origin, period, T, checksum=checksum), checksum=checksum)
 
     def drift(self, slot):

@@ -148,6 +148,69 @@ int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, ui
                    uint64_t origin, uint64_t period, uint64_t phase, uint64_t *out_ticks, void *out_ch, uint32_t ch_bits,
                    uint64_t capacity, uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream);
 
+/* ---- exact counts: what the codec's clip at S-1 drops, as a sparse side list ----------------------------------------
+ * The codec stores min(x, S-1).  An element x > threshold (threshold = S-1) of channel c at sample p is ONE entry of
+ * the list: pos = p (uint32, the sample index inside the channel) and val = x - threshold (uint8, 1 .. 254).  The list
+ * is canonical: channel-major, ascending pos inside a channel; exc_off[0 .. channels] is its CSR index.  It is made in
+ * two passes with ONE read of a number between them, as mhi_unbin_count / mhi_unbin_emit: mhi_excess_count writes
+ * total[0] and exc_off, the caller sizes pos / val from total, and mhi_excess_emit stores the entries.
+ * MHI_EXCESS_ROWS: rows are channels.  Row i is the bytes at in + row_off[i] (row_off: device, rows entries, bytes; a
+ *   row may start at ANY byte address), and its columns [lo[i], min(hi[i], cols)) are examined (lo, hi: device, rows
+ *   entries each; NULL stands for 0 and for cols).  No byte outside that window is read, and pos is the column -- not
+ *   the column minus lo.  cols is the longest row: rows are cut into tiles of 16 KiB at multiples of 16384 columns.
+ * MHI_EXCESS_COLS: in = one contiguous time-major [rows = T, cols = C] block, every column whole: row_off, lo and hi
+ *   must be NULL.  Column c is channel c and pos is the row.  The list is, entry for entry, what the ROWS form gives on
+ *   the transposed matrix; exc_off has cols + 1 entries.
+ * threshold: 1 .. 254.  rows >= 1, cols >= 1, cols < 2^32, and in the COLS form rows < 2^32 (a position is 32-bit); more
+ * than 2^32 - 1 pieces (ROWS: rows * ceil(cols / 16384); COLS: cols * ceil(rows / 512)) are refused.
+ * scratch: device, 16-byte aligned, at least mhi_excess_scratch_bytes(form, rows, cols) bytes; it need not be zeroed,
+ * and every cell of it that is read was written by the same mhi_excess_count, so that calls chain on one scratch.
+ * All return MH_ERR_ARG, before any device work, for a NULL pointer that is used, an unknown form, a row_off, lo or hi
+ * that does not fit the form, and any breach of the rules above.
+ * count, emit and apply only enqueue on `stream`: no synchronisation, allocation or free, so they can be captured into
+ * a hipGraph. */
+#define MHI_EXCESS_ROWS 0u   /* rows are channels: row i = bytes in + row_off[i], columns [lo[i], hi[i]) examined */
+#define MHI_EXCESS_COLS 1u   /* in = one contiguous time-major [rows = T, cols = C] block; every column whole   */
+
+/* Bytes of scratch for (form, rows, cols).  Host arithmetic only: no device is needed or touched.  Never 0, and
+ * non-decreasing in rows and in cols. */
+int mhi_excess_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes);
+
+/* First pass: total[0] = the number of entries (device, 1 entry) and exc_off[0 .. channels] (device; channels = rows in
+ * the ROWS form, cols in the COLS form).  Leaves the 64-bit output base of every piece in the scratch. */
+int mhi_excess_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo, const uint64_t *hi,
+                     uint64_t rows, uint64_t cols, uint32_t threshold, uint64_t *exc_off, uint64_t *total, void *scratch,
+                     uint64_t scratch_bytes, void *stream);
+
+/* Second pass, on the SAME (form, in, row_off, lo, hi, rows, cols, threshold, scratch) as the count before it:
+ * pos[0 .. total) (device, 4-byte aligned) and val[0 .. total).  capacity: the entries pos and val hold.  Nothing is ever
+ * stored at or behind index capacity, whatever the input holds by then: the entries that could not be stored are added
+ * to over[0] (device, 1 entry, zeroed by the caller) -- with capacity >= total and an unchanged input over stays 0,
+ * every entry below total is written and nothing else.  With total == 0 nothing is written. */
+int mhi_excess_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo, const uint64_t *hi,
+                    uint64_t rows, uint64_t cols, uint32_t threshold, uint32_t *pos, uint8_t *val, uint64_t capacity,
+                    uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream);
+
+/* The read side: add a list back onto decoded counts.  Output row i < n_rows takes the entries [first[i], last[i]) of
+ * (pos, val) (first, last: device, n_rows entries; n_entries: the entries pos and val hold).  first[i], last[i] and every
+ * index are clamped to n_entries, and first >= last is an empty row: repeated and re-ordered channels are just rows.
+ * An entry with start <= pos < stop adds val to element b = (pos - start + lead) / r of the row, which lies at
+ * (char *)out + i*row_stride + b*col_stride (strides in bytes: channel-major rows, a wide pitched result and a
+ * time-major block are all targets).  A row has ceil((stop - start + lead) / r) elements and nothing else is stored to.
+ * out_bits = 8: uint8 elements, the sum saturates at 255.  out_bits = 32: 32-bit elements, exact (out and both strides
+ * multiples of 4).  start <= stop <= 2^32, 1 <= r <= 2^32, lead < 2^32.
+ * The list is untrusted: an entry outside [start, stop) is dropped and no address is formed from a value that was not
+ * compared first.  For r > 1 every output element has one owning thread, which searches the row's entries -- they must
+ * ascend in pos for the result to be right; it is the same from run to run.  For r == 1 a thread per entry owns its
+ * element: duplicate positions -- a corrupt list -- leave those elements unspecified, but every store stays in bounds.
+ * The elements must not be written by anything else while the call runs; rows that alias each other are the caller's.
+ * MH_ERR_ARG, before any device work: first, last or out NULL; pos or val NULL with n_entries > 0; pos not 4-byte
+ * aligned; out_bits other than 8 or 32; r == 0; any breach of the ranges above.  n_rows == 0, n_entries == 0 or
+ * start == stop enqueue nothing. */
+int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries, const uint64_t *first, const uint64_t *last,
+                     uint64_t n_rows, uint64_t start, uint64_t stop, uint64_t r, uint64_t lead, void *out, uint32_t out_bits,
+                     uint64_t row_stride, uint64_t col_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
