@@ -35,6 +35,8 @@ int fail(int code, const char *fmt, ...)
 }
 
 static_assert(mh::kGeoCrcWaves == mh::kCrcWaves && mh::kCrcMaxX == mh::kCrcMaxGroups, "mh_launch.hpp sizes the grid by mh_crc.hpp's constants");
+static_assert(mh::kGeoApplyThreads == mh::kApplyThreads && mh::kGeoApplyMaxBlocks == mh::kApplyMaxBlocks,
+              "mh_launch.hpp sizes the apply grids by mh_excess_layout.hpp's constants");
 
 // Where does a table live?  Only a query of the runtime's allocation records: nothing is enqueued, nothing waits.
 enum class Where { kDevice, kBoth, kHostOnly };
@@ -436,9 +438,8 @@ int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(mh::kApplyThreads);
     if (r == 1) {
-        // a row's entries are few against its samples: 64 blocks stride them, one grid row per output row
-        const uint64_t per_row = (n_entries + mh::kApplyThreads - 1) / mh::kApplyThreads;
-        const dim3 grid((unsigned)(per_row < 64 ? per_row : 64), (unsigned)(n_rows < 65535 ? n_rows : 65535));
+        const mh::GridXY g = mh::excess_apply1_grid(n_entries, n_rows);  // capped in x and y (mh_launch.hpp)
+        const dim3 grid(g.x, g.y);
         if (out_bits == 8)
             hipLaunchKernelGGL(mh::k_excess_apply1<uint8_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
                                stop, lead, o8, row_stride, col_stride);
@@ -446,8 +447,7 @@ int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries
             hipLaunchKernelGGL(mh::k_excess_apply1<uint32_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
                                stop, lead, o8, row_stride, col_stride);
     } else {
-        const uint64_t jobs = n_rows * runs, blocks = (jobs + mh::kApplyThreads - 1) / mh::kApplyThreads;
-        const dim3 grid((unsigned)(blocks < mh::kApplyMaxBlocks ? blocks : mh::kApplyMaxBlocks));
+        const dim3 grid(mh::excess_apply_grid(n_rows, runs));  // capped (mh_launch.hpp)
         if (out_bits == 8)
             hipLaunchKernelGGL(mh::k_excess_apply<uint8_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
                                stop, r, lead, elements, runs, o8, row_stride, col_stride);

@@ -135,4 +135,21 @@ inline int bin_events_launch(Msg &m, uint32_t C, uint64_t T, uint64_t period, Bi
 constexpr uint32_t kGeoCrcWaves = 4, kCrcMaxX = 2048;  // mh_crc.hpp: kCrcWaves, kCrcMaxGroups (8 workgroups per CU)
 inline uint32_t seg_crc_grid(uint64_t n_list) { return (uint32_t)clamp_grid(grid_ceil_div(n_list, kGeoCrcWaves), kCrcMaxX); }
 
+// ---- mhi_excess_apply: workgroups of kGeoApplyThreads threads
+constexpr uint32_t kGeoApplyThreads = 256;           // mh_excess_layout.hpp: kApplyThreads
+constexpr uint64_t kGeoApplyMaxBlocks = 1u << 20;    // mh_excess_layout.hpp: kApplyMaxBlocks
+// r == 1 (k_excess_apply1): one grid row per output row, i += gridDim.y; a row's entries are few against its samples,
+// so at most kApply1MaxX workgroups stride them, e += gridDim.x * 256 (x is sized by the whole list: no row has more)
+constexpr uint32_t kApply1MaxX = 64;
+inline GridXY excess_apply1_grid(uint64_t n_entries, uint64_t n_rows)
+{
+    return {(uint32_t)clamp_grid(grid_ceil_div(n_entries, kGeoApplyThreads), kApply1MaxX), (uint32_t)clamp_grid(n_rows, kGridMaxY)};
+}
+// r > 1 (k_excess_apply): a thread per run of a row, n_rows * runs jobs (below 2^63: the call refuses more) in one
+// dimension, job += gridDim.x * 256
+inline uint32_t excess_apply_grid(uint64_t n_rows, uint64_t runs)
+{
+    return (uint32_t)clamp_grid(grid_ceil_div(n_rows * runs, kGeoApplyThreads), kGeoApplyMaxBlocks);
+}
+
 }  // namespace mh

@@ -37,7 +37,8 @@
 // with the vectors here, as --arena does.
 // With --geometry (tests/test_host_launch_geometry.py) the capped launch grids of csrc/mh_launch.hpp, one launch per
 // line: synth max_len C | rebin max_len C r | fills max_fill per_block nfill | transposed T C tpw | items n |
-// compact nseg | bin_events C T period | seg_crc32 n_list | chunk_stride stride bits.  Output per line: the name, the
+// compact nseg | bin_events C T period | seg_crc32 n_list | excess_apply1 n_entries n_rows | excess_apply n_rows runs |
+// chunk_stride stride bits.  Output per line: the name, the
 // grid and the derived kernel arguments, or "name error rc message".
 #include <cstdio>
 #include <cstdlib>
@@ -420,7 +421,7 @@ static int geometry()
     char name[32];
     while (scanf("%31s", name) == 1) {
         unsigned long long v[3] = {0, 0, 0};
-        const bool two = !strcmp(name, "synth") || !strcmp(name, "chunk_stride");
+        const bool two = !strcmp(name, "synth") || !strcmp(name, "chunk_stride") || !strcmp(name, "excess_apply1") || !strcmp(name, "excess_apply");
         const bool one = !strcmp(name, "items") || !strcmp(name, "compact") || !strcmp(name, "seg_crc32");
         for (int i = 0; i < (one ? 1 : two ? 2 : 3); ++i)
             if (scanf("%llu", &v[i]) != 1) return 1;
@@ -461,6 +462,13 @@ static int geometry()
                        (unsigned long long)l.nspans, l.div_mode);
         } else if (!strcmp(name, "seg_crc32")) {
             printf("seg_crc32 %u\n", mh::seg_crc_grid(v[0]));
+        } else if (!strcmp(name, "excess_apply1")) {
+            if (v[0] == 0 || v[1] == 0) return 1;  // (mhi_excess_apply returns before it looks at a grid)
+            const mh::GridXY g = mh::excess_apply1_grid(v[0], v[1]);
+            printf("excess_apply1 %u %u\n", g.x, g.y);
+        } else if (!strcmp(name, "excess_apply")) {
+            if (v[0] == 0 || v[1] == 0 || (unsigned __int128)v[0] * v[1] >= ((unsigned __int128)1 << 63)) return 1;  // (refused)
+            printf("excess_apply %u\n", mh::excess_apply_grid(v[0], v[1]));
         } else if (!strcmp(name, "chunk_stride")) {
             printf("chunk_stride %d\n", (int)mh::chunk_stride_ok(v[0], (uint32_t)v[1]));
         } else {

@@ -1,7 +1,7 @@
 """The capped launch grids of the two libraries (csrc/mh_launch.hpp: what muahuff.hip and mh_ingest.hip launch) read back
 off-device: planner_check --geometry prints the grid and the derived kernel arguments of one launch per line, under
 AddressSanitizer + UBSan, and every rule is restated here in Python -- at the shapes tests/test_gpu_launch_caps.py,
-tests/test_gpu_bin_events_spans.py and tests/test_gpu_checksum.py run on the device, and at the edges of each cap.
+tests/test_gpu_bin_events_spans.py, tests/test_gpu_checksum.py and tests/test_gpu_ingest_trips.py run on the device, and at the edges of each cap.
 DESIGN.md ("Capped launch grids") is the table of the rules.  Runs without a GPU."""
 import os
 import subprocess
@@ -154,6 +154,29 @@ def test_bin_events_spans_and_division(exe):  # noqa: F811
     # more channels than one grid dimension holds fit at no span
     _refused(got[-2], "bin_events", "C=2147483648")
     _refused(got[-1], "bin_events", "C=4294967295")
+
+
+# ---- mhi_excess_apply --------------------------------------------------------------------------------------------------
+def test_excess_apply_grids(exe):  # noqa: F811
+    # r == 1 (k_excess_apply1): x = at most 64 workgroups of 256 threads over the LIST's entries, y = one grid row per
+    # output row up to 65535.  Both sides of each cap, and the shapes of tests/test_gpu_ingest_trips.py
+    ones = [(1, 1), (256, 1), (257, 1), (63 * 256, 7), (64 * 256, 7), (64 * 256 + 1, 7), (65 * 256, 7), (1000, YMAX - 1), (1000, YMAX),
+            (1000, YMAX + 1), (12000, C_BIG), (90000, 3), (2 ** 40, 2 ** 40), (2 ** 64 - 1, 2 ** 64 - 1)]
+    got = _run(exe, ["excess_apply1 %d %d" % s for s in ones])
+    for (n_entries, n_rows), rec in zip(ones, got):
+        assert _ints(rec, "excess_apply1") == [min(_ceil(n_entries, 256), 64), min(n_rows, YMAX)], (n_entries, n_rows)
+    assert [_ints(r, "excess_apply1")[0] for r in got[:7]] == [1, 1, 2, 63, 64, 64, 64]
+    assert [_ints(r, "excess_apply1")[1] for r in got[7:11]] == [YMAX - 1, YMAX, YMAX, YMAX]
+    # r > 1 (k_excess_apply): a thread per run of 32 elements of a row, at most 2^20 workgroups of 256 threads
+    cap = 2 ** 20
+    jobs = [(1, 1), (3, 625), (256, 1), (257, 1), (cap * 256 - 1, 1), (cap * 256, 1), (cap * 256 + 1, 1), (cap, 256), (cap + 1, 256),
+            (2 ** 28 + 1000, 1), (2 ** 31, 2 ** 31), (2 ** 63 - 1, 1), (1, 2 ** 63 - 1)]
+    got = _run(exe, ["excess_apply %d %d" % s for s in jobs])
+    for (n_rows, runs), rec in zip(jobs, got):
+        assert _ints(rec, "excess_apply") == [min(_ceil(n_rows * runs, 256), cap)], (n_rows, runs)
+    assert [_ints(r, "excess_apply")[0] for r in got[:10]] == [1, 8, 1, 2, cap, cap, cap, cap, cap, cap]
+    assert _ceil(cap * 256 - 1, 256) == cap and _ceil((cap - 1) * 256 + 1, 256) == cap
+    assert _ints(_run(exe, ["excess_apply %d 1" % ((cap - 1) * 256)])[0], "excess_apply") == [cap - 1]
 
 
 # ---- mhi_seg_crc32, the chunk-stride rule ------------------------------------------------------------------------------
