@@ -257,15 +257,15 @@ class Reader:
         if rows and n:
             for i, a, b in block_ranges(self._t_first, self._Tb, start, stop):
                 bf = self._checked_block_file(i)
-                _sel, payload, seg_off, segs, peak, enc = cio._range_inputs(bf, a, b, sel, check)
-                lists = cio.gather_excess(bf, a, b, sel, check, "archive block %d" % i) if use and payload is not None else None
-                jobs.append((bf, a, b, int(self._t_first[i]) + a - start, payload, seg_off, peak, enc, i, segs, lists))
+                job = cio._range_job(bf, a, b, sel, check, use=use, what="archive block %d" % i)
+                job.block, job.g0 = i, int(self._t_first[i]) + a - start
+                jobs.append(job)
         if not jobs:
             z = torch.zeros((rows, cols), dtype=dtype, device="cuda") if out is None else out.zero_()
             return z.t().contiguous() if time_major else z
         plans, bads = [], []
         try:
-            res = self._decode(torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads if check else None)
+            res = self._decode(torch, jobs, rows, n, cols, r, saturate, dtype, out, plans, bads, check)
         except BaseException:
             codec.check_decoded(plans, unwinding=True)      # every plan's flag is read and cleared all the same
             raise
@@ -310,61 +310,48 @@ class Reader:
             ch = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int64)).to(ch.device)[ch.long()].to(ch_dtype)
         return ticks, ch
 
-    def _decode(self, torch, jobs, sel, rows, n, cols, r, saturate, dtype, out, plans, bads):
+    def _decode(self, torch, jobs, rows, n, cols, r, saturate, dtype, out, plans, bads, check):
         """Enqueue the decode of every job into its columns of the wide result (out_pitch = the wide row stride); with
-        `bads` a list, the verification of each block's uploaded segments next to its upload: (block, counter) pairs."""
-        from . import codec, excess
+        check, the verification of each block's uploaded segments next to its upload: (block, counter) pairs in `bads`."""
+        from . import codec
 
-        def launch(job, fn, lead=0):
-            bf, a, b, g0, payload, seg_off, peak, enc, i, segs, lists = job
-            plan = self._plan_for(bf)
+        def launch(job, decode, lead=0):
+            plan = self._plan_for(job.src)
             if plan not in plans:
                 plans.append(plan)
-            up = codec.upload_stream(plan.device, payload, seg_off, peak, enc)
-            if bads is not None:
-                bad = cio.enqueue_verify(bf, up[0], up[1], bf.seg_words, segs, True)
-                if bad is not None:
-                    bads.append((i, bad))
-            target = fn(plan, *up, a, b, g0)
-            if lists is not None and len(lists[0]):      # behind the block's decode, into the block's columns
-                excess.apply(*excess.upload(lists[0], lists[1], plan.device), lists[2], lists[3], a, b, 1 if r is None else r,
-                             lead, target)
+            _target, bad = cio._enqueue(plan, job, check, decode, 1 if r is None else r, lead)   # the list: into the block's columns
+            if bad is not None:
+                bads.append((job.block, bad))
 
         if r is None:
             if out is None:     # the first block's local sample t at a byte address congruent to t mod 128
-                out = codec.aligned_rows(rows, n, jobs[0][1], "cuda")
-            for job in jobs:
-                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
-                       plan.decode_range(pay, off, pk, en, sel, a, b, out=out[:, g0:g0 + b - a]))
+                out = codec.aligned_rows(rows, n, jobs[0].a, "cuda")
+            for j in jobs:
+                launch(j, lambda plan, *up: plan.decode_range(*up, j.sel, j.a, j.b, out=out[:, j.g0:j.g0 + j.b - j.a]))
             return out
         # a block whose t_first - start is a multiple of r decodes straight to sums; every bin it touches begins in it
-        aligned = [(job[3] - job[1]) % r == 0 for job in jobs]   # g0 - a == t_first - start: mh_decode_rebin's local rule holds
-        if all(aligned):        # then no bin has samples in two blocks either
-            res = torch.empty((rows, cols), dtype=dtype, device="cuda") if out is None else out
-            for job in jobs:
-                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
-                       plan.decode_rebin(pay, off, pk, en, sel, a, b, r, saturate,
-                                         out=res[:, g0 // r:g0 // r + (b - a + r - 1) // r]))
-            return res
-        # otherwise exact int32 sums: aligned blocks write their bins (in time order, so before any later block adds to
-        # their last, cut bin); the others have no local multiple of r on a global bin boundary -- their samples are
-        # range-decoded behind g0 % r leading zeros and summed per bin on the device
-        acc = torch.zeros((rows, cols), dtype=torch.int32, device="cuda")
-        for job, al in zip(jobs, aligned):
+        aligned = [(j.g0 - j.a) % r == 0 for j in jobs]   # g0 - a == t_first - start: mh_decode_rebin's local rule holds
+        summed = not all(aligned)    # all aligned: no bin has samples in two blocks either, each block writes its own bins;
+        # otherwise exact int32 sums: aligned blocks write theirs (in time order, so before any later block adds to their
+        # last, cut bin); the others are range-decoded behind g0 % r leading zeros and summed per bin on the device
+        res = torch.zeros((rows, cols), dtype=torch.int32, device="cuda") if summed else \
+            torch.empty((rows, cols), dtype=dtype, device="cuda") if out is None else out
+        for j, al in zip(jobs, aligned):
             if al:
-                launch(job, lambda plan, pay, off, pk, en, a, b, g0:
-                       plan.decode_rebin(pay, off, pk, en, sel, a, b, r, False,
-                                         out=acc[:, g0 // r:g0 // r + (b - a + r - 1) // r]))
+                launch(j, lambda plan, *up: plan.decode_rebin(*up, j.sel, j.a, j.b, r, saturate and not summed,
+                                                              out=res[:, j.g0 // r:j.g0 // r + (j.b - j.a + r - 1) // r]))
             else:
-                def edge(plan, pay, off, pk, en, a, b, g0):
-                    lead = g0 % r
-                    k = (lead + b - a + r - 1) // r
+                def edge(plan, *up):
+                    lead = j.g0 % r
+                    k = (lead + j.b - j.a + r - 1) // r
                     tmp = torch.zeros((rows, k * r), dtype=torch.uint8, device=plan.device)
-                    plan.decode_range(pay, off, pk, en, sel, a, b, out=tmp[:, lead:lead + b - a])
-                    acc[:, g0 // r:g0 // r + k] += tmp.view(rows, k, r).sum(dim=2, dtype=torch.int32)
-                    return acc[:, g0 // r:g0 // r + k]
-                launch(job, edge, job[3] % r)
-        res = acc.clamp_(max=255).to(torch.uint8) if saturate else acc
+                    plan.decode_range(*up, j.sel, j.a, j.b, out=tmp[:, lead:lead + j.b - j.a])
+                    res[:, j.g0 // r:j.g0 // r + k] += tmp.view(rows, k, r).sum(dim=2, dtype=torch.int32)
+                    return res[:, j.g0 // r:j.g0 // r + k]
+                launch(j, edge, j.g0 % r)
+        if not summed:
+            return res
+        res = res.clamp_(max=255).to(torch.uint8) if saturate else res
         return res if out is None else out.copy_(res)
 
     def verify(self, device=True):
@@ -379,20 +366,7 @@ class Reader:
         for i in range(len(self.blocks)):
             c = self.block(i)      # read whole: an exact block's lists against excess_crc32 and the directory (ValueError)
             _check_member(c, self.C, self.S, self.mode, self.seg_chunks, self.sclv, checksum=True, exact=self.exact)
-            if device:
-                import torch
-
-                from . import _ingest, codec
-                n = len(c.seg_words)
-                off = np.concatenate([[0], np.cumsum(c.seg_words)[:-1]]).astype(np.int64) if n else np.zeros(1, np.int64)
-                pay, d_off, _pk, _en = codec.upload_stream(torch.device("cuda", torch.cuda.current_device()), c.payload,
-                                                           off, c.peak, c.enc)
-                words = torch.from_numpy(np.ascontiguousarray(c.seg_words, np.uint64).view(np.int64)).to(pay.device)
-                crc = torch.zeros(max(n, 1), dtype=torch.int32, device=pay.device)
-                _ingest.seg_crc32(pay, d_off, words, n, crc=crc, payload_words=pay.numel() - 4)
-                got = crc[:n].cpu().numpy().view(np.uint32)
-            else:
-                got = cio.seg_crc_host(c)
+            got = cio.seg_crc_device(c) if device else cio.seg_crc_host(c)
             bad += [(i, int(s)) for s in np.nonzero(got != np.asarray(c.seg_crc, np.uint32))[0]]
         return bad
 

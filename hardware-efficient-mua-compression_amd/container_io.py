@@ -30,6 +30,7 @@ import io
 import json
 import struct
 import zlib
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -71,6 +72,20 @@ class Compressed:
         """What exact=True costs: 40 bits per entry plus the segment index; 0 without the lists."""
         return 0 if self.exc_pos is None else excess.ENTRY_BITS * int(len(self.exc_pos)) + 64 * int(len(self.exc_seg))
 
+    @property
+    def payload_words(self):
+        return int(self.payload.size)
+
+    @property
+    def excess_entries(self):
+        return int(len(self.exc_pos))
+
+    def read_words(self, first, n):
+        return self.payload[first:first + n]
+
+    def read_excess(self, first, n):
+        return self.exc_pos[first:first + n], self.exc_val[first:first + n]
+
     def tobytes(self):
         buf = io.BytesIO()
         write(buf, self)
@@ -96,21 +111,30 @@ SEG_CRC = ("seg_crc", np.uint32)   # revision 4: between seg_words and payload (
 EXCESS = excess.NAMES              # exact=True: exc_seg, exc_pos, exc_val behind the payload
 
 
-def _has_excess(c):
-    """Does c carry the lists?  ValueError unless the header's "exact" and the three arrays agree."""
-    have = [getattr(c, name, None) is not None for name, _ in EXCESS]
-    if any(have) != all(have) or all(have) != (c.header.get("exact") is True):
-        raise ValueError("container header says exact=%r %s the excess lists" % (c.header.get("exact"), "with" if any(have) else "without"))
-    return all(have)
+def file_arrays(hd, have, reading=False):
+    """The header rule, for writing and reading alike -> (name, dtype) of the arrays a container with header hd holds, in
+    file order.  have: the names present (a Compressed's arrays) or listed (the sizes of a header that was read).  ValueError
+    unless revision 4 <=> seg_crc, "exact": true <=> the three lists; reading: no other "exact", both => excess_crc32."""
+    crc, exc = SEG_CRC[0] in have, [name in have for name, _ in EXCESS]
+    if crc != (hd.get("format_revision") == CHECKSUM_REVISION):
+        raise ValueError("container revision %r %s seg_crc" % (hd.get("format_revision"), "with" if crc else "without"))
+    if any(exc) != all(exc) or all(exc) != (hd.get("exact") is True) or (reading and hd.get("exact", True) is not True):
+        raise ValueError("container header says exact=%r %s the excess lists" % (hd.get("exact"), "with" if any(exc) else "without"))
+    if reading and all(exc) and crc and not isinstance(hd.get("excess_crc32"), int):
+        raise ValueError("corrupt container: checksums without excess_crc32")
+    return ARRAYS[:-1] + ((SEG_CRC,) if crc else ()) + ARRAYS[-1:] + (EXCESS if all(exc) else ())
 
 
 def _file_arrays(c):
-    """(name, dtype) of the arrays c has in a file, in file order.  ValueError unless checksums and revision, and the
-    header's "exact" and the lists, agree."""
-    has = getattr(c, "seg_crc", None) is not None
-    if has != (c.header.get("format_revision") == CHECKSUM_REVISION):
-        raise ValueError("container revision %r %s seg_crc" % (c.header.get("format_revision"), "with" if has else "without"))
-    return (ARRAYS[:-1] + (SEG_CRC,) + ARRAYS[-1:] if has else ARRAYS) + (EXCESS if _has_excess(c) else ())
+    return file_arrays(c.header, [name for name, _ in ARRAYS + (SEG_CRC,) + EXCESS if getattr(c, name, None) is not None])
+
+
+def crc32_padded(parts):
+    """zlib's CRC-32 over arrays as written: parts = (an array's bytes, its padding to 8 -- None: the zeros of write())."""
+    crc = 0
+    for raw, pad in parts:
+        crc = zlib.crc32(b"\0" * (-len(raw) % 8) if pad is None else pad, zlib.crc32(raw, crc))
+    return crc
 
 
 def _raw(c, name, dt):
@@ -122,11 +146,7 @@ def _header_blob(c):
     arrays = _file_arrays(c)
     hdr["sizes"] = {name: int(np.asarray(getattr(c, name)).size) for name, _ in arrays}
     if SEG_CRC in arrays:
-        crc = 0
-        for name, dt in arrays[:arrays.index(ARRAYS[-1])]:
-            raw = _raw(c, name, dt)
-            crc = zlib.crc32(b"\0" * (-raw.size % 8), zlib.crc32(raw, crc))
-        hdr["checksum"], hdr["arrays_crc32"] = "crc32", crc
+        hdr["checksum"], hdr["arrays_crc32"] = "crc32", crc32_padded((_raw(c, name, dt), None) for name, dt in arrays[:arrays.index(ARRAYS[-1])])
         if EXCESS[0] in arrays:
             hdr["excess_crc32"] = excess.crc32(c.exc_seg, c.exc_pos, c.exc_val)
     return json.dumps(hdr, sort_keys=True).encode()
@@ -134,88 +154,74 @@ def _header_blob(c):
 
 def nbytes(c):
     """The number of bytes write() emits for c (archive.py puts it in front of the block)."""
-    n = 12 + len(_header_blob(c))
-    for name, dt in _file_arrays(c):
-        raw = int(np.asarray(getattr(c, name)).size) * np.dtype(dt).itemsize
-        n += raw + (-raw % 8)
-    return n
+    sizes = [int(np.asarray(getattr(c, name)).size) * np.dtype(dt).itemsize for name, dt in _file_arrays(c)]
+    return 12 + len(_header_blob(c)) + sum(n + (-n % 8) for n in sizes)
 
 
 def write(f, c):
     blob = _header_blob(c)
-    f.write(MAGIC)
-    f.write(struct.pack("<I", len(blob)))
-    f.write(blob)
+    f.write(MAGIC + struct.pack("<I", len(blob)) + blob)
     for name, dt in _file_arrays(c):
         raw = _raw(c, name, dt)
         f.write(raw)
         f.write(b"\0" * (-raw.size % 8))
 
 
+def word_offsets(seg_words):
+    """int64 [n_segments + 1]: the first stored word of every directory entry, and the total behind the last."""
+    return np.concatenate([[0], np.cumsum(seg_words)]).astype(np.int64)
+
+
 def seg_crc_host(c):
     """The checksums of c's segments (a `Compressed` or a `ContainerFile`) with zlib, no GPU: uint32 [n_segments],
     zlib.crc32 of each segment's stored words as little-endian bytes, 0 for a segment of 0 words."""
     words = np.asarray(c.seg_words, np.uint64)
-    off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
-    if off[-1] > _stored_words(c):
+    off = word_offsets(words)
+    if off[-1] > c.payload_words:
         raise ValueError("corrupt container: the directory points past the payload")
-    pay = c.read_words(0, int(off[-1])) if isinstance(c, ContainerFile) else np.ascontiguousarray(c.payload, "<u4")
+    pay = np.ascontiguousarray(c.read_words(0, int(off[-1])), "<u4")
     return np.array([zlib.crc32(pay[off[s]:off[s + 1]].tobytes()) if words[s] else 0 for s in range(len(words))], np.uint32)
 
 
-def _read_array(read, skip, hdr, name, dt):
-    """-> (the array `name` of the container, the bytes it takes in the file with its padding)"""
-    size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
-    raw = read(size)
-    if len(raw) != size:
-        raise ValueError("truncated container (%s)" % name)
-    skip(-size % 8)
-    return np.frombuffer(raw, dtype=dt).copy(), size + (-size % 8)
+def _read_arrays(read, skip, hdr, names, crc=False, whole=False):
+    """The arrays `names`, in file order, through read(n) -> bytes; skip(n) passes over padding, with crc it is read (whole:
+    and must be there) -> ({name: array}, bytes taken in the file, crc32_padded of them as written or None)"""
+    out, used, parts = {}, 0, []
+    for name, dt in names:
+        size = int(hdr["sizes"][name]) * np.dtype(dt).itemsize
+        raw = read(size)
+        if len(raw) != size:
+            raise ValueError("truncated container (%s)" % name)
+        pad = (read if crc else skip)(-size % 8)
+        if whole and len(pad) != -size % 8:
+            raise ValueError("truncated container (%s)" % name)
+        out[name] = np.frombuffer(raw, dtype=dt).copy()
+        parts.append((raw, pad))
+        used += size + (-size % 8)
+    return out, used, crc32_padded(parts) if crc else None
 
 
 def read_head(read, skip=None):
     """Everything in front of the payload, through read(n) -> bytes: magic, header length, header, revision check and
     every array of ARRAYS but the payload.  skip(n) passes over padding (default: read it).
     -> (header, {name: array}, bytes consumed: the payload starts that far behind the magic)"""
-    skip = read if skip is None else skip
     if read(8) != MAGIC:
         raise ValueError("not a MUAHUFF1 container")
     (n,) = struct.unpack("<I", read(4))
     hdr = json.loads(read(n).decode())
     if hdr.get("format_revision") not in READ_REVISIONS:
         raise ValueError("unsupported container revision %r" % hdr.get("format_revision"))
-    has = isinstance(hdr.get("sizes"), dict) and SEG_CRC[0] in hdr["sizes"]
-    if has != (hdr["format_revision"] == CHECKSUM_REVISION):
-        raise ValueError("container revision %d %s seg_crc" % (hdr["format_revision"], "with" if has else "without"))
-    listed = [name in hdr["sizes"] for name, _ in EXCESS] if isinstance(hdr.get("sizes"), dict) else [False]
-    if any(listed) != all(listed) or all(listed) != (hdr.get("exact") is True) or ("exact" in hdr and hdr["exact"] is not True):
-        raise ValueError("container header says exact=%r %s the excess lists" % (hdr.get("exact"), "with" if any(listed) else "without"))
-    if all(listed) and has and not isinstance(hdr.get("excess_crc32"), int):
-        raise ValueError("corrupt container: checksums without excess_crc32")
-    arrays, pos, crc = {}, 12 + n, 0
-    for name, dt in ARRAYS[:-1] + ((SEG_CRC,) if has else ()):
-        if has:     # arrays_crc32 covers the padding as written: read, not skipped
-            arrays[name], size = _read_array(read, lambda pad: None, hdr, name, dt)
-            pad = read(size - arrays[name].nbytes)
-            crc = zlib.crc32(pad, zlib.crc32(arrays[name].view(np.uint8), crc))
-        else:
-            arrays[name], size = _read_array(read, skip, hdr, name, dt)
-        pos += size
+    names = file_arrays(hdr, hdr["sizes"] if isinstance(hdr.get("sizes"), dict) else (), reading=True)
+    has = SEG_CRC in names     # arrays_crc32 covers the padding as written: read, not skipped
+    arrays, size, crc = _read_arrays(read, read if skip is None else skip, hdr, names[:names.index(ARRAYS[-1])], crc=has)
     if has and (hdr.get("checksum") != "crc32" or hdr.get("arrays_crc32") != crc):
         raise ValueError("corrupt container: checksum of the arrays in front of the payload does not match")
-    return hdr, arrays, pos
+    return hdr, arrays, 12 + n + size
 
 
 def read_excess(read, hdr):
-    """The three arrays behind the payload, through read(n) -> bytes, with excess_crc32 checked when the header has one.
-    -> {name: array}"""
-    out, crc = {}, 0
-    for name, dt in EXCESS:
-        out[name], size = _read_array(read, lambda pad: None, hdr, name, dt)
-        pad = read(size - out[name].nbytes)
-        if len(pad) != size - out[name].nbytes:
-            raise ValueError("truncated container (%s)" % name)
-        crc = zlib.crc32(pad, zlib.crc32(out[name].view(np.uint8), crc))
+    """The three arrays behind the payload through read(n) -> bytes, excess_crc32 checked when the header has one -> {name: array}"""
+    out, _size, crc = _read_arrays(read, None, hdr, EXCESS, crc=True, whole=True)
     if "excess_crc32" in hdr and hdr["excess_crc32"] != crc:
         raise ValueError("corrupt container: checksum of the excess lists does not match")
     return out
@@ -223,7 +229,7 @@ def read_excess(read, hdr):
 
 def read(f):
     hdr, arrays, _pos = read_head(f.read)
-    arrays["payload"], _size = _read_array(f.read, f.read, hdr, *ARRAYS[-1])
+    arrays.update(_read_arrays(f.read, f.read, hdr, ARRAYS[-1:])[0])
     if hdr.get("exact"):
         arrays.update(read_excess(f.read, hdr))
         c = Compressed(hdr, **arrays)
@@ -257,8 +263,7 @@ def make_header(S, h, mode, window, seg_chunks, sclv, checksum=False, exact=Fals
 def attach_excess(c, exc_off, pos, val):
     """Give the `Compressed` c (header with "exact": true) its lists: (exc_off [C + 1], pos, val) is the channel-major list
     of its channels (host arrays); the segment index is made here from the directory."""
-    hd = c.header
-    ch, lo, _hi = excess.segment_bounds(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd["format_revision"])
+    ch, lo, _hi = Directory.of(c).bounds()
     c.exc_pos = np.ascontiguousarray(pos, np.uint32)
     c.exc_val = np.ascontiguousarray(val, np.uint8)
     c.exc_seg = excess.segment_index(exc_off, c.exc_pos, ch, lo)
@@ -298,13 +303,29 @@ def compress(cs, S, h, mode, sclv, window=None, seg_chunks=0, checksum=False, ex
 def enqueue_seg_crc(plan, dense, out=None):
     """mhi_seg_crc32 over every segment of a compacted stream (dense: the codec.Encoded that Plan.compact returns, with
     its device offsets and sizes), on the current stream -> int32 device tensor [n_segments] holding the uint32 values."""
+    return _enqueue_crc(dense.payload, dense.seg_off, dense.seg_words, plan.n_segments, out)
+
+
+def _enqueue_crc(payload, seg_off, seg_words, n, out=None, payload_words=None):
     import torch
 
     from . import _ingest
-    crc = torch.zeros(max(plan.n_segments, 1), dtype=torch.int32, device=plan.device) if out is None else out
-    if plan.n_segments:
-        _ingest.seg_crc32(dense.payload, dense.seg_off, dense.seg_words, plan.n_segments, crc=crc)
+    crc = torch.zeros(max(n, 1), dtype=torch.int32, device=payload.device) if out is None else out
+    if n:
+        _ingest.seg_crc32(payload, seg_off, seg_words, n, crc=crc, payload_words=payload_words)
     return crc
+
+
+def seg_crc_device(c):
+    """seg_crc_host's values from the current device: c's payload uploaded whole, mhi_seg_crc32 over every segment (synchronises)."""
+    import torch
+
+    from . import codec
+    n, device = len(c.seg_words), torch.device("cuda", torch.cuda.current_device())
+    pay, d_off, _pk, _en = codec.upload_stream(device, c.payload, word_offsets(c.seg_words)[:-1] if n else np.zeros(1, np.int64),
+                                               c.peak, c.enc)
+    words = torch.from_numpy(np.ascontiguousarray(c.seg_words, np.uint64).view(np.int64)).to(device)
+    return _enqueue_crc(pay, d_off, words, n, payload_words=pay.numel() - 4)[:n].cpu().numpy().view(np.uint32)
 
 
 def enqueue_verify(src, pay, d_off, seg_words, segs, check, expect=None):
@@ -328,7 +349,7 @@ def enqueue_verify(src, pay, d_off, seg_words, segs, check, expect=None):
     cached = getattr(src, "_dev_dir", None) if expect is None else None     # a ContainerFile keeps its directory there
     if cached is None or cached[0].device != dev:
         cached = (up(seg_words, np.uint64), up(stored, np.uint32))
-        if expect is None and isinstance(src, ContainerFile):
+        if expect is None and hasattr(src, "_dev_dir"):
             src._dev_dir = cached
     bad = _ingest.verify_state(dev)
     _ingest.seg_crc32(pay, d_off, cached[0], len(seg_words), seg_idx=None if segs is None else up(segs, np.uint64),
@@ -388,10 +409,14 @@ def segments_per_channel(ch_len, h, window, seg_chunks, revision=FORMAT_REVISION
     return channel_layout(ch_len, h, window, seg_chunks, revision)[3]
 
 
+def window_bounds(ch_len, h, window):
+    """(w0, w1): the encoded window [w0, w1) of each channel, in channel samples (channel_layout)."""
+    return channel_layout(ch_len, h, window)[:2]
+
+
 def window_lengths(ch_len, h, window):
-    """Samples in the encoded window of each channel (the rules of include/muahuff.h)."""
-    w0, w1, _head, _nseg = channel_layout(ch_len, h, window)
-    return w1 - w0
+    """Samples in the encoded window of each channel (channel_layout)."""
+    return np.subtract(*window_bounds(ch_len, h, window)[::-1])
 
 
 def _header_fields(hd):
@@ -411,21 +436,53 @@ def _header_fields(hd):
     return S, K, h, window, seg_chunks, mode, sclv
 
 
-def _stored_words(src):
-    return int(src.payload_words if isinstance(src, ContainerFile) else src.payload.size)
+class Directory(namedtuple("Directory", "w0 w1 head nseg first seg")):
+    """A container's directory layout, built once per query from (ch_len, header) by channel_layout: int64 w0, w1, head,
+    nseg per channel; first [C + 1]: each channel's first entry (its segments are consecutive); seg: samples per segment."""
+    __slots__ = ()
+
+    @classmethod
+    def build(cls, ch_len, h, window, seg_chunks, revision=FORMAT_REVISION):
+        from . import CHUNK
+        w0, w1, head, nseg = channel_layout(ch_len, h, window, seg_chunks, revision)
+        return cls(w0, w1, head, nseg, np.concatenate([[0], np.cumsum(nseg)]).astype(np.int64), int(seg_chunks) * CHUNK)
+
+    @classmethod
+    def of(cls, src):
+        return cls.build(src.ch_len, *(src.header[k] for k in ("h", "window", "seg_chunks")),
+                         src.header.get("format_revision", FORMAT_REVISION))
+
+    def range(self, start, stop):
+        """-> int64 (first, end): entries first[c] .. end[c] - 1 hold samples [start, stop) of channel c (equal: none)."""
+        base, head, seg = self.first[:-1], self.head, self.seg
+        a = np.maximum(int(start), self.w0) - self.w0       # window samples [a, b)
+        b = np.minimum(int(stop), self.w1) - self.w0
+        hit = a < b     # index: the segment of window sample r within its channel
+        index = lambda r: np.where(head > 0, np.where(r < head, 0, 1 + (r - head) // seg), r // seg)  # noqa: E731
+        return np.where(hit, base + index(np.maximum(a, 0)), base), np.where(hit, base + index(np.maximum(b - 1, 0)) + 1, base)
+
+    def bounds(self):
+        """-> int64 arrays (channel, lo, hi) of every directory entry: its channel and its samples [lo, hi)."""
+        nseg, seg = self.nseg, self.seg
+        ch = np.repeat(np.arange(len(nseg), dtype=np.int64), nseg)
+        j = np.arange(int(self.first[-1]), dtype=np.int64) - np.repeat(self.first[:-1], nseg)   # entry within its channel
+        w0r, w1r, hd = self.w0[ch], self.w1[ch], self.head[ch]
+        has = hd > 0
+        lo = np.where(has, np.where(j == 0, w0r, w0r + hd + (j - 1) * seg), w0r + j * seg)
+        hi = np.where(has & (j == 0), w0r + hd, np.minimum(lo + seg, w1r))
+        return ch, lo, hi
 
 
-def check_consistent(c, arrays=True, what="container"):
-    """ValueError unless the per-channel arrays agree about the channel count (with `arrays`), no channel is empty and
-    the directory has the entries the header's layout gives these lengths.  -> directory entries per channel"""
-    hd = c.header
+def check_consistent(c, arrays=True, what="container", layout=None):
+    """ValueError unless the per-channel arrays agree about the channel count (with `arrays`), no channel is empty and the
+    directory has the entries the header's layout (a Directory the caller has, else made here) gives.  -> entries per channel"""
     C = len(c.ch_len)
     if arrays and not (len(c.peak) == len(c.enc) == len(c.skipped) == len(c.ch_bits) == C):
         raise ValueError("%s arrays disagree about the channel count" % what)
     if C and int(np.min(c.ch_len)) == 0:
         raise ValueError("%s holds an empty channel" % what)
-    nseg = segments_per_channel(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd.get("format_revision", FORMAT_REVISION))
-    if int(nseg.sum()) != len(c.seg_words) or (C == 0 and _stored_words(c)):
+    nseg = (Directory.of(c) if layout is None else layout).nseg
+    if int(nseg.sum()) != len(c.seg_words) or (C == 0 and c.payload_words):
         raise ValueError("%s directory does not match its header" % what)
     return nseg
 
@@ -518,14 +575,14 @@ def decompress(c, device="cuda", channels=None, check=True, exact=None):
         if use:
             excess.check_container(c)
     hd = c.header
-    nseg_ch = check_consistent(c, arrays=False)
+    layout = Directory.of(c)
+    check_consistent(c, arrays=False, layout=layout)
     seg_words, payload, peak, enc, skipped, ch_bits, ch_len = (c.seg_words, c.payload, c.peak, c.enc, c.skipped,
                                                                 c.ch_bits, c.ch_len)
     stored_crc, segs = getattr(c, "seg_crc", None), None
     if channels is not None:
         sel = codec.select_channels(len(c.ch_len), channels)
-        first = np.concatenate([[0], np.cumsum(nseg_ch)]).astype(np.int64)       # channel -> first segment
-        off = np.concatenate([[0], np.cumsum(c.seg_words)]).astype(np.int64)    # segment -> first word
+        first, off = layout.first, word_offsets(c.seg_words)        # channel -> first segment -> first word
         segs = np.concatenate([np.arange(first[i], first[i + 1]) for i in sel]) if sel.size else np.zeros(0, np.int64)
         payload = (np.concatenate([c.payload[off[s]:off[s + 1]] for s in segs]) if segs.size
                    else np.zeros(0, np.uint32))
@@ -543,7 +600,7 @@ def decompress(c, device="cuda", channels=None, check=True, exact=None):
             raise ValueError("container header: the planner cuts these channels into %d segments, not %d"
                              % (plan.n_segments, len(seg_words)))
         dev = cs.data.device
-        seg_off = np.concatenate([[0], np.cumsum(seg_words)[:-1]]).astype(np.int64) if len(seg_words) else np.zeros(1, np.int64)
+        seg_off = word_offsets(seg_words)[:-1] if len(seg_words) else np.zeros(1, np.int64)
         pay, d_off, d_peak, d_enc = codec.upload_stream(dev, payload, seg_off, peak, enc)
         e = codec.Encoded(pay, torch.from_numpy(seg_words.astype(np.int64)).to(dev),
                           torch.from_numpy(ch_bits.astype(np.int64)).to(dev), d_peak, d_enc,
@@ -551,10 +608,9 @@ def decompress(c, device="cuda", channels=None, check=True, exact=None):
         bad = enqueue_verify(c, pay, d_off, seg_words, None, check, expect=stored_crc)
         plan.decode(e, cs.data)
         if use and len(c.exc_pos):
-            first = np.concatenate([[0], np.cumsum(nseg_ch)]).astype(np.int64)
             ch = np.arange(len(c.ch_len)) if channels is None else sel
             seg_e = np.asarray(c.exc_seg, np.uint64).astype(np.int64)
-            _apply_channel_set(cs, *excess.upload(c.exc_pos, c.exc_val, dev), seg_e[first[ch]], seg_e[first[ch + 1]])
+            _apply_channel_set(cs, *excess.upload(c.exc_pos, c.exc_val, dev), seg_e[layout.first[ch]], seg_e[layout.first[ch + 1]])
         check_verified(bad, [plan], index=segs)
         codec.check_decoded([plan])
     finally:
@@ -580,7 +636,7 @@ class ContainerFile:
         self._f = builtins.open(self.path, "rb")
         try:
             self._f.seek(self.offset)
-            self._read_head()
+            self._read_head(*read_head(self._read, lambda pad: self._f.seek(pad, 1)))
         except Exception:
             self._f.close()
             raise
@@ -590,8 +646,8 @@ class ContainerFile:
         self.bytes_read += len(b)
         return b
 
-    def _read_head(self):
-        self.header, arrays, n = read_head(self._read, lambda pad: self._f.seek(pad, 1))
+    def _read_head(self, header, arrays, n):
+        self.header = header
         for name, a in arrays.items():
             setattr(self, name, a)
         self.payload_offset = self.offset + n           # file offset of payload word 0
@@ -645,14 +701,7 @@ class ContainerFile:
 
     def read_words(self, first, n):
         """payload words [first, first + n) as uint32 (ValueError past the end of the file)"""
-        out = np.empty(int(n), dtype=np.uint32)
-        if n:
-            self._f.seek(self.payload_offset + 4 * int(first))
-            got = self._f.readinto(memoryview(out).cast("B"))
-            self.bytes_read += got
-            if got != out.nbytes:
-                raise ValueError("truncated container (payload)")
-        return out
+        return self._read_at(self.payload_offset + 4 * int(first), n, np.uint32, "payload")
 
     def plan(self):
         """The cached decode plan of this container's layout (created on first use, on the current device)."""
@@ -685,42 +734,19 @@ def _range_plan(c):
                       np.array(hd["sclv"], np.uint8), seg_chunks=hd["seg_chunks"])
 
 
-def window_bounds(ch_len, h, window):
-    """(w0, w1): the encoded window [w0, w1) of each channel, in channel samples (include/muahuff.h)."""
-    return channel_layout(ch_len, h, window)[:2]
-
-
 def range_segments(ch_len, h, window, seg_chunks, start, stop, revision=FORMAT_REVISION):
-    """Directory entries that hold samples [start, stop) of each channel, by arithmetic on the layout: int64 arrays
-    (first, end) -- channel c's overlapping segments are entries first[c] .. end[c] - 1 (first == end: none, the range
-    misses the channel's window).  A channel's segments are consecutive in the directory and in the payload."""
-    from . import CHUNK
-    w0, w1, head, nseg = channel_layout(ch_len, h, window, seg_chunks, revision)
-    base = np.cumsum(nseg) - nseg
-    seg = int(seg_chunks) * CHUNK
-    a = np.maximum(int(start), w0) - w0                # window samples [a, b)
-    b = np.minimum(int(stop), w1) - w0
-    hit = a < b
-
-    def index(r):  # segment of window sample r within its channel
-        return np.where(head > 0, np.where(r < head, 0, 1 + (r - head) // seg), r // seg)
-    first = np.where(hit, base + index(np.maximum(a, 0)), base)
-    end = np.where(hit, base + index(np.maximum(b - 1, 0)) + 1, base)
-    return first, end
+    """Directory.range of these channels: the directory entries (first, end) that hold samples [start, stop) of each."""
+    return Directory.build(ch_len, h, window, seg_chunks, revision).range(start, stop)
 
 
-def gather_range(src, start, stop, sel):
+def gather_range(src, start, stop, sel, layout=None):
     """The payload a range query reads: for each distinct channel of `sel`, the one contiguous run of stored words of
-    its segments that overlap [start, stop) (slices of a `Compressed`, seek + readinto for a `ContainerFile`), back to
-    back.  -> (payload uint32, seg_off uint64 [n_segments]: where each of those segments starts in it -- 0 for the
-    others --, seg_idx uint64: their directory entries)."""
-    hd = src.header
-    h, window, seg_chunks = int(hd["h"]), int(hd["window"]), int(hd["seg_chunks"])
-    rev = int(hd.get("format_revision", FORMAT_REVISION))
-    first, end = range_segments(src.ch_len, h, window, seg_chunks, start, stop, rev)
+    its segments that overlap [start, stop) (src.read_words: slices of a `Compressed`, seek + readinto for a
+    `ContainerFile`), back to back.  layout: the source's Directory when the caller has it.  -> (payload uint32, seg_off
+    uint64 [n_segments]: where each of those segments starts in it, 0 for the others; seg_idx uint64: their entries)."""
+    first, end = (Directory.of(src) if layout is None else layout).range(start, stop)
     seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
-    dense = np.concatenate([[0], np.cumsum(seg_words)]).astype(np.int64)  # segment -> first word in the stored payload
-    stored_words = _stored_words(src)
+    dense = word_offsets(seg_words)         # segment -> first word in the stored payload
     # one contiguous run of payload words per selected channel (once per channel, whatever the repeats)
     runs, seg_off, idx, base = [], np.zeros(max(len(seg_words), 1), np.uint64), [], 0
     for c in np.unique(sel):
@@ -728,9 +754,9 @@ def gather_range(src, start, stop, sel):
         if s0 == s1:
             continue
         w0_, w1_ = int(dense[s0]), int(dense[s1])
-        if w1_ > stored_words:
+        if w1_ > src.payload_words:
             raise ValueError("corrupt container: the directory points past the payload")
-        runs.append(src.read_words(w0_, w1_ - w0_) if isinstance(src, ContainerFile) else src.payload[w0_:w1_])
+        runs.append(src.read_words(w0_, w1_ - w0_))
         seg_off[s0:s1] = base + (dense[s0:s1] - w0_)
         idx.append(np.arange(s0, s1, dtype=np.uint64))
         base += w1_ - w0_
@@ -739,47 +765,19 @@ def gather_range(src, start, stop, sel):
     return payload, seg_off, segs
 
 
-def _range_inputs(src, start, stop, channels, check, r=None):
-    """What a range query of a `Compressed` / `ContainerFile` needs on the host: argument checks (codec.query_args), the
-    payload of the segments that overlap [start, stop) (gather_range) and, with check, their validation
-    (mh_validate_segments).  -> (sel, payload, seg_off, segs, peak, enc); segs: the directory entries whose words
-    `payload` holds; payload is None when the query is empty (no channel or no sample)."""
-    from . import _lib, codec
-    hd = src.header
-    S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
-    ch_len = np.ascontiguousarray(src.ch_len, np.uint64)
-    C = len(ch_len)
-    sel = codec.query_args(int(ch_len.max()) if C else 0, C, start, stop, channels, r)
-    check_consistent(src, arrays=check)
-    if sel.size == 0 or stop == start:
-        return sel, None, None, None, None, None
-    payload, seg_off, segs = gather_range(src, start, stop, sel)
-    peak, enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
-    if check:
-        rows_ = np.ascontiguousarray(sclv, np.uint8)
-        seg_words = np.ascontiguousarray(src.seg_words, np.uint64)
-        rc = _lib.lib().mh_validate_segments(ch_len.ctypes.data, C, S, h, mode, plan_window(hd), rows_.ctypes.data, K,
-                                             seg_chunks, payload.ctypes.data if payload.size else None, payload.size,
-                                             seg_off.ctypes.data, seg_words.ctypes.data if seg_words.size else seg_off.ctypes.data,
-                                             len(seg_words), segs.ctypes.data if segs.size else None, segs.size,
-                                             peak.ctypes.data, enc.ctypes.data)
-        if rc != 0:
-            raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
-    return sel, payload, seg_off, segs, peak, enc
+ExcessLists = namedtuple("ExcessLists", "pos val first last")   # row i of a query takes entries [first[i], last[i]) of (pos, val)
 
 
-def gather_excess(src, start, stop, sel, check, what="container"):
+def gather_excess(src, start, stop, sel, check, what="container", layout=None):
     """The list entries a range query reads: for each distinct channel of `sel`, the one slice of entries of its segments
-    that overlap [start, stop), back to back, next to the payload words gather_range reads.  With check the slices are
-    range-checked on the host (excess.check_index / check_entries) -- they are not CRC'd: excess_crc32 covers the arrays
-    whole.  -> (pos uint32, val uint8, first, last): row i of the query takes entries [first[i], last[i]) of (pos, val)."""
-    hd = src.header
-    h, window, seg_chunks = int(hd["h"]), int(hd["window"]), int(hd["seg_chunks"])
-    rev = int(hd.get("format_revision", FORMAT_REVISION))
-    s_first, s_end = range_segments(src.ch_len, h, window, seg_chunks, start, stop, rev)
+    that overlap [start, stop) (src.read_excess), back to back, next to the payload words gather_range reads.  With check
+    the index and the slices are range-checked on the host (excess.check_index / check_entries) -- they are not CRC'd:
+    excess_crc32 covers the arrays whole.  -> ExcessLists (pos uint32, val uint8, first, last)."""
+    layout = Directory.of(src) if layout is None else layout
+    s_first, s_end = layout.range(start, stop)
     seg_e = np.asarray(src.exc_seg, np.uint64).astype(np.int64)
-    n = int(src.excess_entries if isinstance(src, ContainerFile) else len(src.exc_pos))
-    if not isinstance(src, ContainerFile) and check:
+    n = src.excess_entries
+    if check:
         excess.check_index(seg_e, len(src.seg_words), n, what)
     e0, e1 = np.minimum(seg_e[s_first], n), np.minimum(seg_e[s_end], n)
     base = np.zeros(len(src.ch_len), np.int64)
@@ -788,7 +786,7 @@ def gather_excess(src, start, stop, sel, check, what="container"):
         a, b = int(e0[c]), int(e1[c])
         if b <= a:
             continue
-        p, v = src.read_excess(a, b - a) if isinstance(src, ContainerFile) else (src.exc_pos[a:b], src.exc_val[a:b])
+        p, v = src.read_excess(a, b - a)
         ps.append(p), vs.append(v)
         base[c] = at - a
         at += b - a
@@ -796,24 +794,81 @@ def gather_excess(src, start, stop, sel, check, what="container"):
     pos = np.concatenate(ps) if ps else np.zeros(0, np.uint32)
     val = np.concatenate(vs) if vs else np.zeros(0, np.uint8)
     if check and ps:
-        _ch, lo, hi = excess.segment_bounds(src.ch_len, h, window, seg_chunks, rev)
+        _ch, lo, hi = layout.bounds()
         segs = np.concatenate(segs)
-        excess.check_entries(pos, val, np.concatenate(counts), lo[segs], hi[segs], int(hd["S"]) - 1, what)
+        excess.check_entries(pos, val, np.concatenate(counts), lo[segs], hi[segs], int(src.header["S"]) - 1, what)
     first, last = e0[sel] + base[sel], e1[sel] + base[sel]
-    return pos, val, first, np.maximum(last, first)
+    return ExcessLists(pos, val, first, np.maximum(last, first))
 
 
-def _range_decode(src, payload, seg_off, segs, peak, enc, check, run):
-    """run(plan, payload, seg_off, peak, enc) with the gathered payload on the plan's device, its segments verified
-    next to the upload when the source carries checksums (enqueue_verify); ValueError when one does not match or the
-    decode had to abandon a segment."""
+@dataclass
+class Job:
+    """What one source adds to one range query, from _range_job for _enqueue: rows `sel`, local samples [a, b); payload None: empty."""
+    src: object                 # the `Compressed` or `ContainerFile`
+    sel: np.ndarray
+    a: int
+    b: int
+    payload: np.ndarray = None  # gather_range: the words, where each segment starts in them, the directory entries read
+    seg_off: np.ndarray = None
+    segs: np.ndarray = None
+    peak: np.ndarray = None
+    enc: np.ndarray = None
+    lists: ExcessLists = None   # gather_excess, when the lists are applied
+    block: int = None           # archive.Reader.read: the block's index, and its first column of the wide result
+    g0: int = 0
+
+
+def _range_job(src, start, stop, channels, check, r=None, use=False, what="container"):
+    """The host side of a range query of a `Compressed` / `ContainerFile` -> Job: codec.query_args, ONE Directory for what
+    follows, gather_range, with check mh_validate_segments on what it read and, with use, gather_excess."""
+    from . import _lib, codec
+    hd = src.header
+    S, K, h, window, seg_chunks, mode, sclv = _header_fields(hd)
+    ch_len = np.ascontiguousarray(src.ch_len, np.uint64)
+    C = len(ch_len)
+    job = Job(src, codec.query_args(int(ch_len.max()) if C else 0, C, start, stop, channels, r), start, stop)
+    layout = Directory.of(src)
+    check_consistent(src, arrays=check, layout=layout)
+    if job.sel.size == 0 or stop == start:
+        return job
+    job.payload, job.seg_off, job.segs = gather_range(src, start, stop, job.sel, layout)
+    job.peak, job.enc = np.ascontiguousarray(src.peak, np.uint8), np.ascontiguousarray(src.enc, np.uint8)
+    if check:
+        rows_, seg_words, pay, seg_off, segs = (np.ascontiguousarray(sclv, np.uint8), np.ascontiguousarray(src.seg_words, np.uint64),
+                                                job.payload, job.seg_off, job.segs)
+        rc = _lib.lib().mh_validate_segments(ch_len.ctypes.data, C, S, h, mode, plan_window(hd), rows_.ctypes.data, K,
+                                             seg_chunks, pay.ctypes.data if pay.size else None, pay.size,
+                                             seg_off.ctypes.data, seg_words.ctypes.data if seg_words.size else seg_off.ctypes.data,
+                                             len(seg_words), segs.ctypes.data if segs.size else None, segs.size,
+                                             job.peak.ctypes.data, job.enc.ctypes.data)
+        if rc != 0:
+            raise ValueError("corrupt container: " + _lib.lib().mh_last_error().decode(errors="replace"))
+    if use:
+        job.lists = gather_excess(src, start, stop, job.sel, check, what, layout)
+    return job
+
+
+def _enqueue(plan, job, check, decode, r=1, lead=0):
+    """The device side of one job, on the current stream, no synchronisation: codec.upload_stream, with check enqueue_verify
+    next to it, decode(plan, payload, seg_off, peak, enc) -> the tensor it decoded into, the job's list added onto that behind
+    the decode (bins of r samples, `lead` leading ones).  -> (that tensor, the `bad` tensor for check_verified or None)"""
     from . import codec
-    own = not isinstance(src, ContainerFile)
-    plan = _range_plan(src) if own else src.plan()
+    up = codec.upload_stream(plan.device, job.payload, job.seg_off, job.peak, job.enc)
+    bad = enqueue_verify(job.src, up[0], up[1], job.src.seg_words, job.segs, check)
+    out = decode(plan, *up)
+    if job.lists is not None and len(job.lists.pos):
+        excess.apply(*excess.upload(job.lists.pos, job.lists.val, plan.device), job.lists.first, job.lists.last, job.a, job.b,
+                     r, lead, out)
+    return out, bad
+
+
+def _run(job, check, decode, r=1):
+    """_enqueue on the source's plan (a `ContainerFile` keeps one, a `Compressed` gets one per call), then the two statuses."""
+    from . import codec
+    own = not isinstance(job.src, ContainerFile)
+    plan = _range_plan(job.src) if own else job.src.plan()
     try:
-        up = codec.upload_stream(plan.device, payload, seg_off, peak, enc)
-        bad = enqueue_verify(src, up[0], up[1], src.seg_words, segs, check)
-        out = run(plan, *up)
+        out, bad = _enqueue(plan, job, check, decode, r)
         check_verified(bad, [plan])
         codec.check_decoded([plan])
     finally:
@@ -837,20 +892,11 @@ def decompress_range(src, start, stop, channels=None, device="cuda", check=True,
 
     from . import codec
     start, stop = int(start), int(stop)
-    use = wants_excess(src, exact)
-    sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check)
-    n, rows = stop - start, int(sel.size)
-    if payload is None:
-        z = torch.zeros((rows, n), dtype=torch.uint8, device=device)
+    job = _range_job(src, start, stop, channels, check, use=wants_excess(src, exact))
+    if job.payload is None:
+        z = torch.zeros((int(job.sel.size), stop - start), dtype=torch.uint8, device=device)
         return z.t().contiguous() if time_major else z
-    lists = gather_excess(src, start, stop, sel, check) if use else None
-
-    def run(plan, pay, off, pk, en):
-        out = plan.decode_range(pay, off, pk, en, sel, start, stop)
-        if lists is not None and len(lists[0]):
-            excess.apply(*excess.upload(lists[0], lists[1], out.device), lists[2], lists[3], start, stop, 1, 0, out)
-        return out
-    out = _range_decode(src, payload, seg_off, segs, peak, enc, check, run)
+    out = _run(job, check, lambda plan, *up: plan.decode_range(*up, job.sel, start, stop))
     return codec.to_time_major(out) if time_major else out
 
 
@@ -866,16 +912,8 @@ def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, 
     import torch
     r, start = int(r), int(start)
     stop = (int(np.max(src.ch_len)) if len(src.ch_len) else 0) if stop is None else int(stop)
-    use = wants_excess(src, exact)
-    sel, payload, seg_off, segs, peak, enc = _range_inputs(src, start, stop, channels, check, r)
-    nb, rows = (stop - start + r - 1) // r, int(sel.size)
-    if payload is None:
-        return torch.zeros((rows, nb), dtype=torch.uint8 if saturate else torch.int32, device=device)
-    lists = gather_excess(src, start, stop, sel, check) if use else None
-
-    def run(plan, pay, off, pk, en):
-        out = plan.decode_rebin(pay, off, pk, en, sel, start, stop, r, saturate)
-        if lists is not None and len(lists[0]):
-            excess.apply(*excess.upload(lists[0], lists[1], out.device), lists[2], lists[3], start, stop, r, 0, out)
-        return out
-    return _range_decode(src, payload, seg_off, segs, peak, enc, check, run)
+    job = _range_job(src, start, stop, channels, check, r, wants_excess(src, exact))
+    if job.payload is None:
+        return torch.zeros((int(job.sel.size), (stop - start + r - 1) // r), dtype=torch.uint8 if saturate else torch.int32,
+                           device=device)
+    return _run(job, check, lambda plan, *up: plan.decode_rebin(*up, job.sel, start, stop, r, saturate), r)

@@ -7,8 +7,6 @@ The Huffman stream is what it is without the list; a reader adds the list back o
 This module holds what the container, the stream and the archive share: making the list on the device, indexing it by
 directory segment on the host, range-checking one that came from a file, and putting it back.
 """
-import zlib
-
 import numpy as np
 
 ENTRY_BITS = 40   # a stored entry: uint32 pos + uint8 val
@@ -55,18 +53,9 @@ def from_time_major(block, thr):
 
 
 def segment_bounds(ch_len, h, window, seg_chunks, revision):
-    """-> int64 arrays (channel, lo, hi) of every directory entry: its channel and its samples [lo, hi) (channel_layout)."""
-    from . import CHUNK
-    from .container_io import channel_layout
-    w0, w1, head, nseg = channel_layout(ch_len, h, window, seg_chunks, revision)
-    seg = int(seg_chunks) * CHUNK
-    ch = np.repeat(np.arange(len(nseg), dtype=np.int64), nseg)
-    j = np.arange(int(nseg.sum()), dtype=np.int64) - np.repeat(np.cumsum(nseg) - nseg, nseg)   # entry within its channel
-    w0r, w1r, hd = w0[ch], w1[ch], head[ch]
-    has = hd > 0
-    lo = np.where(has, np.where(j == 0, w0r, w0r + hd + (j - 1) * seg), w0r + j * seg)
-    hi = np.where(has & (j == 0), w0r + hd, np.minimum(lo + seg, w1r))
-    return ch, lo, hi
+    """-> int64 arrays (channel, lo, hi) of every directory entry: its channel and its samples [lo, hi) (Directory.bounds)."""
+    from .container_io import Directory
+    return Directory.build(ch_len, h, window, seg_chunks, revision).bounds()
 
 
 def segment_index(exc_off, pos, seg_ch, seg_lo):
@@ -79,11 +68,9 @@ def segment_index(exc_off, pos, seg_ch, seg_lo):
 
 def crc32(exc_seg, exc_pos, exc_val):
     """zlib's CRC-32 over the three arrays as a container holds them: little-endian, each padded to 8 bytes."""
-    crc = 0
-    for a, (_name, dt) in zip((exc_seg, exc_pos, exc_val), NAMES):
-        raw = np.ascontiguousarray(a, dtype=dt).reshape(-1).view(np.uint8)
-        crc = zlib.crc32(b"\0" * (-raw.size % 8), zlib.crc32(raw, crc))
-    return crc
+    from .container_io import crc32_padded
+    return crc32_padded((np.ascontiguousarray(a, dtype=dt).reshape(-1).view(np.uint8), None)
+                        for a, (_name, dt) in zip((exc_seg, exc_pos, exc_val), NAMES))
 
 
 def check_index(exc_seg, n_segments, n, what="container"):
@@ -114,11 +101,11 @@ def check_entries(pos, val, counts, seg_lo, seg_hi, thr, what="container"):
 
 def check_container(c, what="container"):
     """Everything check_index and check_entries can say about a whole `Compressed` with lists.  ValueError."""
-    hd = c.header
-    n = len(c.exc_pos)
-    check_index(c.exc_seg, len(c.seg_words), n, what)
-    _ch, lo, hi = segment_bounds(c.ch_len, hd["h"], hd["window"], hd["seg_chunks"], hd.get("format_revision", 3))
-    check_entries(c.exc_pos, c.exc_val, np.diff(np.asarray(c.exc_seg, np.uint64).astype(np.int64)), lo, hi, int(hd["S"]) - 1, what)
+    from .container_io import Directory
+    check_index(c.exc_seg, len(c.seg_words), len(c.exc_pos), what)
+    _ch, lo, hi = Directory.of(c).bounds()
+    check_entries(c.exc_pos, c.exc_val, np.diff(np.asarray(c.exc_seg, np.uint64).astype(np.int64)), lo, hi,
+                  int(c.header["S"]) - 1, what)
 
 
 def upload(pos, val, device):

@@ -291,7 +291,7 @@ def test_one_flipped_payload_bit_passes_the_structural_walks_and_fails_the_check
         assert r.verify(device=False) == [(block, seg)]
         c = r.block(block)
         cio.validate(c)                                                         # mh_validate_stream: accepts
-        sel, payload, _off, segs, _pk, _en = cio._range_inputs(c, 0, ALENS[block], None, True)  # mh_validate_segments: too
-        assert payload.size == c.payload.size and seg in segs.tolist()
+        job = cio._range_job(c, 0, ALENS[block], None, True)                    # mh_validate_segments: too
+        assert job.payload.size == c.payload.size and seg in job.segs.tolist()
         bf = r.block_file(block)
-        cio._range_inputs(bf, 2 * CH, 4 * CH, [1], True)
+        cio._range_job(bf, 2 * CH, 4 * CH, [1], True)

@@ -464,3 +464,71 @@ def test_exact_argument_rule(trio):
     assert not cio.wants_excess(c, None) and not cio.wants_excess(c, False)
     with pytest.raises(ValueError, match="exact=True"):
         cio.wants_excess(c, True)
+
+
+# ---- one source interface ------------------------------------------------------------------------------------------
+PARITY_LENS = [9, 5000, 16 * CH + 1000, 5 * CH + 7]    # no window at all, below a chunk, just over 16 chunks: a head segment, three segments
+PARITY_QUERIES = [  # (start, stop, channels, r)
+    (100, 100, None, None),                             # an empty range
+    (70, 71, [1], None),                                # one sample
+    (CH + 5, CH + 900, [2, 3], None),                   # inside one segment
+    (100, 300, [2], None),                              # across the end of the head segment
+    (2 * CH, 2 * CH + 200, [3, 2], None),               # across a segment boundary of channel 3
+    (0, max(PARITY_LENS), None, None),                  # every channel whole
+    (3 * CH, 4 * CH + 1, [3, 0, 3, 2, 2], None),        # repeated and unordered
+    (4096, 2 * CH + 77, [2, 1], 16),                    # a binned query
+]
+
+
+@pytest.mark.parametrize("rev,crc,exact", [(2, False, False), (2, False, True), (3, False, False), (3, False, True),
+                                           (3, True, False), (3, True, True)])
+def test_a_compressed_and_its_file_gather_the_same_job(rev, crc, exact, tmp_path):
+    """The gather stage sees a `Compressed` and a `ContainerFile` through one interface (payload_words, excess_entries,
+    read_words, read_excess): the Job of a query is the same field by field from either, and the file is read for exactly
+    that -- four bytes per payload word, five per list entry, exc_seg once.  (Checksums make a container revision 4, which
+    is revision 3's layout: there is no revision-2 container with them.)"""
+    import dataclasses
+    c, chans = _oracle_container(PARITY_LENS, 3, 6, 2, 2, rev, seed=7)
+    if exact:
+        orig = [np.where(x >= 2, np.minimum(x.astype(np.int64) + (np.arange(len(x)) % 3), 255), x).astype(np.uint8) for x in chans]
+        c.header = dict(c.header, exact=True)
+        cio.attach_excess(c, *_lists(c, orig))
+        assert len(c.exc_pos) > 100
+    if crc:
+        c = _with_crc(c)
+    layout = cio.Directory.of(c)
+    assert (layout.head > 0).tolist() == [False, False, rev == 3, False] and layout.nseg.tolist() == [0, 1, 9 + (rev == 3), 3]
+    path = tmp_path / "p.mh"
+    cio.save(path, c)
+    with cio.open(path) as f:
+        assert f.payload_words == c.payload_words == c.payload.size and f.bytes_read == f.head_bytes
+        assert np.array_equal(f.read_words(3, 40), c.read_words(3, 40)) and np.shares_memory(c.read_words(3, 40), c.payload)
+        if exact:
+            assert f.excess_entries == c.excess_entries == len(c.exc_pos)
+            assert all(np.array_equal(x, y) for x, y in zip(f.read_excess(5, 9), c.read_excess(5, 9)))
+            assert np.shares_memory(c.read_excess(5, 9)[0], c.exc_pos) and np.shares_memory(c.read_excess(5, 9)[1], c.exc_val)
+        index_read = False
+        for start, stop, channels, r in PARITY_QUERIES:
+            for check in (True, False):
+                mem = cio._range_job(c, start, stop, channels, check, r, use=exact)
+                before = f.bytes_read
+                got = cio._range_job(f, start, stop, channels, check, r, use=exact)
+                want = 0 if mem.payload is None else 4 * mem.payload.size
+                if mem.lists is not None:
+                    want += 5 * len(mem.lists.pos) + (0 if index_read else 8 * len(c.exc_seg))
+                    index_read = True
+                assert f.bytes_read - before == want, (start, stop, channels, check)
+                assert mem.src is c and got.src is f and (mem.payload is None) == (stop == start)
+                for field in dataclasses.fields(cio.Job):
+                    a, b = getattr(mem, field.name), getattr(got, field.name)
+                    if field.name == "src":
+                        continue
+                    if field.name == "lists":
+                        assert (a is None) == (b is None) == (not exact or mem.payload is None)
+                        a, b = a or (), b or ()
+                        assert len(a) == len(b) and all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
+                    elif isinstance(a, np.ndarray):
+                        assert a.dtype == b.dtype and np.array_equal(a, b), field.name
+                    else:
+                        assert a == b, field.name
+        assert index_read == exact
