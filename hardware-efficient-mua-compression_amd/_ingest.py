@@ -25,7 +25,10 @@ PROTOTYPES = {
     "mhi_excess_count": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
     "mhi_excess_emit": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
     "mhi_excess_apply": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u32, _u64, _u64, _vp]),
+    "mhi_windows": (_int, [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _u32, _vp, _u32, _u64, _u64, _vp, _u64, _u32,
+                           _vp, _vp]),
 }
+WIN_STACK, WIN_SUM = 0, 1         # MHI_WIN_STACK, MHI_WIN_SUM
 EXCESS_ROWS, EXCESS_COLS = 0, 1   # MHI_EXCESS_ROWS, MHI_EXCESS_COLS
 UNBIN_CSR, UNBIN_AER = 0, 1       # MHI_UNBIN_CSR, MHI_UNBIN_AER
 AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
@@ -152,6 +155,21 @@ def excess_apply(pos, val, first, last, start, stop, r, lead, out_ptr, out_bits,
                                  _vp(first.data_ptr()), _vp(last.data_ptr()), int(first.numel()), int(start), int(stop), int(r),
                                  int(lead), _vp(int(out_ptr)), int(out_bits), int(row_stride), int(col_stride),
                                  _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def windows(x_ptr, row_stride, rows, cols, win_off, win_idx, n_out, W, r, mode, out_ptr, out_bits, out_win_stride,
+            out_row_stride, bad, sumsq=None, sq_row_stride=0, accumulate=False, n_win=None):
+    """Enqueue mhi_windows on the current stream.  x_ptr: the address of the matrix's first byte (row i at
+    x_ptr + i*row_stride, cols bytes); win_off: 64-bit device tensor of window starts (columns); win_idx: None or a 64-bit
+    device tensor of output slots; out_ptr: the address of element (0, 0, 0), the strides in bytes; bad: verify_state();
+    sumsq: None or an int64 device tensor whose rows are sq_row_stride bytes apart (WIN_SUM)."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    n = int(win_off.numel()) if n_win is None else int(n_win)
+    check(lib().mhi_windows(_vp(int(x_ptr)), int(row_stride), int(rows), int(cols), p(win_off), p(win_idx), n, int(n_out),
+                            int(W), int(r), int(mode), _vp(int(out_ptr)), int(out_bits), int(out_win_stride),
+                            int(out_row_stride), p(sumsq), int(sq_row_stride), int(bool(accumulate)), p(bad),
+                            _vp(torch.cuda.current_stream().cuda_stream)))
 
 
 def seg_crc32(payload, seg_off, seg_words, n_segments, seg_idx=None, crc=None, expect=None, bad=None, payload_words=None):

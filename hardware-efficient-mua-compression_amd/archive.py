@@ -146,7 +146,7 @@ class _BlockFile(cio.ContainerFile):
 
 class Reader:
     """archive.open(path): C, S, T (total steps), meta, truncated, checksum, blocks (Block tuples), block(i), words(),
-    read(), verify()."""
+    read(), read_windows(), verify()."""
 
     def __init__(self, path):
         self.path = str(path)
@@ -275,6 +275,28 @@ class Reader:
         if not time_major:
             return res
         return codec.to_time_major(res) if r is None else res.t().contiguous()
+
+    def read_windows(self, triggers, pre, post, channels=None, bin=None, reduce=None, moments=1, saturate=True,  # noqa: A002
+                     check=True, exact=None, join=None, max_bytes=None):
+        """The same window around many trigger times in one call: window k is the global samples [triggers[k] - pre,
+        triggers[k] + post) of the selected channels (pre, post >= 0, pre + post >= 1; triggers: host integers in any
+        order, repeats allowed; ValueError names a trigger whose window is not inside [0, T)).  bin=r (1..4096) sums each
+        window in bins of r samples from ITS OWN first sample -- not on read()'s global grid; the last bin may be cut.
+        reduce=None -> device tensor [n, n_sel, ceil((pre + post) / r)] in the order of `triggers`: uint8 = min(sum,
+        255), or int32 sums with saturate=False.  reduce="sum" -> what windows.psth returns: the int32 sum over the
+        triggers [n_sel, nb], and with moments=2 (sum, sumsq) with the int64 sum of the squared per-window bin values.
+        windows.plan_spans joins the windows into spans -- a gap shorter than `join` samples (default: one chunk) is
+        bridged -- and every span is read ONCE with read(a, b, channels, check=check, exact=exact) into its columns of a
+        scratch matrix of at most max_bytes bytes (default windows.MAX_BYTES; more spans than fit are further batches):
+        blocks, checksums, exact lists and the decode status are read()'s.  One mhi_windows per batch then cuts, bins and
+        stacks or sums the windows on the device.  An empty trigger list gives an empty or zero result."""
+        from . import codec, windows
+        starts, W, r, nb = windows.window_args(triggers, pre, post, bin, reduce, moments, self.T)
+        cio.wants_excess(self, exact, "archive")
+        rows = int(codec.select_channels(self.C, channels).size)
+        return windows.read_windows(lambda a, b, view: self.read(a, b, channels, check=check, exact=exact, out=view), rows,
+                                    starts, W, r, nb, reduce, moments, saturate, self.T,
+                                    windows.CHUNK if join is None else join, windows.MAX_BYTES if max_bytes is None else max_bytes)
 
     def read_events(self, start, stop, channels=None, origin=0, period=1, phase=0, check=True, aer=False,  # noqa: A002
                     ch_dtype=None, exact=None):

@@ -28,6 +28,7 @@ directory order (mh_compact); segment s starts at word sum(seg_words[:s]).
 import builtins
 import io
 import json
+import os
 import struct
 import zlib
 from collections import namedtuple
@@ -917,3 +918,29 @@ def decompress_binned(src, r, start=0, stop=None, channels=None, saturate=True, 
         return torch.zeros((int(job.sel.size), (stop - start + r - 1) // r), dtype=torch.uint8 if saturate else torch.int32,
                            device=device)
     return _run(job, check, lambda plan, *up: plan.decode_rebin(*up, job.sel, start, stop, r, saturate), r)
+
+
+def decompress_windows(src, triggers, pre, post, channels=None, bin=None, reduce=None, moments=1, saturate=True,  # noqa: A002
+                       check=True, exact=None, device="cuda", join=None, max_bytes=None):
+    """archive.Reader.read_windows over decompress_range: the samples [triggers[k] - pre, triggers[k] + post) of the selected
+    channels of a `Compressed`, a `ContainerFile` or a path (opened for the call), stacked [n, n_sel, nb] in the order of
+    `triggers` or, with reduce="sum", summed over them (windows.psth's result; moments=2 adds the sum of squares).  A
+    window lies inside [0, the longest channel's length); a shorter channel is zero past its end, as decompress_range
+    has it.  bin, saturate, join and max_bytes as read_windows; check and exact as decompress_range, once per span.
+    There is no CPU path: a host array is not a source."""
+    from . import codec, windows
+    if isinstance(src, (str, os.PathLike)):
+        with open(src) as f:
+            return decompress_windows(f, triggers, pre, post, channels, bin, reduce, moments, saturate, check, exact, device,
+                                      join, max_bytes)
+    if not hasattr(src, "ch_len"):
+        raise ValueError("decompress_windows takes a Compressed, a ContainerFile or a path: there is no CPU path")
+    T = int(np.max(src.ch_len)) if len(src.ch_len) else 0
+    starts, W, r, nb = windows.window_args(triggers, pre, post, bin, reduce, moments, T)
+    rows = int(codec.select_channels(len(src.ch_len), channels).size)
+
+    def read_span(a, b, view):
+        view.copy_(decompress_range(src, a, b, channels, device, check, exact=exact))
+    return windows.read_windows(read_span, rows, starts, W, r, nb, reduce, moments, saturate, T,
+                                windows.CHUNK if join is None else join, windows.MAX_BYTES if max_bytes is None else max_bytes,
+                                device)

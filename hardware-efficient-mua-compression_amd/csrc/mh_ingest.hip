@@ -1,7 +1,8 @@
 // mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
 // in mh_aer.hpp, the segment checksum in mh_crc.hpp, the way back from counts to events in mh_unbin.hpp and the side
-// list of what the clip at S-1 drops in mh_excess.hpp: argument checks and the launches.  A companion of libmuahuff.so,
-// not part of it; there is no CPU fallback here either.
+// list of what the clip at S-1 drops in mh_excess.hpp and the trial-aligned windows of a decoded recording in
+// mh_windows.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
+// fallback here either.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -16,6 +17,8 @@
 #include "mh_launch.hpp"
 #include "mh_unbin.hpp"
 #include "mh_unbin_layout.hpp"
+#include "mh_windows.hpp"
+#include "mh_windows_layout.hpp"
 // built with -fvisibility=hidden: the mhi_* functions of the header are ALL the library exports
 #pragma GCC visibility push(default)
 #include "muahuff_ingest.h"
@@ -457,6 +460,50 @@ int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_apply: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t cols, const uint64_t *win_off,
+                const uint64_t *win_idx, uint64_t n_win, uint64_t n_out, uint64_t W, uint64_t r, uint32_t mode, void *out,
+                uint32_t out_bits, uint64_t out_win_stride, uint64_t out_row_stride, uint64_t *sumsq, uint64_t sq_row_stride,
+                uint32_t accumulate, uint64_t *bad, void *stream)
+{
+    static_assert(mh::kWinStack == MHI_WIN_STACK && mh::kWinSum == MHI_WIN_SUM, "the header publishes the forms");
+    const mh::WinArgs a = {(uintptr_t)in, row_stride, rows, cols, (uintptr_t)win_off, (uintptr_t)win_idx, n_win, n_out, W, r, mode,
+                           (uintptr_t)out, out_bits, out_win_stride, out_row_stride, (uintptr_t)sumsq, sq_row_stride, accumulate,
+                           (uintptr_t)bad};
+    mh::Msg m;
+    if (int rc = mh::windows_check(m, a)) return fail(rc, "%s", m.text);
+    mh::WinLayout L;  // the form, the tiles and the capped grid (mh_windows_layout.hpp)
+    mh::windows_layout(mode, rows, W, r, n_win, &L);
+    if (L.items == 0) return MH_OK;  // STACK of no windows
+    const mh::WinParams p = {in, row_stride, rows, cols, win_off, win_idx, n_out, (uint32_t)n_win, (uint32_t)W, (uint32_t)r, L.nb,
+                             L.tile_bins, L.tiles, L.items, static_cast<uint8_t *>(out), out_win_stride, out_row_stride,
+                             reinterpret_cast<uint8_t *>(sumsq), sq_row_stride, accumulate,
+                             reinterpret_cast<unsigned long long *>(bad)};
+    const dim3 grid(L.grid), block(mh::kWinThreads);
+    hipStream_t st = (hipStream_t)stream;
+    const bool sum = mode == mh::kWinSum, o32 = out_bits == 32, sq = sumsq != nullptr;
+#define MH_WIN_GO(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, st, p)
+    if (L.form == mh::kWinLane) {
+        if (!sum && o32) MH_WIN_GO(mh::k_win_lane_stack<true>);
+        else if (!sum) MH_WIN_GO(mh::k_win_lane_stack<false>);
+        else if (sq) MH_WIN_GO(mh::k_win_lane_sum<true>);
+        else MH_WIN_GO(mh::k_win_lane_sum<false>);
+    } else if (L.form == mh::kWinStage) {
+        if (!sum && o32) MH_WIN_GO((mh::k_win_stage<false, true, false>));
+        else if (!sum) MH_WIN_GO((mh::k_win_stage<false, false, false>));
+        else if (sq) MH_WIN_GO((mh::k_win_stage<true, true, true>));
+        else MH_WIN_GO((mh::k_win_stage<true, true, false>));
+    } else {
+        if (!sum && o32) MH_WIN_GO((mh::k_win_wave<false, true, false>));
+        else if (!sum) MH_WIN_GO((mh::k_win_wave<false, false, false>));
+        else if (sq) MH_WIN_GO((mh::k_win_wave<true, true, true>));
+        else MH_WIN_GO((mh::k_win_wave<true, true, false>));
+    }
+#undef MH_WIN_GO
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_windows: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

@@ -17,6 +17,9 @@
  * And the way back: mhi_unbin_count / mhi_unbin_emit expand a matrix of counts -- a decoded recording -- into spike events
  * again, per channel (the input of mhi_bin_events) or as one merged pair list (the input of mhi_aer_to_csr).
  *
+ * And the commonest query on a decoded recording: mhi_windows cuts the same window around many trigger times out of every
+ * row in one call, re-binned on each window's own grid, stacked per trial or summed over the trials into a PSTH.
+ *
  * Neither a binner nor a checksum is a codec operation, so they are not part of muahuff.h: that ABI is closed.  The conventions are the
  * same: every function returns MH_OK or a negative MH_ERR_* code of muahuff.h and never throws, mhi_last_error()
  * returns a thread-local message for the last failure on this thread, every argument check comes before any device
@@ -210,6 +213,42 @@ int mhi_excess_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, c
 int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries, const uint64_t *first, const uint64_t *last,
                      uint64_t n_rows, uint64_t start, uint64_t stop, uint64_t r, uint64_t lead, void *out, uint32_t out_bits,
                      uint64_t row_stride, uint64_t col_stride, void *stream);
+
+/* ---- trial-aligned windows: many windows of a matrix of counts in one call, stacked or summed -------------------------
+ * in: device.  Row i is the cols bytes at in + i*row_stride, at ANY byte address (a decoded range, a column slice of
+ * one, a pitched matrix); no byte outside a row's cols bytes is read.  win_off: device, n_win column indices: window k
+ * is the columns [win_off[k], win_off[k] + W) of every row.  It is cut into nb = ceil(W / r) bins from ITS OWN first
+ * sample: bin b of window k in row i is the sum of the window's samples [b*r, min(b*r + r, W)) -- the last bin may be
+ * cut, as in mh_decode_rebin.
+ * MHI_WIN_STACK: element (slot, i, b) at (char *)out + slot*out_win_stride + i*out_row_stride + b*elem, where slot =
+ *   win_idx ? win_idx[k] : k (win_idx: NULL, or device, n_win entries: the caller may sort the windows for reading and
+ *   keep its own order in the result) and slot < n_out.  out_bits = 8: uint8 elements min(sum, 255).  out_bits = 32:
+ *   32-bit elements, the sum itself (modulo 2^32, which only bins of 2^24 samples and more can reach); out and both
+ *   strides multiples of 4.  sumsq must be NULL and accumulate 0.  Two windows with the same slot are the caller's
+ *   business: one of them wins, every store stays in bounds.
+ * MHI_WIN_SUM: out_bits must be 32.  Element (i, b) at (char *)out + i*out_row_stride + 4*b is the sum of the bin value
+ *   over the valid windows, and with sumsq (NULL, or device, 8-byte aligned as is sq_row_stride) the uint64 at
+ *   (char *)sumsq + i*sq_row_stride + 8*b is the sum of the SQUARES of the per-window bin values -- the square of the
+ *   bin's sum, not the sum of the samples' squares.  accumulate = 0 overwrites, 1 adds to what is there (one result
+ *   from several calls; the 32-bit bound below is then the caller's).  win_idx, n_out and out_win_stride are ignored.
+ * The lists are untrusted: no address is formed from a value that was not compared first.  A window with win_off[k] + W
+ * > cols (tested so that a sum that wraps 64 bits fails too) or with a slot >= n_out is skipped: it contributes nothing,
+ * nothing is stored for it, bad[0] += 1 and bad[1] = min(bad[1], k).  The caller initialises bad (device, 2 entries)
+ * to {0, UINT64_MAX}, as for mhi_seg_crc32; several calls may share it.
+ * Every output element has one owner, a thread or a wave, which walks the windows itself: no atomics touch the result
+ * and it is the same from run to run.  The elements must not be written by anything else while the call runs.
+ * MH_ERR_ARG, before any device work: in, out or bad NULL, win_off NULL with n_win > 0; an unknown mode; out_bits that
+ * does not fit the mode; sumsq or accumulate in the STACK form, accumulate above 1; a misaligned 32-bit out or 64-bit
+ * sumsq, or a stride of theirs; rows, cols, W or r == 0; W, r or n_win >= 2^32; row_stride < cols with rows > 1; the
+ * SUM form without accumulate when n_win * 255 * min(r, W) >= 2^32; rows so large that rows * n_win * nb reaches 2^63.
+ * n_win == 0 enqueues nothing in the STACK form and, without accumulate, zero-fills out and sumsq in the SUM form.
+ * Only enqueues on `stream`: no synchronisation, allocation or free, so it can be captured into a hipGraph. */
+#define MHI_WIN_STACK 0u
+#define MHI_WIN_SUM   1u
+int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t cols, const uint64_t *win_off,
+                const uint64_t *win_idx, uint64_t n_win, uint64_t n_out, uint64_t W, uint64_t r, uint32_t mode, void *out,
+                uint32_t out_bits, uint64_t out_win_stride, uint64_t out_row_stride, uint64_t *sumsq, uint64_t sq_row_stride,
+                uint32_t accumulate, uint64_t *bad, void *stream);
 
 #ifdef __cplusplus
 }
