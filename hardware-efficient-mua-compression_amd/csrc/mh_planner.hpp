@@ -16,6 +16,12 @@
 namespace mh {
 
 constexpr uint32_t kHistTileBytes = 256 * 16 * 32;  // bytes of one histogram tile (128 KiB)
+// Invariant: a tile must not exceed 63 * 256 * 16 bytes.  k_hist<NS> (mh_kernels.hpp) adds up to 4 per byte field and
+// 16-byte vector and drains the fields into its 32-bit counters once a thread has 63 vectors pending (252 <= 255).  A
+// thread sees at most kHistTileBytes / (256 * 16) = 32 vectors of a tile, so that in-loop drain never runs and no
+// test reaches it: the one after the loop does all the work.  A larger tile has to come with a test of the drain.
+static_assert(kHistTileBytes <= 63 * 256 * 16,
+              "k_hist<NS> drains its byte fields after 63 vectors per thread: a larger tile runs an untested branch");
 constexpr uint64_t kCalDirect = 4096;                // longest calibration window k_calibrate scans itself
 // mh_measure as ONE launch (the workgroup of a channel's last tile finishes the channel) pays two atomic round
 // trips at the end of every workgroup and a serial tail per channel; it wins while the call is bound by its

@@ -19,6 +19,11 @@ that the library's own selection puts every case and layout on its cell's instan
   mixed    the layouts here keep every channel on ONE route per chunk (all staged or all oversize); transitions within
            a segment -- staged and oversize chunks side by side -- are tests/mixed_chunks.py, run by
            tests/test_host_mixed_chunks.py and tests/test_gpu_mixed_chunks.py
+  aligned  the layouts here are flattened by oracle.c.flatten -- channel offsets padded to 16 bytes -- and coded whole
+           (MH_WIN_FULL), so every 16-byte row load and store is aligned and only padding follows a window; the
+           byte-layout cells at odd addresses, with touching channels and windows that start 1..8 samples into a
+           channel and end inside it, are tests/misaligned.py, run by tests/test_host_misaligned.py and
+           tests/test_gpu_misaligned.py
 """
 from dataclasses import dataclass
 

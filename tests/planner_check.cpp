@@ -12,6 +12,8 @@
 // byte plans, of its k_decode_range and k_decode_rebin<..., true> instances.
 // With --forms (tests/async_table.py) the same input gives the form of the plan, which decides what each call enqueues:
 // "wave_tasks measure_fused fused_calibration tickets_fit cal_tiles head_segments skipped short_channels".
+// With --tiles (tests/test_host_misaligned.py) the same input gives what cuts a plan's histogram work:
+// "kHistTileBytes kCalDirect window_tiles cal_tiles", then the window tiles' sample counts on one line.
 // With --worklist (tests/test_host_worklist.py) a case in the first format is followed by a query count and that many
 // queries  n_sel sel[0..n_sel) t0 t1 r out_pitch  (r = 0: mh_decode_range's list, else mh_decode_rebin's), built by
 // csrc/mh_worklist.hpp as the library builds them.  Output: "D nseg" and the directory's ch / first / n lines, then per
@@ -113,7 +115,7 @@ static int read_plan(bool with_bits, mh::PlanHost &p)
     return 1;
 }
 
-static int cells(bool forms)
+static int cells(bool forms, bool tiles = false)
 {
     mh::PlanHost p;
     int got;
@@ -121,6 +123,12 @@ static int cells(bool forms)
         if (got == 2) continue;
         const unsigned C = p.info.C, h = p.info.h, window = p.info.window;
         const std::vector<uint64_t> &len = p.ch_len;
+        if (tiles) {
+            printf("%u %llu %zu %zu\n", mh::kHistTileBytes, (unsigned long long)mh::kCalDirect, p.tile_ch.size(), p.cal_tile_ch.size());
+            for (uint32_t n : p.tile_n) printf("%u ", n);
+            printf("\n");
+            continue;
+        }
         if (forms) {
             unsigned heads = 0, shorter = 0;
             for (unsigned c = 0; c < C; ++c) {
@@ -487,6 +495,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "--arena")) return arena();
     if (argc > 1 && !strcmp(argv[1], "--cells")) return cells(false);
     if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);
+    if (argc > 1 && !strcmp(argv[1], "--tiles")) return cells(false, true);
     if (argc > 1 && !strcmp(argv[1], "--worklist")) return worklist();
     mh::PlanHost p;
     int got;

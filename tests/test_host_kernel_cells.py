@@ -81,9 +81,9 @@ def planned(exe, lines):  # noqa: F811  (a path here, the fixture's value)
     return out
 
 
-def _line(lens, S, h, mode, rows, sc, input_bits):
-    return "%d %d %d %d 3 %d %d %d  %s  %s" % (len(lens), S, h, mode, len(rows), sc, input_bits, " ".join(map(str, lens)),
-                                               " ".join(str(v) for r in rows for v in r))
+def _line(lens, S, h, mode, rows, sc, input_bits, window=3):
+    return "%d %d %d %d %d %d %d %d  %s  %s" % (len(lens), S, h, mode, window, len(rows), sc, input_bits,
+                                                " ".join(map(str, lens)), " ".join(str(v) for r in rows for v in r))
 
 
 @pytest.fixture(scope="module")
