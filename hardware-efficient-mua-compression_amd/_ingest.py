@@ -27,6 +27,7 @@ PROTOTYPES = {
     "mhi_excess_apply": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u32, _u64, _u64, _vp]),
     "mhi_windows": (_int, [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _u32, _vp, _u32, _u64, _u64, _vp, _u64, _u32,
                            _vp, _vp]),
+    "mhi_gram": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u32, _vp]),
 }
 WIN_STACK, WIN_SUM = 0, 1         # MHI_WIN_STACK, MHI_WIN_SUM
 EXCESS_ROWS, EXCESS_COLS = 0, 1   # MHI_EXCESS_ROWS, MHI_EXCESS_COLS
@@ -170,6 +171,20 @@ def windows(x_ptr, row_stride, rows, cols, win_off, win_idx, n_out, W, r, mode, 
                             int(W), int(r), int(mode), _vp(int(out_ptr)), int(out_bits), int(out_win_stride),
                             int(out_row_stride), p(sumsq), int(sq_row_stride), int(bool(accumulate)), p(bad),
                             _vp(torch.cuda.current_stream().cuda_stream)))
+
+
+def gram(a_ptr, a_row_stride, a_rows, b_ptr, b_row_stride, b_rows, cols, out, sum_a=None, sum_b=None, accumulate=False):
+    """Enqueue mhi_gram on the current stream.  a_ptr / b_ptr: the address of each matrix's first byte (row i at
+    ptr + i*row_stride, cols bytes); b_ptr None: the symmetric form.  out: int64 device tensor [a_rows, b_rows] with unit
+    stride along its last axis; sum_a / sum_b: None or contiguous int64 device tensors of one entry per row."""
+    import torch
+    p = lambda t: _vp(t.data_ptr()) if t is not None else None  # noqa: E731
+    if out.dtype != torch.int64 or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError("the result is an int64 [a_rows, b_rows] tensor with unit stride along its last axis")
+    stride = 8 * (int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1]))
+    check(lib().mhi_gram(_vp(int(a_ptr)), int(a_row_stride), int(a_rows), None if b_ptr is None else _vp(int(b_ptr)),
+                         int(b_row_stride), int(b_rows), int(cols), p(out), stride, p(sum_a), p(sum_b), int(bool(accumulate)),
+                         _vp(torch.cuda.current_stream().cuda_stream)))
 
 
 def seg_crc32(payload, seg_off, seg_words, n_segments, seg_idx=None, crc=None, expect=None, bad=None, payload_words=None):

@@ -298,6 +298,26 @@ class Reader:
                                     starts, W, r, nb, reduce, moments, saturate, self.T,
                                     windows.CHUNK if join is None else join, windows.MAX_BYTES if max_bytes is None else max_bytes)
 
+    def read_gram(self, start, stop, channels=None, bin=None, check=True, exact=None, max_bytes=None):  # noqa: A002
+        """The spike-count Gram matrix of the global samples [start, stop) of the selected channels, without holding the
+        decoded range: -> gram.Gram with gram[i, j] = sum over the bins of x_i * x_j (int64, exact), the row sums and n,
+        from which Gram.cov() and Gram.corr() follow.  bin=r (1..4096, start % r == 0) takes the products of the counts
+        in bins of r samples.  Only WHOLE bins count: n = (stop - start) // r, and the samples behind the last whole bin
+        are left out -- unlike a read, a cut bin would bias a covariance.  With r > 1 the operand is what read(...,
+        bin=r, saturate=True) returns: uint8, a bin's sum clipped at 255, the reference's own dtype for binned MUA at
+        every bin period it uses.  The range is walked in batches of whole bins of at most max_bytes bytes (default
+        windows.MAX_BYTES); each is decoded with read(a, b, channels, bin=, check=check, exact=exact, out=) into one
+        reused scratch matrix and added by one symmetric mhi_gram: blocks, checksums, exact lists and the decode status
+        are read()'s.  Lag 0 only: a lagged product needs overlapping batches."""
+        from . import codec, gram
+        start, r, n = gram.gram_args(start, stop, bin, self.T)
+        cio.wants_excess(self, exact, "archive")
+        rows = int(codec.select_channels(self.C, channels).size)
+
+        def read_bins(b0, nb, view):
+            self.read(start + b0 * r, start + (b0 + nb) * r, channels, bin=bin, check=check, exact=exact, out=view)
+        return gram.read_gram(read_bins, rows, n, gram.MAX_BYTES if max_bytes is None else max_bytes)
+
     def read_events(self, start, stop, channels=None, origin=0, period=1, phase=0, check=True, aer=False,  # noqa: A002
                     ch_dtype=None, exact=None):
         """Global samples [start, stop) of the selected channels as spike events on the recording's clock: sample t of a

@@ -944,3 +944,29 @@ def decompress_windows(src, triggers, pre, post, channels=None, bin=None, reduce
     return windows.read_windows(read_span, rows, starts, W, r, nb, reduce, moments, saturate, T,
                                 windows.CHUNK if join is None else join, windows.MAX_BYTES if max_bytes is None else max_bytes,
                                 device)
+
+
+def decompress_gram(src, start=0, stop=None, channels=None, bin=None, check=True, exact=None, device="cuda",  # noqa: A002
+                    max_bytes=None):
+    """archive.Reader.read_gram over decompress_range / decompress_binned: the Gram matrix (gram.Gram: int64 products,
+    row sums, n) of the samples [start, stop) of the selected channels of a `Compressed`, a `ContainerFile` or a path
+    (opened for the call).  stop=None: the longest channel's length; a shorter channel is zero past its end.  Only whole
+    bins count, and with bin > 1 the operand is the saturated uint8 bin, as read_gram says; check and exact as
+    decompress_range, once per batch.  There is no CPU path: a host array is not a source."""
+    from . import codec, gram
+    if isinstance(src, (str, os.PathLike)):
+        with open(src) as f:
+            return decompress_gram(f, start, stop, channels, bin, check, exact, device, max_bytes)
+    if not hasattr(src, "ch_len"):
+        raise ValueError("decompress_gram takes a Compressed, a ContainerFile or a path: there is no CPU path")
+    T = int(np.max(src.ch_len)) if len(src.ch_len) else 0
+    start, r, n = gram.gram_args(start, T if stop is None else stop, bin, T)
+    rows = int(codec.select_channels(len(src.ch_len), channels).size)
+
+    def read_bins(b0, nb, view):
+        a, b = start + b0 * r, start + (b0 + nb) * r
+        if bin is None:
+            view.copy_(decompress_range(src, a, b, channels, device, check, exact=exact))
+        else:
+            view.copy_(decompress_binned(src, r, a, b, channels, True, check, device, exact))
+    return gram.read_gram(read_bins, rows, n, gram.MAX_BYTES if max_bytes is None else max_bytes, device)

@@ -1,7 +1,7 @@
 // mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
 // in mh_aer.hpp, the segment checksum in mh_crc.hpp, the way back from counts to events in mh_unbin.hpp and the side
-// list of what the clip at S-1 drops in mh_excess.hpp and the trial-aligned windows of a decoded recording in
-// mh_windows.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
+// list of what the clip at S-1 drops in mh_excess.hpp, the trial-aligned windows of a decoded recording in
+// mh_windows.hpp and the channel-by-channel Gram matrix of one in mh_gram.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
 // fallback here either.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,8 @@
 #include "mh_crc.hpp"
 #include "mh_excess.hpp"
 #include "mh_excess_layout.hpp"
+#include "mh_gram.hpp"
+#include "mh_gram_layout.hpp"
 #include "mh_ingest.hpp"
 #include "mh_launch.hpp"
 #include "mh_unbin.hpp"
@@ -504,6 +506,37 @@ int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t 
 #undef MH_WIN_GO
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_windows: launch failed: %s", hipGetErrorString(e));
+    return MH_OK;
+}
+
+int mhi_gram(const uint8_t *a, uint64_t a_row_stride, uint64_t a_rows, const uint8_t *b, uint64_t b_row_stride, uint64_t b_rows,
+             uint64_t cols, int64_t *gram, uint64_t gram_row_stride, int64_t *sum_a, int64_t *sum_b, uint32_t accumulate,
+             void *stream)
+{
+    const mh::GramArgs g = {(uintptr_t)a, a_row_stride, a_rows, (uintptr_t)b, b_row_stride, b_rows, cols, (uintptr_t)gram,
+                            gram_row_stride, (uintptr_t)sum_a, (uintptr_t)sum_b, accumulate};
+    mh::Msg m;
+    if (int rc = mh::gram_check(m, g)) return fail(rc, "%s", m.text);
+    const bool symmetric = b == nullptr;
+    if (symmetric) b = a, b_row_stride = a_row_stride, b_rows = a_rows;
+    mh::GramLayout L;  // the tiles, the runs of K slices and the capped grid (mh_gram_layout.hpp)
+    mh::gram_layout(a_rows, b_rows, cols, symmetric, &L);
+    hipStream_t st = (hipStream_t)stream;
+    if (!accumulate) {
+        hipError_t e = a_rows == 1 || gram_row_stride == 8 * b_rows
+                           ? hipMemsetAsync(gram, 0, a_rows == 1 ? 8 * b_rows : a_rows * gram_row_stride, st)
+                           : hipMemset2DAsync(gram, gram_row_stride, 0, 8 * b_rows, a_rows, st);
+        if (e == hipSuccess && sum_a) e = hipMemsetAsync(sum_a, 0, 8 * a_rows, st);
+        if (e == hipSuccess && sum_b) e = hipMemsetAsync(sum_b, 0, 8 * b_rows, st);
+        if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_gram: zeroing the result failed: %s", hipGetErrorString(e));
+    }
+    const mh::GramParams p = {a, a_row_stride, a_rows, b, b_row_stride, b_rows, cols, reinterpret_cast<uint8_t *>(gram),
+                              gram_row_stride, reinterpret_cast<unsigned long long *>(sum_a),
+                              reinterpret_cast<unsigned long long *>(sum_b), L.symmetric, L.nta, L.ntb, L.run_slices, L.tiles,
+                              L.items};
+    hipLaunchKernelGGL(mh::k_gram, dim3(L.grid), dim3(mh::kGramThreads), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_gram: launch failed: %s", hipGetErrorString(e));
     return MH_OK;
 }
 

@@ -250,6 +250,29 @@ int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t 
                 uint32_t out_bits, uint64_t out_win_stride, uint64_t out_row_stride, uint64_t *sumsq, uint64_t sq_row_stride,
                 uint32_t accumulate, uint64_t *bad, void *stream);
 
+/* ---- spike-count covariance: the channel-by-channel Gram matrix of a matrix of counts, exact ---------------------------
+ * gram[i][j] (+)= sum over t < cols of a[i][t] * b[j][t]      (int64, exact)
+ * sum_a[i]   (+)= sum over t of a[i][t];  sum_b[j] likewise   (int64; NULL = not wanted)
+ * a, b: device.  Row i of a is the cols bytes at a + i*a_row_stride, at ANY byte address (a decoded range, a column
+ * slice of one, the same matrix shifted by a lag); no byte outside a row's cols bytes is read.  b == NULL: b = a, b_rows
+ * and b_row_stride are ignored, only the tiles on or above the diagonal are computed and the result is mirrored, so the
+ * output is the full symmetric matrix (and sum_b, if given, receives what sum_a does).  gram[i][j] is the int64 at
+ * (char *)gram + i*gram_row_stride + 8*j: a_rows rows of b_rows elements.
+ * accumulate = 0 overwrites -- gram and the sums are zeroed on the stream first -- and 1 adds to what is there, so one
+ * result can be built from many batches of columns.
+ * The products run on the int8 matrix cores over x XOR 0x80 and are corrected exactly in int64; no int32 accumulator
+ * sums more than 65536 columns.  The partial results of the runs of columns are added with 64-bit atomics: integer sums
+ * do not depend on the order, the result is the same from run to run.  gram and the sums must not be written by
+ * anything else while the call runs and must not overlap a or b.
+ * MH_ERR_ARG, before any device work: a or gram NULL; a_rows, b_rows (b given) or cols == 0; cols >= 2^40; a_rows or
+ * b_rows above 2^31, or so large that tiles x column slices reaches 2^62; a row stride below cols with more than one row;
+ * gram or gram_row_stride not a multiple of 8, gram_row_stride below 8*b_rows with more than one row; sum_a or sum_b not
+ * 8-byte aligned; accumulate above 1.
+ * Only enqueues on `stream`: no synchronisation, allocation or free, so it can be captured into a hipGraph. */
+int mhi_gram(const uint8_t *a, uint64_t a_row_stride, uint64_t a_rows, const uint8_t *b, uint64_t b_row_stride, uint64_t b_rows,
+             uint64_t cols, int64_t *gram, uint64_t gram_row_stride, int64_t *sum_a, int64_t *sum_b, uint32_t accumulate,
+             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
