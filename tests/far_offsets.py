@@ -26,7 +26,10 @@ and its alias differ, and the argument rules.  tests/test_gpu_far_offsets.py upl
 compares every window whole.
 
 Where the arena bounds a shape of the table: an index i >= 2 times a stride >= 2^32 lies behind the arena, so far VALUES
-come with index 1 (2 rows, 2 draws, 2 output slots) and three rows / draws / elements come with far PRODUCTS."""
+come with index 1 (2 rows, 2 draws, 2 output slots) and three rows / draws / elements come with far PRODUCTS.  For the
+same reason the mirror store of mhi_gram's symmetric form, at j * gram_row_stride, is not in the table: it happens only
+between different tiles, i.e. for a row index >= 128, and 128 times a far stride lies behind the arena (its pitch is
+checked near the base by tests/test_gpu_gram_tiles.py)."""
 import zlib
 from dataclasses import dataclass, field
 
@@ -745,6 +748,122 @@ def build_windows_public(kind):
 
 for _k in ("value", "product"):
     _case("windows", "windows.gather / windows.psth", "row_stride", _k, "every form", build_windows_public, _k)
+
+
+# =====================================================================================================================
+# mhi_gram
+# =====================================================================================================================
+GRAM_COLS, GRAM_NEAR = 333, 5
+GRAM_A, GRAM_B, GRAM_G = 0x10001, 0x40003, 0x80000         # the first byte of a and of b (odd), of gram (8-byte aligned)
+GRAM_FAR_D = 0xC0008                                       # a far base pointer is 2^32 + this
+
+
+def _gram_strides(kind):
+    """(rows of the far operand, its row stride in bytes, the far gram_row_stride)"""
+    if kind == "value":
+        return 2, STRIDE_VALUE + 5, STRIDE_VALUE + 40
+    return 3, STRIDE_PRODUCT + 4096 + 3, STRIDE_PRODUCT + 4104
+
+
+def build_gram(far, kind, form, accumulate):
+    """cols = 333; the near operand has 5 rows, the far one 2 (far value) or 3 (far product); a and b begin at an odd
+    byte and near rows are an even number of bytes apart, so each begins at an odd byte; the far strides are odd, so far
+    rows take both parities, none on a 16-byte boundary.
+    a_row_stride / b_row_stride  the rows of that operand are far; "sym": b NULL, so a_row_stride strides both operands
+    gram_row_stride              the result's rows are far: accumulate = 0 zeroes them through the 2-D memset whose pitch
+                                 is the far stride (canary before the call), accumulate = 1 adds to `initial` values
+    sum_a / sum_b / gram         (kind "offset") that base pointer is 2^32 + GRAM_FAR_D, canary at GRAM_FAR_D
+    The mirror store of the symmetric form, gram + j * gram_row_stride + 8 i, happens only off the diagonal TILE, i.e. for
+    i >= 128: times a far stride that lies behind the arena, as an index >= 2 times a far value does.  The symmetric
+    cases here are one tile: their far rows are written by the i * gram_row_stride store alone."""
+    rng = _rng("gram", far, kind, form, accumulate)
+    s = Setup("A", Image())
+    n, in_far, g_far = _gram_strides(kind) if kind != "offset" else (3, None, None)
+    ra, rb = (GRAM_NEAR, n) if far == "b_row_stride" else (n, n if form == "sym" else GRAM_NEAR)
+    sym = form == "sym"
+    a_rs = in_far if far == "a_row_stride" else GRAM_COLS + 5
+    b_rs = a_rs if sym else in_far if far == "b_row_stride" else GRAM_COLS + 9
+    g_rs = g_far if far == "gram_row_stride" else 8 * (rb + 1)
+    x = _counts(rng, ra * GRAM_COLS).reshape(ra, GRAM_COLS)
+    y = x if sym else _counts(rng, rb * GRAM_COLS).reshape(rb, GRAM_COLS)
+    for i in range(ra):
+        s.read("a_row_stride", (Term(i, a_rs),), x[i], base=GRAM_A)
+    if not sym:
+        for j in range(rb):
+            s.read("b_row_stride", (Term(j, b_rs),), y[j], base=GRAM_B)
+    g0 = rng.randint(1, 1 << 40, size=(ra, rb)).astype("<i8")
+    s0 = rng.randint(1, 1 << 40, size=(2, max(ra, rb))).astype("<i8")
+    lead = (Term(1, FAR + GRAM_G),) if far == "gram" else ()
+    g_at = 0 if far == "gram" else GRAM_G
+    outs = [s.write("gram" if far == "gram" else "gram_row_stride", lead + (Term(i, g_rs),), 8 * rb, base=g_at,
+                    initial=g0[i] if accumulate else None) for i in range(ra)]
+    far_sum = None
+    if far in ("sum_a", "sum_b"):
+        k = ra if far == "sum_a" else rb
+        far_sum = s.write(far, _table_terms(FAR + GRAM_FAR_D), 8 * k, initial=s0[int(far == "sum_b"), :k] if accumulate else None)
+    s.seal()
+    xi, yi = x.astype(np.int64), y.astype(np.int64)
+    G, sa, sb = xi @ yi.T, xi.sum(1), yi.sum(1)
+    if accumulate:
+        G, sa, sb = G + g0, sa + s0[0, :ra], sb + s0[1, :rb]
+    for i in range(ra):
+        s.expect(outs[i], G[i].astype("<i8"))
+    if far_sum is not None:
+        s.expect(far_sum, (sa if far == "sum_a" else sb).astype("<i8"))
+    top = {"a_row_stride": ("(a_rows - 1) * a_row_stride", (ra - 1) * a_rs), "b_row_stride": ("(b_rows - 1) * b_row_stride", (rb - 1) * b_rs),
+           "gram_row_stride": ("(a_rows - 1) * gram_row_stride", (ra - 1) * g_rs), "gram": ("gram - base", FAR + GRAM_G),
+           "sum_a": ("sum_a - base", FAR + GRAM_FAR_D), "sum_b": ("sum_b - base", FAR + GRAM_FAR_D)}[far]
+    s.crossing = [top + ("bytes",)]
+    far_rs = {"a_row_stride": a_rs, "b_row_stride": b_rs, "gram_row_stride": g_rs}.get(far)
+    s.rules += [("a_rows, b_rows, cols >= 1; cols < 2^40", min(ra, rb, GRAM_COLS) >= 1 and GRAM_COLS < 1 << 40),
+                ("a_row_stride >= cols, b_row_stride >= cols", a_rs >= GRAM_COLS and b_rs >= GRAM_COLS),
+                ("gram and gram_row_stride are multiples of 8", GRAM_G % 8 == 0 and FAR % 8 == 0 and g_rs % 8 == 0),
+                ("gram_row_stride >= 8 * b_rows", g_rs >= 8 * rb), ("sum_a and sum_b are multiples of 8", GRAM_FAR_D % 8 == 0),
+                ("accumulate is 0 or 1", accumulate in (0, 1)),
+                ("a and b begin at an odd byte, no row on a 16-byte boundary, every near row at an odd byte",
+                 GRAM_A % 2 == 1 and GRAM_B % 2 == 1 and all((GRAM_A + i * a_rs) % 16 for i in range(ra))
+                 and all((GRAM_B + j * b_rs) % 16 for j in range(rb))
+                 and (far == "a_row_stride" or all((GRAM_A + i * a_rs) % 2 for i in range(ra)))
+                 and (far == "b_row_stride" or sym or all((GRAM_B + j * b_rs) % 2 for j in range(rb)))),
+                ("one tile: no mirror store", max(ra, rb) <= 128),
+                ("a pitched result: an overwrite call zeroes it with the 2-D memset", ra > 1 and g_rs != 8 * rb),
+                ("far value" if kind == "value" else "far product" if kind == "product" else "a far base pointer",
+                 far_rs is None if kind == "offset" else (far_rs >= FAR) == (kind == "value"))]
+
+    def run(ctx):
+        def small(k, init, skip):
+            if skip:
+                return None
+            t = ctx.canary(k + 2, np.int64)
+            if accumulate:
+                t[1:1 + k] = ctx.dev(init[:k])
+            return t
+        d_sa, d_sb = small(ra, s0[0], far == "sum_a"), small(rb, s0[1], far == "sum_b")
+        p_sa = ctx.at(FAR + GRAM_FAR_D) if far == "sum_a" else ctx.p(d_sa, 1)
+        p_sb = ctx.at(FAR + GRAM_FAR_D) if far == "sum_b" else ctx.p(d_sb, 1)
+        rc = ctx.ilib.mhi_gram(ctx.at(GRAM_A), a_rs, ra, None if sym else ctx.at(GRAM_B), 0 if sym else b_rs, 0 if sym else rb, GRAM_COLS,
+                               ctx.at(FAR + GRAM_G if far == "gram" else GRAM_G), g_rs, p_sa, p_sb, accumulate, None)
+        assert rc == 0, ctx.ilib.mhi_last_error()
+        ctx.sync()
+        if d_sa is not None:
+            ctx.framed(d_sa, 1, sa.astype("<i8"), "sum_a")
+        if d_sb is not None:
+            ctx.framed(d_sb, 1, sb.astype("<i8"), "sum_b")
+    s.run = run
+    return s
+
+
+for _k in ("value", "product"):
+    _case("gram", "mhi_gram", "a_row_stride", _k, "%d x 5 rows, cols = 333" % (2 if _k == "value" else 3), build_gram, "a_row_stride", _k, "cross", 0)
+    _case("gram", "mhi_gram", "b_row_stride", _k, "5 x %d rows, cols = 333" % (2 if _k == "value" else 3), build_gram, "b_row_stride", _k, "cross", 0)
+    for _acc in (0, 1):
+        _case("gram", "mhi_gram", "gram_row_stride", _k, "%d x 5 rows, cols = 333, accumulate = %d" % (2 if _k == "value" else 3, _acc),
+              build_gram, "gram_row_stride", _k, "cross", _acc)
+_case("gram", "mhi_gram", "a_row_stride (symmetric)", "product", "3 rows, cols = 333", build_gram, "a_row_stride", "product", "sym", 0)
+_case("gram", "mhi_gram", "gram_row_stride (symmetric)", "product", "3 rows, cols = 333", build_gram, "gram_row_stride", "product", "sym", 0)
+for _far in ("sum_a", "sum_b", "gram"):
+    for _acc in (0, 1):
+        _case("gram", "mhi_gram", _far, "offset", "3 x 5 rows, cols = 333, accumulate = %d" % _acc, build_gram, _far, "offset", "cross", _acc)
 
 
 # =====================================================================================================================

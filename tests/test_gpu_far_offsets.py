@@ -209,6 +209,11 @@ def test_windows(mh, arena, case):
     run_case(mh, arena, case)
 
 
+@_row("gram")
+def test_gram(mh, arena, case):
+    run_case(mh, arena, case)
+
+
 # the 16-GiB arena is allocated for these three alone: a test function of their own keeps the rest of the file quick
 _W = [c for c in fo.CASES if c.arena == "W"]
 

@@ -1,8 +1,9 @@
 """mhi_gram on the GPU (include/muahuff_ingest.h, csrc/mh_gram.hpp): the channel-by-channel Gram matrix of uint8 counts on
 the int8 matrix cores against NumPy's int64 product -- equal, not close: the value boundaries of the XOR-0x80 operands,
 the C/D lane map on data whose every element is distinct, ragged shapes and pitches, every byte alignment of both
-operands with 255 around the rows, runs of K slices past the int32 bound, a grid past its cap, accumulate, the symmetric
-form against the cross form, lags, the float results and the stream order."""
+operands with 255 around the rows, more columns than one int32 accumulator could sum (in runs of one slice: the runs of
+full length, 2^30 in an accumulator, are tests/test_gpu_gram_tiles.py's), a grid past its cap, accumulate, the symmetric
+form against the cross form, lags, the float results, the stream order, and capture into a graph and replay."""
 import numpy as np
 import pytest
 import torch
@@ -114,9 +115,14 @@ def test_every_alignment_of_both_operands(lead_a, lead_b):
 
 @pytest.mark.parametrize("kind", ["zero", "full", "mixed"])
 def test_more_columns_than_an_int32_accumulator_holds(kind):
-    """18 x (131072 + 65): z = x XOR 0x80 is -128 for x = 0, so the all-zero matrix is the accumulators' worst case"""
+    """18 x (131072 + 65): more columns than an int32 accumulator could sum in one go (z = x XOR 0x80 is -128 for x = 0, so
+    the all-zero matrix is the worst case), so the result is right only if the columns are cut into runs and each run is
+    widened.  With one tile the layout cuts them into 33 runs of ONE slice: no accumulator holds more than 2^26 here.
+    Runs of full length, 2^30 in an accumulator, are
+    tests/test_gpu_gram_tiles.py::test_the_shipped_regime_full_runs_many_tiles_worst_case_values."""
     rows, cols = 18, 131072 + 65
     assert layout(rows, rows, cols, 1)[5] >= 3              # at least three runs of K slices
+    assert layout(rows, rows, cols, 1)[4:6] == [1, 33]      # (of one slice each)
     if kind == "mixed":
         x = _random(rows, cols, 9)
         x[0], x[1], x[2, ::2] = 0, 255, 0
@@ -248,3 +254,52 @@ def test_the_call_is_ordered_on_the_current_stream_and_host_tensors_are_refused(
         gram.gram(torch.from_numpy(x))
     with pytest.raises(ValueError):
         gram.gram(src.to(torch.int32))
+
+
+def test_captured_calls_replay_on_other_contents():
+    """mhi_gram only enqueues -- memset nodes and one kernel --: the pitched cross form (the 2-D memset node) and the
+    symmetric form, overwriting, are captured once on a side stream and replayed on three other contents of the same
+    input buffers, gram and sums poisoned in between; an accumulate = 1 call replayed twice on a zeroed result gives
+    twice the product.  3 x 2 tiles, both last tiles ragged."""
+    ra, rb, cols = 260, 129, 200
+    a, b = _dev(_random(ra, cols, 30)), _dev(_random(rb, cols, 31), lead=3)
+    base = torch.zeros((ra, rb + 3), dtype=torch.int64, device="cuda")
+    out, sym = base[:, :rb], torch.zeros((ra, ra), dtype=torch.int64, device="cuda")
+    acc = torch.zeros((ra, rb), dtype=torch.int64, device="cuda")
+    sums = [torch.zeros((n,), dtype=torch.int64, device="cuda") for n in (ra, rb, ra, ra, ra, rb)]
+    targets = [base, sym] + sums[:4]
+
+    def calls(add):
+        if add:
+            _ingest.gram(a.data_ptr(), a.stride(0), ra, b.data_ptr(), b.stride(0), rb, cols, acc, sums[4], sums[5], True)
+        else:
+            _ingest.gram(a.data_ptr(), a.stride(0), ra, b.data_ptr(), b.stride(0), rb, cols, out, sums[0], sums[1], False)
+            _ingest.gram(a.data_ptr(), a.stride(0), ra, None, 0, 0, cols, sym, sums[2], sums[3], False)
+
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        calls(False), calls(True)                           # warm: the module is loaded
+    side.synchronize()
+    g, g_add = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        calls(False)
+    with torch.cuda.graph(g_add, stream=side):
+        calls(True)
+    for seed in (32, 34, 36):
+        x, y = _random(ra, cols, seed), _random(rb, cols, seed + 1)
+        with torch.cuda.stream(side):
+            a.copy_(torch.from_numpy(x).cuda()), b.copy_(torch.from_numpy(y).cuda())
+            for t in targets:
+                t.fill_(2 ** 62 + 12345)
+            g.replay()
+        side.synchronize()
+        _same((out.cpu().numpy(), sums[0].cpu().numpy(), sums[1].cpu().numpy()), _ref(x, y))
+        _same((sym.cpu().numpy(), sums[2].cpu().numpy(), sums[3].cpu().numpy()), _ref(x))
+        assert (base[:, rb:] == 2 ** 62 + 12345).all()      # the 2-D memset node keeps to the rows
+    with torch.cuda.stream(side):
+        for t in (acc, sums[4], sums[5]):
+            t.zero_()
+        g_add.replay()
+        g_add.replay()
+    side.synchronize()
+    _same((acc.cpu().numpy(), sums[4].cpu().numpy(), sums[5].cpu().numpy()), tuple(2 * w for w in _ref(x, y)))

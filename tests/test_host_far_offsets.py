@@ -41,7 +41,7 @@ def test_the_arenas_are_what_the_layout_needs():
 def test_ids_are_unique_and_every_row_is_there():
     assert len(set(IDS)) == len(IDS)
     rows = {c.row for c in fo.CASES}
-    assert rows >= {"rebin", "transpose", "synth", "sweep", "analysis", "crc", "unbin", "excess", "apply", "windows"}, rows
+    assert rows >= {"rebin", "transpose", "synth", "sweep", "analysis", "crc", "unbin", "excess", "apply", "windows", "gram"}, rows
 
 
 @pytest.mark.parametrize("case", fo.CASES, ids=IDS)
@@ -109,12 +109,14 @@ def test_strided_arguments_come_as_far_value_and_as_far_product():
 
 # ---- the host-only builders that take the far argument as it is -----------------------------------------------------------
 from tests import helpers  # noqa: E402
+from tests import test_host_gram as hg  # noqa: E402
 from tests import test_host_windows as hw  # noqa: E402
 from tests import test_host_worklist as wl  # noqa: E402
 from tests import test_planner_sanitized as ps  # noqa: E402
 
 plan_exe = ps.exe          # fixture: tests/planner_check.cpp under AddressSanitizer + UBSan
 win_exe = hw.exe           # fixture: tests/windows_check.cpp, likewise
+gram_exe = hg.exe          # fixture: tests/gram_check.cpp, likewise
 
 
 def _rc(idx, pitch, n_sel, width):
@@ -216,6 +218,33 @@ def test_the_work_list_builder_takes_the_far_pitches(plan_exe):
             _sparse_range(head, rec, seg, arr, w0, w1, sel, t0, t1, pitch)
         else:
             _sparse_rebin(head, rec, seg, arr, w0, w1, sel, t0, t1, rr, pitch)
+
+
+def test_the_gram_check_program_takes_the_far_strides(gram_exe):
+    """tests/gram_check.cpp: the argument check accepts the strides of the "gram" cases, in both forms and with
+    accumulate 0 and 1"""
+    lines, n = "", 0
+    near_a, near_b = fo.GRAM_COLS + 5, fo.GRAM_COLS + 9
+    for kind in ("value", "product"):
+        rows, rs, gs = fo._gram_strides(kind)
+        assert (rs >= fo.FAR) == (gs >= fo.FAR) == (kind == "value") and (rows - 1) * rs >= fo.FAR and (rows - 1) * gs >= fo.FAR
+        for over in (dict(a_rows=rows, a_row_stride=rs, b_rows=fo.GRAM_NEAR, b_row_stride=near_b, gram_row_stride=8 * (fo.GRAM_NEAR + 1)),
+                     dict(a_rows=fo.GRAM_NEAR, a_row_stride=near_a, b_rows=rows, b_row_stride=rs, gram_row_stride=8 * (rows + 1)),
+                     dict(a_rows=rows, a_row_stride=near_a, b_rows=fo.GRAM_NEAR, b_row_stride=near_b, gram_row_stride=gs),
+                     dict(hg.SYM, a_rows=rows, a_row_stride=rs, gram_row_stride=8 * (rows + 1)),
+                     dict(hg.SYM, a_rows=rows, a_row_stride=near_a, gram_row_stride=gs)):
+            for acc in (0, 1):
+                odd = dict(a_shift=1) if "b" in over else dict(a_shift=1, b_shift=3)          # (b stays NULL in the symmetric form)
+                _keep, a = hg._args(cols=fo.GRAM_COLS, accumulate=acc, **odd, **over)
+                lines += hg._line(a)
+                n += 1
+    assert hg._run(gram_exe, lines) == ["ok"] * n
+    # the table's own strides are these
+    cases = {c.args: c.setup() for c in fo.CASES if c.row == "gram" and c.kind != "offset"}
+    for (far, kind, _form, _acc), s in cases.items():
+        rows, rs, gs = fo._gram_strides(kind)
+        strides = {t.stride for a in s.accesses if a.arg == far for t in a.terms}
+        assert (gs if far == "gram_row_stride" else rs) in strides and len([a for a in s.accesses if a.arg == far]) >= rows, (far, kind)
 
 
 def test_the_windows_check_program_takes_the_far_strides(win_exe):

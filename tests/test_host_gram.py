@@ -149,6 +149,9 @@ def layout(a_rows, b_rows, cols, symmetric):
 
 ROWS = [1, 15, 16, 17, 127, 129, 1024, 16385]
 COLS = [1, 63, 64, 65, 131071, 131072, 10 ** 7, 2 ** 40 - 1]
+# the shapes of tests/test_gpu_gram_tiles.py: the header itself answers for them, not only its restatement
+GPU_SHAPES = [(260, 129, 200, 0), (129, 260, 200, 0), (643, 643, 130, 1), (515, 515, 139 * SLICE + 65, 1),
+              (7803, 7803, 131072 + 65, 1), (7803, 300, 131072 + 65, 0), (1, 1, 2 ** 32 + 4099, 1), (1, 1, 2 ** 32 + 4092, 0)]
 
 
 def test_tiles_slices_runs_and_the_grid_over_the_sweep(exe):
@@ -156,6 +159,7 @@ def test_tiles_slices_runs_and_the_grid_over_the_sweep(exe):
     no int32 run above 131071 columns, the symmetric grid owns exactly the tiles with j >= i, the grid under its cap"""
     grid = [(ra, rb, c, 0) for ra in ROWS for rb in (ROWS[0], ROWS[-1], ra) for c in COLS]
     grid += [(ra, ra, c, 1) for ra in ROWS for c in COLS]
+    grid += GPU_SHAPES
     lines = _run(exe, "".join("layout %d %d %d %d\n" % g for g in grid))
     assert len(lines) == len(grid)
     strided = 0
@@ -168,6 +172,17 @@ def test_tiles_slices_runs_and_the_grid_over_the_sweep(exe):
     # the shapes tests/test_gpu_gram.py relies on: at least three runs in the int32 case, a strided grid in the long one
     assert layout(18, 18, 131072 + 65, 1)[5] >= 3
     assert layout(18, 18, MAX_BLOCKS * SLICE * RUN_SLICES + SLICE + 65, 1)[6] > MAX_BLOCKS
+    # ... and tests/test_gpu_gram_tiles.py: [nta, ntb, tiles, slices, run_slices, runs, items, grid] of each of its shapes
+    assert layout(18, 18, 131072 + 65, 1)[:6] == [1, 1, 1, 33, 1, 33]          # the int32 case above: runs of ONE slice
+    assert layout(260, 129, 200, 0)[:8] == [3, 2, 6, 1, 1, 1, 6, 8] and layout(129, 260, 200, 0)[:8] == [2, 3, 6, 1, 1, 1, 6, 8]
+    assert layout(643, 643, 130, 1)[:8] == [6, 6, 21, 1, 1, 1, 21, 24]
+    assert layout(515, 515, 139 * SLICE + 65, 1)[:8] == [5, 5, 15, 140, 1, 140, 2100, MAX_BLOCKS]
+    assert layout(7803, 7803, 131072 + 65, 1) == [61, 61, 1891, 33, 16, 3, 5673, MAX_BLOCKS, MAX_BLOCKS, 65536]
+    assert layout(7803, 300, 131072 + 65, 0) == [61, 3, 183, 33, 2, 17, 3111, MAX_BLOCKS, MAX_BLOCKS, 8192]
+    assert layout(1, 1, 2 ** 32 + 4099, 1) == [1, 1, 1, 2 ** 20 + 2, 16, 65537, 65537, MAX_BLOCKS, MAX_BLOCKS, 65536]
+    assert layout(1, 1, 2 ** 32 + 4099 - 7, 0)[4:7] == [16, 65537, 65537]
+    # the headline shape of DESIGN.md, for comparison: the same regime as the 7803-row case
+    assert layout(1024, 1024, 10 ** 7, 1)[:7] == [8, 8, 36, 2442, 16, 153, 5508]
 
 
 def test_the_xor_fix_up_identity_on_the_boundary_values():
