@@ -206,6 +206,10 @@ def test_stream_path_at_full_size(mh, S, C, T):
     nseg = plan_p.n_segments
     seg_p = plan_p.segments()
     assert plan_p.input_bits == bits
+    # the encoder's own slot offsets: with 4-bit pieces the slotted payload is longer than 4 GiB and the last segments'
+    # slots begin behind byte 2^32 (word 2^30).  With S = 3 -- at most 2 bits a sample -- it is 0.61 of that: no crossing
+    if bits == 4:
+        assert int(seg_p["off"][-1]) >= 1 << 30 and plan_p.payload_cap_words * 4 > 1 << 32
     sw = dense.seg_words[:nseg]
     assert int(tot[0]) == int(sw.sum())
     assert torch.equal(dense.seg_off[:nseg], torch.cumsum(sw, 0) - sw)
