@@ -20,7 +20,7 @@ INGEST_SOURCES = ["csrc/mh_ingest.hip"]
 INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_aer.hpp", "csrc/mh_aer_layout.hpp",
                   "csrc/mh_crc.hpp", "csrc/mh_crc_tables.hpp", "csrc/mh_unbin.hpp", "csrc/mh_unbin_layout.hpp",
                   "csrc/mh_excess.hpp", "csrc/mh_excess_layout.hpp", "csrc/mh_windows.hpp", "csrc/mh_windows_layout.hpp",
-                  "csrc/mh_gram.hpp", "csrc/mh_gram_layout.hpp",
+                  "csrc/mh_gram.hpp", "csrc/mh_gram_layout.hpp", "csrc/mh_ingest_check.hpp",
                   "csrc/mh_device.hpp", "csrc/mh_msg.hpp", "csrc/mh_launch.hpp", "../include/muahuff.h",
                   "../include/muahuff_ingest.h"]
 

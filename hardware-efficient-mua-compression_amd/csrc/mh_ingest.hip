@@ -1,8 +1,8 @@
-// mh_ingest.hip -- C ABI (include/muahuff_ingest.h) over the binner kernel in mh_ingest.hpp, the pair-list partition
-// in mh_aer.hpp, the segment checksum in mh_crc.hpp, the way back from counts to events in mh_unbin.hpp and the side
-// list of what the clip at S-1 drops in mh_excess.hpp, the trial-aligned windows of a decoded recording in
-// mh_windows.hpp and the channel-by-channel Gram matrix of one in mh_gram.hpp: argument checks and the launches.  A companion of libmuahuff.so, not part of it; there is no CPU
-// fallback here either.
+// mh_ingest.hip -- the C ABI of include/muahuff_ingest.h over the kernels of mh_ingest.hpp, mh_aer.hpp, mh_crc.hpp,
+// mh_unbin.hpp, mh_excess.hpp, mh_windows.hpp and mh_gram.hpp.  Every entry point builds its argument struct, asks the
+// check of its host-only header (mh_*_layout.hpp, mh_ingest_check.hpp) for a verdict and the layout, and launches what
+// came back: no argument rule and no grid is worked out here.  A companion of libmuahuff.so, not part of it; there is no
+// CPU fallback here either.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -16,6 +16,7 @@
 #include "mh_gram.hpp"
 #include "mh_gram_layout.hpp"
 #include "mh_ingest.hpp"
+#include "mh_ingest_check.hpp"
 #include "mh_launch.hpp"
 #include "mh_unbin.hpp"
 #include "mh_unbin_layout.hpp"
@@ -39,23 +40,37 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+// what a host-only header reported
+int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
+
+// how every entry point ends: MH_OK, or what its launches left behind.  `fn` names the entry point.
+int launched(const char *fn)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MH_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return MH_OK;
+}
+
 static_assert(mh::kGeoCrcWaves == mh::kCrcWaves && mh::kCrcMaxX == mh::kCrcMaxGroups, "mh_launch.hpp sizes the grid by mh_crc.hpp's constants");
 static_assert(mh::kGeoApplyThreads == mh::kApplyThreads && mh::kGeoApplyMaxBlocks == mh::kApplyMaxBlocks,
               "mh_launch.hpp sizes the apply grids by mh_excess_layout.hpp's constants");
+static_assert(mh::kAerLayoutColThreads == mh::kAerColThreads, "mh_aer_layout.hpp sizes the column grid by mh_aer.hpp's constant");
+static_assert(mh::kAerMaxChannels == MHI_AER_MAX_CHANNELS, "the header publishes the layout's limit");
+static_assert(mh::kUnbinCsr == MHI_UNBIN_CSR && mh::kUnbinAer == MHI_UNBIN_AER, "the header publishes the forms");
+static_assert(mh::kExcessRows == MHI_EXCESS_ROWS && mh::kExcessCols == MHI_EXCESS_COLS, "the header publishes the forms");
+static_assert(mh::kWinStack == MHI_WIN_STACK && mh::kWinSum == MHI_WIN_SUM, "the header publishes the forms");
 
 // Where does a table live?  Only a query of the runtime's allocation records: nothing is enqueued, nothing waits.
-enum class Where { kDevice, kBoth, kHostOnly };
-
-Where where_is(const void *p)
+uint32_t where_is(const void *p)
 {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();  // not an allocation the runtime knows (or no runtime at all): plain host memory
-        return Where::kHostOnly;
+        return mh::kWhereHostOnly;
     }
-    if (a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged) return Where::kBoth;
-    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) return Where::kDevice;
-    return Where::kHostOnly;
+    if (a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged) return mh::kWhereBoth;
+    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) return mh::kWhereDevice;
+    return mh::kWhereHostOnly;
 }
 
 template <typename CH>
@@ -66,8 +81,8 @@ void aer_launch(const uint64_t *ticks, const void *channels, uint64_t n, uint32_
     uint32_t *const partial = reinterpret_cast<uint32_t *>(scratch + L.off_partial);
     uint32_t *const drop = reinterpret_cast<uint32_t *>(scratch + L.off_drop);
     const CH *const ch = static_cast<const CH *>(channels);
-    const dim3 tiles((unsigned)((L.rows + L.waves - 1) / L.waves)), waves(64u * L.waves);
-    const dim3 cols((C + mh::kAerColThreads - 1) / mh::kAerColThreads, (unsigned)L.groups), col(mh::kAerColThreads);
+    const dim3 tiles(L.grid_tiles), waves(64u * L.waves);
+    const dim3 cols(L.grid_cols_x, L.grid_cols_y), col(mh::kAerColThreads);
     if (L.rows) {
         hipLaunchKernelGGL(mh::k_aer_count<CH>, tiles, waves, L.lds_bytes, st, ch, n, C, L.run, L.rows, matrix, drop);
         hipLaunchKernelGGL(mh::k_aer_group_sum, cols, col, 0, st, matrix, C, L.rows, mh::kAerGroupRows, partial);
@@ -81,62 +96,30 @@ void aer_launch(const uint64_t *ticks, const void *channels, uint64_t n, uint32_
     }
 }
 
-// What mhi_unbin_count and mhi_unbin_emit share: the form, the shape and the scratch.  `fn` names the caller.
-int unbin_args(const char *fn, uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
-               const void *scratch, uint64_t scratch_bytes, mh::UnbinLayout *L)
-{
-    if (form != mh::kUnbinCsr && form != mh::kUnbinAer)
-        return fail(MH_ERR_ARG, "%s: form=%u (MHI_UNBIN_CSR or MHI_UNBIN_AER)", fn, form);
-    if (!in || !scratch) return fail(MH_ERR_ARG, "%s: NULL pointer", fn);
-    if (form == mh::kUnbinCsr && !row_off) return fail(MH_ERR_ARG, "%s: the CSR form needs row_off", fn);
-    if (form == mh::kUnbinAer && row_off) return fail(MH_ERR_ARG, "%s: the AER form is one contiguous block: row_off must be NULL", fn);
-    const int rc = mh::unbin_layout(form, rows, cols, L);
-    if (rc == -1)
-        return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu (each at least 1; AER form: cols <= 2^32)", fn,
-                    (unsigned long long)rows, (unsigned long long)cols);
-    if (rc) return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu make more than 2^32 - 1 tiles", fn, (unsigned long long)rows,
-                        (unsigned long long)cols);
-    if (scratch_bytes < L->bytes)
-        return fail(MH_ERR_ARG, "%s: scratch_bytes=%llu, mhi_unbin_scratch_bytes asks for %llu", fn,
-                    (unsigned long long)scratch_bytes, (unsigned long long)L->bytes);
-    if ((uintptr_t)scratch % 16) return fail(MH_ERR_ARG, "%s: scratch is not 16-byte aligned", fn);
-    return MH_OK;
-}
-
 template <uint32_t FORM, typename CH>
 void unbin_emit_launch(const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols, const mh::UnbinLayout &L,
                        uint64_t first_tick, uint64_t period, const uint64_t *base, uint64_t *out_ticks, void *out_ch,
                        uint64_t capacity, uint64_t *over, hipStream_t st)
 {
-    const dim3 grid((unsigned)((L.tiles + mh::kUnbinWaves - 1) / mh::kUnbinWaves)), block(64u * mh::kUnbinWaves);
+    const dim3 grid(L.grid), block(64u * mh::kUnbinWaves);
     hipLaunchKernelGGL((mh::k_unbin_emit<FORM, CH>), grid, block, 0, st, in, row_off, cols, (uint32_t)L.tiles_per_row,
                        rows * cols, (uint32_t)L.tiles, first_tick, period, base, out_ticks, static_cast<CH *>(out_ch), capacity,
                        reinterpret_cast<unsigned long long *>(over));
 }
 
-// What mhi_excess_count and mhi_excess_emit share: the form, the shape, the threshold and the scratch.
-int excess_args(const char *fn, uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo,
-                const uint64_t *hi, uint64_t rows, uint64_t cols, uint32_t threshold, const void *scratch,
-                uint64_t scratch_bytes, mh::ExcessLayout *L)
+// The scan mhi_unbin_count and mhi_excess_count end in, over the three regions of their scratch (u32 sums[pieces], u64
+// base[pieces], u64 partial[groups + 1]): the pieces' sums become their 64-bit bases, *total the sum of all, and -- where
+// `offs` is given -- offs[0 .. n_rows] the base of every row's first piece (`per` pieces to a row) and the total.
+void scan_launch(uint8_t *scratch, uint64_t off_sum, uint64_t off_base, uint64_t off_partial, uint32_t pieces, uint32_t per,
+                 uint64_t groups, uint32_t grid_scan, uint64_t *total, uint64_t *offs, uint64_t n_rows, hipStream_t st)
 {
-    if (form != mh::kExcessRows && form != mh::kExcessCols)
-        return fail(MH_ERR_ARG, "%s: form=%u (MHI_EXCESS_ROWS or MHI_EXCESS_COLS)", fn, form);
-    if (!in || !scratch) return fail(MH_ERR_ARG, "%s: NULL pointer", fn);
-    if (form == mh::kExcessRows && !row_off) return fail(MH_ERR_ARG, "%s: the ROWS form needs row_off", fn);
-    if (form == mh::kExcessCols && (row_off || lo || hi))
-        return fail(MH_ERR_ARG, "%s: the COLS form is one contiguous block, every column whole: row_off, lo and hi must be NULL", fn);
-    if (threshold < 1 || threshold > 254) return fail(MH_ERR_ARG, "%s: threshold=%u (1 .. 254)", fn, threshold);
-    const int rc = mh::excess_layout(form, rows, cols, L);
-    if (rc == -1)
-        return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu (each at least 1, cols below 2^32; COLS form: rows below 2^32)", fn,
-                    (unsigned long long)rows, (unsigned long long)cols);
-    if (rc) return fail(MH_ERR_ARG, "%s: rows=%llu, cols=%llu make more than 2^32 - 1 pieces", fn, (unsigned long long)rows,
-                        (unsigned long long)cols);
-    if (scratch_bytes < L->bytes)
-        return fail(MH_ERR_ARG, "%s: scratch_bytes=%llu, mhi_excess_scratch_bytes asks for %llu", fn,
-                    (unsigned long long)scratch_bytes, (unsigned long long)L->bytes);
-    if ((uintptr_t)scratch % 16) return fail(MH_ERR_ARG, "%s: scratch is not 16-byte aligned", fn);
-    return MH_OK;
+    uint32_t *const sums = reinterpret_cast<uint32_t *>(scratch + off_sum);
+    uint64_t *const base = reinterpret_cast<uint64_t *>(scratch + off_base);
+    uint64_t *const partial = reinterpret_cast<uint64_t *>(scratch + off_partial);
+    const dim3 grid(grid_scan), per_group(mh::kUnbinBaseThreads);
+    hipLaunchKernelGGL(mh::k_unbin_group_sum, grid, per_group, 0, st, sums, pieces, partial);
+    hipLaunchKernelGGL(mh::k_unbin_scan, dim3(1), dim3(mh::kUnbinScanThreads), 0, st, partial, groups, total, offs, n_rows);
+    hipLaunchKernelGGL(mh::k_unbin_bases, grid, per_group, 0, st, sums, pieces, partial, base, per, offs);
 }
 
 }  // namespace
@@ -151,30 +134,13 @@ int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, ui
                    uint64_t T, uint32_t bits, uint8_t *out, const uint64_t *out_off, uint64_t chunk_stride,
                    void *stream)
 {
-    if (!ticks || !ev_off || !out || !out_off) return fail(MH_ERR_ARG, "mhi_bin_events: NULL pointer");
-    if (C == 0 || T == 0 || period == 0)
-        return fail(MH_ERR_ARG, "mhi_bin_events: C=%u, T=%llu, period=%llu (each at least 1)", C, (unsigned long long)T,
-                    (unsigned long long)period);
-    if (bits != 8 && bits != 4 && bits != 2) return fail(MH_ERR_ARG, "mhi_bin_events: bits=%u (8, 4 or 2)", bits);
-    if (!mh::chunk_stride_ok(chunk_stride, bits))
-        return fail(MH_ERR_ARG, "mhi_bin_events: chunk_stride=%llu (packed output only, a multiple of 16, at least one chunk)",
-                    (unsigned long long)chunk_stride);
-    const unsigned __int128 end = (unsigned __int128)origin + (unsigned __int128)T * period;
-    if (end > ((unsigned __int128)1 << 63))
-        return fail(MH_ERR_ARG, "mhi_bin_events: origin + T*period exceeds 2^63 (origin=%llu, T=%llu, period=%llu)",
-                    (unsigned long long)origin, (unsigned long long)T, (unsigned long long)period);
-    if (bits != 8) {
-        const Where w = where_is(out_off);
-        if (w != Where::kDevice)
-            for (uint32_t c = 0; c < C; ++c)
-                if (out_off[c] % 16)
-                    return fail(MH_ERR_ARG, "mhi_bin_events: out_off[%u]=%llu is not a multiple of 16 (packed output)", c,
-                                (unsigned long long)out_off[c]);
-        if (w == Where::kHostOnly) return fail(MH_ERR_ARG, "mhi_bin_events: out_off is host memory the device cannot read");
-    }
+    const mh::BinArgs a = {(uintptr_t)ticks, (uintptr_t)ev_off, C, origin, period, T, bits, (uintptr_t)out, (uintptr_t)out_off,
+                           chunk_stride};
     mh::Msg m;
     mh::BinLaunch l;  // chunks per workgroup and the grid (mh_launch.hpp)
-    if (int rc = mh::bin_events_launch(m, C, T, period, &l)) return fail(rc, "%s", m.text);
+    if (int rc = mh::bin_events_check(m, a)) return fail(rc, m);
+    // a packed call's out_off is walked where the host can read it: the runtime is asked only once the rest holds
+    if (int rc = mh::bin_events_table_check(m, a, bits != 8 ? where_is(out_off) : mh::kWhereDevice, &l)) return fail(rc, m);
     const dim3 grid(l.grid), block(mh::kBinThreads);
     hipStream_t st = (hipStream_t)stream;
     if (bits == 8)
@@ -186,20 +152,14 @@ int mhi_bin_events(const uint64_t *ticks, const uint64_t *ev_off, uint32_t C, ui
     else
         hipLaunchKernelGGL(mh::k_bin_events<2>, grid, block, 0, st, ticks, ev_off, origin, period, T, l.nchunks, l.span, l.nspans,
                            l.div_mode, out, out_off, chunk_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_bin_events: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_bin_events");
 }
 
 int mhi_aer_scratch_bytes(uint64_t n, uint32_t C, uint64_t *bytes)
 {
-    static_assert(mh::kAerMaxChannels == MHI_AER_MAX_CHANNELS, "the header publishes the layout's limit");
-    if (!bytes) return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: NULL pointer");
+    mh::Msg m;
     mh::AerLayout L;
-    const int rc = mh::aer_layout(n, C, &L);
-    if (rc == -1)
-        return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: C=%u (1 .. MHI_AER_MAX_CHANNELS = %u)", C, mh::kAerMaxChannels);
-    if (rc) return fail(MH_ERR_ARG, "mhi_aer_scratch_bytes: n=%llu (below 2^32: positions are 32-bit)", (unsigned long long)n);
+    if (int rc = mh::aer_scratch_check(m, n, C, (uintptr_t)bytes, &L)) return fail(rc, m);
     *bytes = L.bytes;
     return MH_OK;
 }
@@ -208,61 +168,41 @@ int mhi_aer_to_csr(const uint64_t *ticks, const void *channels, uint32_t ch_bits
                    uint64_t *out_ticks, uint64_t *ev_off, uint64_t *dropped, void *scratch, uint64_t scratch_bytes,
                    void *stream)
 {
-    if (!ticks || !channels || !out_ticks || !ev_off || !dropped || !scratch)
-        return fail(MH_ERR_ARG, "mhi_aer_to_csr: NULL pointer");
-    if (ch_bits != 16 && ch_bits != 32) return fail(MH_ERR_ARG, "mhi_aer_to_csr: ch_bits=%u (16 or 32)", ch_bits);
-    mh::AerLayout L;
-    const int rc = mh::aer_layout(n, C, &L);
-    if (rc == -1) return fail(MH_ERR_ARG, "mhi_aer_to_csr: C=%u (1 .. MHI_AER_MAX_CHANNELS = %u)", C, mh::kAerMaxChannels);
-    if (rc) return fail(MH_ERR_ARG, "mhi_aer_to_csr: n=%llu (below 2^32: positions are 32-bit)", (unsigned long long)n);
-    if (scratch_bytes < L.bytes)
-        return fail(MH_ERR_ARG, "mhi_aer_to_csr: scratch_bytes=%llu, mhi_aer_scratch_bytes asks for %llu",
-                    (unsigned long long)scratch_bytes, (unsigned long long)L.bytes);
-    const uintptr_t a = (uintptr_t)ticks, b = (uintptr_t)out_ticks;
-    if (n && a < b + n * 8 && b < a + n * 8) return fail(MH_ERR_ARG, "mhi_aer_to_csr: out_ticks overlaps ticks");
-    if ((uintptr_t)scratch % 16)
-        return fail(MH_ERR_ARG, "mhi_aer_to_csr: scratch is not 16-byte aligned");
+    const mh::AerArgs a = {(uintptr_t)ticks, (uintptr_t)channels, ch_bits, n, C, (uintptr_t)out_ticks, (uintptr_t)ev_off,
+                           (uintptr_t)dropped, (uintptr_t)scratch, scratch_bytes};
+    mh::Msg m;
+    mh::AerLayout L;  // the sub-runs, the scratch sections and the grids (mh_aer_layout.hpp)
+    if (int rc = mh::aer_check(m, a, &L)) return fail(rc, m);
     hipStream_t st = (hipStream_t)stream;
     if (ch_bits == 16)
         aer_launch<uint16_t>(ticks, channels, n, C, L, (uint8_t *)scratch, out_ticks, ev_off, dropped, st);
     else
         aer_launch<uint32_t>(ticks, channels, n, C, L, (uint8_t *)scratch, out_ticks, ev_off, dropped, st);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_aer_to_csr: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_aer_to_csr");
 }
 
 int mhi_seg_crc32(const void *payload, uint64_t payload_words, const uint64_t *seg_off, const uint64_t *seg_words,
                   uint64_t n_segments, const uint64_t *seg_idx, uint64_t n_idx, uint32_t *crc, const uint32_t *expect,
                   uint64_t *bad, void *stream)
 {
-    if (!payload || !seg_off || !seg_words) return fail(MH_ERR_ARG, "mhi_seg_crc32: NULL pointer");
-    if (!crc && !expect) return fail(MH_ERR_ARG, "mhi_seg_crc32: neither crc nor expect is given");
-    if (expect && !bad) return fail(MH_ERR_ARG, "mhi_seg_crc32: expect is given without bad");
-    if ((uintptr_t)payload % 4) return fail(MH_ERR_ARG, "mhi_seg_crc32: payload is not 4-byte aligned");
-    const uint64_t n_list = seg_idx ? n_idx : n_segments;
-    if (n_list == 0) return MH_OK;
-    const dim3 grid(mh::seg_crc_grid(n_list)), block(64u * mh::kCrcWaves);
+    const mh::CrcArgs a = {(uintptr_t)payload, payload_words, (uintptr_t)seg_off, (uintptr_t)seg_words, n_segments,
+                           (uintptr_t)seg_idx, n_idx, (uintptr_t)crc, (uintptr_t)expect, (uintptr_t)bad};
+    mh::Msg m;
+    mh::CrcLaunch l;  // the length of the list and the capped grid (mh_launch.hpp)
+    if (int rc = mh::seg_crc_check(m, a, &l)) return fail(rc, m);
+    if (l.n_list == 0) return MH_OK;
+    const dim3 grid(l.grid), block(64u * mh::kCrcWaves);
     hipLaunchKernelGGL(mh::k_seg_crc32, grid, block, 0, (hipStream_t)stream, static_cast<const uint32_t *>(payload),
-                       payload_words, seg_off, seg_words, n_segments, seg_idx, n_list, crc, expect,
+                       payload_words, seg_off, seg_words, n_segments, seg_idx, l.n_list, crc, expect,
                        reinterpret_cast<unsigned long long *>(bad));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_seg_crc32: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_seg_crc32");
 }
 
 int mhi_unbin_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes)
 {
-    static_assert(mh::kUnbinCsr == MHI_UNBIN_CSR && mh::kUnbinAer == MHI_UNBIN_AER, "the header publishes the forms");
-    if (!bytes) return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: NULL pointer");
+    mh::Msg m;
     mh::UnbinLayout L;
-    const int rc = mh::unbin_layout(form, rows, cols, &L);
-    if (rc == -1)
-        return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: form=%u, rows=%llu, cols=%llu (a known form, each at least 1; AER form: cols <= 2^32)",
-                    form, (unsigned long long)rows, (unsigned long long)cols);
-    if (rc)
-        return fail(MH_ERR_ARG, "mhi_unbin_scratch_bytes: rows=%llu, cols=%llu make more than 2^32 - 1 tiles",
-                    (unsigned long long)rows, (unsigned long long)cols);
+    if (int rc = mh::unbin_scratch_check(m, form, rows, cols, (uintptr_t)bytes, &L)) return fail(rc, m);
     *bytes = L.bytes;
     return MH_OK;
 }
@@ -270,60 +210,35 @@ int mhi_unbin_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_
 int mhi_unbin_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
                     uint64_t *ev_off, uint64_t *total, void *scratch, uint64_t scratch_bytes, void *stream)
 {
-    mh::UnbinLayout L;
-    const int rc = unbin_args("mhi_unbin_count", form, in, row_off, rows, cols, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (!total) return fail(MH_ERR_ARG, "mhi_unbin_count: NULL pointer");
-    if (form == mh::kUnbinCsr && !ev_off) return fail(MH_ERR_ARG, "mhi_unbin_count: the CSR form needs ev_off");
+    const mh::UnbinCountArgs a = {{form, (uintptr_t)in, (uintptr_t)row_off, rows, cols, (uintptr_t)scratch, scratch_bytes},
+                                  (uintptr_t)ev_off, (uintptr_t)total};
+    mh::Msg m;
+    mh::UnbinLayout L;  // the tiles, the scratch sections and the grids (mh_unbin_layout.hpp)
+    if (int rc = mh::unbin_count_check(m, a, &L)) return fail(rc, m);
     uint8_t *const s8 = static_cast<uint8_t *>(scratch);
     uint32_t *const sums = reinterpret_cast<uint32_t *>(s8 + L.off_sum);
-    uint64_t *const base = reinterpret_cast<uint64_t *>(s8 + L.off_base);
-    uint64_t *const partial = reinterpret_cast<uint64_t *>(s8 + L.off_partial);
     const uint32_t tiles = (uint32_t)L.tiles, tpr = (uint32_t)L.tiles_per_row;
-    const dim3 grid((unsigned)((L.tiles + mh::kUnbinWaves - 1) / mh::kUnbinWaves)), block(64u * mh::kUnbinWaves);
-    const dim3 groups((unsigned)L.groups), per_group(mh::kUnbinBaseThreads);
+    const dim3 grid(L.grid), block(64u * mh::kUnbinWaves);
     hipStream_t st = (hipStream_t)stream;
     if (form == mh::kUnbinCsr)
         hipLaunchKernelGGL(mh::k_unbin_count<mh::kUnbinCsr>, grid, block, 0, st, in, row_off, cols, tpr, rows * cols, tiles, sums);
     else
         hipLaunchKernelGGL(mh::k_unbin_count<mh::kUnbinAer>, grid, block, 0, st, in, row_off, cols, tpr, rows * cols, tiles, sums);
-    hipLaunchKernelGGL(mh::k_unbin_group_sum, groups, per_group, 0, st, sums, tiles, partial);
-    uint64_t *const offs = form == mh::kUnbinCsr ? ev_off : nullptr;
-    hipLaunchKernelGGL(mh::k_unbin_scan, dim3(1), dim3(mh::kUnbinScanThreads), 0, st, partial, L.groups, total, offs, rows);
-    hipLaunchKernelGGL(mh::k_unbin_bases, groups, per_group, 0, st, sums, tiles, partial, base, tpr, offs);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_unbin_count: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    scan_launch(s8, L.off_sum, L.off_base, L.off_partial, tiles, tpr, L.groups, L.grid_scan, total,
+                form == mh::kUnbinCsr ? ev_off : nullptr, rows, st);
+    return launched("mhi_unbin_count");
 }
 
 int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, uint64_t rows, uint64_t cols,
                    uint64_t origin, uint64_t period, uint64_t phase, uint64_t *out_ticks, void *out_ch, uint32_t ch_bits,
                    uint64_t capacity, uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream)
 {
+    const mh::UnbinEmitArgs a = {{form, (uintptr_t)in, (uintptr_t)row_off, rows, cols, (uintptr_t)scratch, scratch_bytes},
+                                 origin, period, phase, (uintptr_t)out_ticks, (uintptr_t)out_ch, ch_bits, capacity,
+                                 (uintptr_t)over};
+    mh::Msg m;
     mh::UnbinLayout L;
-    const int rc = unbin_args("mhi_unbin_emit", form, in, row_off, rows, cols, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (!out_ticks || !over) return fail(MH_ERR_ARG, "mhi_unbin_emit: NULL pointer");
-    if (period == 0 || phase >= period)
-        return fail(MH_ERR_ARG, "mhi_unbin_emit: period=%llu, phase=%llu (period at least 1, phase below it)",
-                    (unsigned long long)period, (unsigned long long)phase);
-    const uint64_t steps = form == mh::kUnbinCsr ? cols : rows;
-    const unsigned __int128 last = (unsigned __int128)origin + (unsigned __int128)(steps - 1) * period + phase;
-    if (last >= ((unsigned __int128)1 << 63))
-        return fail(MH_ERR_ARG, "mhi_unbin_emit: the largest tick reaches 2^63 (origin=%llu, period=%llu, phase=%llu, %llu steps)",
-                    (unsigned long long)origin, (unsigned long long)period, (unsigned long long)phase,
-                    (unsigned long long)steps);
-    if (form == mh::kUnbinAer) {
-        if (!out_ch) return fail(MH_ERR_ARG, "mhi_unbin_emit: the AER form needs out_ch");
-        if (ch_bits != 16 && ch_bits != 32) return fail(MH_ERR_ARG, "mhi_unbin_emit: ch_bits=%u (16 or 32)", ch_bits);
-        if (ch_bits == 16 && cols > 65536)
-            return fail(MH_ERR_ARG, "mhi_unbin_emit: cols=%llu does not fit 16-bit channels", (unsigned long long)cols);
-    }
-    {   // out_ticks[0 .. capacity) against the input: the whole block in the AER form, where its extent is known here
-        const unsigned __int128 a = (uintptr_t)in, b = (uintptr_t)out_ticks;
-        const unsigned __int128 na = form == mh::kUnbinAer ? (unsigned __int128)rows * cols : 1, nb = (unsigned __int128)capacity * 8;
-        if (nb && a < b + nb && b < a + na) return fail(MH_ERR_ARG, "mhi_unbin_emit: out_ticks overlaps the input");
-    }
+    if (int rc = mh::unbin_emit_check(m, a, &L)) return fail(rc, m);
     const uint8_t *const s8 = static_cast<const uint8_t *>(scratch);
     const uint64_t *const base = reinterpret_cast<const uint64_t *>(s8 + L.off_base);
     const uint64_t first_tick = origin + phase;
@@ -337,23 +252,14 @@ int mhi_unbin_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, ui
     else
         unbin_emit_launch<mh::kUnbinAer, uint32_t>(in, row_off, rows, cols, L, first_tick, period, base, out_ticks, out_ch, capacity,
                                                    over, st);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_unbin_emit: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_unbin_emit");
 }
 
 int mhi_excess_scratch_bytes(uint32_t form, uint64_t rows, uint64_t cols, uint64_t *bytes)
 {
-    static_assert(mh::kExcessRows == MHI_EXCESS_ROWS && mh::kExcessCols == MHI_EXCESS_COLS, "the header publishes the forms");
-    if (!bytes) return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: NULL pointer");
+    mh::Msg m;
     mh::ExcessLayout L;
-    const int rc = mh::excess_layout(form, rows, cols, &L);
-    if (rc == -1)
-        return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: form=%u, rows=%llu, cols=%llu (a known form, each at least 1, cols below 2^32; COLS form: rows below 2^32)",
-                    form, (unsigned long long)rows, (unsigned long long)cols);
-    if (rc)
-        return fail(MH_ERR_ARG, "mhi_excess_scratch_bytes: rows=%llu, cols=%llu make more than 2^32 - 1 pieces",
-                    (unsigned long long)rows, (unsigned long long)cols);
+    if (int rc = mh::excess_scratch_check(m, form, rows, cols, (uintptr_t)bytes, &L)) return fail(rc, m);
     *bytes = L.bytes;
     return MH_OK;
 }
@@ -362,83 +268,60 @@ int mhi_excess_count(uint32_t form, const uint8_t *in, const uint64_t *row_off, 
                      uint64_t rows, uint64_t cols, uint32_t threshold, uint64_t *exc_off, uint64_t *total, void *scratch,
                      uint64_t scratch_bytes, void *stream)
 {
-    mh::ExcessLayout L;
-    const int rc = excess_args("mhi_excess_count", form, in, row_off, lo, hi, rows, cols, threshold, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (!exc_off || !total) return fail(MH_ERR_ARG, "mhi_excess_count: NULL pointer");
+    const mh::ExcessCountArgs a = {{form, (uintptr_t)in, (uintptr_t)row_off, (uintptr_t)lo, (uintptr_t)hi, rows, cols, threshold,
+                                    (uintptr_t)scratch, scratch_bytes},
+                                   (uintptr_t)exc_off, (uintptr_t)total};
+    mh::Msg m;
+    mh::ExcessLayout L;  // the pieces, the scratch sections and the grids (mh_excess_layout.hpp)
+    if (int rc = mh::excess_count_check(m, a, &L)) return fail(rc, m);
     uint8_t *const s8 = static_cast<uint8_t *>(scratch);
     uint32_t *const sums = reinterpret_cast<uint32_t *>(s8 + L.off_sum);
-    uint64_t *const base = reinterpret_cast<uint64_t *>(s8 + L.off_base);
-    uint64_t *const partial = reinterpret_cast<uint64_t *>(s8 + L.off_partial);
     const uint32_t pieces = (uint32_t)L.pieces, per = (uint32_t)L.per_channel, k = (255u - threshold) * 0x01010101u;
-    const dim3 block(64u * mh::kExcessWaves), groups((unsigned)L.groups), per_group(mh::kUnbinBaseThreads);
+    const dim3 grid(L.grid), block(64u * mh::kExcessWaves);
     hipStream_t st = (hipStream_t)stream;
-    if (form == mh::kExcessRows) {
-        const dim3 grid((unsigned)((L.pieces + mh::kExcessWaves - 1) / mh::kExcessWaves));
+    if (form == mh::kExcessRows)
         hipLaunchKernelGGL(mh::k_excess_rows_count, grid, block, 0, st, in, row_off, lo, hi, cols, per, pieces, k, sums);
-    } else {
-        const uint64_t waves = L.strips * L.per_channel;
-        const dim3 grid((unsigned)((waves + mh::kExcessWaves - 1) / mh::kExcessWaves));
-        hipLaunchKernelGGL(mh::k_excess_cols_count, grid, block, 0, st, in, rows, cols, per, waves, k, sums);
-    }
-    hipLaunchKernelGGL(mh::k_unbin_group_sum, groups, per_group, 0, st, sums, pieces, partial);
-    hipLaunchKernelGGL(mh::k_unbin_scan, dim3(1), dim3(mh::kUnbinScanThreads), 0, st, partial, L.groups, total, exc_off, L.channels);
-    hipLaunchKernelGGL(mh::k_unbin_bases, groups, per_group, 0, st, sums, pieces, partial, base, per, exc_off);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_count: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    else
+        hipLaunchKernelGGL(mh::k_excess_cols_count, grid, block, 0, st, in, rows, cols, per, L.waves, k, sums);
+    scan_launch(s8, L.off_sum, L.off_base, L.off_partial, pieces, per, L.groups, L.grid_scan, total, exc_off, L.channels, st);
+    return launched("mhi_excess_count");
 }
 
 int mhi_excess_emit(uint32_t form, const uint8_t *in, const uint64_t *row_off, const uint64_t *lo, const uint64_t *hi,
                     uint64_t rows, uint64_t cols, uint32_t threshold, uint32_t *pos, uint8_t *val, uint64_t capacity,
                     uint64_t *over, void *scratch, uint64_t scratch_bytes, void *stream)
 {
+    const mh::ExcessEmitArgs a = {{form, (uintptr_t)in, (uintptr_t)row_off, (uintptr_t)lo, (uintptr_t)hi, rows, cols, threshold,
+                                   (uintptr_t)scratch, scratch_bytes},
+                                  (uintptr_t)pos, (uintptr_t)val, capacity, (uintptr_t)over};
+    mh::Msg m;
     mh::ExcessLayout L;
-    const int rc = excess_args("mhi_excess_emit", form, in, row_off, lo, hi, rows, cols, threshold, scratch, scratch_bytes, &L);
-    if (rc) return rc;
-    if (!pos || !val || !over) return fail(MH_ERR_ARG, "mhi_excess_emit: NULL pointer");
-    if ((uintptr_t)pos % 4) return fail(MH_ERR_ARG, "mhi_excess_emit: pos is not 4-byte aligned");
+    if (int rc = mh::excess_emit_check(m, a, &L)) return fail(rc, m);
     const uint8_t *const s8 = static_cast<const uint8_t *>(scratch);
     const uint64_t *const base = reinterpret_cast<const uint64_t *>(s8 + L.off_base);
     const uint32_t pieces = (uint32_t)L.pieces, per = (uint32_t)L.per_channel, k = (255u - threshold) * 0x01010101u;
-    const dim3 block(64u * mh::kExcessWaves);
+    const dim3 grid(L.grid), block(64u * mh::kExcessWaves);
     unsigned long long *const ov = reinterpret_cast<unsigned long long *>(over);
     hipStream_t st = (hipStream_t)stream;
-    if (form == mh::kExcessRows) {
-        const dim3 grid((unsigned)((L.pieces + mh::kExcessWaves - 1) / mh::kExcessWaves));
+    if (form == mh::kExcessRows)
         hipLaunchKernelGGL(mh::k_excess_rows_emit, grid, block, 0, st, in, row_off, lo, hi, cols, per, pieces, k, threshold, base,
                            pos, val, capacity, ov);
-    } else {
-        const uint64_t waves = L.strips * L.per_channel;
-        const dim3 grid((unsigned)((waves + mh::kExcessWaves - 1) / mh::kExcessWaves));
-        hipLaunchKernelGGL(mh::k_excess_cols_emit, grid, block, 0, st, in, rows, cols, per, waves, k, threshold, base, pos, val,
+    else
+        hipLaunchKernelGGL(mh::k_excess_cols_emit, grid, block, 0, st, in, rows, cols, per, L.waves, k, threshold, base, pos, val,
                            capacity, ov);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_emit: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_excess_emit");
 }
 
 int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries, const uint64_t *first, const uint64_t *last,
                      uint64_t n_rows, uint64_t start, uint64_t stop, uint64_t r, uint64_t lead, void *out, uint32_t out_bits,
                      uint64_t row_stride, uint64_t col_stride, void *stream)
 {
-    if (!first || !last || !out || (n_entries && (!pos || !val))) return fail(MH_ERR_ARG, "mhi_excess_apply: NULL pointer");
-    if (out_bits != 8 && out_bits != 32) return fail(MH_ERR_ARG, "mhi_excess_apply: out_bits=%u (8 or 32)", out_bits);
-    if (r == 0 || r > mh::kExcessMaxLen || lead >= mh::kExcessMaxLen)
-        return fail(MH_ERR_ARG, "mhi_excess_apply: r=%llu, lead=%llu (r 1 .. 2^32, lead below 2^32)", (unsigned long long)r,
-                    (unsigned long long)lead);
-    if (start > stop || stop > mh::kExcessMaxLen)
-        return fail(MH_ERR_ARG, "mhi_excess_apply: start=%llu, stop=%llu (start <= stop <= 2^32)", (unsigned long long)start,
-                    (unsigned long long)stop);
-    if (out_bits == 32 && ((uintptr_t)out % 4 || row_stride % 4 || col_stride % 4))
-        return fail(MH_ERR_ARG, "mhi_excess_apply: out_bits=32 needs out and both strides to be multiples of 4");
-    if ((uintptr_t)pos % 4) return fail(MH_ERR_ARG, "mhi_excess_apply: pos is not 4-byte aligned");
-    if (n_rows == 0 || n_entries == 0 || start == stop) return MH_OK;  // nothing to add
-    const uint64_t elements = mh::apply_elements(start, stop, r, lead);
-    const uint64_t runs = (elements + mh::kApplyRun - 1) / mh::kApplyRun;
-    if ((unsigned __int128)n_rows * runs >= ((unsigned __int128)1 << 63))
-        return fail(MH_ERR_ARG, "mhi_excess_apply: n_rows=%llu is too large", (unsigned long long)n_rows);
+    const mh::ApplyArgs a = {(uintptr_t)pos, (uintptr_t)val, n_entries, (uintptr_t)first, (uintptr_t)last, n_rows, start, stop, r,
+                             lead, (uintptr_t)out, out_bits, row_stride, col_stride};
+    mh::Msg m;
+    mh::ApplyLayout L;  // a row's elements and its runs of kApplyRun (mh_excess_layout.hpp)
+    if (int rc = mh::excess_apply_check(m, a, &L)) return fail(rc, m);
+    if (L.runs == 0) return MH_OK;  // nothing to add
     uint8_t *const o8 = static_cast<uint8_t *>(out);
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(mh::kApplyThreads);
@@ -452,17 +335,15 @@ int mhi_excess_apply(const uint32_t *pos, const uint8_t *val, uint64_t n_entries
             hipLaunchKernelGGL(mh::k_excess_apply1<uint32_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
                                stop, lead, o8, row_stride, col_stride);
     } else {
-        const dim3 grid(mh::excess_apply_grid(n_rows, runs));  // capped (mh_launch.hpp)
+        const dim3 grid(mh::excess_apply_grid(n_rows, L.runs));  // capped (mh_launch.hpp)
         if (out_bits == 8)
             hipLaunchKernelGGL(mh::k_excess_apply<uint8_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
-                               stop, r, lead, elements, runs, o8, row_stride, col_stride);
+                               stop, r, lead, L.elements, L.runs, o8, row_stride, col_stride);
         else
             hipLaunchKernelGGL(mh::k_excess_apply<uint32_t>, grid, block, 0, st, pos, val, n_entries, first, last, n_rows, start,
-                               stop, r, lead, elements, runs, o8, row_stride, col_stride);
+                               stop, r, lead, L.elements, L.runs, o8, row_stride, col_stride);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_excess_apply: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_excess_apply");
 }
 
 int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t cols, const uint64_t *win_off,
@@ -470,12 +351,11 @@ int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t 
                 uint32_t out_bits, uint64_t out_win_stride, uint64_t out_row_stride, uint64_t *sumsq, uint64_t sq_row_stride,
                 uint32_t accumulate, uint64_t *bad, void *stream)
 {
-    static_assert(mh::kWinStack == MHI_WIN_STACK && mh::kWinSum == MHI_WIN_SUM, "the header publishes the forms");
     const mh::WinArgs a = {(uintptr_t)in, row_stride, rows, cols, (uintptr_t)win_off, (uintptr_t)win_idx, n_win, n_out, W, r, mode,
                            (uintptr_t)out, out_bits, out_win_stride, out_row_stride, (uintptr_t)sumsq, sq_row_stride, accumulate,
                            (uintptr_t)bad};
     mh::Msg m;
-    if (int rc = mh::windows_check(m, a)) return fail(rc, "%s", m.text);
+    if (int rc = mh::windows_check(m, a)) return fail(rc, m);
     mh::WinLayout L;  // the form, the tiles and the capped grid (mh_windows_layout.hpp)
     mh::windows_layout(mode, rows, W, r, n_win, &L);
     if (L.items == 0) return MH_OK;  // STACK of no windows
@@ -504,9 +384,7 @@ int mhi_windows(const uint8_t *in, uint64_t row_stride, uint64_t rows, uint64_t 
         else MH_WIN_GO((mh::k_win_wave<true, true, false>));
     }
 #undef MH_WIN_GO
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_windows: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_windows");
 }
 
 int mhi_gram(const uint8_t *a, uint64_t a_row_stride, uint64_t a_rows, const uint8_t *b, uint64_t b_row_stride, uint64_t b_rows,
@@ -516,7 +394,7 @@ int mhi_gram(const uint8_t *a, uint64_t a_row_stride, uint64_t a_rows, const uin
     const mh::GramArgs g = {(uintptr_t)a, a_row_stride, a_rows, (uintptr_t)b, b_row_stride, b_rows, cols, (uintptr_t)gram,
                             gram_row_stride, (uintptr_t)sum_a, (uintptr_t)sum_b, accumulate};
     mh::Msg m;
-    if (int rc = mh::gram_check(m, g)) return fail(rc, "%s", m.text);
+    if (int rc = mh::gram_check(m, g)) return fail(rc, m);
     const bool symmetric = b == nullptr;
     if (symmetric) b = a, b_row_stride = a_row_stride, b_rows = a_rows;
     mh::GramLayout L;  // the tiles, the runs of K slices and the capped grid (mh_gram_layout.hpp)
@@ -535,9 +413,7 @@ int mhi_gram(const uint8_t *a, uint64_t a_row_stride, uint64_t a_rows, const uin
                               reinterpret_cast<unsigned long long *>(sum_b), L.symmetric, L.nta, L.ntb, L.run_slices, L.tiles,
                               L.items};
     hipLaunchKernelGGL(mh::k_gram, dim3(L.grid), dim3(mh::kGramThreads), 0, st, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "mhi_gram: launch failed: %s", hipGetErrorString(e));
-    return MH_OK;
+    return launched("mhi_gram");
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@ CSRC = os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "aer_layout_check.cpp")
 EXE = os.path.join(ROOT, "tests", "aer_layout_check_asan")
 FIELDS = ("run", "waves", "tile", "nbits", "lds_bytes", "rows", "groups", "rows_alloc", "groups_alloc", "off_matrix",
-          "off_partial", "off_drop", "bytes")
+          "off_partial", "off_drop", "bytes", "grid_tiles", "grid_cols_x", "grid_cols_y")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -28,7 +28,7 @@ def built():
 
 @pytest.fixture(scope="module")
 def exe():
-    deps = [SRC, os.path.join(CSRC, "mh_aer_layout.hpp")]
+    deps = [SRC, os.path.join(CSRC, "mh_aer_layout.hpp"), os.path.join(CSRC, "mh_msg.hpp")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                                "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, SRC, "-o", EXE])
@@ -123,6 +123,24 @@ def test_scratch_bytes_is_the_layout_programs_under_the_sanitizers(exe):
         assert rc == _lib.MH_OK and lay is not None and b == lay["bytes"] and b > 0, (n, C, b, lay)
     bad = layouts(exe, [(5, 0), (5, published_limit() + 1), (1 << 32, 4), (5, 1 << 33)])
     assert bad == [None] * 4
+
+
+def test_the_grids_are_the_rule_restated(exe):
+    """count / scatter: a workgroup per `waves` sub-runs; the two column kernels: 256 channels by one group of 64 rows.
+    Neither is capped -- n is below 2^32 and C at most 16384"""
+    pairs = _pairs()
+    for (n, C), lay in zip(pairs, layouts(exe, pairs)):
+        rows = -(-n // lay["run"])
+        assert lay["rows"] == rows and lay["waves"] == (4 if C <= 4096 else 2 if C <= 8192 else 1)
+        assert (lay["grid_tiles"], lay["grid_cols_x"], lay["grid_cols_y"]) == (-(-rows // lay["waves"]), -(-C // 256), -(-rows // 64)), (n, C, lay)
+
+
+def test_the_check_program_and_the_library_give_the_same_codes_and_messages(exe):
+    """every row of tests/test_host_ingest_messages.py for the two entry points through mh_aer_layout.hpp's checks under
+    the sanitizers"""
+    from tests import test_host_ingest_messages as pinned
+    refused, accepted = pinned.check_program_agrees(exe, "mhi_aer_scratch_bytes", "mhi_aer_to_csr")
+    assert refused >= len(BAD) + 7 and accepted >= 5
 
 
 @pytest.mark.parametrize("C", [1, 1000, 4097, 16384])

@@ -1,5 +1,6 @@
 """Payload checksums without a GPU: the CRC-32 arithmetic of k_seg_crc32 (csrc/mh_crc_tables.hpp built alone under
-AddressSanitizer + UBSan, tests/crc_check.cpp) against zlib, the argument errors of mhi_seg_crc32 on host stand-ins,
+AddressSanitizer + UBSan, tests/crc_check.cpp) against zlib, the argument errors of mhi_seg_crc32 on host stand-ins --
+with the text the same program prints from csrc/mh_ingest_check.hpp, for mhi_bin_events too, which shares that header --
 container revision 4 and archive revision 2 on oracle-made blocks with zlib's values (container_io.seg_crc_host), and
 the point of it all: one flipped payload bit that the structural walks accept and the checksum names."""
 import ctypes as ct
@@ -31,10 +32,11 @@ CH = muahuff.CHUNK
 # ---- the arithmetic ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def exe():
-    deps = [SRC, os.path.join(CSRC, "mh_crc_tables.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("mh_crc_tables.hpp", "mh_ingest_check.hpp", "mh_launch.hpp", "mh_msg.hpp")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, SRC, "-o", EXE])
+                               "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror", "-I" + CSRC,
+                               "-I" + os.path.join(ROOT, "include"), SRC, "-o", EXE])
     return EXE
 
 
@@ -95,6 +97,16 @@ def test_misaligned_payload_is_refused():
                            None) == _lib.ERR_ARG
     assert "aligned" in L.mhi_last_error().decode()
     assert L.mhi_version() == 103
+
+
+def test_the_check_program_and_the_library_give_the_same_codes_and_messages(exe):
+    """every row of tests/test_host_ingest_messages.py for mhi_seg_crc32 and mhi_bin_events through
+    csrc/mh_ingest_check.hpp under the sanitizers; the binner's out_off entries sit in a heap block of exactly C entries"""
+    from tests import test_host_ingest_messages as pinned
+    refused, accepted = pinned.check_program_agrees(exe, "mhi_seg_crc32")
+    assert refused >= 8 and accepted >= 2
+    refused, accepted = pinned.check_program_agrees(exe, "mhi_bin_events")
+    assert refused >= 21 + 5 and accepted == 0
 
 
 # ---- container revision 4 -----------------------------------------------------------------------------

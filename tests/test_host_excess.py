@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "excess_layout_check.cpp")
 FIELDS = ("tile", "tile_t", "strip", "channels", "length", "per_channel", "pieces", "groups", "strips", "off_sum", "off_base",
-          "off_partial", "bytes")
+          "off_partial", "bytes", "waves", "grid", "grid_scan")
 ROWS, COLS = 0, 1
 CH = muahuff.CHUNK
 NAMES = ("mhi_excess_scratch_bytes", "mhi_excess_count", "mhi_excess_emit", "mhi_excess_apply")
@@ -131,6 +131,36 @@ def test_scratch_bytes_is_the_layout_program_under_the_sanitizers(exe):
     assert bad == ["error -1"] * 6
     assert _run(exe, "apply 0 100 7 3\napply 5 5 1 0\napply 0 4294967296 4294967296 4294967295\napply 10 4106 4096 0\n") == \
         ["15", "0", "2", "1"]
+
+
+def test_the_grids_are_the_rule_restated(exe):
+    """count / emit: workgroups of 4 waves -- a wave per piece in the ROWS form, a wave per (strip of 256 channels, time
+    tile) in the COLS form; the scan's two group kernels: a workgroup per 1024 pieces.  None is capped -- the layout
+    refuses more than 2^32 - 1 pieces"""
+    grid = [(ROWS, rows, cols) for cols in (1, 16384, 16385, 10 ** 7, (1 << 32) - 1) for rows in (1, 3, 4, 5, 1023, 1025)]
+    grid += [(COLS, T, C) for T in (1, 512, 513, 4097, 10 ** 6, (1 << 32) - 1) for C in (1, 255, 256, 257, 1023, 1025)]
+    grid += [(ROWS, (1 << 32) - 1, 16384), (COLS, (1 << 32) - 1, 511)]
+    lines = _run(exe, "".join("%d %d %d\n" % t for t in grid))
+    assert sum(ln.startswith("error") for ln in lines) == 2        # 2^32 - 1 time steps of 1023 and of 1025 channels
+    for (form, rows, cols), ln in zip(grid, lines):
+        if ln.startswith("error"):
+            continue
+        lay = dict(zip(FIELDS, (int(v) for v in ln.split())))
+        pieces = rows * -(-cols // 16384) if form == ROWS else cols * -(-rows // 512)
+        waves = 0 if form == ROWS else -(-cols // 256) * -(-rows // 512)
+        assert lay["waves"] == waves and lay["grid_scan"] == -(-pieces // 1024), (form, rows, cols, lay)
+        assert lay["grid"] == -(-(pieces if form == ROWS else waves) // 4), (form, rows, cols, lay)
+
+
+def test_the_check_program_and_the_library_give_the_same_codes_and_messages(exe):
+    """every row of tests/test_host_ingest_messages.py for the four entry points -- 2^32, 2^63 and 2^64 - 1 among the
+    values -- through mh_excess_layout.hpp's checks under the sanitizers"""
+    from tests import test_host_ingest_messages as pinned
+    refused, accepted = pinned.check_program_agrees(exe, *NAMES)
+    assert refused >= 2 * len(SHARED_BAD) + len(APPLY_BAD) + 11 and accepted >= 10
+    # what the apply check hands the launch: the elements of a row and its runs of 32
+    assert _run(exe, "check apply 4 1 8 1 1 2 0 50 5 0 1 8 16 4\ncheck apply 4 1 8 1 1 2 10 4106 1 0 1 8 16 4\n"
+                     "check apply 4 1 0 1 1 2 0 50 5 0 1 8 16 4\n") == ["ok 10 1", "ok 4096 128", "ok 0 0"]
 
 
 # ---- argument errors -----------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Counts back to events (mhi_unbin_scratch_bytes, mhi_unbin_count, mhi_unbin_emit; include/muahuff_ingest.h), the part
 that needs no GPU: every argument error comes back before a pointer is used, and the scratch size is host arithmetic and
 equals what tests/unbin_layout_check.cpp -- csrc/mh_unbin_layout.hpp built alone under AddressSanitizer + UBSan --
-prints, over a grid of shapes around every step of the layout."""
+prints, over a grid of shapes around every step of the layout; the launch grids follow their rule, and the argument rules
+give the same codes and texts in that program as in the library."""
 import ctypes as ct
 import importlib
 import os
@@ -15,7 +16,7 @@ from muahuff import _ingest, _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hardware-efficient-mua-compression_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "unbin_layout_check.cpp")
-FIELDS = ("tile", "group", "tiles_per_row", "tiles", "groups", "off_sum", "off_base", "off_partial", "bytes")
+FIELDS = ("tile", "group", "tiles_per_row", "tiles", "groups", "off_sum", "off_base", "off_partial", "bytes", "grid", "grid_scan")
 CSR, AER = 0, 1
 
 
@@ -194,6 +195,25 @@ def test_scratch_bytes_is_the_layout_programs_under_the_sanitizers(exe):
     assert seen_tiles == {1, 2, 3, 4, 5} and seen_groups == {1, 2, 3, 4}
     bad = layouts(exe, [(2, 5, 5), (CSR, 0, 5), (AER, 5, 0), (CSR, 1 << 32, 5), (AER, 5, (1 << 32) + 1), (1 << 33, 5, 5)])
     assert bad == [None] * 6
+
+
+def test_the_grids_are_the_rule_restated(exe):
+    """count / emit: a workgroup of 4 waves, a wave per tile; the scan's two group kernels: a workgroup per 1024 tiles.
+    Neither is capped -- the layout refuses more than 2^32 - 1 tiles"""
+    grid = _grid()
+    for (form, rows, cols), lay in zip(grid, layouts(exe, grid)):
+        tiles = rows * -(-cols // 16384) if form == CSR else -(-rows * cols // 16384)
+        assert (lay["grid"], lay["grid_scan"]) == (-(-tiles // 4), -(-tiles // 1024)), (form, rows, cols, lay)
+    top = layouts(exe, [(CSR, (1 << 32) - 1, 1)])[0]
+    assert top["grid"] == 1 << 30 and top["grid_scan"] == 1 << 22
+
+
+def test_the_check_program_and_the_library_give_the_same_codes_and_messages(exe):
+    """every row of tests/test_host_ingest_messages.py for the three entry points -- 2^32, 2^63 and 2^64 - 1 among the
+    values -- through mh_unbin_layout.hpp's checks under the sanitizers"""
+    from tests import test_host_ingest_messages as pinned
+    refused, accepted = pinned.check_program_agrees(exe, "mhi_unbin_scratch_bytes", "mhi_unbin_count", "mhi_unbin_emit")
+    assert refused >= len(COUNT_BAD) + len(EMIT_BAD) + 11 and accepted >= 5
 
 
 def test_host_arrays_are_refused():
