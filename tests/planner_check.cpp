@@ -14,6 +14,9 @@
 // "wave_tasks measure_fused fused_calibration tickets_fit cal_tiles head_segments skipped short_channels".
 // With --tiles (tests/test_host_misaligned.py) the same input gives what cuts a plan's histogram work:
 // "kHistTileBytes kCalDirect window_tiles cal_tiles", then the window tiles' sample counts on one line.
+// With --tasks (tests/test_host_big_codec.py) a case in the first format gives "K ntask ntile ncaltile seg_src_stride slot_full",
+// one line "G src_off dst_off n_last ch seg0 nseg" per workgroup task, "H ch start n" per window tile and "P ch start n" per
+// calibration tile.
 // With --worklist (tests/test_host_worklist.py) a case in the first format is followed by a query count and that many
 // queries  n_sel sel[0..n_sel) t0 t1 r out_pitch  (r = 0: mh_decode_range's list, else mh_decode_rebin's), built by
 // csrc/mh_worklist.hpp as the library builds them.  Output: "D nseg" and the directory's ch / first / n lines, then per
@@ -113,6 +116,24 @@ static int read_plan(bool with_bits, mh::PlanHost &p)
     p.input_bits = a.bits;
     mh::plan_host_build(p, a.off.data(), a.len.data(), a.sclv.data());
     return 1;
+}
+
+// --tasks: what the kernels index a long channel by -- the workgroup tasks and the histogram tiles of a plan
+static int tasks()
+{
+    mh::PlanHost p;
+    int got;
+    while ((got = read_plan(false, p)) > 0) {
+        if (got == 2) continue;
+        printf("K %zu %zu %zu %llu %llu\n", p.wg_tasks.size(), p.tile_start.size(), p.cal_tile_start.size(),
+               (unsigned long long)p.seg_src_stride, (unsigned long long)p.slot_full);
+        for (const mh::WgTask &w : p.wg_tasks)
+            printf("G %llu %llu %u %u %u %u\n", (unsigned long long)w.src_off, (unsigned long long)w.dst_off, w.n_last, w.ch, w.seg0, w.nseg);
+        for (size_t i = 0; i < p.tile_start.size(); ++i) printf("H %u %llu %u\n", p.tile_ch[i], (unsigned long long)p.tile_start[i], p.tile_n[i]);
+        for (size_t i = 0; i < p.cal_tile_start.size(); ++i)
+            printf("P %u %llu %u\n", p.cal_tile_ch[i], (unsigned long long)p.cal_tile_start[i], p.cal_tile_n[i]);
+    }
+    return got < 0;
 }
 
 static int cells(bool forms, bool tiles = false)
@@ -497,6 +518,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "--forms")) return cells(true);
     if (argc > 1 && !strcmp(argv[1], "--tiles")) return cells(false, true);
     if (argc > 1 && !strcmp(argv[1], "--worklist")) return worklist();
+    if (argc > 1 && !strcmp(argv[1], "--tasks")) return tasks();
     mh::PlanHost p;
     int got;
     while ((got = read_plan(false, p)) > 0) {
