@@ -23,6 +23,11 @@ INGEST_HEADERS = ["csrc/exports_ingest.map", "csrc/mh_ingest.hpp", "csrc/mh_aer.
                   "csrc/mh_gram.hpp", "csrc/mh_gram_layout.hpp", "csrc/mh_ingest_check.hpp",
                   "csrc/mh_device.hpp", "csrc/mh_msg.hpp", "csrc/mh_launch.hpp", "../include/muahuff.h",
                   "../include/muahuff_ingest.h"]
+# the second companion (include/muahuff_wiener.h): a lagged linear decoder on the counts, its cross products and its prediction
+WIENER_SO = os.path.join(HERE, "libmuahuff_wiener.so")
+WIENER_SOURCES = ["csrc/mh_wiener.hip"]
+WIENER_HEADERS = ["csrc/exports_wiener.map", "csrc/mh_wiener.hpp", "csrc/mh_wiener_layout.hpp", "csrc/mh_msg.hpp",
+                  "../include/muahuff.h", "../include/muahuff_wiener.h"]
 
 
 def stale():
@@ -65,6 +70,24 @@ def build_ingest(force=False, verbose=False):
     return INGEST_SO
 
 
+def build_wiener(force=False, verbose=False):
+    """libmuahuff_wiener.so, exporting the C ABI of include/muahuff_wiener.h and nothing else
+    (csrc/exports_wiener.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(WIENER_SO):
+        t = os.path.getmtime(WIENER_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in WIENER_SOURCES + WIENER_HEADERS):
+            return WIENER_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_wiener.map")]
+    cmd += [os.path.join(HERE, s) for s in WIENER_SOURCES] + ["-o", WIENER_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return WIENER_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -82,3 +105,4 @@ def build_example(force=False):
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_ingest(force=True, verbose=True))
+    print(build_wiener(force=True, verbose=True))

@@ -1,0 +1,291 @@
+"""Behavioural decoding from spike counts: the Wiener filter -- a ridge regression of covariates (hand or cursor velocity)
+onto the last `lags` bins of every channel -- fitted from sufficient statistics and applied on the device, with no design
+matrix ever built.
+
+Counts x are uint8 [C, T], covariates y float32 [K, T].  With L lags, a lead of g >= 0 bins (neural data precede the
+kinematics) and a clip q (xq = min(x, q)), DESIGN ROW t, for t in [L-1, T-g), has the features f = l*C + c = xq[c][t-l]
+(l = 0..L-1) and the targets y[k][t+g].  A range of design rows is [t0, t1) with L-1 <= t0 <= t1 <= T-g.
+
+stats() gives, per range, what the normal equations need: the exact int64 Gram matrix of the features from mhi_gram
+(one call per lag difference plus two small edge terms), the float64 products with the covariates from mhw_xty, and the
+covariates' own sums.  Stats of disjoint ranges add, so cross-validation over contiguous folds (folds()) costs one pass
+over the recording plus one small solve per fold.  WienerFilter.fit() restates z-scoring, centring and the ridge solve
+from the statistics alone; predict() is mhw_fir on raw counts.  There is no CPU path: host matrices are refused."""
+import numpy as np
+import torch
+
+from .windows import MAX_BYTES, _matrix
+
+MAX_FEATURES = 16384  # lags * channels at most: the int64 Gram matrix is then 2 GiB
+
+
+class Stats:
+    """The sufficient statistics of n design rows.  sum_x int64 [L*C], gram int64 [L*C, L*C], xty float64 [L*C, K], sum_y
+    float64 [K], sum_yy float64 [K, K]; lags, lead, clip (1..255, 255 = none), channels."""
+
+    def __init__(self, n, sum_x, gram, xty, sum_y, sum_yy, lags, lead, clip, channels):
+        self.n, self.sum_x, self.gram, self.xty, self.sum_y, self.sum_yy = int(n), sum_x, gram, xty, sum_y, sum_yy
+        self.lags, self.lead, self.clip, self.channels = int(lags), int(lead), int(clip), int(channels)
+
+    def __add__(self, other):
+        """Two results over the same channels, covariates and settings and disjoint design rows -> the result over both"""
+        if not isinstance(other, Stats):
+            return NotImplemented
+        if ((self.lags, self.lead, self.clip, self.channels) != (other.lags, other.lead, other.clip, other.channels)
+                or self.xty.shape != other.xty.shape):
+            raise ValueError("the two results are not over the same features and targets")
+        return Stats(self.n + other.n, self.sum_x + other.sum_x, self.gram + other.gram, self.xty + other.xty,
+                     self.sum_y + other.sum_y, self.sum_yy + other.sum_yy, self.lags, self.lead, self.clip, self.channels)
+
+    def __radd__(self, other):  # sum() starts from 0
+        return self if other == 0 else NotImplemented
+
+    def to(self, device):
+        m = lambda t: t.to(device)  # noqa: E731
+        return Stats(self.n, m(self.sum_x), m(self.gram), m(self.xty), m(self.sum_y), m(self.sum_yy), self.lags, self.lead,
+                     self.clip, self.channels)
+
+
+def _clip(clip):
+    q = 255 if clip is None else int(clip)
+    if not 1 <= q <= 255:
+        raise ValueError("clip %d outside 1..255" % q)
+    return q
+
+
+def _covariates(y, x, cols):
+    if not (isinstance(y, torch.Tensor) and y.is_cuda):
+        raise ValueError("covariates are a device tensor: there is no CPU path")
+    if y.dim() == 1:
+        y = y.unsqueeze(0)
+    if y.dtype != torch.float32 or y.dim() != 2:
+        raise ValueError("covariates are a float32 tensor [K, bins]")
+    if y.device != x.device:
+        raise ValueError("counts and covariates are on the same device")
+    from ._wiener import MAX_K
+    K = int(y.shape[0])
+    if not 1 <= K <= MAX_K:
+        raise ValueError("%d covariates outside 1..%d" % (K, MAX_K))
+    if int(y.shape[1]) != cols:
+        raise ValueError("counts and covariates have the same number of bins (%d, %d)" % (cols, int(y.shape[1])))
+    if cols > 1 and y.stride(1) != 1:
+        raise ValueError("the bins of a covariate lie back to back (unit stride along the last axis)")
+    return y, K
+
+
+def _settings(lags, lead, rows, cols):
+    from ._wiener import MAX_LAGS, MAX_ROWS
+    L, g = int(lags), int(lead)
+    if not 1 <= L <= MAX_LAGS:
+        raise ValueError("lags %d outside 1..%d" % (L, MAX_LAGS))
+    if g < 0:
+        raise ValueError("lead %d is negative" % g)
+    if rows > MAX_ROWS:
+        raise ValueError("%d channels above %d" % (rows, MAX_ROWS))
+    if L * rows > MAX_FEATURES:
+        raise ValueError("lags * channels = %d above %d" % (L * rows, MAX_FEATURES))
+    if cols - g < L:
+        raise ValueError("%d bins leave no design row at lags %d, lead %d" % (cols, L, g))
+    return L, g
+
+
+def _ranges(ranges, L, g, cols):
+    if ranges is None:
+        return [(L - 1, cols - g)]
+    out = [(int(a), int(b)) for a, b in ranges]
+    for a, b in out:
+        if not L - 1 <= a <= b <= cols - g:
+            raise ValueError("range [%d, %d) is not inside the design rows [%d, %d)" % (a, b, L - 1, cols - g))
+    return out
+
+
+def _edge_products(xe, L, d):
+    """xe: int64 [C, L-1], the clipped columns [e-(L-1), e) before an edge e.  -> int64 [L-d, C, C]: entry l1 is
+    F_d(e-l1, e) = sum over u in [e-l1, e) of x[:, u] x[:, u-d]^T (entry 0 is zero); l1 + d <= L-1, so no column before
+    e-(L-1) is needed."""
+    n = xe.shape[1]
+    a = xe[:, n - (L - 1 - d):]                        # u = e-(L-1-d) .. e-1
+    b = xe[:, n - (L - 1 - d) - d:n - d]               # u - d
+    outer = a.t().unsqueeze(2) * b.t().unsqueeze(1)    # [L-1-d, C, C], in ascending u
+    cum = torch.flip(torch.cumsum(torch.flip(outer, [0]), 0), [0])  # entry i: the sum over u >= e-(L-1-d)+i
+    zero = torch.zeros((1,) + tuple(outer.shape[1:]), dtype=torch.int64, device=xe.device)
+    return torch.flip(torch.cat([cum, zero], 0), [0])  # entry l1: the sum over u in [e-l1, e)
+
+
+def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
+    from . import _wiener
+    from .gram import batches, enqueue
+    dev, n, F = x.device, t1 - t0, L * rows
+    G = torch.zeros((F, F), dtype=torch.int64, device=dev)
+    sx = torch.zeros((F,), dtype=torch.int64, device=dev)
+    xty = torch.zeros((F, K), dtype=torch.float64, device=dev)
+    yr = y[:, t0 + g:t1 + g].double()
+    sum_y, sum_yy = yr.sum(1), yr @ yr.t()
+    if n == 0:
+        return Stats(0, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+    # ---- the float part: one call, out [L, C, K] is xty's own layout
+    _wiener.xty(x.data_ptr() + t0 - (L - 1), x.stride(0) if rows > 1 else n + L - 1, rows, n, L, q,
+                y.data_ptr() + 4 * (t0 + g), 4 * y.stride(0) if K > 1 else 4 * n, K, xty, scratch_xty)
+    # ---- the integer part: F_d(t0, t1) for every lag difference d, with the row sums of the d = 0 call
+    base = torch.zeros((L, rows, rows), dtype=torch.int64, device=dev)
+    s0 = torch.zeros((rows,), dtype=torch.int64, device=dev)
+    if q == 255:
+        for d in range(L):
+            if d == 0:
+                enqueue(x, rows, n, None, 0, base[0], s0, None, False, t0)
+            else:
+                enqueue(x, rows, n, x, rows, base[d], None, None, False, t0, t0 - d)
+    else:  # mhi_gram has no clip: a clamped copy, in column batches, added up
+        plan = batches(n, rows, max_bytes)
+        scratch = torch.empty((rows, plan[0][1] + L - 1), dtype=torch.uint8, device=dev)
+        for b0, nb in plan:
+            view = scratch[:, :nb + L - 1]
+            view.copy_(torch.clamp(x[:, t0 + b0 - (L - 1):t0 + b0 + nb], max=q))
+            for d in range(L):
+                if d == 0:
+                    enqueue(view, rows, nb, None, 0, base[0], s0, None, True, L - 1)
+                else:
+                    enqueue(view, rows, nb, view, rows, base[d], None, None, True, L - 1, L - 1 - d)
+    # ---- the edges: at most L - 1 outer products on either side
+    lo = torch.clamp(x[:, t0 - (L - 1):t0], max=q).long()        # columns [t0-(L-1), t0): all that is read before t0
+    hi = torch.clamp(x[:, t1 - (L - 1):t1], max=q).long()
+    for d in range(L):
+        blocks = base[d].unsqueeze(0) + _edge_products(lo, L, d) - _edge_products(hi, L, d)   # [L-d, C, C]: l1 = 0..L-1-d
+        for l1 in range(L - d):
+            r, c = l1 * rows, (l1 + d) * rows
+            G[r:r + rows, c:c + rows] = blocks[l1]
+            if d:
+                G[c:c + rows, r:r + rows] = blocks[l1].t()
+    zero = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
+    before = torch.cat([zero, torch.cumsum(torch.flip(lo, [1]), 1)], 1)   # [:, l]: the sum over [t0-l, t0)
+    after = torch.cat([zero, torch.cumsum(torch.flip(hi, [1]), 1)], 1)
+    sx = (s0.unsqueeze(0) + before.t() - after.t()).reshape(F).contiguous()
+    return Stats(n, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+
+
+def stats(x, y, lags, lead=0, clip=None, ranges=None, max_bytes=MAX_BYTES):
+    """The sufficient statistics of a Wiener filter -> [Stats], one per range of design rows (default: the single range
+    of all of them).  x: counts, a 2-D uint8 device tensor with unit stride along its last axis or a ChannelSet of
+    equal-length channels; y: float32 device tensor [K, bins] (or [bins]) of as many bins; lags 1..32; lead >= 0 bins by
+    which the counts precede the covariates; clip: None or 1..255, counts enter as min(x, clip).  The integers are exact
+    (mhi_gram), xty is float64 and deterministic (mhw_xty).  With a clip the count products go through a clamped scratch
+    copy in column batches of at most max_bytes."""
+    x, rows, cols = _matrix(x, "wiener.stats")
+    y, K = _covariates(y, x, cols)
+    L, g = _settings(lags, lead, rows, cols)
+    q = _clip(clip)
+    rs = _ranges(ranges, L, g, cols)
+    from . import _wiener
+    longest = max(b - a for a, b in rs)
+    scratch = torch.empty((max(_wiener.xty_scratch_bytes(rows, max(longest, 1), L, K), 8),), dtype=torch.uint8, device=x.device)
+    return [_range_stats(x, rows, y, K, L, g, q, a, b, max_bytes, scratch) for a, b in rs]
+
+
+def fold_ranges(n, num_fold, first=0):
+    """The contiguous folds of n rows: floor(n / num_fold) rows each, what is left over at the end belongs to none.
+    -> [(t0, t1)], shifted by `first`"""
+    n, num_fold = int(n), int(num_fold)
+    if num_fold < 2 or n < num_fold:
+        raise ValueError("%d rows do not make %d folds (at least 2, at most one per row)" % (n, num_fold))
+    per = n // num_fold
+    return [(first + i * per, first + (i + 1) * per) for i in range(num_fold)]
+
+
+def folds(n_rows_or_x, num_fold, lags=1, lead=0):
+    """Contiguous cross-validation splits as ranges of design rows -> [(train, valid, test)] for i in range(num_fold):
+    valid is fold i, test the fold i + 1 (cyclically), train the list of the other folds' ranges.  n_rows_or_x: a number
+    of rows (the ranges then start at 0) or the counts (the ranges are over the design rows [lags-1, bins-lead))."""
+    if isinstance(n_rows_or_x, (int, np.integer)):
+        n, first = int(n_rows_or_x), 0
+    else:
+        _x, _rows, cols = _matrix(n_rows_or_x, "wiener.folds")
+        n, first = cols - int(lead) - (int(lags) - 1), int(lags) - 1
+    fr = fold_ranges(n, num_fold, first)
+    out = []
+    for i in range(num_fold):
+        v, t = i, (i + 1) % num_fold
+        out.append(([fr[k] for k in range(num_fold) if k not in (v, t)], fr[v], fr[t]))
+    return out
+
+
+class WienerFilter:
+    """Ridge regression onto the z-scored lagged counts, from Stats alone.  After fit(): weights float64 [K, L, C] and
+    bias float64 [K], which apply to raw clipped counts: estimate of y[k][t + lead] = bias[k] + sum over l, c of
+    weights[k][l][c] * min(x[c][t - l], clip)."""
+
+    def __init__(self, alpha=0.0):
+        if alpha < 0:
+            raise ValueError("alpha is not negative")
+        self.alpha = float(alpha)
+        self.weights = self.bias = None
+        self.lags = self.lead = self.clip = self.channels = None
+
+    def fit(self, stats):  # noqa: A002
+        s = stats[0] if isinstance(stats, (list, tuple)) and len(stats) == 1 else stats
+        if not isinstance(s, Stats) or s.n < 1:
+            raise ValueError("fit takes the Stats of at least one design row")
+        n = float(s.n)
+        G, sx = s.gram.double(), s.sum_x.double()
+        mean = sx / n
+        # the variance times n^2, an integer: exactly zero for a constant feature wherever int64 holds it
+        diag = torch.diagonal(s.gram)
+        if s.n * 255 * 255 * s.n < 2 ** 63:
+            keep = (s.n * diag - s.sum_x * s.sum_x) > 0
+        else:
+            num = n * diag.double() - sx * sx
+            keep = num > 2.0 ** -40 * n * diag.double()
+        idx = torch.nonzero(keep).flatten()
+        if idx.numel() == 0:
+            raise ValueError("every feature is constant: nothing to fit")
+        m = mean[idx]
+        std = torch.sqrt(torch.diagonal(G)[idx] / n - m * m)                       # ddof = 0
+        ybar = s.sum_y / n
+        ztz = (G[idx][:, idx] - n * m.unsqueeze(1) * m.unsqueeze(0)) / (std.unsqueeze(1) * std.unsqueeze(0))
+        zty = (s.xty[idx] - m.unsqueeze(1) * s.sum_y.unsqueeze(0)) / std.unsqueeze(1)
+        a = ztz + self.alpha * torch.eye(idx.numel(), dtype=torch.float64, device=G.device)
+        chol, info = torch.linalg.cholesky_ex(a)
+        # not positive definite, or only by rounding: a pivot at the level of the factorisation's own error
+        floor = 64 * 2.0 ** -52 * idx.numel() * float(torch.diagonal(a).max())
+        if int(info) != 0 or float((torch.diagonal(chol) ** 2).min()) <= floor:
+            raise ValueError("the normal equations are not positive definite (collinear features or too few rows): "
+                             "use alpha > 0")
+        wz = torch.cholesky_solve(zty, chol)                                      # [kept, K]
+        w = torch.zeros((s.gram.shape[0], s.xty.shape[1]), dtype=torch.float64, device=G.device)
+        w[idx] = wz / std.unsqueeze(1)
+        self.bias = ybar - (w * mean.unsqueeze(1)).sum(0)
+        self.weights = w.t().reshape(s.xty.shape[1], s.lags, s.channels).contiguous()
+        self.lags, self.lead, self.clip, self.channels = s.lags, s.lead, s.clip, s.channels
+        return self
+
+    def predict(self, x):
+        """-> float32 [K, T - L + 1]: column i is the estimate of y[:, i + L-1 + lead]"""
+        from . import _wiener
+        if self.weights is None:
+            raise ValueError("predict comes after fit")
+        x, rows, cols = _matrix(x, "WienerFilter.predict")
+        if rows != self.channels:
+            raise ValueError("the filter was fitted on %d channels, not %d" % (self.channels, rows))
+        if cols < self.lags:
+            raise ValueError("%d bins are fewer than the %d lags" % (cols, self.lags))
+        K, n = int(self.weights.shape[0]), cols - self.lags + 1
+        w = self.weights.to(device=x.device, dtype=torch.float32).contiguous()
+        b = self.bias.to(device=x.device, dtype=torch.float32).contiguous()
+        out = torch.empty((K, n), dtype=torch.float32, device=x.device)
+        _wiener.fir(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, n, self.lags, self.clip, w, b, K, out)
+        return out
+
+    def score(self, x, y):
+        """-> (rmse [K], cc [K]), float64: the root mean squared error and Pearson's r of the prediction against y over
+        the columns where the target exists"""
+        pred = self.predict(x)
+        if y.dim() == 1:
+            y = y.unsqueeze(0)
+        n = pred.shape[1] - self.lead
+        if n < 1 or y.shape[0] != pred.shape[0] or y.shape[1] != pred.shape[1] + self.lags - 1:
+            raise ValueError("counts and covariates do not match, or no target lies inside them")
+        p = pred[:, :n].double()
+        t = y[:, self.lags - 1 + self.lead:].to(p.device).double()
+        rmse = torch.sqrt(((p - t) ** 2).mean(1))
+        pc, tc = p - p.mean(1, keepdim=True), t - t.mean(1, keepdim=True)
+        cc = (pc * tc).sum(1) / torch.sqrt((pc * pc).sum(1) * (tc * tc).sum(1))
+        return rmse, cc
