@@ -28,6 +28,12 @@ WIENER_SO = os.path.join(HERE, "libmuahuff_wiener.so")
 WIENER_SOURCES = ["csrc/mh_wiener.hip"]
 WIENER_HEADERS = ["csrc/exports_wiener.map", "csrc/mh_wiener.hpp", "csrc/mh_wiener_layout.hpp", "csrc/mh_msg.hpp",
                   "../include/muahuff.h", "../include/muahuff_wiener.h"]
+# the third companion (include/muahuff_cascade.h): the power sums of a prediction against its target and the polynomial
+# stage of the Wiener cascade
+CASCADE_SO = os.path.join(HERE, "libmuahuff_cascade.so")
+CASCADE_SOURCES = ["csrc/mh_cascade.hip"]
+CASCADE_HEADERS = ["csrc/exports_cascade.map", "csrc/mh_cascade.hpp", "csrc/mh_cascade_layout.hpp", "csrc/mh_msg.hpp",
+                   "../include/muahuff.h", "../include/muahuff_cascade.h"]
 
 
 def stale():
@@ -88,6 +94,24 @@ def build_wiener(force=False, verbose=False):
     return WIENER_SO
 
 
+def build_cascade(force=False, verbose=False):
+    """libmuahuff_cascade.so, exporting the C ABI of include/muahuff_cascade.h and nothing else
+    (csrc/exports_cascade.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(CASCADE_SO):
+        t = os.path.getmtime(CASCADE_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in CASCADE_SOURCES + CASCADE_HEADERS):
+            return CASCADE_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_cascade.map")]
+    cmd += [os.path.join(HERE, s) for s in CASCADE_SOURCES] + ["-o", CASCADE_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return CASCADE_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -106,3 +130,4 @@ if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_ingest(force=True, verbose=True))
     print(build_wiener(force=True, verbose=True))
+    print(build_cascade(force=True, verbose=True))
