@@ -34,6 +34,12 @@ CASCADE_SO = os.path.join(HERE, "libmuahuff_cascade.so")
 CASCADE_SOURCES = ["csrc/mh_cascade.hip"]
 CASCADE_HEADERS = ["csrc/exports_cascade.map", "csrc/mh_cascade.hpp", "csrc/mh_cascade_layout.hpp", "csrc/mh_msg.hpp",
                    "../include/muahuff.h", "../include/muahuff_cascade.h"]
+# the fourth companion (include/muahuff_smooth.h): the box sums of the decoders' moving-average window, as byte planes of
+# the counts and on a float prediction
+SMOOTH_SO = os.path.join(HERE, "libmuahuff_smooth.so")
+SMOOTH_SOURCES = ["csrc/mh_smooth.hip"]
+SMOOTH_HEADERS = ["csrc/exports_smooth.map", "csrc/mh_smooth.hpp", "csrc/mh_smooth_layout.hpp", "csrc/mh_msg.hpp",
+                  "../include/muahuff.h", "../include/muahuff_smooth.h"]
 
 
 def stale():
@@ -112,6 +118,24 @@ def build_cascade(force=False, verbose=False):
     return CASCADE_SO
 
 
+def build_smooth(force=False, verbose=False):
+    """libmuahuff_smooth.so, exporting the C ABI of include/muahuff_smooth.h and nothing else
+    (csrc/exports_smooth.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(SMOOTH_SO):
+        t = os.path.getmtime(SMOOTH_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in SMOOTH_SOURCES + SMOOTH_HEADERS):
+            return SMOOTH_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_smooth.map")]
+    cmd += [os.path.join(HERE, s) for s in SMOOTH_SOURCES] + ["-o", SMOOTH_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return SMOOTH_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -131,3 +155,4 @@ if __name__ == "__main__":
     print(build_ingest(force=True, verbose=True))
     print(build_wiener(force=True, verbose=True))
     print(build_cascade(force=True, verbose=True))
+    print(build_smooth(force=True, verbose=True))

@@ -233,12 +233,19 @@ class WienerCascade:
         return m.rmse(), m.cc()
 
 
-def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), num_fold=5):
+def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), num_fold=5, window=1):
     """The study's cross-validation -> {(alpha, degree): dict(rmse_valid, rmse_test, cc_valid, cc_test)}, each float64
     [num_fold, K] on the device: split i validates on fold i, tests on fold i + 1 (cyclically) and trains on the others
     (wiener.folds).  degree None is the linear decoder alone.  One wiener.stats pass; per (fold, alpha) one solve, one
     mhw_fir over the recording and one mhc_moments at the largest degree over the training ranges; per degree one
-    mhc_polyval and one mhc_moments over the two held-out folds."""
+    mhc_polyval and one mhc_moments over the two held-out folds.
+
+    window > 1 is the study's moving-average window (wiener.stats(window=)); every prediction then passes through
+    mhs_box_f32.  With a window a channel that is constant over the recording is a constant FEATURE only behind the
+    warm-up of window - 1 rows, where its partial sums still grow.  A fold that holds the warm-up therefore keeps that
+    channel's features, and since its lags are exactly collinear there (each is the other, shifted, and all are the same
+    ramp), alpha = 0 raises the "not positive definite" error of WienerFilter.fit: use alpha > 0, or ranges that leave
+    the warm-up out."""
     x, rows, cols = _matrix(x, "cascade.cross_validate")
     y, K = wiener._covariates(y, x, cols)
     L, g = wiener._settings(lags, lead, rows, cols)
@@ -249,7 +256,7 @@ def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), n
         raise ValueError("%d folds leave none to train on (at least 3)" % int(num_fold))
     F = int(num_fold)
     fr = wiener.fold_ranges(cols - g - (L - 1), F, L - 1)
-    st = wiener.stats(x, y, L, g, clip, ranges=fr)
+    st = wiener.stats(x, y, L, g, clip, ranges=fr, window=window)
     top = max([d for d in degrees if d is not None], default=None)
     names = ("rmse_valid", "rmse_test", "cc_valid", "cc_test")
     res = {(a, d): {k: [] for k in names} for a in alphas for d in degrees}

@@ -10,7 +10,9 @@ stats() gives, per range, what the normal equations need: the exact int64 Gram m
 (one call per lag difference plus two small edge terms), the float64 products with the covariates from mhw_xty, and the
 covariates' own sums.  Stats of disjoint ranges add, so cross-validation over contiguous folds (folds()) costs one pass
 over the recording plus one small solve per fold.  WienerFilter.fit() restates z-scoring, centring and the ridge solve
-from the statistics alone; predict() is mhw_fir on raw counts.  There is no CPU path: host matrices are refused."""
+from the statistics alone; predict() is mhw_fir on raw counts.  stats(window=) adds the study's moving-average window:
+the features become box sums of the clipped counts (mhs_box, smooth.py), predict() the box sum of mhw_fir's output
+(mhs_box_f32).  There is no CPU path: host matrices are refused."""
 import numpy as np
 import torch
 
@@ -21,21 +23,23 @@ MAX_FEATURES = 16384  # lags * channels at most: the int64 Gram matrix is then 2
 
 class Stats:
     """The sufficient statistics of n design rows.  sum_x int64 [L*C], gram int64 [L*C, L*C], xty float64 [L*C, K], sum_y
-    float64 [K], sum_yy float64 [K, K]; lags, lead, clip (1..255, 255 = none), channels."""
+    float64 [K], sum_yy float64 [K, K]; lags, lead, clip (1..255, 255 = none), channels; window (1 = none): the features
+    are the integer sums of `window` clipped bins, at most window * clip."""
 
-    def __init__(self, n, sum_x, gram, xty, sum_y, sum_yy, lags, lead, clip, channels):
+    def __init__(self, n, sum_x, gram, xty, sum_y, sum_yy, lags, lead, clip, channels, window=1):
         self.n, self.sum_x, self.gram, self.xty, self.sum_y, self.sum_yy = int(n), sum_x, gram, xty, sum_y, sum_yy
-        self.lags, self.lead, self.clip, self.channels = int(lags), int(lead), int(clip), int(channels)
+        self.lags, self.lead, self.clip, self.channels, self.window = int(lags), int(lead), int(clip), int(channels), int(window)
 
     def __add__(self, other):
         """Two results over the same channels, covariates and settings and disjoint design rows -> the result over both"""
         if not isinstance(other, Stats):
             return NotImplemented
-        if ((self.lags, self.lead, self.clip, self.channels) != (other.lags, other.lead, other.clip, other.channels)
-                or self.xty.shape != other.xty.shape):
+        if ((self.lags, self.lead, self.clip, self.channels, self.window)
+                != (other.lags, other.lead, other.clip, other.channels, other.window) or self.xty.shape != other.xty.shape):
             raise ValueError("the two results are not over the same features and targets")
         return Stats(self.n + other.n, self.sum_x + other.sum_x, self.gram + other.gram, self.xty + other.xty,
-                     self.sum_y + other.sum_y, self.sum_yy + other.sum_yy, self.lags, self.lead, self.clip, self.channels)
+                     self.sum_y + other.sum_y, self.sum_yy + other.sum_yy, self.lags, self.lead, self.clip, self.channels,
+                     self.window)
 
     def __radd__(self, other):  # sum() starts from 0
         return self if other == 0 else NotImplemented
@@ -43,7 +47,7 @@ class Stats:
     def to(self, device):
         m = lambda t: t.to(device)  # noqa: E731
         return Stats(self.n, m(self.sum_x), m(self.gram), m(self.xty), m(self.sum_y), m(self.sum_yy), self.lags, self.lead,
-                     self.clip, self.channels)
+                     self.clip, self.channels, self.window)
 
 
 def _clip(clip):
@@ -116,12 +120,12 @@ def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
     from . import _wiener
     from .gram import batches, enqueue
     dev, n, F = x.device, t1 - t0, L * rows
-    G = torch.zeros((F, F), dtype=torch.int64, device=dev)
-    sx = torch.zeros((F,), dtype=torch.int64, device=dev)
     xty = torch.zeros((F, K), dtype=torch.float64, device=dev)
     yr = y[:, t0 + g:t1 + g].double()
     sum_y, sum_yy = yr.sum(1), yr @ yr.t()
     if n == 0:
+        G = torch.zeros((F, F), dtype=torch.int64, device=dev)
+        sx = torch.zeros((F,), dtype=torch.int64, device=dev)
         return Stats(0, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
     # ---- the float part: one call, out [L, C, K] is xty's own layout
     _wiener.xty(x.data_ptr() + t0 - (L - 1), x.stride(0) if rows > 1 else n + L - 1, rows, n, L, q,
@@ -149,6 +153,15 @@ def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
     # ---- the edges: at most L - 1 outer products on either side
     lo = torch.clamp(x[:, t0 - (L - 1):t0], max=q).long()        # columns [t0-(L-1), t0): all that is read before t0
     hi = torch.clamp(x[:, t1 - (L - 1):t1], max=q).long()
+    G, sx = _assemble(base, s0, lo, hi, L, rows)
+    return Stats(n, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+
+
+def _assemble(base, s0, lo, hi, L, rows):
+    """base int64 [L, C, C]: F_d(t0, t1) per lag difference d; s0 int64 [C]: the row sums over [t0, t1); lo, hi: int64
+    [C, L-1], the L-1 columns before t0 and before t1 -> (gram [L*C, L*C], sum_x [L*C]) of the design rows [t0, t1)"""
+    dev, F = base.device, L * rows
+    G = torch.zeros((F, F), dtype=torch.int64, device=dev)
     for d in range(L):
         blocks = base[d].unsqueeze(0) + _edge_products(lo, L, d) - _edge_products(hi, L, d)   # [L-d, C, C]: l1 = 0..L-1-d
         for l1 in range(L - d):
@@ -160,25 +173,121 @@ def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
     before = torch.cat([zero, torch.cumsum(torch.flip(lo, [1]), 1)], 1)   # [:, l]: the sum over [t0-l, t0)
     after = torch.cat([zero, torch.cumsum(torch.flip(hi, [1]), 1)], 1)
     sx = (s0.unsqueeze(0) + before.t() - after.t()).reshape(F).contiguous()
-    return Stats(n, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+    return G, sx
 
 
-def stats(x, y, lags, lead=0, clip=None, ranges=None, max_bytes=MAX_BYTES):
+def _box_edge(x, e, L, w, q):
+    """int64 [C, L-1]: the box sums B[:, u] = sum over j < w of xq[:, u-j] of the columns u in [e-(L-1), e), by cumsum on
+    the L+w-2 columns before e; e >= L-1 + w-1"""
+    seg = torch.clamp(x[:, e - (L - 1) - (w - 1):e], max=q).long()
+    zero = torch.zeros((seg.shape[0], 1), dtype=torch.int64, device=x.device)
+    cs = torch.cat([zero, torch.cumsum(seg, 1)], 1)                # cs[:, i]: the sum of the first i columns
+    return cs[:, w:] - cs[:, :L - 1]
+
+
+def _pure_stats(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty):
+    """-> (gram, sum_x, xty) of the design rows [t0, t1) behind the warm-up (t0 >= L-1 + w-1), whose features are the
+    box sums B[c][t-l]: _range_stats with B = lo + 256 hi in the place of the counts.  Per column batch one mhs_box
+    writes the planes [C, nb + L-1]; the Gram matrix is G(lo,lo) + 256 (G(lo,hi) + G(hi,lo)) + 65536 G(hi,hi), 4L - 1
+    calls of mhi_gram (L where one plane is enough), and mhw_xty runs once per plane."""
+    from . import _wiener, smooth
+    from .gram import batches, enqueue
+    dev, n, F = x.device, t1 - t0, L * rows
+    two = w * q > 255
+    P = 2 if two else 1
+    plan = batches(n, rows, max_bytes)
+    lo, hi = smooth.planes(rows, plan[0][1] + L - 1, two, dev)
+    acc = torch.zeros((4 if two else 1, L, rows, rows), dtype=torch.int64, device=dev)   # (lo,lo), (hi,hi), (lo,hi), (hi,lo)
+    s = torch.zeros((P, rows), dtype=torch.int64, device=dev)
+    xt = torch.zeros((P, L, rows, K), dtype=torch.float64, device=dev)
+    for b0, nb in plan:
+        m = nb + L - 1
+        pl, ph = lo[:, :m], (hi[:, :m] if two else None)
+        smooth.enqueue(x, rows, m, w, q, pl, ph, t0 + b0 - (L - 1) - (w - 1))
+        for d in range(L):
+            if d == 0:
+                enqueue(pl, rows, nb, None, 0, acc[0, 0], s[0], None, True, L - 1)
+                if two:
+                    enqueue(ph, rows, nb, None, 0, acc[1, 0], s[1], None, True, L - 1)
+                    enqueue(pl, rows, nb, ph, rows, acc[2, 0], None, None, True, L - 1, L - 1)
+            else:
+                enqueue(pl, rows, nb, pl, rows, acc[0, d], None, None, True, L - 1, L - 1 - d)
+                if two:
+                    enqueue(ph, rows, nb, ph, rows, acc[1, d], None, None, True, L - 1, L - 1 - d)
+                    enqueue(pl, rows, nb, ph, rows, acc[2, d], None, None, True, L - 1, L - 1 - d)
+                    enqueue(ph, rows, nb, pl, rows, acc[3, d], None, None, True, L - 1, L - 1 - d)
+        for i, pv in enumerate((pl, ph)[:P]):
+            _wiener.xty(pv.data_ptr(), pv.stride(0) if rows > 1 else m, rows, nb, L, 255, y.data_ptr() + 4 * (t0 + b0 + g),
+                        4 * y.stride(0) if K > 1 else 4 * nb, K, xt[i], scratch_xty, True)
+    if two:
+        acc[3, 0] = acc[2, 0].t()                                  # G(hi,lo) at d = 0 is the transpose of G(lo,hi)
+        base = acc[0] + 256 * (acc[2] + acc[3]) + 65536 * acc[1]
+        s0, xty = s[0] + 256 * s[1], xt[0] + 256.0 * xt[1]
+    else:
+        base, s0, xty = acc[0], s[0], xt[0]
+    G, sx = _assemble(base, s0, _box_edge(x, t0, L, w, q), _box_edge(x, t1, L, w, q), L, rows)
+    return G, sx, xty.reshape(F, K)
+
+
+def _warm_stats(x, y, L, g, q, a, b):
+    """-> (gram, sum_x, xty) of the warm-up rows [a, b), all before L-1 + w-1, built explicitly: the reference pads its
+    design matrix with zeros in front of the first row, so feature (l, c) of row L-1 + r is the sum of the r + 1 design
+    entries xq[c][L-1-l .. L-1-l+r].  The Gram matrix is a float64 product: its entries stay below 255 * 65280^2 < 2^53,
+    so it is exact (there is no int64 matmul on the device)."""
+    r0, r1 = a - (L - 1), b - (L - 1)
+    xs = torch.clamp(x[:, :L - 1 + r1], max=q).long()
+    X = torch.cat([torch.cumsum(xs[:, L - 1 - l:L - 1 - l + r1], 1)[:, r0:].t() for l in range(L)], 1)   # [b-a, L*C]
+    Xd = X.double()
+    return (Xd.t() @ Xd).long(), X.sum(0), Xd.t() @ y[:, a + g:b + g].double().t()
+
+
+def _range_stats_window(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty):
+    dev, F = x.device, L * rows
+    yr = y[:, t0 + g:t1 + g].double()
+    sum_y, sum_yy = yr.sum(1), yr @ yr.t()
+    end = L - 1 + w - 1                                             # the first row whose window is whole
+    parts = []
+    if t0 < min(t1, end):
+        parts.append(_warm_stats(x, y, L, g, q, t0, min(t1, end)))
+    if t1 > max(t0, end):
+        parts.append(_pure_stats(x, rows, y, K, L, g, q, w, max(t0, end), t1, max_bytes, scratch_xty))
+    if not parts:                                                   # an empty range
+        parts.append((torch.zeros((F, F), dtype=torch.int64, device=dev), torch.zeros((F,), dtype=torch.int64, device=dev),
+                      torch.zeros((F, K), dtype=torch.float64, device=dev)))
+    G, sx, xty = parts[0]
+    for pg, ps, px in parts[1:]:
+        G, sx, xty = G + pg, sx + ps, xty + px
+    return Stats(t1 - t0, sx, G, xty, sum_y, sum_yy, L, g, q, rows, w)
+
+
+def stats(x, y, lags, lead=0, clip=None, ranges=None, max_bytes=MAX_BYTES, window=1):
     """The sufficient statistics of a Wiener filter -> [Stats], one per range of design rows (default: the single range
     of all of them).  x: counts, a 2-D uint8 device tensor with unit stride along its last axis or a ChannelSet of
     equal-length channels; y: float32 device tensor [K, bins] (or [bins]) of as many bins; lags 1..32; lead >= 0 bins by
     which the counts precede the covariates; clip: None or 1..255, counts enter as min(x, clip).  The integers are exact
     (mhi_gram), xty is float64 and deterministic (mhw_xty).  With a clip the count products go through a clamped scratch
-    copy in column batches of at most max_bytes."""
+    copy in column batches of at most max_bytes.
+
+    window > 1 (at most 256, window * clip <= 65535) is the study's moving average over the lag-stacked, clipped design
+    matrix, kept as integer sums: feature l*C + c of design row t is the sum over j = 0..min(window-1, t-(L-1)) of
+    min(x[c][t-l-j], clip).  Zeros stand in front of the first design row, as in the reference, so the first window - 1
+    rows (the warm-up) hold partial sums; they are built explicitly.  From row L-1 + window-1 on the features are box
+    sums, which mhs_box writes as two byte planes per column batch for mhi_gram and mhw_xty (smooth.py)."""
     x, rows, cols = _matrix(x, "wiener.stats")
     y, K = _covariates(y, x, cols)
     L, g = _settings(lags, lead, rows, cols)
     q = _clip(clip)
+    w = int(window)
+    if w != 1:
+        from .smooth import _window
+        w = _window(w, q)
     rs = _ranges(ranges, L, g, cols)
     from . import _wiener
     longest = max(b - a for a, b in rs)
     scratch = torch.empty((max(_wiener.xty_scratch_bytes(rows, max(longest, 1), L, K), 8),), dtype=torch.uint8, device=x.device)
-    return [_range_stats(x, rows, y, K, L, g, q, a, b, max_bytes, scratch) for a, b in rs]
+    if w == 1:
+        return [_range_stats(x, rows, y, K, L, g, q, a, b, max_bytes, scratch) for a, b in rs]
+    return [_range_stats_window(x, rows, y, K, L, g, q, w, a, b, max_bytes, scratch) for a, b in rs]
 
 
 def fold_ranges(n, num_fold, first=0):
@@ -211,7 +320,9 @@ def folds(n_rows_or_x, num_fold, lags=1, lead=0):
 class WienerFilter:
     """Ridge regression onto the z-scored lagged counts, from Stats alone.  After fit(): weights float64 [K, L, C] and
     bias float64 [K], which apply to raw clipped counts: estimate of y[k][t + lead] = bias[k] + sum over l, c of
-    weights[k][l][c] * min(x[c][t - l], clip)."""
+    weights[k][l][c] * min(x[c][t - l], clip).  Fitted on Stats with a window, the weights apply to the box SUMS of
+    stats(window=) -- not to the study's means, which are the sums over the window: z-scoring makes the fit the same and
+    the weights differ by that factor."""
 
     def __init__(self, alpha=0.0):
         if alpha < 0:
@@ -219,6 +330,7 @@ class WienerFilter:
         self.alpha = float(alpha)
         self.weights = self.bias = None
         self.lags = self.lead = self.clip = self.channels = None
+        self.window = 1                                                           # until fit() reads the Stats' own
 
     def fit(self, stats):  # noqa: A002
         s = stats[0] if isinstance(stats, (list, tuple)) and len(stats) == 1 else stats
@@ -229,7 +341,8 @@ class WienerFilter:
         mean = sx / n
         # the variance times n^2, an integer: exactly zero for a constant feature wherever int64 holds it
         diag = torch.diagonal(s.gram)
-        if s.n * 255 * 255 * s.n < 2 ** 63:
+        top = s.window * s.clip                                                   # the largest value of a feature
+        if s.n * top * top * s.n < 2 ** 63:
             keep = (s.n * diag - s.sum_x * s.sum_x) > 0
         else:
             num = n * diag.double() - sx * sx
@@ -254,11 +367,13 @@ class WienerFilter:
         w[idx] = wz / std.unsqueeze(1)
         self.bias = ybar - (w * mean.unsqueeze(1)).sum(0)
         self.weights = w.t().reshape(s.xty.shape[1], s.lags, s.channels).contiguous()
-        self.lags, self.lead, self.clip, self.channels = s.lags, s.lead, s.clip, s.channels
+        self.lags, self.lead, self.clip, self.channels, self.window = s.lags, s.lead, s.clip, s.channels, s.window
         return self
 
     def predict(self, x):
-        """-> float32 [K, T - L + 1]: column i is the estimate of y[:, i + L-1 + lead]"""
+        """-> float32 [K, T - L + 1]: column i is design row L-1 + i, the estimate of y[:, i + L-1 + lead].  With a window the
+        box and the filter commute: mhw_fir with a zero bias on the raw counts, then mhs_box_f32 with the real bias sums
+        the last `window` columns of that -- fewer in front, where the reference's zero padding stands."""
         from . import _wiener
         if self.weights is None:
             raise ValueError("predict comes after fit")
@@ -271,6 +386,12 @@ class WienerFilter:
         w = self.weights.to(device=x.device, dtype=torch.float32).contiguous()
         b = self.bias.to(device=x.device, dtype=torch.float32).contiguous()
         out = torch.empty((K, n), dtype=torch.float32, device=x.device)
+        if self.window > 1:
+            from . import _smooth
+            raw = torch.empty((K, n), dtype=torch.float32, device=x.device)
+            _wiener.fir(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, n, self.lags, self.clip, w, torch.zeros_like(b), K, raw)
+            _smooth.box_f32(raw, self.window, b, out)
+            return out
         _wiener.fir(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, n, self.lags, self.clip, w, b, K, out)
         return out
 

@@ -46,7 +46,9 @@ extern "C" {
  *                           that overlap the range
  *   mh_validate_segments -- mh_validate_stream restricted to listed segments (what a range query reads)
  *   mh_decode_rebin      -- mh_decode_range + mh_rebin in one pass: sums of r decoded samples, no byte-per-sample buffer
- *   mh_measure           -- also on packed plans: calibrates and prices the 2- / 4-bit pieces directly (drift tracking) */
+ *   mh_measure           -- also on packed plans: calibrates and prices the 2- / 4-bit pieces directly (drift tracking)
+ *   muahuff_smooth.h     -- a fifth library, libmuahuff_smooth.so (mhs_box, mhs_box_f32): the trailing box sums of the
+ *                           Wiener decoders' moving-average window, as byte planes and on a float prediction */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
