@@ -40,6 +40,12 @@ SMOOTH_SO = os.path.join(HERE, "libmuahuff_smooth.so")
 SMOOTH_SOURCES = ["csrc/mh_smooth.hip"]
 SMOOTH_HEADERS = ["csrc/exports_smooth.map", "csrc/mh_smooth.hpp", "csrc/mh_smooth_layout.hpp", "csrc/mh_msg.hpp",
                   "../include/muahuff.h", "../include/muahuff_smooth.h"]
+# the fifth companion (include/muahuff_sweep.h): the Wiener statistics of every clip, lag difference and range in one pass
+SWEEP_SO = os.path.join(HERE, "libmuahuff_sweep.so")
+SWEEP_SOURCES = ["csrc/mh_sweep.hip"]
+SWEEP_HEADERS = ["csrc/exports_sweep.map", "csrc/mh_sweep.hpp", "csrc/mh_sweep_layout.hpp", "csrc/mh_gram_layout.hpp",
+                 "csrc/mh_wiener_layout.hpp", "csrc/mh_device.hpp", "csrc/mh_msg.hpp", "../include/muahuff.h",
+                 "../include/muahuff_sweep.h"]
 
 
 def stale():
@@ -136,6 +142,24 @@ def build_smooth(force=False, verbose=False):
     return SMOOTH_SO
 
 
+def build_sweep(force=False, verbose=False):
+    """libmuahuff_sweep.so, exporting the C ABI of include/muahuff_sweep.h and nothing else
+    (csrc/exports_sweep.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(SWEEP_SO):
+        t = os.path.getmtime(SWEEP_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in SWEEP_SOURCES + SWEEP_HEADERS):
+            return SWEEP_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_sweep.map")]
+    cmd += [os.path.join(HERE, s) for s in SWEEP_SOURCES] + ["-o", SWEEP_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return SWEEP_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -156,3 +180,4 @@ if __name__ == "__main__":
     print(build_wiener(force=True, verbose=True))
     print(build_cascade(force=True, verbose=True))
     print(build_smooth(force=True, verbose=True))
+    print(build_sweep(force=True, verbose=True))

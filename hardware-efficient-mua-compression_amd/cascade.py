@@ -249,14 +249,25 @@ def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), n
     x, rows, cols = _matrix(x, "cascade.cross_validate")
     y, K = wiener._covariates(y, x, cols)
     L, g = wiener._settings(lags, lead, rows, cols)
+    alphas, degrees, F = _cv_settings(alphas, degrees, num_fold)
+    fr = wiener.fold_ranges(cols - g - (L - 1), F, L - 1)
+    st = wiener.stats(x, y, L, g, clip, ranges=fr, window=window)
+    return _validate_folds(x, y, st, fr, alphas, degrees)
+
+
+def _cv_settings(alphas, degrees, num_fold):
     alphas, degrees = [float(a) for a in alphas], [None if d is None else _degree(d) for d in degrees]
     if not alphas or not degrees or len(set(alphas)) != len(alphas) or len(set(degrees)) != len(degrees):
         raise ValueError("at least one alpha and one degree, each once")
     if int(num_fold) < 3:
         raise ValueError("%d folds leave none to train on (at least 3)" % int(num_fold))
-    F = int(num_fold)
-    fr = wiener.fold_ranges(cols - g - (L - 1), F, L - 1)
-    st = wiener.stats(x, y, L, g, clip, ranges=fr, window=window)
+    return alphas, degrees, int(num_fold)
+
+
+def _validate_folds(x, y, st, fr, alphas, degrees):
+    """cross_validate behind its statistics: st the wiener.Stats of the folds fr (ranges of design rows), x and y the
+    checked counts and covariates, alphas and degrees as _cv_settings returns them -> cross_validate's result"""
+    F = len(fr)
     top = max([d for d in degrees if d is not None], default=None)
     names = ("rmse_valid", "rmse_test", "cc_valid", "cc_test")
     res = {(a, d): {k: [] for k in names} for a in alphas for d in degrees}
@@ -288,3 +299,23 @@ def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), n
                 r["rmse_valid"].append(rmse[iv]), r["rmse_test"].append(rmse[it])
                 r["cc_valid"].append(cc[iv]), r["cc_test"].append(cc[it])
     return {key: {k: torch.stack(vals) for k, vals in r.items()} for key, r in res.items()}
+
+
+def sweep_clips(x, y, lags, lead=0, clips=range(2, 40), alphas=(0.0,), degrees=(3,), num_fold=5, window=1):
+    """The study's dynamic-range sweep (`for S in S_vector: X_in[X_in > S] = S` around the whole grid) -> {clip: what
+    cross_validate(x, y, lags, lead, clip, alphas, degrees, num_fold, window) returns}, the same bits.  clips: 1..255,
+    strictly ascending (default: S = 2..39).  The fold statistics of all clips come from wiener.iter_stats_clips -- one
+    mhq_gram_clips and one mhq_xty_clips per group of clips --; the solves, mhw_fir and the moments per (clip, fold,
+    alpha) are cross_validate's own.
+
+    window > 1 clamps before the box sum, so the fused kernels do not apply: that case is the loop over
+    wiener.stats(clip=q, window=) it replaces, inside this function."""
+    x, rows, cols = _matrix(x, "cascade.sweep_clips")
+    y, K = wiener._covariates(y, x, cols)
+    L, g = wiener._settings(lags, lead, rows, cols)
+    alphas, degrees, F = _cv_settings(alphas, degrees, num_fold)
+    qs = wiener._clip_list(clips)
+    fr = wiener.fold_ranges(cols - g - (L - 1), F, L - 1)
+    if int(window) != 1:
+        return {q: _validate_folds(x, y, wiener.stats(x, y, L, g, q, ranges=fr, window=window), fr, alphas, degrees) for q in qs}
+    return {q: _validate_folds(x, y, st, fr, alphas, degrees) for q, st in wiener.iter_stats_clips(x, y, L, g, qs, ranges=fr)}

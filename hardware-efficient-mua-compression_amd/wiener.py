@@ -12,7 +12,8 @@ covariates' own sums.  Stats of disjoint ranges add, so cross-validation over co
 over the recording plus one small solve per fold.  WienerFilter.fit() restates z-scoring, centring and the ridge solve
 from the statistics alone; predict() is mhw_fir on raw counts.  stats(window=) adds the study's moving-average window:
 the features become box sums of the clipped counts (mhs_box, smooth.py), predict() the box sum of mhw_fir's output
-(mhs_box_f32).  There is no CPU path: host matrices are refused."""
+(mhs_box_f32).  iter_stats_clips() / stats_clips() are stats() for a whole list of clips -- the study's dynamic-range sweep --
+from one mhq_gram_clips and one mhq_xty_clips per group of clips.  There is no CPU path: host matrices are refused."""
 import numpy as np
 import torch
 
@@ -176,6 +177,36 @@ def _assemble(base, s0, lo, hi, L, rows):
     return G, sx
 
 
+def _edge_products_clips(xe, L, d):
+    """_edge_products with leading axes: xe int64 [..., C, L-1] -> int64 [..., L-d, C, C]"""
+    n = xe.shape[-1]
+    a = xe[..., n - (L - 1 - d):].transpose(-1, -2)                 # [..., L-1-d, C]: u = e-(L-1-d) .. e-1
+    b = xe[..., n - (L - 1 - d) - d:n - d].transpose(-1, -2)        # u - d
+    outer = a.unsqueeze(-1) * b.unsqueeze(-2)                       # [..., L-1-d, C, C], in ascending u
+    cum = torch.flip(torch.cumsum(torch.flip(outer, [-3]), -3), [-3])
+    zero = torch.zeros(tuple(outer.shape[:-3]) + (1,) + tuple(outer.shape[-2:]), dtype=torch.int64, device=xe.device)
+    return torch.flip(torch.cat([cum, zero], -3), [-3])
+
+
+def _assemble_clips(base, s0, lo, hi, L, rows):
+    """_assemble with leading axes (range, clip): base int64 [..., L, C, C], s0 [..., C], lo, hi [..., C, L-1] ->
+    (gram [..., L*C, L*C], sum_x [..., L*C]).  Integers: the same values as _assemble gives slice by slice."""
+    dev, F, lead = base.device, L * rows, tuple(base.shape[:-3])
+    G = torch.zeros(lead + (F, F), dtype=torch.int64, device=dev)
+    for d in range(L):
+        blocks = base[..., d, :, :].unsqueeze(-3) + _edge_products_clips(lo, L, d) - _edge_products_clips(hi, L, d)   # [..., L-d, C, C]
+        for l1 in range(L - d):
+            r, c = l1 * rows, (l1 + d) * rows
+            G[..., r:r + rows, c:c + rows] = blocks[..., l1, :, :]
+            if d:
+                G[..., c:c + rows, r:r + rows] = blocks[..., l1, :, :].transpose(-1, -2)
+    zero = torch.zeros(lead + (rows, 1), dtype=torch.int64, device=dev)
+    before = torch.cat([zero, torch.cumsum(torch.flip(lo, [-1]), -1)], -1)   # [..., C, l]: the sum over [t0-l, t0)
+    after = torch.cat([zero, torch.cumsum(torch.flip(hi, [-1]), -1)], -1)
+    sx = (s0.unsqueeze(-2) + before.transpose(-1, -2) - after.transpose(-1, -2)).reshape(lead + (F,)).contiguous()
+    return G, sx
+
+
 def _box_edge(x, e, L, w, q):
     """int64 [C, L-1]: the box sums B[:, u] = sum over j < w of xq[:, u-j] of the columns u in [e-(L-1), e), by cumsum on
     the L+w-2 columns before e; e >= L-1 + w-1"""
@@ -288,6 +319,81 @@ def stats(x, y, lags, lead=0, clip=None, ranges=None, max_bytes=MAX_BYTES, windo
     if w == 1:
         return [_range_stats(x, rows, y, K, L, g, q, a, b, max_bytes, scratch) for a, b in rs]
     return [_range_stats_window(x, rows, y, K, L, g, q, w, a, b, max_bytes, scratch) for a, b in rs]
+
+
+def _clip_list(clips):
+    qs = [_clip(q) for q in clips]
+    if not qs or any(b <= a for a, b in zip(qs, qs[1:])):
+        raise ValueError("clips: at least one, strictly ascending")
+    return qs
+
+
+def _clip_groups(qs, R, L, rows, max_bytes):
+    """the clips in groups whose int64 block [R, n, L, C, C] stays within max_bytes (at least one clip), and within what
+    one call takes"""
+    from ._sweep import MAX_CLIPS
+    per = max(R, 1) * L * rows * rows * 8
+    n = min(max(int(max_bytes) // per, 1), MAX_CLIPS)
+    return [qs[i:i + n] for i in range(0, len(qs), n)]
+
+
+def iter_stats_clips(x, y, lags, lead=0, clips=range(2, 40), ranges=None, max_bytes=MAX_BYTES):
+    """stats() for every clip of a list in one pass -> an iterator of (clip, [Stats per range]) in clip order; every
+    Stats is what stats(x, y, lags, lead, clip=q, ranges=ranges) returns -- gram and sum_x the same integers, xty the
+    same bits.  clips: 1..255, strictly ascending (default: the study's S = 2..39); ranges: ascending and disjoint.
+
+    The clips are taken in groups whose count products, an int64 block [ranges, clips, lags, C, C], stay within
+    max_bytes (at least one clip a group); the Gram matrices assembled from it are `lags` times that and live until
+    the next group is asked for.  Per group ONE mhq_gram_clips gives the count products of every (range, clip, lag
+    difference) and ONE mhq_xty_clips the products with the covariates (muahuff_sweep.h): the counts are clamped in
+    registers, no clamped copy is written.  The edge terms and the assembly run batched over (range, clip).  There is
+    no window here: see cascade.sweep_clips."""
+    from . import _sweep
+    x, rows, cols = _matrix(x, "wiener.iter_stats_clips")
+    y, K = _covariates(y, x, cols)
+    L, g = _settings(lags, lead, rows, cols)
+    qs = _clip_list(clips)
+    rs = _ranges(ranges, L, g, cols)
+    if any(b[0] < a[1] for a, b in zip(rs, rs[1:])):
+        raise ValueError("the ranges are ascending and disjoint")
+    groups = _clip_groups(qs, len(rs), L, rows, max_bytes)
+
+    def walk():
+        dev, R, F = x.device, len(rs), L * rows
+        ysum = []
+        for t0, t1 in rs:                                           # as _range_stats: the same operations, the same bits
+            yr = y[:, t0 + g:t1 + g].double()
+            ysum.append((yr.sum(1), yr @ yr.t()))
+        xlo = torch.stack([x[:, t0 - (L - 1):t0] for t0, _t1 in rs]).long()      # [R, C, L-1]: the columns before t0
+        xhi = torch.stack([x[:, t1 - (L - 1):t1] for _t0, t1 in rs]).long()
+        calls = [rs[i:i + _sweep.MAX_RANGES] for i in range(0, R, _sweep.MAX_RANGES)]
+        nmax = len(groups[0])
+        scratch = torch.empty((max(_sweep.xty_clips_scratch_bytes(rows, cols, L, K, len(calls[0]), nmax), 8),), dtype=torch.uint8, device=dev)
+        xs, ys = (x.stride(0) if rows > 1 else cols), (4 * y.stride(0) if K > 1 else 4 * cols)
+        for part in groups:
+            n = len(part)
+            base = torch.zeros((R, n, L, rows, rows), dtype=torch.int64, device=dev)
+            s0 = torch.zeros((R, n, rows), dtype=torch.int64, device=dev)
+            xt = torch.empty((R, n, L, rows, K), dtype=torch.float64, device=dev)
+            r0 = 0
+            for sub in calls:
+                m = len(sub)
+                _sweep.gram_clips(x.data_ptr(), xs, rows, cols, sub, part, L, base[r0:r0 + m], s0[r0:r0 + m])
+                _sweep.xty_clips(x.data_ptr(), xs, rows, cols, sub, part, L, g, y.data_ptr(), ys, K, xt[r0:r0 + m], scratch)
+                r0 += m
+            qt = torch.tensor(part, dtype=torch.int64, device=dev).reshape(1, n, 1, 1)
+            G, sx = _assemble_clips(base, s0, torch.minimum(xlo.unsqueeze(1), qt), torch.minimum(xhi.unsqueeze(1), qt), L, rows)
+            del base
+            for i, q in enumerate(part):
+                yield q, [Stats(t1 - t0, sx[r, i], G[r, i], xt[r, i].reshape(F, K), ysum[r][0], ysum[r][1], L, g, q, rows)
+                          for r, (t0, t1) in enumerate(rs)]
+
+    return walk()
+
+
+def stats_clips(x, y, lags, lead=0, clips=range(2, 40), ranges=None, max_bytes=MAX_BYTES):
+    """iter_stats_clips as a list [(clip, [Stats per range])], for shapes where the statistics of all clips fit at once"""
+    return list(iter_stats_clips(x, y, lags, lead, clips, ranges, max_bytes))
 
 
 def fold_ranges(n, num_fold, first=0):

@@ -48,7 +48,9 @@ extern "C" {
  *   mh_decode_rebin      -- mh_decode_range + mh_rebin in one pass: sums of r decoded samples, no byte-per-sample buffer
  *   mh_measure           -- also on packed plans: calibrates and prices the 2- / 4-bit pieces directly (drift tracking)
  *   muahuff_smooth.h     -- a fifth library, libmuahuff_smooth.so (mhs_box, mhs_box_f32): the trailing box sums of the
- *                           Wiener decoders' moving-average window, as byte planes and on a float prediction */
+ *                           Wiener decoders' moving-average window, as byte planes and on a float prediction
+ *   muahuff_sweep.h      -- a sixth library, libmuahuff_sweep.so (mhq_gram_clips, mhq_xty_clips): the Wiener statistics of
+ *                           every clip of the dynamic-range sweep, every lag difference and every fold in one pass */
 
 /* ---- error codes -------------------------------------------------------------------- */
 #define MH_OK 0
