@@ -46,6 +46,12 @@ SWEEP_SOURCES = ["csrc/mh_sweep.hip"]
 SWEEP_HEADERS = ["csrc/exports_sweep.map", "csrc/mh_sweep.hpp", "csrc/mh_sweep_layout.hpp", "csrc/mh_gram_layout.hpp",
                  "csrc/mh_wiener_layout.hpp", "csrc/mh_device.hpp", "csrc/mh_msg.hpp", "../include/muahuff.h",
                  "../include/muahuff_sweep.h"]
+# the sixth companion (include/muahuff_kalman.h): the prediction of a Kalman filter decoder, a constant projection of the
+# counts and the scan of an affine recurrence
+KALMAN_SO = os.path.join(HERE, "libmuahuff_kalman.so")
+KALMAN_SOURCES = ["csrc/mh_kalman.hip"]
+KALMAN_HEADERS = ["csrc/exports_kalman.map", "csrc/mh_kalman.hpp", "csrc/mh_kalman_layout.hpp", "csrc/mh_msg.hpp",
+                  "../include/muahuff.h", "../include/muahuff_kalman.h"]
 
 
 def stale():
@@ -160,6 +166,24 @@ def build_sweep(force=False, verbose=False):
     return SWEEP_SO
 
 
+def build_kalman(force=False, verbose=False):
+    """libmuahuff_kalman.so, exporting the C ABI of include/muahuff_kalman.h and nothing else
+    (csrc/exports_kalman.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(KALMAN_SO):
+        t = os.path.getmtime(KALMAN_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in KALMAN_SOURCES + KALMAN_HEADERS):
+            return KALMAN_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_kalman.map")]
+    cmd += [os.path.join(HERE, s) for s in KALMAN_SOURCES] + ["-o", KALMAN_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return KALMAN_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -181,3 +205,4 @@ if __name__ == "__main__":
     print(build_cascade(force=True, verbose=True))
     print(build_smooth(force=True, verbose=True))
     print(build_sweep(force=True, verbose=True))
+    print(build_kalman(force=True, verbose=True))
