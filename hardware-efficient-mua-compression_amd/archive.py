@@ -298,7 +298,23 @@ class Reader:
                                     starts, W, r, nb, reduce, moments, saturate, self.T,
                                     windows.CHUNK if join is None else join, windows.MAX_BYTES if max_bytes is None else max_bytes)
 
-    def read_gram(self, start, stop, channels=None, bin=None, check=True, exact=None, max_bytes=None):  # noqa: A002
+    def bins(self, start, stop, channels=None, bin=None, check=True, exact=None, max_bytes=None):  # noqa: A002
+        """The whole bins of the global samples [start, stop) of the selected channels as a gram.BinSource: what
+        read_gram, wiener.stats_from, WienerFilter.predict_from, cascade.cross_validate_from and the Kalman filter's
+        file routes walk in batches of at most max_bytes bytes (default windows.MAX_BYTES) without holding the decoded
+        range.  The argument rules and the operand are read_gram's: n = (stop - start) // r bins, start % r == 0, and
+        with r > 1 the saturated uint8 bin.  Every batch is one read(a, b, channels, bin=, check=check, exact=exact,
+        out=): blocks, checksums, exact lists and the decode status are read()'s.  Nothing is read here."""
+        from . import codec, gram
+        start, r, n = gram.gram_args(start, stop, bin, self.T)
+        cio.wants_excess(self, exact, "archive")
+        rows = int(codec.select_channels(self.C, channels).size)
+
+        def read_bins(b0, nb, view):
+            self.read(start + b0 * r, start + (b0 + nb) * r, channels, bin=bin, check=check, exact=exact, out=view)
+        return gram.BinSource(rows, n, "cuda", max_bytes, read_bins)
+
+    def read_gram(self, start, stop, channels=None, bin=None, check=True, exact=None, max_bytes=None, lag=0):  # noqa: A002
         """The spike-count Gram matrix of the global samples [start, stop) of the selected channels, without holding the
         decoded range: -> gram.Gram with gram[i, j] = sum over the bins of x_i * x_j (int64, exact), the row sums and n,
         from which Gram.cov() and Gram.corr() follow.  bin=r (1..4096, start % r == 0) takes the products of the counts
@@ -308,15 +324,10 @@ class Reader:
         every bin period it uses.  The range is walked in batches of whole bins of at most max_bytes bytes (default
         windows.MAX_BYTES); each is decoded with read(a, b, channels, bin=, check=check, exact=exact, out=) into one
         reused scratch matrix and added by one symmetric mhi_gram: blocks, checksums, exact lists and the decode status
-        are read()'s.  Lag 0 only: a lagged product needs overlapping batches."""
-        from . import codec, gram
-        start, r, n = gram.gram_args(start, stop, bin, self.T)
-        cio.wants_excess(self, exact, "archive")
-        rows = int(codec.select_channels(self.C, channels).size)
-
-        def read_bins(b0, nb, view):
-            self.read(start + b0 * r, start + (b0 + nb) * r, channels, bin=bin, check=check, exact=exact, out=view)
-        return gram.read_gram(read_bins, rows, n, gram.MAX_BYTES if max_bytes is None else max_bytes)
+        are read()'s.  lag: what gram.gram takes, an int >= 0 below n or a sequence of them, with the same result in
+        every field; a batch then keeps the last max(lag) bins of the one before (gram.walk)."""
+        from . import gram
+        return gram.source_gram(self.bins(start, stop, channels, bin, check, exact, max_bytes), lag)
 
     def read_events(self, start, stop, channels=None, origin=0, period=1, phase=0, check=True, aer=False,  # noqa: A002
                     ch_dtype=None, exact=None):

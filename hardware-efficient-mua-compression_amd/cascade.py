@@ -203,8 +203,12 @@ class WienerCascade:
         from a pass over the prediction."""
         s = stats[0] if isinstance(stats, (list, tuple)) and len(stats) == 1 else stats
         self.linear.fit(s)
+        return self._fit_stage(s, self.linear.predict(x), y, ranges)
+
+    def _fit_stage(self, s, pred, y, ranges=None):
+        """fit behind the linear fit: pred is the fitted linear filter's prediction over the recording (predict, or
+        predict_from on a file)"""
         self.center, self.scale = _linear_spread(s, self.linear)
-        pred = self.linear.predict(x)
         p, t, n = self._targets(pred, y)
         m = moments(p, t, self._columns(ranges, n), self.degree, self.center, self.scale).total()
         if int(m.n[0]) != s.n:
@@ -228,9 +232,16 @@ class WienerCascade:
     def score(self, x, y, ranges=None):
         """-> (rmse, cc), float64 [R, K]: per range of design rows (default: the one range of all of them), from mhc_moments
         at degree 1 on the final prediction"""
-        p, t, n = self._targets(self.predict(x), y)
+        return self._score_stage(self.linear.predict(x), y, ranges)
+
+    def _score_stage(self, pred, y, ranges=None):
+        """score behind the linear prediction `pred`, which is overwritten with the cascade's"""
+        if self.coef is None:
+            raise ValueError("predict comes after fit")
+        p, t, n = self._targets(self._apply(pred, self.coef, pred), y)
         m = moments(p, t, self._columns(ranges, n), 1)
         return m.rmse(), m.cc()
+
 
 
 def cross_validate(x, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), num_fold=5, window=1):
@@ -264,40 +275,51 @@ def _cv_settings(alphas, degrees, num_fold):
     return alphas, degrees, int(num_fold)
 
 
-def _validate_folds(x, y, st, fr, alphas, degrees):
+def _validate_folds(x, y, st, fr, alphas, degrees, predictions=None):
     """cross_validate behind its statistics: st the wiener.Stats of the folds fr (ranges of design rows), x and y the
-    checked counts and covariates, alphas and degrees as _cv_settings returns them -> cross_validate's result"""
+    checked counts and covariates, alphas and degrees as _cv_settings returns them -> cross_validate's result.
+    predictions: None, or what stands in for WienerFilter.predict(x): a function of the list of fitted filters that
+    gives their predictions one at a time, in order (the file route, where x is None)"""
     F = len(fr)
     top = max([d for d in degrees if d is not None], default=None)
     names = ("rmse_valid", "rmse_test", "cc_valid", "cc_test")
     res = {(a, d): {k: [] for k in names} for a in alphas for d in degrees}
-    tmp = None
+    fits = []
     for i in range(F):
         v, t = i, (i + 1) % F
         train = [k for k in range(F) if k not in (v, t)]
         tot = sum(st[k] for k in train)
-        held = sorted((v, t))                                                      # mhc_moments takes ascending ranges
-        iv, it = held.index(v), held.index(t)
         for a in alphas:
             c = WienerCascade(a, top or 1)
             c.linear.fit(tot)
-            pred = c.linear.predict(x)
-            p, tg, n = c._targets(pred, y)
             if top is not None:
                 c.center, c.scale = _linear_spread(tot, c.linear)
-                m = moments(p, tg, c._columns([fr[k] for k in train], n), top, c.center, c.scale).total()
-                if tmp is None:
-                    tmp = torch.empty_like(pred)
-            for d in degrees:
-                if d is None:
-                    q = p
-                else:
-                    q = c._apply(pred, polyfit(m, d), tmp)[:, :n]
-                s = moments(q, tg, c._columns([fr[k] for k in held], n), 1)
-                rmse, cc = s.rmse(), s.cc()
-                r = res[(a, d)]
-                r["rmse_valid"].append(rmse[iv]), r["rmse_test"].append(rmse[it])
-                r["cc_valid"].append(cc[iv]), r["cc_test"].append(cc[it])
+            fits.append((i, a, c))
+    if predictions is None:
+        preds = (c.linear.predict(x) for _i, _a, c in fits)
+    else:
+        preds = predictions([c.linear for _i, _a, c in fits])
+    tmp = None
+    for (i, a, c), pred in zip(fits, preds):
+        v, t = i, (i + 1) % F
+        train = [k for k in range(F) if k not in (v, t)]
+        held = sorted((v, t))                                                      # mhc_moments takes ascending ranges
+        iv, it = held.index(v), held.index(t)
+        p, tg, n = c._targets(pred, y)
+        if top is not None:
+            m = moments(p, tg, c._columns([fr[k] for k in train], n), top, c.center, c.scale).total()
+            if tmp is None:
+                tmp = torch.empty_like(pred)
+        for d in degrees:
+            if d is None:
+                q = p
+            else:
+                q = c._apply(pred, polyfit(m, d), tmp)[:, :n]
+            s = moments(q, tg, c._columns([fr[k] for k in held], n), 1)
+            rmse, cc = s.rmse(), s.cc()
+            r = res[(a, d)]
+            r["rmse_valid"].append(rmse[iv]), r["rmse_test"].append(rmse[it])
+            r["cc_valid"].append(cc[iv]), r["cc_test"].append(cc[it])
     return {key: {k: torch.stack(vals) for k, vals in r.items()} for key, r in res.items()}
 
 
@@ -319,3 +341,36 @@ def sweep_clips(x, y, lags, lead=0, clips=range(2, 40), alphas=(0.0,), degrees=(
     if int(window) != 1:
         return {q: _validate_folds(x, y, wiener.stats(x, y, L, g, q, ranges=fr, window=window), fr, alphas, degrees) for q in qs}
     return {q: _validate_folds(x, y, st, fr, alphas, degrees) for q, st in wiener.iter_stats_clips(x, y, L, g, qs, ranges=fr)}
+
+
+def _source_settings(src, y, lags, lead, alphas, degrees, num_fold, who):
+    rows, cols = wiener._source(src, who)
+    y, _K = wiener._source_covariates(y, src)
+    L, g = wiener._settings(lags, lead, rows, cols)
+    alphas, degrees, F = _cv_settings(alphas, degrees, num_fold)
+    return y, L, g, alphas, degrees, wiener.fold_ranges(cols - g - (L - 1), F, L - 1)
+
+
+def cross_validate_from(src, y, lags, lead=0, clip=None, alphas=(0.0,), degrees=(3,), num_fold=5, window=1):
+    """cross_validate with the counts in a gram.BinSource (archive.Reader.bins, container_io.bins) -> the same dict.  y:
+    float32 [K, src.n] on the source's bin grid.  One pass over the source for the fold statistics (wiener.stats_from),
+    then wiener.predict_many_from over the fitted (split, alpha) filters: one more pass per group of them whose
+    predictions fit the source's max_bytes.  The polynomial fits and the fold scores run on the resident predictions,
+    as in cross_validate."""
+    y, L, g, alphas, degrees, fr = _source_settings(src, y, lags, lead, alphas, degrees, num_fold, "cascade.cross_validate_from")
+    st = wiener.stats_from(src, y, L, g, clip, ranges=fr, window=window)
+    return _validate_folds(None, y, st, fr, alphas, degrees, lambda fs: wiener.iter_predict_from(src, fs))
+
+
+def sweep_clips_from(src, y, lags, lead=0, clips=range(2, 40), alphas=(0.0,), degrees=(3,), num_fold=5, window=1):
+    """sweep_clips with the counts in a gram.BinSource -> {clip: what cross_validate_from gives at that clip}.  The fold
+    statistics of all clips come from one pass (wiener.stats_clips_from; with a window, one wiener.stats_from pass per
+    clip), the predictions from cross_validate_from's passes per clip."""
+    y, L, g, alphas, degrees, fr = _source_settings(src, y, lags, lead, alphas, degrees, num_fold, "cascade.sweep_clips_from")
+    qs = wiener._clip_list(clips)
+    predictions = lambda fs: wiener.iter_predict_from(src, fs)  # noqa: E731
+    if int(window) != 1:
+        return {q: _validate_folds(None, y, wiener.stats_from(src, y, L, g, q, ranges=fr, window=window), fr, alphas, degrees,
+                                   predictions) for q in qs}
+    return {q: _validate_folds(None, y, st, fr, alphas, degrees, predictions)
+            for q, st in wiener.stats_clips_from(src, y, L, g, qs, ranges=fr)}

@@ -946,22 +946,28 @@ def decompress_windows(src, triggers, pre, post, channels=None, bin=None, reduce
                                 device)
 
 
-def decompress_gram(src, start=0, stop=None, channels=None, bin=None, check=True, exact=None, device="cuda",  # noqa: A002
-                    max_bytes=None):
-    """archive.Reader.read_gram over decompress_range / decompress_binned: the Gram matrix (gram.Gram: int64 products,
-    row sums, n) of the samples [start, stop) of the selected channels of a `Compressed`, a `ContainerFile` or a path
-    (opened for the call).  stop=None: the longest channel's length; a shorter channel is zero past its end.  Only whole
-    bins count, and with bin > 1 the operand is the saturated uint8 bin, as read_gram says; check and exact as
-    decompress_range, once per batch.  There is no CPU path: a host array is not a source."""
+def bins(src, start=0, stop=None, channels=None, bin=None, check=True, exact=None, device="cuda", max_bytes=None):  # noqa: A002
+    """archive.Reader.bins over decompress_range / decompress_binned: the whole bins of the samples [start, stop) of the
+    selected channels of a `Compressed`, a `ContainerFile` or a path as a gram.BinSource.  A path is opened here and
+    stays open until the source's close() (the source is a context manager).  stop=None: the longest channel's length;
+    a shorter channel is zero past its end.  Only whole bins count, and with bin > 1 the operand is the saturated uint8
+    bin, as read_gram says; check and exact as decompress_range, once per batch.  There is no CPU path: a host array is
+    not a source."""
     from . import codec, gram
+    close = None
     if isinstance(src, (str, os.PathLike)):
-        with open(src) as f:
-            return decompress_gram(f, start, stop, channels, bin, check, exact, device, max_bytes)
-    if not hasattr(src, "ch_len"):
-        raise ValueError("decompress_gram takes a Compressed, a ContainerFile or a path: there is no CPU path")
-    T = int(np.max(src.ch_len)) if len(src.ch_len) else 0
-    start, r, n = gram.gram_args(start, T if stop is None else stop, bin, T)
-    rows = int(codec.select_channels(len(src.ch_len), channels).size)
+        src = open(src)
+        close = src.close
+    try:
+        if not hasattr(src, "ch_len"):
+            raise ValueError("a source of bins is a Compressed, a ContainerFile or a path: there is no CPU path")
+        T = int(np.max(src.ch_len)) if len(src.ch_len) else 0
+        start, r, n = gram.gram_args(start, T if stop is None else stop, bin, T)
+        rows = int(codec.select_channels(len(src.ch_len), channels).size)
+    except BaseException:
+        if close is not None:
+            close()
+        raise
 
     def read_bins(b0, nb, view):
         a, b = start + b0 * r, start + (b0 + nb) * r
@@ -969,4 +975,18 @@ def decompress_gram(src, start=0, stop=None, channels=None, bin=None, check=True
             view.copy_(decompress_range(src, a, b, channels, device, check, exact=exact))
         else:
             view.copy_(decompress_binned(src, r, a, b, channels, True, check, device, exact))
-    return gram.read_gram(read_bins, rows, n, gram.MAX_BYTES if max_bytes is None else max_bytes, device)
+    return gram.BinSource(rows, n, device, max_bytes, read_bins, close)
+
+
+def decompress_gram(src, start=0, stop=None, channels=None, bin=None, check=True, exact=None, device="cuda",  # noqa: A002
+                    max_bytes=None, lag=0):
+    """archive.Reader.read_gram over decompress_range / decompress_binned: the Gram matrix (gram.Gram: int64 products,
+    row sums, n) of the samples [start, stop) of the selected channels of a `Compressed`, a `ContainerFile` or a path
+    (opened for the call).  stop=None: the longest channel's length; a shorter channel is zero past its end.  Only whole
+    bins count, and with bin > 1 the operand is the saturated uint8 bin, as read_gram says; check and exact as
+    decompress_range, once per batch; lag as read_gram.  There is no CPU path: a host array is not a source."""
+    from . import gram
+    if not isinstance(src, (str, os.PathLike)) and not hasattr(src, "ch_len"):
+        raise ValueError("decompress_gram takes a Compressed, a ContainerFile or a path: there is no CPU path")
+    with bins(src, start, stop, channels, bin, check, exact, device, max_bytes) as b:
+        return gram.source_gram(b, lag)

@@ -5,7 +5,10 @@ one lag, the all-pairs cross-correlogram.
 
 gram works on matrices that are resident on the device.  read_gram is what the readers (archive.Reader.read_gram,
 container_io.decompress_gram) share: it walks a range in batches of whole bins, decodes each batch into one reused
-scratch matrix and adds its products to the result.  There is no CPU path: host matrices are refused."""
+scratch matrix and adds its products to the result.  BinSource, halo_plan and walk are what every decoder's file route
+(source_gram here, wiener.stats_from, WienerFilter.predict_from, ...) stands on: batches of whole bins that keep a halo of
+the bins in front of them, carried on the device from one batch to the next.  There is no CPU path: host matrices are
+refused."""
 import numpy as np
 import torch
 
@@ -151,3 +154,141 @@ def read_gram(read_bins, rows, n, max_bytes, device="cuda"):
             read_bins(b0, nb, view)
             enqueue(view, rows, nb, None, 0, g, s, None, True)
     return Gram(n, s, s.clone(), g, True)
+
+
+# ---- decoders from a file: one source of bins, one walker that carries a halo ------------------------------------------
+def halo_plan(n, rows, halo, max_bytes):
+    """[(first bin, bins)] that tile [0, n) in order, for a walk in which every batch also keeps the min(halo, first bin)
+    bins in front of it: the scratch of a batch, rows * (bins + min(halo, first bin)) bytes, is at most max_bytes.  A
+    budget that does not exceed the halo gives batches of one bin instead of a walk that stalls.  Pure Python."""
+    n, rows, halo = int(n), max(int(rows), 1), int(halo)
+    if halo < 0:
+        raise ValueError("halo %d is negative" % halo)
+    cap = int(max_bytes) // rows                                    # the columns of the scratch
+    out, b = [], 0
+    while b < n:
+        nb = min(max(cap - min(halo, b), 1), n - b)
+        out.append((b, nb))
+        b += nb
+    return out
+
+
+class BinSource:
+    """Where the file routes of the decoders take their counts from: rows channels of n whole bins on `device`, read in
+    batches of at most max_bytes bytes.  read_bins(b0, nb, view) fills the uint8 view [rows, nb] (unit stride along its
+    last axis, any pitch) with the bins [b0, b0 + nb).  archive.Reader.bins and container_io.bins make one over a file,
+    BinSource.of over a matrix that is resident."""
+
+    def __init__(self, rows, n, device, max_bytes, read_bins, close=None):
+        self.rows, self.n, self.device = int(rows), int(n), torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("a source of bins lives on a device: there is no CPU path")
+        if self.device.index is None:                               # "cuda" is the current device, named as a tensor's is
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_bytes = MAX_BYTES if max_bytes is None else int(max_bytes)
+        self._read, self._close = read_bins, close
+
+    def read_bins(self, b0, nb, view):
+        b0, nb = int(b0), int(nb)
+        if not 0 <= b0 <= b0 + nb <= self.n:
+            raise ValueError("bins [%d, %d) are not inside [0, %d)" % (b0, b0 + nb, self.n))
+        if view.dtype != torch.uint8 or tuple(view.shape) != (self.rows, nb):
+            raise ValueError("the view is a uint8 tensor [%d, %d]" % (self.rows, nb))
+        self._read(b0, nb, view)
+
+    @classmethod
+    def of(cls, x, max_bytes=None):
+        """a resident matrix (what gram takes) as a source: read_bins copies its columns"""
+        x, rows, cols = _matrix(x, "BinSource.of")
+        return cls(rows, cols, x.device, max_bytes, lambda b0, nb, view: view.copy_(x[:, b0:b0 + nb]))
+
+    def close(self):
+        """what the source opened itself (container_io.bins on a path) is closed; anything else is left as it is"""
+        if self._close is not None:
+            self._close()
+            self._close = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def walk(src, halo, lo=0, hi=None):
+    """Walk the bins [lo, hi) of a BinSource in the batches of halo_plan -> a generator of (b0, nb, h, view): view is
+    uint8 [rows, h + nb] and holds the bins [b0 - h, b0 + nb), h = min(halo, b0 - lo) of them in front of the batch's own.
+    One scratch serves the call, so a view is good until the next one is asked for.  The halo is not read again: the last
+    h columns of the view before move to the front on the device, in stream order -- through a temporary where the two
+    overlap (nb < halo).  Nothing outside [lo, hi) is read."""
+    halo, lo = int(halo), int(lo)
+    hi = src.n if hi is None else int(hi)
+    if not 0 <= lo <= hi <= src.n:
+        raise ValueError("bins [%d, %d) are not inside [0, %d)" % (lo, hi, src.n))
+    plan = halo_plan(hi - lo, src.rows, halo, src.max_bytes)
+    if not plan or src.rows < 1:
+        return
+    width = max(nb + min(halo, b) for b, nb in plan)
+    scratch = torch.empty((src.rows, width), dtype=torch.uint8, device=src.device)
+    before = 0                                                      # the columns of the view before
+    for b, nb in plan:
+        h = min(halo, b)
+        if h:
+            tail = scratch[:, before - h:before]
+            scratch[:, :h].copy_(tail.clone() if before - h < h else tail)
+        view = scratch[:, :h + nb]
+        src.read_bins(lo + b, nb, view[:, h:])
+        before = h + nb
+        yield lo + b, nb, h, view
+
+
+def walk_ranges(src, halo, ranges):
+    """walk for ranges [(a, b)] of bins, each of which needs the halo bins in front of it (fewer at the source's first
+    bin): ranges that touch or lie within a halo of each other share one walk, bins between ranges further apart are
+    not read.  -> a generator of (b0, nb, h, view, pieces), pieces: [(index of the range, a, b)], what the ranges have
+    inside [b0, b0 + nb); batches without a piece are left out (they are read: the next halo is in them)."""
+    order = sorted((i for i, (a, b) in enumerate(ranges) if b > a), key=lambda i: ranges[i][0])
+    groups = []
+    for i in order:
+        a, b = ranges[i]
+        if groups and max(a - halo, 0) <= groups[-1][1]:
+            groups[-1][1] = max(groups[-1][1], b)
+            groups[-1][2].append(i)
+        else:
+            groups.append([max(a - halo, 0), b, [i]])
+    for lo, hi, members in groups:
+        for b0, nb, h, view in walk(src, halo, lo, hi):
+            pieces = [(i, max(ranges[i][0], b0), min(ranges[i][1], b0 + nb)) for i in members]
+            pieces = [p for p in pieces if p[1] < p[2]]
+            if pieces:
+                yield b0, nb, h, view, pieces
+
+
+def source_gram(src, lag=0):
+    """gram(x, lag=lag) of the bins of a BinSource, without holding them: the halo is max(lag), and a batch adds the
+    products whose LATER bin lies in it.  lag=0 is read_gram's symmetric single call per batch.  -> Gram"""
+    lags, many = _lags(lag)
+    if lags == [0] and not many:
+        return read_gram(src.read_bins, src.rows, src.n, src.max_bytes, src.device)
+    if src.rows < 1 or src.n < 1:
+        raise ValueError("at least one channel and one bin")
+    if max(lags) >= src.n:
+        raise ValueError("lag %d leaves no bin of the %d" % (max(lags), src.n))
+    rows, dev = src.rows, src.device
+    g = torch.zeros((len(lags), rows, rows), dtype=torch.int64, device=dev)
+    sa = torch.zeros((len(lags), rows), dtype=torch.int64, device=dev)
+    sb = torch.zeros((len(lags), rows), dtype=torch.int64, device=dev)
+    for b0, nb, h, view in walk(src, max(lags)):
+        for k, lg in enumerate(lags):
+            first = max(b0, lg)                                     # the first later bin of this batch
+            m = b0 + nb - first
+            if m <= 0:
+                continue
+            at = first - (b0 - h)
+            if lg == 0:
+                enqueue(view, rows, m, None, 0, g[k], sa[k], sb[k], True, at)
+            else:
+                enqueue(view, rows, m, view, rows, g[k], sa[k], sb[k], True, at - lg, at)
+    n = [src.n - lg for lg in lags]
+    return Gram(n, sa, sb, g, False) if many else Gram(n[0], sa[0], sb[0], g[0], False)

@@ -195,9 +195,36 @@ class KalmanFilter:
         if self.A is None:
             raise ValueError("predict comes after fit")
         x, rows, cols = _matrix(x, "KalmanFilter.predict")
+        dev = x.device
+        rs, init = self._scan_args(rows, cols, dev, y0, ranges)
+        v = torch.empty((int(self.A.shape[0]), cols), dtype=torch.float64, device=dev)
+        _kalman.project(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, cols, self.clip, self.m.to(dev), self.m0.to(dev), v)
+        return self._scan(v, cols, rs, init)
+
+    def predict_from(self, src, y0=None, ranges=None):
+        """predict on the bins of a gram.BinSource (archive.Reader.bins, container_io.bins), without holding them: one
+        mhk_project per batch into its columns of v [K, n], then the scans over the whole of v as in predict.  With
+        ranges only the batches that hold a bin of one are read."""
+        from . import _kalman
+        from .gram import walk_ranges
+        if self.A is None:
+            raise ValueError("predict comes after fit")
+        rows, cols = wiener._source(src, "KalmanFilter.predict_from")
+        dev = src.device
+        rs, init = self._scan_args(rows, cols, dev, y0, ranges)
+        K = int(self.A.shape[0])
+        whole = len(rs) == 1 and rs[0] == (0, cols)
+        v = (torch.empty if whole else torch.zeros)((K, cols), dtype=torch.float64, device=dev)
+        m, m0 = self.m.to(dev), self.m0.to(dev)
+        for b0, nb, h, view, _pieces in walk_ranges(src, 0, rs):
+            _kalman.project(view.data_ptr() + h, view.stride(0) if rows > 1 else nb, rows, nb, self.clip, m, m0, v[:, b0:b0 + nb])
+        return self._scan(v, cols, rs, init)
+
+    def _scan_args(self, rows, cols, dev, y0, ranges):
+        """the checks of predict behind the counts' shape -> (ranges, the centred first states [ranges, K])"""
         if rows != self.channels:
             raise ValueError("the filter was fitted on %d channels, not %d" % (self.channels, rows))
-        dev, K = x.device, int(self.A.shape[0])
+        K = int(self.A.shape[0])
         rs = [(0, cols)] if ranges is None else [(int(a), int(b)) for a, b in ranges]
         prev = 0
         for a, b in rs:
@@ -209,9 +236,14 @@ class KalmanFilter:
             init = torch.zeros((len(rs), K), dtype=torch.float64, device=dev)
         else:
             init = (torch.as_tensor(y0, device=dev).double().reshape(len(rs), K) - mean.unsqueeze(0)).contiguous()
+        return rs, init
+
+    def _scan(self, v, cols, rs, init):
+        """predict behind mhk_project: v float64 [K, cols], projected wherever a range lies -> the prediction"""
+        from . import _kalman
+        dev, K = v.device, int(v.shape[0])
+        mean = self.mean_y.to(dev)
         F, B = self._device_table(dev)
-        v = torch.empty((K, cols), dtype=torch.float64, device=dev)
-        _kalman.project(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, cols, self.clip, self.m.to(dev), self.m0.to(dev), v)
         whole = len(rs) == 1 and rs[0] == (0, cols)
         out = v if whole else torch.full((K, cols), float("nan"), dtype=torch.float64, device=dev)
         n = min(len(rs), _kalman.MAX_RANGES)
@@ -227,12 +259,25 @@ class KalmanFilter:
         reference's predict(X_test, y_test) does, and that first column is counted, as the reference counts it."""
         x, _rows, cols = _matrix(x, "KalmanFilter.score")
         y, _K = wiener._covariates(y, x, cols)
+        rs, y0 = self._scored(y, cols, ranges)
+        return self._score(self.predict(x, y0, rs), y, rs)
+
+    def score_from(self, src, y, ranges=None):
+        """score with the counts in a gram.BinSource: the prediction is predict_from's"""
+        _rows, cols = wiener._source(src, "KalmanFilter.score_from")
+        y, _K = wiener._source_covariates(y, src)
+        rs, y0 = self._scored(y, cols, ranges)
+        return self._score(self.predict_from(src, y0, rs), y, rs)
+
+    def _scored(self, y, cols, ranges):
         g = self.lead
         rs = [(0, cols - g)] if ranges is None else [(int(a), int(b)) for a, b in ranges]
         if any(b + g > cols or b <= a for a, b in rs):
             raise ValueError("a scored range holds a bin and its targets lie inside the recording")
-        y0 = torch.stack([y[:, a + g] for a, _b in rs]).double()
-        pred = self.predict(x, y0, rs)
+        return rs, torch.stack([y[:, a + g] for a, _b in rs]).double()
+
+    def _score(self, pred, y, rs):
+        g = self.lead
         rmse, cc = [], []
         for a, b in rs:
             p, t = pred[:, a:b], y[:, a + g:b + g].double()
@@ -256,7 +301,14 @@ def cross_validate(x, y, lead=0, clip=None, alphas=(0.0,), num_fold=5):
         raise ValueError("at least one alpha, each once, and at least 3 folds")
     fr = wiener.fold_ranges(cols - g, num_fold)
     st = stats(x, y, g, clip, fr)
-    res = {k: torch.empty((len(alphas), num_fold, K), dtype=torch.float64, device=x.device)
+    return _validate_folds(st, fr, alphas, K, x.device, lambda f, rs: f.score(x, y, rs))
+
+
+def _validate_folds(st, fr, alphas, K, device, score):
+    """cross_validate behind its statistics: st the KalmanStats of the folds fr, score(filter, ranges) the fitted
+    filter's score over the held-out folds"""
+    num_fold = len(fr)
+    res = {k: torch.empty((len(alphas), num_fold, K), dtype=torch.float64, device=device)
            for k in ("rmse_valid", "rmse_test", "cc_valid", "cc_test")}
     for i in range(num_fold):
         v, t = i, (i + 1) % num_fold
@@ -264,7 +316,33 @@ def cross_validate(x, y, lead=0, clip=None, alphas=(0.0,), num_fold=5):
         held = sorted((v, t))
         iv, it = held.index(v), held.index(t)
         for j, a in enumerate(alphas):
-            rmse, cc = KalmanFilter(a).fit(tot).score(x, y, [fr[k] for k in held])
+            rmse, cc = score(KalmanFilter(a).fit(tot), [fr[k] for k in held])
             res["rmse_valid"][j, i], res["rmse_test"][j, i] = rmse[iv], rmse[it]
             res["cc_valid"][j, i], res["cc_test"][j, i] = cc[iv], cc[it]
     return res
+
+
+def stats_from(src, y, lead=0, clip=None, ranges=None):
+    """stats() with the counts in a gram.BinSource (archive.Reader.bins, container_io.bins) -> [KalmanStats]: the count
+    statistics are wiener.stats_from at one lag, one pass over the bins the ranges hold; the pair moments are those of
+    y, which is resident.  y: float32 [K, src.n] on the source's bin grid."""
+    _rows, cols = wiener._source(src, "kalman.stats_from")
+    ws = wiener.stats_from(src, y, 1, lead, clip, ranges)
+    y, _K = wiener._source_covariates(y, src)
+    g = int(lead)
+    return [KalmanStats(w, *_pair_moments(y[:, a + g:b + g].double()))
+            for (a, b), w in zip(wiener._ranges(ranges, 1, g, cols), ws)]
+
+
+def cross_validate_from(src, y, lead=0, clip=None, alphas=(0.0,), num_fold=5):
+    """cross_validate with the counts in a gram.BinSource -> the same dict.  One pass over the source for the fold
+    statistics; per (split, alpha) KalmanFilter.score_from reads the two held-out folds again for its projection."""
+    rows, cols = wiener._source(src, "kalman.cross_validate_from")
+    y, K = wiener._source_covariates(y, src)
+    _L, g = wiener._settings(1, lead, rows, cols)
+    alphas, num_fold = [float(a) for a in alphas], int(num_fold)
+    if not alphas or len(set(alphas)) != len(alphas) or num_fold < 3:
+        raise ValueError("at least one alpha, each once, and at least 3 folds")
+    fr = wiener.fold_ranges(cols - g, num_fold)
+    st = stats_from(src, y, g, clip, fr)
+    return _validate_folds(st, fr, alphas, K, y.device, lambda f, rs: f.score_from(src, y, rs))

@@ -13,7 +13,9 @@ over the recording plus one small solve per fold.  WienerFilter.fit() restates z
 from the statistics alone; predict() is mhw_fir on raw counts.  stats(window=) adds the study's moving-average window:
 the features become box sums of the clipped counts (mhs_box, smooth.py), predict() the box sum of mhw_fir's output
 (mhs_box_f32).  iter_stats_clips() / stats_clips() are stats() for a whole list of clips -- the study's dynamic-range sweep --
-from one mhq_gram_clips and one mhq_xty_clips per group of clips.  There is no CPU path: host matrices are refused."""
+from one mhq_gram_clips and one mhq_xty_clips per group of clips.  stats_from(), stats_clips_from(), predict_from() and
+predict_many_from() are the same on a gram.BinSource -- a recording file walked in batches, never resident (the end of
+this module).  There is no CPU path: host matrices are refused."""
 import numpy as np
 import torch
 
@@ -118,8 +120,6 @@ def _edge_products(xe, L, d):
 
 
 def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
-    from . import _wiener
-    from .gram import batches, enqueue
     dev, n, F = x.device, t1 - t0, L * rows
     xty = torch.zeros((F, K), dtype=torch.float64, device=dev)
     yr = y[:, t0 + g:t1 + g].double()
@@ -128,6 +128,22 @@ def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
         G = torch.zeros((F, F), dtype=torch.int64, device=dev)
         sx = torch.zeros((F,), dtype=torch.int64, device=dev)
         return Stats(0, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+    base, s0 = _range_parts(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty, xty)
+    # ---- the edges: at most L - 1 outer products on either side
+    lo = torch.clamp(x[:, t0 - (L - 1):t0], max=q).long()        # columns [t0-(L-1), t0): all that is read before t0
+    hi = torch.clamp(x[:, t1 - (L - 1):t1], max=q).long()
+    G, sx = _assemble(base, s0, lo, hi, L, rows)
+    return Stats(n, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+
+
+def _range_parts(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty, xty):
+    """What the design rows [t0, t1), t1 > t0, give before their edges are known: xty [L*C, K] (written) and -> (base int64
+    [L, C, C], the count products F_d(t0, t1) per lag difference d; s0 int64 [C], the row sums over [t0, t1)).  Both add
+    over adjoining ranges, which _assemble does not need to see one by one: only the first range's columns before t0
+    and the last one's before t1."""
+    from . import _wiener
+    from .gram import batches, enqueue
+    dev, n = x.device, t1 - t0
     # ---- the float part: one call, out [L, C, K] is xty's own layout
     _wiener.xty(x.data_ptr() + t0 - (L - 1), x.stride(0) if rows > 1 else n + L - 1, rows, n, L, q,
                 y.data_ptr() + 4 * (t0 + g), 4 * y.stride(0) if K > 1 else 4 * n, K, xty, scratch_xty)
@@ -151,11 +167,7 @@ def _range_stats(x, rows, y, K, L, g, q, t0, t1, max_bytes, scratch_xty):
                     enqueue(view, rows, nb, None, 0, base[0], s0, None, True, L - 1)
                 else:
                     enqueue(view, rows, nb, view, rows, base[d], None, None, True, L - 1, L - 1 - d)
-    # ---- the edges: at most L - 1 outer products on either side
-    lo = torch.clamp(x[:, t0 - (L - 1):t0], max=q).long()        # columns [t0-(L-1), t0): all that is read before t0
-    hi = torch.clamp(x[:, t1 - (L - 1):t1], max=q).long()
-    G, sx = _assemble(base, s0, lo, hi, L, rows)
-    return Stats(n, sx, G, xty, sum_y, sum_yy, L, g, q, rows)
+    return base, s0
 
 
 def _assemble(base, s0, lo, hi, L, rows):
@@ -218,7 +230,14 @@ def _box_edge(x, e, L, w, q):
 
 def _pure_stats(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty):
     """-> (gram, sum_x, xty) of the design rows [t0, t1) behind the warm-up (t0 >= L-1 + w-1), whose features are the
-    box sums B[c][t-l]: _range_stats with B = lo + 256 hi in the place of the counts.  Per column batch one mhs_box
+    box sums B[c][t-l]: _range_stats with B = lo + 256 hi in the place of the counts"""
+    base, s0, xty = _pure_parts(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty)
+    G, sx = _assemble(base, s0, _box_edge(x, t0, L, w, q), _box_edge(x, t1, L, w, q), L, rows)
+    return G, sx, xty
+
+
+def _pure_parts(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty):
+    """_range_parts for the box sums -> (base, s0, xty [L*C, K]).  Per column batch one mhs_box
     writes the planes [C, nb + L-1]; the Gram matrix is G(lo,lo) + 256 (G(lo,hi) + G(hi,lo)) + 65536 G(hi,hi), 4L - 1
     calls of mhi_gram (L where one plane is enough), and mhw_xty runs once per plane."""
     from . import _wiener, smooth
@@ -256,8 +275,7 @@ def _pure_stats(x, rows, y, K, L, g, q, w, t0, t1, max_bytes, scratch_xty):
         s0, xty = s[0] + 256 * s[1], xt[0] + 256.0 * xt[1]
     else:
         base, s0, xty = acc[0], s[0], xt[0]
-    G, sx = _assemble(base, s0, _box_edge(x, t0, L, w, q), _box_edge(x, t1, L, w, q), L, rows)
-    return G, sx, xty.reshape(F, K)
+    return base, s0, xty.reshape(F, K)
 
 
 def _warm_stats(x, y, L, g, q, a, b):
@@ -359,36 +377,56 @@ def iter_stats_clips(x, y, lags, lead=0, clips=range(2, 40), ranges=None, max_by
     groups = _clip_groups(qs, len(rs), L, rows, max_bytes)
 
     def walk():
-        dev, R, F = x.device, len(rs), L * rows
+        R, F = len(rs), L * rows
         ysum = []
         for t0, t1 in rs:                                           # as _range_stats: the same operations, the same bits
             yr = y[:, t0 + g:t1 + g].double()
             ysum.append((yr.sum(1), yr @ yr.t()))
-        xlo = torch.stack([x[:, t0 - (L - 1):t0] for t0, _t1 in rs]).long()      # [R, C, L-1]: the columns before t0
-        xhi = torch.stack([x[:, t1 - (L - 1):t1] for _t0, t1 in rs]).long()
-        calls = [rs[i:i + _sweep.MAX_RANGES] for i in range(0, R, _sweep.MAX_RANGES)]
         nmax = len(groups[0])
-        scratch = torch.empty((max(_sweep.xty_clips_scratch_bytes(rows, cols, L, K, len(calls[0]), nmax), 8),), dtype=torch.uint8, device=dev)
-        xs, ys = (x.stride(0) if rows > 1 else cols), (4 * y.stride(0) if K > 1 else 4 * cols)
+        scratch = torch.empty((max(_sweep.xty_clips_scratch_bytes(rows, cols, L, K, min(R, _sweep.MAX_RANGES), nmax), 8),),
+                              dtype=torch.uint8, device=x.device)
+        ys = 4 * y.stride(0) if K > 1 else 4 * cols
         for part in groups:
-            n = len(part)
-            base = torch.zeros((R, n, L, rows, rows), dtype=torch.int64, device=dev)
-            s0 = torch.zeros((R, n, rows), dtype=torch.int64, device=dev)
-            xt = torch.empty((R, n, L, rows, K), dtype=torch.float64, device=dev)
-            r0 = 0
-            for sub in calls:
-                m = len(sub)
-                _sweep.gram_clips(x.data_ptr(), xs, rows, cols, sub, part, L, base[r0:r0 + m], s0[r0:r0 + m])
-                _sweep.xty_clips(x.data_ptr(), xs, rows, cols, sub, part, L, g, y.data_ptr(), ys, K, xt[r0:r0 + m], scratch)
-                r0 += m
-            qt = torch.tensor(part, dtype=torch.int64, device=dev).reshape(1, n, 1, 1)
-            G, sx = _assemble_clips(base, s0, torch.minimum(xlo.unsqueeze(1), qt), torch.minimum(xhi.unsqueeze(1), qt), L, rows)
-            del base
+            G, sx, xt = _clips_group(x, rows, cols, y.data_ptr(), ys, K, L, g, rs, part, scratch)
             for i, q in enumerate(part):
                 yield q, [Stats(t1 - t0, sx[r, i], G[r, i], xt[r, i].reshape(F, K), ysum[r][0], ysum[r][1], L, g, q, rows)
                           for r, (t0, t1) in enumerate(rs)]
 
     return walk()
+
+
+def _clips_group(x, rows, cols, y_ptr, ys, K, L, g, rs, part, scratch):
+    """One group of clips over the ranges rs of the checked matrix x: one mhq_gram_clips and one mhq_xty_clips per 16
+    ranges, the edge terms and the assembly batched over (range, clip) -> (gram [R, n, L*C, L*C], sum_x [R, n, L*C], xty
+    [R, n, L, C, K]).  y_ptr: the address of the covariate of column 0, rows ys bytes apart."""
+    xlo = torch.stack([x[:, t0 - (L - 1):t0] for t0, _t1 in rs]).long()      # [R, C, L-1]: the columns before t0
+    xhi = torch.stack([x[:, t1 - (L - 1):t1] for _t0, t1 in rs]).long()
+    base, s0, xt = _clips_parts(x, rows, cols, y_ptr, ys, K, L, g, rs, part, scratch)
+    G, sx = _assemble_group(base, s0, xlo, xhi, part, L, rows)
+    return G, sx, xt
+
+
+def _assemble_group(base, s0, xlo, xhi, part, L, rows):
+    """_assemble_clips for the clips `part`, clamping the raw edge columns xlo, xhi [R, C, L-1] per clip"""
+    qt = torch.tensor(part, dtype=torch.int64, device=base.device).reshape(1, len(part), 1, 1)
+    return _assemble_clips(base, s0, torch.minimum(xlo.unsqueeze(1), qt), torch.minimum(xhi.unsqueeze(1), qt), L, rows)
+
+
+def _clips_parts(x, rows, cols, y_ptr, ys, K, L, g, rs, part, scratch):
+    """_clips_group before the edges -> (base [R, n, L, C, C], s0 [R, n, C], xty [R, n, L, C, K]): what adds over
+    adjoining ranges"""
+    from . import _sweep
+    dev, R, n = x.device, len(rs), len(part)
+    xs = x.stride(0) if rows > 1 else cols
+    base = torch.zeros((R, n, L, rows, rows), dtype=torch.int64, device=dev)
+    s0 = torch.zeros((R, n, rows), dtype=torch.int64, device=dev)
+    xt = torch.empty((R, n, L, rows, K), dtype=torch.float64, device=dev)
+    for r0 in range(0, R, _sweep.MAX_RANGES):
+        sub = rs[r0:r0 + _sweep.MAX_RANGES]
+        m = len(sub)
+        _sweep.gram_clips(x.data_ptr(), xs, rows, cols, sub, part, L, base[r0:r0 + m], s0[r0:r0 + m])
+        _sweep.xty_clips(x.data_ptr(), xs, rows, cols, sub, part, L, g, y_ptr, ys, K, xt[r0:r0 + m], scratch)
+    return base, s0, xt
 
 
 def stats_clips(x, y, lags, lead=0, clips=range(2, 40), ranges=None, max_bytes=MAX_BYTES):
@@ -504,7 +542,19 @@ class WienerFilter:
     def score(self, x, y):
         """-> (rmse [K], cc [K]), float64: the root mean squared error and Pearson's r of the prediction against y over
         the columns where the target exists"""
-        pred = self.predict(x)
+        return self._score(self.predict(x), y)
+
+    def predict_from(self, src):
+        """predict on the bins of a gram.BinSource (archive.Reader.bins, container_io.bins), without holding them ->
+        float32 [K, n - L + 1]: one mhw_fir per batch into its columns of the result, the batch keeping the L-1 bins in
+        front of it; with a window one mhs_box_f32 over the whole raw result, as predict orders the two."""
+        return predict_many_from(src, [self])[0]
+
+    def score_from(self, src, y):
+        """score on the result of predict_from"""
+        return self._score(self.predict_from(src), y)
+
+    def _score(self, pred, y):
         if y.dim() == 1:
             y = y.unsqueeze(0)
         n = pred.shape[1] - self.lead
@@ -516,3 +566,227 @@ class WienerFilter:
         pc, tc = p - p.mean(1, keepdim=True), t - t.mean(1, keepdim=True)
         cc = (pc * tc).sum(1) / torch.sqrt((pc * pc).sum(1) * (tc * tc).sum(1))
         return rmse, cc
+
+
+# ---- the file routes: the same statistics and predictions from a gram.BinSource, batch by batch -----------------------
+def _source(src, who):
+    from .gram import BinSource
+    if not isinstance(src, BinSource):
+        raise ValueError("%s takes a gram.BinSource (archive.Reader.bins, container_io.bins, BinSource.of)" % who)
+    if src.rows < 1 or src.n < 1:
+        raise ValueError("at least one channel and one bin")
+    return src.rows, src.n
+
+
+def _source_covariates(y, src):
+    """_covariates against a source, which has what it reads of the counts: the device and the number of bins"""
+    return _covariates(y, src, src.n)
+
+
+def _zero_stats(rows, K, L, g, q, w, dev):
+    F = L * rows
+    z = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)  # noqa: E731
+    return Stats(0, torch.zeros((F,), dtype=torch.int64, device=dev), torch.zeros((F, F), dtype=torch.int64, device=dev),
+                 z(F, K), z(K), z(K, K), L, g, q, rows, w)
+
+
+def _batch_cols(src, cols):
+    """the most bins a batch of the source's walks brings of its own"""
+    return min(cols, max(src.max_bytes // max(src.rows, 1), 1))
+
+
+def stats_from(src, y, lags, lead=0, clip=None, ranges=None, window=1):
+    """stats() on the bins of a gram.BinSource, without holding them -> [Stats], one per range.  y: float32 [K, src.n] on
+    the source's device, on its bin grid; ranges: design rows in the source's bins, as in stats.  The source is walked
+    once (gram.walk_ranges: the bins no range needs are not read) with a halo of lags-1 + window-1 bins, and per batch
+    the kernels of stats() run on the scratch for what every range has in the batch.  What adds over the pieces of a
+    range is added as it comes -- the count products per lag difference [lags, C, C], the row sums, xty --; the edge
+    terms of adjoining pieces cancel, so the [lags*C, lags*C] matrix is assembled once per range, from the columns in
+    front of its first and of its last row, kept when their batch was resident.  The warm-up rows of window > 1 are
+    relative to the source's first bin: a batch behind the first has its halo in front of every row.  gram, sum_x and n
+    are the integers of stats(read(...), y, ...); xty, sum_y and sum_yy are float64 sums taken batch by batch, in
+    another order.  Next to the walk's scratch a clip or a window takes a clamped copy or the box planes of a batch: up
+    to three times max_bytes in all."""
+    from .gram import walk_ranges
+    rows, cols = _source(src, "wiener.stats_from")
+    y, K = _source_covariates(y, src)
+    L, g = _settings(lags, lead, rows, cols)
+    q = _clip(clip)
+    w = int(window)
+    if w != 1:
+        from .smooth import _window
+        w = _window(w, q)
+    rs = _ranges(ranges, L, g, cols)
+    from . import _wiener
+    scratch = torch.empty((max(_wiener.xty_scratch_bytes(rows, _batch_cols(src, cols), L, K), 8),), dtype=torch.uint8, device=y.device)
+    dev, F, halo = y.device, L * rows, L - 1 + w - 1
+    # per range: [base, s0, xty, lo, hi] of its rows behind the warm-up, (gram, sum_x, xty) of those in it, sum_y, sum_yy
+    pure, warm = [None] * len(rs), [None] * len(rs)
+    sy = [torch.zeros((K,), dtype=torch.float64, device=dev) for _ in rs]
+    syy = [torch.zeros((K, K), dtype=torch.float64, device=dev) for _ in rs]
+    for b0, _nb, h, view, pieces in walk_ranges(src, halo, rs):
+        o = b0 - h                                                  # the view's first bin
+        yv = y[:, o:]
+        for i, a, b in pieces:
+            a0, b0_ = a - o, b - o                                  # the piece in the view's columns
+            yr = yv[:, a0 + g:b0_ + g].double()
+            sy[i] += yr.sum(1)
+            syy[i] += yr @ yr.t()
+            if w > 1 and a0 < halo:                                 # warm-up rows: the view starts at the source's first bin
+                part = _warm_stats(view, yv, L, g, q, a0, min(b0_, halo))
+                warm[i] = part if warm[i] is None else tuple(u + v for u, v in zip(warm[i], part))
+                a0 = min(b0_, halo)
+            if a0 == b0_:
+                continue
+            if w == 1:
+                xty = torch.zeros((F, K), dtype=torch.float64, device=dev)
+                base, s0 = _range_parts(view, rows, yv, K, L, g, q, a0, b0_, src.max_bytes, scratch, xty)
+                edge = lambda e: torch.clamp(view[:, e - (L - 1):e], max=q).long()  # noqa: E731
+            else:
+                base, s0, xty = _pure_parts(view, rows, yv, K, L, g, q, w, a0, b0_, src.max_bytes, scratch)
+                edge = lambda e: _box_edge(view, e, L, w, q)  # noqa: E731
+            if pure[i] is None:
+                pure[i] = [base, s0, xty, edge(a0), None]
+            else:
+                for k, t in enumerate((base, s0, xty)):
+                    pure[i][k] += t
+            if b == rs[i][1]:
+                pure[i][4] = edge(b0_)
+    out = []
+    for i, (t0, t1) in enumerate(rs):
+        if pure[i] is None and warm[i] is None:                     # an empty range
+            out.append(_zero_stats(rows, K, L, g, q, w, dev))
+            continue
+        if pure[i] is None:
+            G, sx, xty = warm[i]
+        else:
+            G, sx = _assemble(pure[i][0], pure[i][1], pure[i][3], pure[i][4], L, rows)
+            xty = pure[i][2]
+            if warm[i] is not None:                                 # in place: no third matrix next to the two
+                G += warm[i][0]
+                sx += warm[i][1]
+                xty += warm[i][2]
+        pure[i] = warm[i] = None
+        out.append(Stats(t1 - t0, sx, G, xty, sy[i], syy[i], L, g, q, rows, w))
+    return out
+
+
+def stats_clips_from(src, y, lags, lead=0, clips=range(2, 40), ranges=None):
+    """stats_clips() on the bins of a gram.BinSource -> [(clip, [Stats per range])], every Stats what stats_from(src, y,
+    lags, lead, clip=q, ranges=ranges) returns: the same integers, xty summed batch by batch.  One walk with a halo of
+    lags-1 bins; per batch and group of clips (the groups of iter_stats_clips, for what the ranges have in the batch) one
+    mhq_gram_clips and one mhq_xty_clips, added into the count products [ranges, clips, lags, C, C] of the walk; the
+    matrices are assembled once at its end, from every range's own edge columns.  The statistics of ALL clips are
+    returned together, ranges * clips * (lags*C)^2 * 8 bytes: cut a long list of clips where that is too much."""
+    from . import _sweep
+    from .gram import walk_ranges
+    rows, cols = _source(src, "wiener.stats_clips_from")
+    y, K = _source_covariates(y, src)
+    L, g = _settings(lags, lead, rows, cols)
+    qs = _clip_list(clips)
+    rs = _ranges(ranges, L, g, cols)
+    if any(b[0] < a[1] for a, b in zip(rs, rs[1:])):
+        raise ValueError("the ranges are ascending and disjoint")
+    dev, R, F = y.device, len(rs), L * rows
+    groups = _clip_groups(qs, R, L, rows, src.max_bytes)
+    base = torch.zeros((R, len(qs), L, rows, rows), dtype=torch.int64, device=dev)
+    s0 = torch.zeros((R, len(qs), rows), dtype=torch.int64, device=dev)
+    xt = torch.zeros((R, len(qs), L, rows, K), dtype=torch.float64, device=dev)
+    xlo = torch.zeros((R, rows, L - 1), dtype=torch.int64, device=dev)           # the raw columns in front of a range's first
+    xhi = torch.zeros((R, rows, L - 1), dtype=torch.int64, device=dev)           # and of its last row, kept as they pass
+    sy = torch.zeros((R, K), dtype=torch.float64, device=dev)
+    syy = torch.zeros((R, K, K), dtype=torch.float64, device=dev)
+    scratch = None
+    ys = 4 * y.stride(0) if K > 1 else 4 * cols
+    for b0, _nb, h, view, pieces in walk_ranges(src, L - 1, rs):
+        o, width = b0 - h, int(view.shape[1])
+        idx = torch.tensor([i for i, _a, _b in pieces], dtype=torch.int64, device=dev)
+        local = [(a - o, b - o) for _i, a, b in pieces]
+        for i, a, b in pieces:
+            yr = y[:, a + g:b + g].double()
+            sy[i] += yr.sum(1)
+            syy[i] += yr @ yr.t()
+            if a == rs[i][0]:
+                xlo[i] = view[:, a - o - (L - 1):a - o]
+            if b == rs[i][1]:
+                xhi[i] = view[:, b - o - (L - 1):b - o]
+        need =max(_sweep.xty_clips_scratch_bytes(rows, width, L, K, min(len(local), _sweep.MAX_RANGES), len(groups[0])), 8)
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
+        c0 = 0
+        for part in groups:                                         # the lead is in the address: column t meets y[t + g]
+            pb, ps, px = _clips_parts(view, rows, width, y.data_ptr() + 4 * (o + g), ys, K, L, 0, local, part, scratch)
+            base[idx, c0:c0 + len(part)] += pb
+            s0[idx, c0:c0 + len(part)] += ps
+            xt[idx, c0:c0 + len(part)] += px
+            c0 += len(part)
+    out, c0 = [], 0
+    for part in groups:                                             # assembled once per range and clip, from the range's own edges
+        G, sx = _assemble_group(base[:, c0:c0 + len(part)], s0[:, c0:c0 + len(part)], xlo, xhi, part, L, rows)
+        for i, q in enumerate(part):
+            out.append((q, [Stats(t1 - t0, sx[r, i], G[r, i], xt[r, c0 + i].reshape(F, K), sy[r], syy[r], L, g, q, rows)
+                            for r, (t0, t1) in enumerate(rs)]))
+        c0 += len(part)
+    return out
+
+
+def _fitted(src, filters, who):
+    rows, cols = _source(src, who)
+    for f in filters:
+        if not isinstance(f, WienerFilter) or f.weights is None:
+            raise ValueError("predict comes after fit")
+        if rows != f.channels:
+            raise ValueError("the filter was fitted on %d channels, not %d" % (f.channels, rows))
+        if cols < f.lags:
+            raise ValueError("%d bins are fewer than the %d lags" % (cols, f.lags))
+    return rows, cols
+
+
+def iter_predict_from(src, filters):
+    """predict_many_from as a generator, one prediction at a time in the order of `filters`: what a group's pass made is
+    handed out before the next group's pass begins."""
+    from . import _wiener
+    from .gram import walk
+    filters = list(filters)
+    rows, cols = _fitted(src, filters, "wiener.predict_many_from")
+    dev = src.device
+    size = lambda f: 4 * int(f.weights.shape[0]) * (cols - f.lags + 1) * (2 if f.window > 1 else 1)  # noqa: E731
+    groups, room = [], 0
+    for f in filters:
+        if groups and room + size(f) <= src.max_bytes:
+            groups[-1].append(f)
+            room += size(f)
+        else:
+            groups.append([f])
+            room = size(f)
+    for group in groups:
+        jobs = []
+        for f in group:
+            K, L = int(f.weights.shape[0]), f.lags
+            w = f.weights.to(device=dev, dtype=torch.float32).contiguous()
+            b = f.bias.to(device=dev, dtype=torch.float32).contiguous()
+            raw = torch.empty((K, cols - L + 1), dtype=torch.float32, device=dev)
+            jobs.append((f, K, L, w, b, torch.zeros_like(b) if f.window > 1 else b, raw))
+        for b0, nb, h, view in walk(src, max(f.lags for f in group) - 1):
+            o, pitch = b0 - h, (view.stride(0) if rows > 1 else int(view.shape[1]))
+            for f, K, L, w, _b, b_fir, raw in jobs:
+                first = max(b0, L - 1)                              # the first design row of this batch
+                m = b0 + nb - first
+                if m > 0:
+                    _wiener.fir(view.data_ptr() + first - o - (L - 1), pitch, rows, m, L, f.clip, w, b_fir, K,
+                                raw[:, first - (L - 1):first - (L - 1) + m])
+        while jobs:
+            f, K, L, w, b, _b_fir, raw = jobs.pop(0)
+            if f.window > 1:
+                from . import _smooth
+                out = torch.empty_like(raw)
+                _smooth.box_f32(raw, f.window, b, out)
+                raw = out
+            yield raw
+
+
+def predict_many_from(src, filters):
+    """WienerFilter.predict_from for several fitted filters -> [float32 [K, n - L + 1]] in their order: every batch of
+    the source meets, while it is resident, one mhw_fir per filter.  One pass over the source per group of filters whose
+    results (twice that with a window) fit the source's max_bytes; at least one filter a pass."""
+    return list(iter_predict_from(src, filters))
