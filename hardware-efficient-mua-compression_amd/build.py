@@ -52,6 +52,12 @@ KALMAN_SO = os.path.join(HERE, "libmuahuff_kalman.so")
 KALMAN_SOURCES = ["csrc/mh_kalman.hip"]
 KALMAN_HEADERS = ["csrc/exports_kalman.map", "csrc/mh_kalman.hpp", "csrc/mh_kalman_layout.hpp", "csrc/mh_msg.hpp",
                   "../include/muahuff.h", "../include/muahuff_kalman.h"]
+# the seventh companion (include/muahuff_lstm.h): the prediction of an LSTM decoder, the input half of the gate
+# pre-activations once per bin and the recurrence over every window
+LSTM_SO = os.path.join(HERE, "libmuahuff_lstm.so")
+LSTM_SOURCES = ["csrc/mh_lstm.hip"]
+LSTM_HEADERS = ["csrc/exports_lstm.map", "csrc/mh_lstm.hpp", "csrc/mh_lstm_layout.hpp", "csrc/mh_msg.hpp",
+                "../include/muahuff.h", "../include/muahuff_lstm.h"]
 
 
 def stale():
@@ -184,6 +190,24 @@ def build_kalman(force=False, verbose=False):
     return KALMAN_SO
 
 
+def build_lstm(force=False, verbose=False):
+    """libmuahuff_lstm.so, exporting the C ABI of include/muahuff_lstm.h and nothing else
+    (csrc/exports_lstm.map); the flags of libmuahuff.so."""
+    if not force and os.path.exists(LSTM_SO):
+        t = os.path.getmtime(LSTM_SO)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in LSTM_SOURCES + LSTM_HEADERS):
+            return LSTM_SO
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
+           "-Wl,--version-script=" + os.path.join(HERE, "csrc", "exports_lstm.map")]
+    cmd += [os.path.join(HERE, s) for s in LSTM_SOURCES] + ["-o", LSTM_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=HERE)
+    return LSTM_SO
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -206,3 +230,4 @@ if __name__ == "__main__":
     print(build_smooth(force=True, verbose=True))
     print(build_sweep(force=True, verbose=True))
     print(build_kalman(force=True, verbose=True))
+    print(build_lstm(force=True, verbose=True))
