@@ -3,12 +3,9 @@ binned counts in front of the codec, per-segment payload checksums and the way b
 import ctypes as ct
 import os
 
-from ._lib import MH_OK, MuaHuffError
+from ._loader import HERE, Library, _int, _u32, _u64, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libmuahuff_ingest.so")
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff_ingest.h declares, with its prototype
 PROTOTYPES = {
@@ -34,30 +31,8 @@ EXCESS_ROWS, EXCESS_COLS = 0, 1   # MHI_EXCESS_ROWS, MHI_EXCESS_COLS
 UNBIN_CSR, UNBIN_AER = 0, 1       # MHI_UNBIN_CSR, MHI_UNBIN_AER
 AER_MAX_CHANNELS = 16384  # MHI_AER_MAX_CHANNELS
 
-_lib = None
-
-
-def lib():
-    """Load libmuahuff_ingest.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff_ingest.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mhi_last_error().decode(errors="replace"))
-    return rc
+_library = Library(globals(), "libmuahuff_ingest.so", "mhi_last_error")
+lib, check = _library.lib, _library.check
 
 
 def bin_events(ev, origin, period, T, bits, out, d_off, chunk_stride=0):

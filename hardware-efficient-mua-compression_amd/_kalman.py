@@ -4,12 +4,9 @@ of columns.  Fails loudly: there is no CPU path."""
 import ctypes as ct
 import os
 
-from ._lib import MH_OK, MuaHuffError
+from ._loader import HERE, Library, _int, _u32, _u64, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libmuahuff_kalman.so")
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff_kalman.h declares, with its prototype
 PROTOTYPES = {
@@ -24,30 +21,8 @@ PROTOTYPES = {
 MAX_K, MAX_ROWS, MAX_GAINS, MAX_RANGES = 8, 65536, 4096, 16
 PROJ_TILE_COLS, PROJ_MAX_BLOCKS, SCAN_TILE, SCAN_THREADS, SCAN_MAX_BLOCKS = 1024, 4096, 512, 64, 512
 
-_lib = None
-
-
-def lib():
-    """Load libmuahuff_kalman.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff_kalman.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mhk_last_error().decode(errors="replace"))
-    return rc
+_library = Library(globals(), "libmuahuff_kalman.so", "mhk_last_error")
+lib, check = _library.lib, _library.check
 
 
 def _rows(t, what):

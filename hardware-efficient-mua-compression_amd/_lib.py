@@ -2,10 +2,10 @@
 import ctypes as ct
 import os
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from ._loader import HERE, MH_OK, Library, MuaHuffError, _int, _u32, _u64, _vp  # noqa: F401
+
 SO = os.path.join(HERE, "libmuahuff.so")
 
-MH_OK = 0
 ERR_ARG, ERR_EMPTY_CHANNEL, ERR_SCLV, ERR_CAPACITY, ERR_HIP, ERR_NO_DEVICE, ERR_STREAM = -1, -2, -3, -4, -5, -6, -7
 
 MODE_NOSORT, MODE_APPROX = 0, 1
@@ -18,18 +18,10 @@ CHUNK = SUB * LANES
 HDR_WORDS = LANES // 2
 
 
-class MuaHuffError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("libmuahuff error %d: %s" % (code, msg))
-        self.code = code
-
-
 class PlanInfo(ct.Structure):
     _fields_ = [(n, ct.c_uint32) for n in ("C", "S", "h", "mode", "window", "K", "seg_chunks", "maxlen")] + \
                [(n, ct.c_uint64) for n in ("n_segments", "payload_cap_words", "window_samples", "n_skipped")]
 
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff.h declares, with its prototype
 PROTOTYPES = {
@@ -70,42 +62,17 @@ PROTOTYPES = {
     "mh_sweep_run": (_int, [_vp, _vp, _vp, _vp]),
 }
 
-_lib = None
+_library = Library(globals(), "libmuahuff.so", "mh_last_error")
+lib, check = _library.lib, _library.check
 
 
 def use_library(path):
     """Load the kernels from another build of libmuahuff.so (same-box A/B runs in tools/).  Must be
     called before the first use; there is no environment override."""
-    global SO, _lib
-    if _lib is not None:
+    global SO
+    if _library.handle is not None:
         raise RuntimeError("libmuahuff.so is already loaded")
     SO = str(path)
-
-
-def lib():
-    """Load libmuahuff.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        # torch first: its wheel bundles the HIP runtime, and a process must not end up with two of them -- a
-        # libmuahuff.so loaded before torch binds the system libamdhip64, torch then brings its own, and the
-        # library's runtime finds no device (seen as MH_ERR_NO_DEVICE when build() and smoke() share a process)
-        import torch  # noqa: F401
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mh_last_error().decode(errors="replace"))
-    return rc
 
 
 def device_info(device=0):

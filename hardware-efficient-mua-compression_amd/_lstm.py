@@ -4,12 +4,9 @@ of an LSTM decoder, the input half of the gate pre-activations once per bin and 
 import ctypes as ct
 import os
 
-from ._lib import MH_OK, MuaHuffError
+from ._loader import HERE, Library, _int, _u32, _u64, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libmuahuff_lstm.so")
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff_lstm.h declares, with its prototype
 PROTOTYPES = {
@@ -24,30 +21,8 @@ MAX_UNITS, MAX_LAGS, MAX_K, MAX_ROWS = 128, 32, 8, 65536
 IN_TILE_COLS, IN_GTILE, IN_MAX_BLOCKS = 512, 32, 8192
 WIN_TILE, WIN_WAVES, WIN_BLOCK_UNITS, WIN_KGROUP, WIN_MAX_BLOCKS = 32, 8, 8, 8, 4096
 
-_lib = None
-
-
-def lib():
-    """Load libmuahuff_lstm.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff_lstm.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mhl_last_error().decode(errors="replace"))
-    return rc
+_library = Library(globals(), "libmuahuff_lstm.so", "mhl_last_error")
+lib, check = _library.lib, _library.check
 
 
 def inproj_bytes(cols, units):

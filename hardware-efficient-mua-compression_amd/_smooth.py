@@ -4,12 +4,9 @@ there is no CPU path."""
 import ctypes as ct
 import os
 
-from ._lib import MH_OK, MuaHuffError
+from ._loader import HERE, Library, _int, _u32, _u64, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libmuahuff_smooth.so")
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff_smooth.h declares, with its prototype
 PROTOTYPES = {
@@ -22,30 +19,8 @@ PROTOTYPES = {
 MAX_WINDOW, MAX_K, MAX_ROWS, TILE_COLS, MAX_BLOCKS = 256, 8, 65536, 3824, 2048
 MAX_SUM = 65535  # window * clip at most: a box sum fits two byte planes
 
-_lib = None
-
-
-def lib():
-    """Load libmuahuff_smooth.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff_smooth.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mhs_last_error().decode(errors="replace"))
-    return rc
+_library = Library(globals(), "libmuahuff_smooth.so", "mhs_last_error")
+lib, check = _library.lib, _library.check
 
 
 def box(x_ptr, x_row_stride, rows, cols, window, clip, lo, hi):

@@ -4,12 +4,9 @@ no CPU path."""
 import ctypes as ct
 import os
 
-from ._lib import MH_OK, MuaHuffError
+from ._loader import HERE, Library, _int, _u32, _u64, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libmuahuff_wiener.so")
-
-_vp, _u32, _u64, _int = ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_int
 
 # every symbol include/muahuff_wiener.h declares, with its prototype
 PROTOTYPES = {
@@ -21,30 +18,8 @@ PROTOTYPES = {
 }
 MAX_LAGS, MAX_K, MAX_ROWS = 32, 8, 65536  # mh_wiener_layout.hpp: kWienerMaxLags, kWienerMaxK, kWienerMaxRows
 
-_lib = None
-
-
-def lib():
-    """Load libmuahuff_wiener.so.  Raises if it has not been built: the product has no fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO):
-            raise ImportError(
-                "libmuahuff_wiener.so is missing (%s). Build it with `python __graft_entry__.py` or "
-                "`python hardware-efficient-mua-compression_amd/build.py`; there is no CPU fallback." % SO)
-        import torch  # noqa: F401  (first, as in _lib.lib(): one HIP runtime per process)
-        l = ct.CDLL(SO)
-        for name, (res, args) in PROTOTYPES.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != MH_OK:
-        raise MuaHuffError(rc, lib().mhw_last_error().decode(errors="replace"))
-    return rc
+_library = Library(globals(), "libmuahuff_wiener.so", "mhw_last_error")
+lib, check = _library.lib, _library.check
 
 
 def xty_scratch_bytes(rows, cols, lags, k):

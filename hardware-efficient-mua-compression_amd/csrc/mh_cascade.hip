@@ -3,9 +3,7 @@
 // rule and no grid is worked out here.  A companion of libmuahuff.so, not part of it; there is no CPU fallback here either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
+#include "mh_abi.hpp"
 #include "mh_cascade.hpp"
 #include "mh_cascade_layout.hpp"
 // built with -fvisibility=hidden: the mhc_* functions of the header are ALL the library exports
@@ -14,28 +12,6 @@
 #pragma GCC visibility pop
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// what the host-only header reported
-int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
-
-// how every entry point ends: MH_OK, or what its launches left behind.  `fn` names the entry point.
-int launched(const char *fn)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return MH_OK;
-}
 
 template <int D>
 void moments_launch(const mh::MomParams &p, uint32_t grid, hipStream_t st)

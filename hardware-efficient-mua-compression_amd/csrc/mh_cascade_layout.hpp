@@ -18,20 +18,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_CASCADE_HD __host__ __device__
-#else
-#define MH_CASCADE_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
 constexpr uint32_t kCascadeMaxK = 8;
 constexpr uint32_t kCascadeMaxDegree = 6;
-constexpr uint64_t kCascadeMaxCols = 1ull << 40;  // cols is below this
 
 constexpr uint32_t kMomMaxRanges = 16;
 constexpr uint32_t kMomThreads = 256;      // 4 waves
@@ -91,13 +83,13 @@ struct PolyLayout {
     uint32_t grid;
 };
 
-MH_CASCADE_HD inline uint32_t mom_per(uint32_t degree) { return 3 * degree + 4; }
+MH_HD inline uint32_t mom_per(uint32_t degree) { return 3 * degree + 4; }
 
 // the limits mhc_moments and its scratch size share; `fn` names the call
 inline int mom_shape_check(Msg &m, const char *fn, uint64_t cols, uint32_t k, uint32_t degree, uint32_t n_ranges)
 {
-    if (k < 1 || k > kCascadeMaxK) return m.set(MH_ERR_ARG, "%s: k=%u outside 1..%u", fn, k, kCascadeMaxK);
-    if (cols < 1 || cols >= kCascadeMaxCols) return m.set(MH_ERR_ARG, "%s: cols=%llu outside 1..2^40-1", fn, (unsigned long long)cols);
+    if (int rc = k_rule(m, fn, k, kCascadeMaxK)) return rc;
+    if (int rc = cols_rule(m, fn, cols)) return rc;
     if (degree < 1 || degree > kCascadeMaxDegree) return m.set(MH_ERR_ARG, "%s: degree=%u outside 1..%u", fn, degree, kCascadeMaxDegree);
     if (n_ranges < 1 || n_ranges > kMomMaxRanges) return m.set(MH_ERR_ARG, "%s: n_ranges=%u outside 1..%u", fn, n_ranges, kMomMaxRanges);
     return MH_OK;
@@ -141,7 +133,7 @@ inline void mom_layout(const uint64_t *ranges, uint32_t n_ranges, uint32_t k, ui
 }
 
 // the range a run belongs to and its columns [c0, c1); run < R.run_first[kMomMaxRanges]
-MH_CASCADE_HD inline uint32_t mom_run_cols(const MomRanges &R, uint64_t run, uint64_t *c0, uint64_t *c1)
+MH_HD inline uint32_t mom_run_cols(const MomRanges &R, uint64_t run, uint64_t *c0, uint64_t *c1)
 {
     uint32_t r = 0;
     while (run >= R.run_first[r + 1]) ++r;  // at most kMomMaxRanges - 1 steps: run_first[kMomMaxRanges] is above run
@@ -189,8 +181,8 @@ inline void poly_layout(uint64_t cols, uint32_t k, PolyLayout *L)
 inline int poly_check(Msg &m, const PolyArgs &a)
 {
     if (!a.p || !a.coef || !a.out) return m.set(MH_ERR_ARG, "mhc_polyval: NULL pointer");
-    if (a.k < 1 || a.k > kCascadeMaxK) return m.set(MH_ERR_ARG, "mhc_polyval: k=%u outside 1..%u", a.k, kCascadeMaxK);
-    if (a.cols < 1 || a.cols >= kCascadeMaxCols) return m.set(MH_ERR_ARG, "mhc_polyval: cols=%llu outside 1..2^40-1", (unsigned long long)a.cols);
+    if (int rc = k_rule(m, "mhc_polyval", a.k, kCascadeMaxK)) return rc;
+    if (int rc = cols_rule(m, "mhc_polyval", a.cols)) return rc;
     if (a.degree < 1 || a.degree > kCascadeMaxDegree)
         return m.set(MH_ERR_ARG, "mhc_polyval: degree=%u outside 1..%u", a.degree, kCascadeMaxDegree);
     if (a.p % 4 || a.p_row_stride % 4 || a.out % 4 || a.out_row_stride % 4)
@@ -202,13 +194,13 @@ inline int poly_check(Msg &m, const PolyArgs &a)
     // in place (the same rows) is the one overlap of p and out that is allowed; the strides are below 2^60 here or the
     // sums below wrap, which only refuses more
     const uint64_t row = 4 * a.cols;
-    const uint64_t p_end = a.p + (a.k - 1) * (a.k > 1 ? a.p_row_stride : 0) + row;
-    const uint64_t o_end = a.out + (a.k - 1) * (a.k > 1 ? a.out_row_stride : 0) + row;
+    const uint64_t p_end = strided_end(a.p, a.k, a.p_row_stride, row);
+    const uint64_t o_end = strided_end(a.out, a.k, a.out_row_stride, row);
     const bool in_place = a.p == a.out && (a.k == 1 || a.p_row_stride == a.out_row_stride);
-    if (!in_place && a.p < o_end && a.out < p_end)
+    if (!in_place && ranges_overlap(a.p, p_end, a.out, o_end))
         return m.set(MH_ERR_ARG, "mhc_polyval: out overlaps p without being p itself with the same row stride");
     const uint64_t c_end = a.coef + 4ull * a.k * (a.degree + 1);
-    if (a.coef < o_end && a.out < c_end) return m.set(MH_ERR_ARG, "mhc_polyval: out overlaps coef");
+    if (ranges_overlap(a.coef, c_end, a.out, o_end)) return m.set(MH_ERR_ARG, "mhc_polyval: out overlaps coef");
     return MH_OK;
 }
 

@@ -19,14 +19,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_GRAM_HD __host__ __device__
-#else
-#define MH_GRAM_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
@@ -43,7 +36,7 @@ constexpr uint32_t kGramXcds = 8;
 constexpr uint32_t kGramMaxBlocks = 2048;  // the grid is capped; the kernel strides
 constexpr uint32_t kGramTargetItems = 4096;
 static_assert(kGramMaxBlocks % kGramXcds == 0, "every XCD takes the same share of the grid");
-constexpr uint64_t kGramMaxCols = 1ull << 40;  // cols is below this
+constexpr uint64_t kGramMaxCols = kMaxCols;
 constexpr uint64_t kGramMaxRows = 1ull << 31;  // a_rows and b_rows are at most this
 
 // mhi_gram's arguments, pointers as plain addresses: nothing here reads through them
@@ -125,13 +118,13 @@ inline void gram_layout(uint64_t a_rows, uint64_t b_rows, uint64_t cols, bool sy
 }
 
 // the first item of workgroup `block`; it goes on with item += grid while item < items
-MH_GRAM_HD inline uint64_t gram_first_item(uint32_t block, uint32_t grid)
+MH_HD inline uint64_t gram_first_item(uint32_t block, uint32_t grid)
 {
     return (uint64_t)(block % kGramXcds) * (grid / kGramXcds) + block / kGramXcds;
 }
 
 // item -> its tile and its columns
-MH_GRAM_HD inline GramItem gram_owner(uint32_t symmetric, uint32_t nta, uint32_t ntb, uint64_t tiles, uint32_t run_slices,
+MH_HD inline GramItem gram_owner(uint32_t symmetric, uint32_t nta, uint32_t ntb, uint64_t tiles, uint32_t run_slices,
                                       uint64_t cols, uint64_t item)
 {
     GramItem it;

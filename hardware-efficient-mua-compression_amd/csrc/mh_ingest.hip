@@ -5,9 +5,7 @@
 // CPU fallback here either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
+#include "mh_abi.hpp"
 #include "mh_aer.hpp"
 #include "mh_aer_layout.hpp"
 #include "mh_crc.hpp"
@@ -28,28 +26,6 @@
 #pragma GCC visibility pop
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// what a host-only header reported
-int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
-
-// how every entry point ends: MH_OK, or what its launches left behind.  `fn` names the entry point.
-int launched(const char *fn)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return MH_OK;
-}
 
 static_assert(mh::kGeoCrcWaves == mh::kCrcWaves && mh::kCrcMaxX == mh::kCrcMaxGroups, "mh_launch.hpp sizes the grid by mh_crc.hpp's constants");
 static_assert(mh::kGeoApplyThreads == mh::kApplyThreads && mh::kGeoApplyMaxBlocks == mh::kApplyMaxBlocks,

@@ -3,9 +3,7 @@
 // and no grid is worked out here.  A companion of libmuahuff.so, not part of it; there is no CPU fallback here either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
+#include "mh_abi.hpp"
 #include "mh_kalman.hpp"
 #include "mh_kalman_layout.hpp"
 // built with -fvisibility=hidden: the mhk_* functions of the header are ALL the library exports
@@ -14,28 +12,6 @@
 #pragma GCC visibility pop
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// what the host-only header reported
-int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
-
-// how every entry point ends: MH_OK, or what its launch left behind.  `fn` names the entry point.
-int launched(const char *fn)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return MH_OK;
-}
 
 template <int K>
 void launch_project(const mh::ProjectParams &q, uint32_t grid, hipStream_t st)
@@ -52,18 +28,6 @@ void launch_scan(const mh::ScanParams &q, hipStream_t st)
 }
 
 }  // namespace
-
-#define MH_KALMAN_DISPATCH(k, call) \
-    switch (k) {                    \
-        case 1: call(1); break;     \
-        case 2: call(2); break;     \
-        case 3: call(3); break;     \
-        case 4: call(4); break;     \
-        case 5: call(5); break;     \
-        case 6: call(6); break;     \
-        case 7: call(7); break;     \
-        default: call(8); break;    \
-    }
 
 extern "C" {
 
@@ -82,9 +46,7 @@ int mhk_project(const uint8_t *x, uint64_t x_row_stride, uint64_t rows, uint64_t
     hipStream_t st = (hipStream_t)stream;
     const mh::ProjectParams q = {x, rows > 1 ? x_row_stride : 0, (uint32_t)rows, cols, clip, m, m0, reinterpret_cast<uint8_t *>(v),
                                  k > 1 ? v_row_stride : 0, L.tiles};
-#define MH_CALL(K) launch_project<K>(q, L.grid, st)
-    MH_KALMAN_DISPATCH(k, MH_CALL)
-#undef MH_CALL
+    dispatch_k(k, [&](auto K) { launch_project<K>(q, L.grid, st); });
     return launched("mhk_project");
 }
 
@@ -108,9 +70,7 @@ int mhk_scan(const double *v, uint64_t v_row_stride, uint32_t k, uint64_t cols, 
                         k > 1 ? out_row_stride : 0, static_cast<double *>(scratch), {}};
     mh::scan_layout(ranges, n_ranges, k, &q.L);  // the ranges by value, their tiles and the capped grid (mh_kalman_layout.hpp)
     hipStream_t st = (hipStream_t)stream;
-#define MH_CALL(K) launch_scan<K>(q, st)
-    MH_KALMAN_DISPATCH(k, MH_CALL)
-#undef MH_CALL
+    dispatch_k(k, [&](auto K) { launch_scan<K>(q, st); });
     return launched("mhk_scan");
 }
 

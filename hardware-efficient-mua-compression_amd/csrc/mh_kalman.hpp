@@ -35,23 +35,6 @@ struct ProjectParams {
     uint64_t v_row_stride, tiles;
 };
 
-// the bytes of the columns t .. t + 3 of a row as one dword, byte b in bits 8 b; columns from cols on read as 0
-__device__ inline uint32_t proj_load4(const uint8_t *row, uint64_t t, uint64_t cols)
-{
-    const uint32_t sh = (uint32_t)((uintptr_t)row & 3);  // t is a multiple of 4
-    if (proj_dwords_ok(t, sh, cols)) {
-        const uint32_t *const a0 = reinterpret_cast<const uint32_t *>(row + t - sh);
-        const uint32_t lo = a0[0];
-        if (sh == 0) return lo;
-        return (uint32_t)((((uint64_t)a0[1] << 32) | lo) >> (8 * sh));
-    }
-    uint32_t d = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b)
-        if (t + b < cols) d |= (uint32_t)row[t + b] << (8 * b);
-    return d;
-}
-
 template <int K>
 __device__ inline void proj_add(double (&acc)[K][4], uint32_t d, uint32_t clip, const double *m, uint32_t rows, uint32_t c)
 {
@@ -85,11 +68,11 @@ __global__ __launch_bounds__(kProjThreads) void k_project(ProjectParams p)
         for (; c + U <= p.rows; c += U) {
             uint32_t d[U];
 #pragma unroll
-            for (uint32_t i = 0; i < U; ++i) d[i] = proj_load4(p.x + (uint64_t)(c + i) * p.x_row_stride, t, p.cols);
+            for (uint32_t i = 0; i < U; ++i) d[i] = load4(p.x + (uint64_t)(c + i) * p.x_row_stride, t, p.cols);
 #pragma unroll
             for (uint32_t i = 0; i < U; ++i) proj_add<K>(acc, d[i], p.clip, p.m, p.rows, c + i);
         }
-        for (; c < p.rows; ++c) proj_add<K>(acc, proj_load4(p.x + (uint64_t)c * p.x_row_stride, t, p.cols), p.clip, p.m, p.rows, c);
+        for (; c < p.rows; ++c) proj_add<K>(acc, load4(p.x + (uint64_t)c * p.x_row_stride, t, p.cols), p.clip, p.m, p.rows, c);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             double *const o = reinterpret_cast<double *>(p.v + (uint64_t)j * p.v_row_stride) + t;

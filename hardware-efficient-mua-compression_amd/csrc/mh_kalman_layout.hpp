@@ -7,7 +7,7 @@
 //
 // mhk_project.  The columns are cut into TILES of kProjTileCols = 4 * kProjThreads; thread t of a workgroup owns the 4
 // columns from 4 t on of its tile and walks the channels.  The 4 bytes of a channel come from the aligned dwords that hold
-// them where both lie inside the row (proj_dwords_ok), byte by byte otherwise: nothing outside a row's cols bytes is read.
+// them where both lie inside the row (dwords_ok of mh_rows.hpp), byte by byte otherwise: nothing outside a row's cols bytes is read.
 // The grid is capped at kProjMaxBlocks; workgroup b starts at tile b and strides by the grid.
 //
 // mhk_scan.  A range [a, b) has b - a - 1 STEPS, step i at column a + 1 + i with gain min(i, n_gain - 1).  The steps are cut
@@ -19,21 +19,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_KALMAN_HD __host__ __device__
-#else
-#define MH_KALMAN_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
 constexpr uint32_t kKalmanMaxK = 8;
 constexpr uint64_t kKalmanMaxRows = 65536;
-constexpr uint64_t kKalmanMaxCols = 1ull << 40;    // cols is below this
-constexpr uint64_t kKalmanMaxStride = 1ull << 48;  // a row stride is below this: rows * stride stays inside 64 bits
 constexpr uint32_t kKalmanMaxGains = 4096;
 constexpr uint32_t kKalmanMaxRanges = 16;
 
@@ -47,7 +38,7 @@ constexpr uint32_t kScanThreads = 64;               // one wave: a thread owns a
 constexpr uint32_t kScanTile = 512;                 // steps of a tile
 constexpr uint32_t kScanMaxBlocks = 512;            // the grids of kernels 1 and 3 are capped; they stride
 
-MH_KALMAN_HD inline uint32_t scan_per_tile(uint32_t k) { return k * (k + 2); }
+MH_HD inline uint32_t scan_per_tile(uint32_t k) { return k * (k + 2); }
 
 // the arguments, pointers as plain addresses: nothing here reads through them
 struct ProjectArgs {
@@ -90,47 +81,36 @@ inline void project_layout(uint64_t cols, ProjectLayout *L)
     L->grid = (uint32_t)(L->tiles < kProjMaxBlocks ? L->tiles : kProjMaxBlocks);
 }
 
-// May the 4 columns from t on (t a multiple of 4, t < cols) of a row whose first byte sits `sh` = 0..3 bytes behind a dword
-// boundary be taken from aligned dwords?  They lie in the dword at byte t - sh of the row and, with sh > 0, the next one:
-// both must lie inside the row's cols bytes.
-MH_KALMAN_HD inline bool proj_dwords_ok(uint64_t t, uint32_t sh, uint64_t cols)
-{
-    return sh == 0 ? t + 4 <= cols : (t >= sh && t - sh + 8 <= cols);
-}
-
-inline bool kalman_overlap(uint64_t a, uint64_t a_end, uint64_t b, uint64_t b_end) { return a < b_end && b < a_end; }
-
 // MH_OK, or MH_ERR_ARG with the text in m: every rule of the header's comment, before any device work
 inline int project_check(Msg &m, const ProjectArgs &a)
 {
     if (!a.x || !a.m || !a.v) return m.set(MH_ERR_ARG, "mhk_project: NULL pointer");
-    if (a.k < 1 || a.k > kKalmanMaxK) return m.set(MH_ERR_ARG, "mhk_project: k=%u outside 1..%u", a.k, kKalmanMaxK);
-    if (a.rows < 1 || a.rows > kKalmanMaxRows)
-        return m.set(MH_ERR_ARG, "mhk_project: rows=%llu outside 1..%llu", (unsigned long long)a.rows, (unsigned long long)kKalmanMaxRows);
-    if (a.cols < 1 || a.cols >= kKalmanMaxCols) return m.set(MH_ERR_ARG, "mhk_project: cols=%llu outside 1..2^40-1", (unsigned long long)a.cols);
-    if (a.clip < 1 || a.clip > 255) return m.set(MH_ERR_ARG, "mhk_project: clip=%u outside 1..255", a.clip);
+    if (int rc = k_rule(m, "mhk_project", a.k, kKalmanMaxK)) return rc;
+    if (int rc = rows_rule(m, "mhk_project", a.rows, kKalmanMaxRows)) return rc;
+    if (int rc = cols_rule(m, "mhk_project", a.cols)) return rc;
+    if (int rc = clip_rule(m, "mhk_project", a.clip)) return rc;
     if (a.m % 8 || a.m0 % 8 || a.v % 8 || a.v_row_stride % 8)
         return m.set(MH_ERR_ARG, "mhk_project: m, m0, v and v_row_stride must be multiples of 8");
-    if (a.rows > 1 && (a.x_row_stride < a.cols || a.x_row_stride >= kKalmanMaxStride))
+    if (a.rows > 1 && (a.x_row_stride < a.cols || a.x_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhk_project: x_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.x_row_stride, (unsigned long long)a.cols);
-    if (a.k > 1 && (a.v_row_stride < 8 * a.cols || a.v_row_stride >= kKalmanMaxStride))
+    if (a.k > 1 && (a.v_row_stride < 8 * a.cols || a.v_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhk_project: v_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.v_row_stride, (unsigned long long)(8 * a.cols));
-    const uint64_t x_end = a.x + (a.rows - 1) * (a.rows > 1 ? a.x_row_stride : 0) + a.cols;
-    const uint64_t v_end = a.v + (a.k - 1) * (a.k > 1 ? a.v_row_stride : 0) + 8 * a.cols;
-    if (kalman_overlap(a.v, v_end, a.x, x_end) || kalman_overlap(a.v, v_end, a.m, a.m + 8 * a.k * a.rows) ||
-        (a.m0 && kalman_overlap(a.v, v_end, a.m0, a.m0 + 8ull * a.k)))
+    const uint64_t x_end = strided_end(a.x, a.rows, a.x_row_stride, a.cols);
+    const uint64_t v_end = strided_end(a.v, a.k, a.v_row_stride, 8 * a.cols);
+    if (ranges_overlap(a.v, v_end, a.x, x_end) || ranges_overlap(a.v, v_end, a.m, a.m + 8 * a.k * a.rows) ||
+        (a.m0 && ranges_overlap(a.v, v_end, a.m0, a.m0 + 8ull * a.k)))
         return m.set(MH_ERR_ARG, "mhk_project: v overlaps x, m or m0");
     return MH_OK;
 }
 
 // ---- mhk_scan ---------------------------------------------------------------------------------------------------------------
-MH_KALMAN_HD inline uint64_t scan_range_steps(uint64_t a, uint64_t b) { return b - a > 1 ? b - a - 1 : 0; }
-MH_KALMAN_HD inline uint64_t scan_range_tiles(uint64_t a, uint64_t b) { return (scan_range_steps(a, b) + kScanTile - 1) / kScanTile; }
+MH_HD inline uint64_t scan_range_steps(uint64_t a, uint64_t b) { return b - a > 1 ? b - a - 1 : 0; }
+MH_HD inline uint64_t scan_range_tiles(uint64_t a, uint64_t b) { return (scan_range_steps(a, b) + kScanTile - 1) / kScanTile; }
 
 // the steps [i0, i1) of tile q of a range: step i is column a + 1 + i
-MH_KALMAN_HD inline void scan_tile_steps(uint64_t q, uint64_t a, uint64_t b, uint64_t *i0, uint64_t *i1)
+MH_HD inline void scan_tile_steps(uint64_t q, uint64_t a, uint64_t b, uint64_t *i0, uint64_t *i1)
 {
     const uint64_t n = scan_range_steps(a, b);
     *i0 = q * kScanTile;
@@ -145,8 +125,8 @@ inline uint64_t scan_scratch_bytes(uint64_t cols, uint32_t k, uint32_t n_ranges)
 
 inline int scan_shape_check(Msg &m, const char *fn, uint64_t cols, uint32_t k, uint32_t n_ranges)
 {
-    if (k < 1 || k > kKalmanMaxK) return m.set(MH_ERR_ARG, "%s: k=%u outside 1..%u", fn, k, kKalmanMaxK);
-    if (cols < 1 || cols >= kKalmanMaxCols) return m.set(MH_ERR_ARG, "%s: cols=%llu outside 1..2^40-1", fn, (unsigned long long)cols);
+    if (int rc = k_rule(m, fn, k, kKalmanMaxK)) return rc;
+    if (int rc = cols_rule(m, fn, cols)) return rc;
     if (n_ranges < 1 || n_ranges > kKalmanMaxRanges) return m.set(MH_ERR_ARG, "%s: n_ranges=%u outside 1..%u", fn, n_ranges, kKalmanMaxRanges);
     return MH_OK;
 }
@@ -177,7 +157,7 @@ inline void scan_layout(const uint64_t *ranges, uint32_t n_ranges, uint32_t k, S
 }
 
 // the range of a tile: the last one whose first tile is not behind it and that has tiles
-MH_KALMAN_HD inline uint32_t scan_tile_range(uint64_t tile, const uint64_t *tile_base, uint32_t n_ranges)
+MH_HD inline uint32_t scan_tile_range(uint64_t tile, const uint64_t *tile_base, uint32_t n_ranges)
 {
     uint32_t r = 0;
     for (uint32_t i = 1; i < n_ranges; ++i)
@@ -194,7 +174,7 @@ inline int scan_check(Msg &m, const ScanArgs &a)
         return m.set(MH_ERR_ARG, "mhk_scan: v, out and their row strides must be multiples of 8");
     if (a.f % 8 || a.b % 8 || a.init % 8 || a.scratch % 8) return m.set(MH_ERR_ARG, "mhk_scan: F, B, init and scratch must be multiples of 8");
     const uint64_t row = 8 * a.cols;
-    if (a.k > 1 && (a.v_row_stride < row || a.out_row_stride < row || a.v_row_stride >= kKalmanMaxStride || a.out_row_stride >= kKalmanMaxStride))
+    if (a.k > 1 && (a.v_row_stride < row || a.out_row_stride < row || a.v_row_stride >= kMaxStride || a.out_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhk_scan: v_row_stride=%llu or out_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.v_row_stride, (unsigned long long)a.out_row_stride, (unsigned long long)row);
     uint64_t prev = 0;
@@ -205,10 +185,10 @@ inline int scan_check(Msg &m, const ScanArgs &a)
                          r, (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)prev, (unsigned long long)a.cols);
         prev = hi;
     }
-    const uint64_t v_end = a.v + (a.k - 1) * (a.k > 1 ? a.v_row_stride : 0) + row;
-    const uint64_t out_end = a.out + (a.k - 1) * (a.k > 1 ? a.out_row_stride : 0) + row;
+    const uint64_t v_end = strided_end(a.v, a.k, a.v_row_stride, row);
+    const uint64_t out_end = strided_end(a.out, a.k, a.out_row_stride, row);
     const bool same = a.out == a.v && (a.k == 1 || a.out_row_stride == a.v_row_stride);
-    if (!same && kalman_overlap(a.out, out_end, a.v, v_end))
+    if (!same && ranges_overlap(a.out, out_end, a.v, v_end))
         return m.set(MH_ERR_ARG, "mhk_scan: out overlaps v without being v with the same row stride");
     ScanLayout L;
     scan_layout(a.ranges, a.n_ranges, a.k, &L);
@@ -216,9 +196,9 @@ inline int scan_check(Msg &m, const ScanArgs &a)
         return m.set(MH_ERR_ARG, "mhk_scan: scratch_bytes=%llu is below the %llu these ranges need (mhk_scan_scratch_bytes gives enough for any)",
                      (unsigned long long)a.scratch_bytes, (unsigned long long)L.scratch_bytes);
     const uint64_t kk = 8ull * a.k * a.k * a.n_gain;
-    if (kalman_overlap(a.out, out_end, a.scratch, a.scratch + L.scratch_bytes) || kalman_overlap(a.v, v_end, a.scratch, a.scratch + L.scratch_bytes) ||
-        kalman_overlap(a.out, out_end, a.f, a.f + kk) || kalman_overlap(a.out, out_end, a.b, a.b + kk) ||
-        kalman_overlap(a.out, out_end, a.init, a.init + 8ull * a.k * a.n_ranges))
+    if (ranges_overlap(a.out, out_end, a.scratch, a.scratch + L.scratch_bytes) || ranges_overlap(a.v, v_end, a.scratch, a.scratch + L.scratch_bytes) ||
+        ranges_overlap(a.out, out_end, a.f, a.f + kk) || ranges_overlap(a.out, out_end, a.b, a.b + kk) ||
+        ranges_overlap(a.out, out_end, a.init, a.init + 8ull * a.k * a.n_ranges))
         return m.set(MH_ERR_ARG, "mhk_scan: scratch overlaps v or out, or out overlaps F, B or init");
     return MH_OK;
 }

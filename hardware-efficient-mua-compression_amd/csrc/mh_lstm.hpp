@@ -38,26 +38,6 @@ struct InprojParams {
     uint64_t items;
 };
 
-// the 4 bytes at row + u .. row + u + 3 (u a multiple of 4, below cols) as one dword: from the aligned dwords that hold
-// them where those lie inside the row, byte by byte otherwise (zeros past the row's end).  Nothing outside the row's cols
-// bytes is read.
-__device__ inline uint32_t lstm_load4(const uint8_t *row, uint64_t u, uint64_t cols)
-{
-    const uint32_t sh = (uint32_t)((uintptr_t)row & 3);
-    if (lstm_dwords_ok(u, sh, cols)) {
-        const uint32_t *const a0 = reinterpret_cast<const uint32_t *>(row + u - sh);
-        const uint32_t lo = a0[0];
-        if (!sh) return lo;
-        const uint32_t hi = a0[1];
-        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh));
-    }
-    uint32_t d = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b)
-        if (u + b < cols) d |= (uint32_t)row[u + b] << (8 * b);
-    return d;
-}
-
 __global__ __launch_bounds__(kInThreads) void k_inproj(InprojParams q)
 {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
@@ -82,7 +62,7 @@ __global__ __launch_bounds__(kInThreads) void k_inproj(InprojParams q)
         uint32_t d_n = 0;
         if (h < q.rows) {
             if (bcol) w_n = wr[h];
-            if (live) d_n = lstm_load4(q.x + (uint64_t)h * q.x_row_stride, u, q.cols);
+            if (live) d_n = load4(q.x + (uint64_t)h * q.x_row_stride, u, q.cols);
         }
         for (uint32_t c2 = 0; c2 < q.rows; c2 += 2) {
             const float w = w_n;
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(kInThreads) void k_inproj(InprojParams q)
             w_n = 0.f, d_n = 0;
             if (c < q.rows) {
                 if (bcol) w_n = wr[c];
-                if (live) d_n = lstm_load4(q.x + (uint64_t)c * q.x_row_stride, u, q.cols);
+                if (live) d_n = load4(q.x + (uint64_t)c * q.x_row_stride, u, q.cols);
             }
             const float a0 = fminf((float)(d & 0xffu), q.clip), a1 = fminf((float)((d >> 8) & 0xffu), q.clip);
             const float a2 = fminf((float)((d >> 16) & 0xffu), q.clip), a3 = fminf((float)(d >> 24), q.clip);

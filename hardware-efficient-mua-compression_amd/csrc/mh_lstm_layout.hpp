@@ -6,7 +6,7 @@
 //
 // mhl_inproj.  p[t][g] is a [cols, 4U] x [rows] product on v_mfma_f32_32x32x2_f32 with TIME as the M dimension.  The
 // columns are cut into TILES of kInTileCols = 4 waves x 128; a lane owns 4 consecutive columns (one dword of every
-// channel, taken from aligned dwords where both lie inside the row: lstm_dwords_ok, byte by byte otherwise).  The 4U
+// channel, taken from aligned dwords where both lie inside the row: dwords_ok of mh_rows.hpp, byte by byte otherwise).  The 4U
 // pre-activations are cut into G-TILES of 32 (the N dimension).  An ITEM is (tile, g-tile); the grid is capped at
 // kInMaxBlocks, workgroup b starts at item b and strides by the grid.  The scratch matrix p holds inproj_bytes(cols,
 // units) = cols * 4U * 4 bytes.
@@ -21,14 +21,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_LSTM_HD __host__ __device__
-#else
-#define MH_LSTM_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
@@ -36,8 +29,6 @@ constexpr uint32_t kLstmMaxUnits = 128;
 constexpr uint32_t kLstmMaxLags = 32;
 constexpr uint32_t kLstmMaxK = 8;
 constexpr uint64_t kLstmMaxRows = 65536;
-constexpr uint64_t kLstmMaxCols = 1ull << 40;    // cols is below this
-constexpr uint64_t kLstmMaxStride = 1ull << 48;  // a row stride is below this: rows * stride stays inside 64 bits
 
 constexpr uint32_t kInThreads = 256;             // 4 waves
 constexpr uint32_t kInWaveCols = 128;            // 32 lanes x 4 bytes of a dword
@@ -85,7 +76,7 @@ struct WinLayout {
     uint32_t grid;
 };
 
-MH_LSTM_HD inline uint64_t inproj_bytes(uint64_t cols, uint32_t units) { return cols * 16ull * units; }  // below 2^51
+MH_HD inline uint64_t inproj_bytes(uint64_t cols, uint32_t units) { return cols * 16ull * units; }  // below 2^51
 
 // ---- mhl_inproj -------------------------------------------------------------------------------------------------------------
 inline void inproj_layout(uint64_t cols, uint32_t units, InprojLayout *L)
@@ -96,33 +87,22 @@ inline void inproj_layout(uint64_t cols, uint32_t units, InprojLayout *L)
     L->grid = (uint32_t)(L->items < kInMaxBlocks ? L->items : kInMaxBlocks);
 }
 
-// May the 4 columns from t on (t a multiple of 4, t < cols) of a row whose first byte sits `sh` = 0..3 bytes behind a dword
-// boundary be taken from aligned dwords?  They lie in the dword at byte t - sh of the row and, with sh > 0, the next one:
-// both must lie inside the row's cols bytes.
-MH_LSTM_HD inline bool lstm_dwords_ok(uint64_t t, uint32_t sh, uint64_t cols)
-{
-    return sh == 0 ? t + 4 <= cols : (t >= sh && t - sh + 8 <= cols);
-}
-
-inline bool lstm_overlap(uint64_t a, uint64_t a_end, uint64_t b, uint64_t b_end) { return a < b_end && b < a_end; }
-
 // MH_OK, or MH_ERR_ARG with the text in m: every rule of the header's comment, before any device work
 inline int inproj_check(Msg &m, const InprojArgs &a)
 {
     if (!a.x || !a.wx || !a.bias || !a.p) return m.set(MH_ERR_ARG, "mhl_inproj: NULL pointer");
     if (a.units < 1 || a.units > kLstmMaxUnits) return m.set(MH_ERR_ARG, "mhl_inproj: units=%u outside 1..%u", a.units, kLstmMaxUnits);
-    if (a.rows < 1 || a.rows > kLstmMaxRows)
-        return m.set(MH_ERR_ARG, "mhl_inproj: rows=%llu outside 1..%llu", (unsigned long long)a.rows, (unsigned long long)kLstmMaxRows);
-    if (a.cols < 1 || a.cols >= kLstmMaxCols) return m.set(MH_ERR_ARG, "mhl_inproj: cols=%llu outside 1..2^40-1", (unsigned long long)a.cols);
-    if (a.clip < 1 || a.clip > 255) return m.set(MH_ERR_ARG, "mhl_inproj: clip=%u outside 1..255", a.clip);
+    if (int rc = rows_rule(m, "mhl_inproj", a.rows, kLstmMaxRows)) return rc;
+    if (int rc = cols_rule(m, "mhl_inproj", a.cols)) return rc;
+    if (int rc = clip_rule(m, "mhl_inproj", a.clip)) return rc;
     if (a.wx % 4 || a.bias % 4 || a.p % 4) return m.set(MH_ERR_ARG, "mhl_inproj: wx, bias and p must be multiples of 4");
-    if (a.rows > 1 && (a.x_row_stride < a.cols || a.x_row_stride >= kLstmMaxStride))
+    if (a.rows > 1 && (a.x_row_stride < a.cols || a.x_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhl_inproj: x_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.x_row_stride, (unsigned long long)a.cols);
-    const uint64_t x_end = a.x + (a.rows - 1) * (a.rows > 1 ? a.x_row_stride : 0) + a.cols;
+    const uint64_t x_end = strided_end(a.x, a.rows, a.x_row_stride, a.cols);
     const uint64_t p_end = a.p + inproj_bytes(a.cols, a.units);
-    if (lstm_overlap(a.p, p_end, a.x, x_end) || lstm_overlap(a.p, p_end, a.wx, a.wx + 16ull * a.units * a.rows) ||
-        lstm_overlap(a.p, p_end, a.bias, a.bias + 16ull * a.units))
+    if (ranges_overlap(a.p, p_end, a.x, x_end) || ranges_overlap(a.p, p_end, a.wx, a.wx + 16ull * a.units * a.rows) ||
+        ranges_overlap(a.p, p_end, a.bias, a.bias + 16ull * a.units))
         return m.set(MH_ERR_ARG, "mhl_inproj: p overlaps x, wx or bias");
     return MH_OK;
 }
@@ -139,30 +119,30 @@ inline void windows_layout(uint64_t cols, uint32_t lags, uint32_t units, WinLayo
 }
 
 // the unit and the gate of register r (0..15) of lane half h (0..1) in block q
-MH_LSTM_HD inline uint32_t win_unit(uint32_t q, uint32_t h, uint32_t r) { return q * kWinBlockUnits + 4 * h + (r & 3); }
-MH_LSTM_HD inline uint32_t win_gate(uint32_t r) { return r >> 2; }
+MH_HD inline uint32_t win_unit(uint32_t q, uint32_t h, uint32_t r) { return q * kWinBlockUnits + 4 * h + (r & 3); }
+MH_HD inline uint32_t win_gate(uint32_t r) { return r >> 2; }
 // the permuted row m (0..31) of block q as a row g = gate * units + unit of Wh; units <= unit: a row of zeros
-MH_LSTM_HD inline uint32_t win_row_unit(uint32_t q, uint32_t m) { return q * kWinBlockUnits + (m & 7); }
-MH_LSTM_HD inline uint32_t win_row_gate(uint32_t m) { return m >> 3; }
+MH_HD inline uint32_t win_row_unit(uint32_t q, uint32_t m) { return q * kWinBlockUnits + (m & 7); }
+MH_HD inline uint32_t win_row_gate(uint32_t m) { return m >> 3; }
 
 inline int windows_check(Msg &m, const WindowsArgs &a)
 {
     if (!a.p || !a.wh || !a.wd || !a.bd || !a.out) return m.set(MH_ERR_ARG, "mhl_windows: NULL pointer");
     if (a.units < 1 || a.units > kLstmMaxUnits) return m.set(MH_ERR_ARG, "mhl_windows: units=%u outside 1..%u", a.units, kLstmMaxUnits);
     if (a.lags < 1 || a.lags > kLstmMaxLags) return m.set(MH_ERR_ARG, "mhl_windows: lags=%u outside 1..%u", a.lags, kLstmMaxLags);
-    if (a.k < 1 || a.k > kLstmMaxK) return m.set(MH_ERR_ARG, "mhl_windows: k=%u outside 1..%u", a.k, kLstmMaxK);
-    if (a.cols < a.lags || a.cols >= kLstmMaxCols)
+    if (int rc = k_rule(m, "mhl_windows", a.k, kLstmMaxK)) return rc;
+    if (a.cols < a.lags || a.cols >= kMaxCols)
         return m.set(MH_ERR_ARG, "mhl_windows: cols=%llu outside lags=%u..2^40-1", (unsigned long long)a.cols, a.lags);
     if (a.p % 4 || a.wh % 4 || a.wd % 4 || a.bd % 4 || a.out % 4 || a.out_row_stride % 4)
         return m.set(MH_ERR_ARG, "mhl_windows: p, wh, wd, bd, out and out_row_stride must be multiples of 4");
     const uint64_t row = 4 * (a.cols - a.lags + 1);
-    if (a.k > 1 && (a.out_row_stride < row || a.out_row_stride >= kLstmMaxStride))
+    if (a.k > 1 && (a.out_row_stride < row || a.out_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhl_windows: out_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.out_row_stride, (unsigned long long)row);
-    const uint64_t out_end = a.out + (a.k - 1) * (a.k > 1 ? a.out_row_stride : 0) + row;
+    const uint64_t out_end = strided_end(a.out, a.k, a.out_row_stride, row);
     const uint64_t uu = 4ull * a.units;
-    if (lstm_overlap(a.out, out_end, a.p, a.p + inproj_bytes(a.cols, a.units)) || lstm_overlap(a.out, out_end, a.wh, a.wh + 4 * uu * a.units) ||
-        lstm_overlap(a.out, out_end, a.wd, a.wd + uu * a.k) || lstm_overlap(a.out, out_end, a.bd, a.bd + 4ull * a.k))
+    if (ranges_overlap(a.out, out_end, a.p, a.p + inproj_bytes(a.cols, a.units)) || ranges_overlap(a.out, out_end, a.wh, a.wh + 4 * uu * a.units) ||
+        ranges_overlap(a.out, out_end, a.wd, a.wd + uu * a.k) || ranges_overlap(a.out, out_end, a.bd, a.bd + 4ull * a.k))
         return m.set(MH_ERR_ARG, "mhl_windows: out overlaps p, wh, wd or bd");
     return MH_OK;
 }

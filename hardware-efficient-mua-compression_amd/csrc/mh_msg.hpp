@@ -1,5 +1,5 @@
 // mh_msg.hpp -- how the host-only headers report an error: the MH_* code as the return value, the text in a buffer the
-// caller passes in.  Pure C++ (no HIP, no global or thread-local state): the fail() of muahuff.hip / mh_ingest.hip
+// caller passes in.  Pure C++ (no HIP, no global or thread-local state): the fail() of mh_abi.hpp
 // copies the text into what mh_last_error returns and stays the only writer of that; tests/planner_check.cpp prints it.
 #pragma once
 #include <cstdarg>

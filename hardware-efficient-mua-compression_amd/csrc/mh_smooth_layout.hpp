@@ -19,21 +19,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_SMOOTH_HD __host__ __device__
-#else
-#define MH_SMOOTH_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
 constexpr uint32_t kBoxMaxWindow = 256;
 constexpr uint64_t kBoxMaxRows = 65536;
-constexpr uint64_t kBoxMaxCols = 1ull << 40;    // cols is below this
-constexpr uint64_t kBoxMaxStride = 1ull << 48;  // a row stride is below this: rows * stride stays inside 64 bits
 
 constexpr uint32_t kBoxThreads = 256;           // 4 waves
 constexpr uint32_t kBoxGroup = 16;              // bytes a thread loads
@@ -86,14 +77,14 @@ inline void box_layout(uint64_t rows, uint64_t cols, bool two_planes, BoxLayout 
 }
 
 // the channel and the tile of an item
-MH_SMOOTH_HD inline void box_item(uint64_t item, uint64_t tiles, uint64_t *c, uint64_t *tile)
+MH_HD inline void box_item(uint64_t item, uint64_t tiles, uint64_t *c, uint64_t *tile)
 {
     *c = item / tiles;
     *tile = item - *c * tiles;
 }
 
 // the first output column i0 of a tile and its number of outputs; it reads the columns [i0, i0 + n + window - 1) of x
-MH_SMOOTH_HD inline uint32_t box_tile_outputs(uint64_t tile, uint64_t cols, uint64_t *i0)
+MH_HD inline uint32_t box_tile_outputs(uint64_t tile, uint64_t cols, uint64_t *i0)
 {
     *i0 = tile * kBoxTileCols;
     return cols - *i0 < kBoxTileCols ? (uint32_t)(cols - *i0) : kBoxTileCols;
@@ -101,9 +92,7 @@ MH_SMOOTH_HD inline uint32_t box_tile_outputs(uint64_t tile, uint64_t cols, uint
 
 // May the aligned dword at address a be loaded?  Only if it holds a byte of the row [row, row_end) and a byte the tile
 // needs, [row, need_end) with need_end <= row_end: so no dword without a byte of the row is ever touched.
-MH_SMOOTH_HD inline bool box_dword_ok(uint64_t a, uint64_t row, uint64_t need_end) { return a + 4 > row && a < need_end; }
-
-inline bool smooth_overlap(uint64_t a, uint64_t a_end, uint64_t b, uint64_t b_end) { return a < b_end && b < a_end; }
+MH_HD inline bool box_dword_ok(uint64_t a, uint64_t row, uint64_t need_end) { return a + 4 > row && a < need_end; }
 
 // Do two planes of `rows` rows of `cols` bytes, both `stride` apart, share a byte?  Row by row, not as two ranges: planes
 // whose rows interleave (hi's rows in the gaps of lo's pitch) are apart.  stride >= cols where rows > 1.
@@ -120,23 +109,22 @@ inline int box_check(Msg &m, const BoxArgs &a)
 {
     if (!a.x || !a.lo) return m.set(MH_ERR_ARG, "mhs_box: NULL pointer");
     if (a.window < 1 || a.window > kBoxMaxWindow) return m.set(MH_ERR_ARG, "mhs_box: window=%u outside 1..%u", a.window, kBoxMaxWindow);
-    if (a.clip < 1 || a.clip > 255) return m.set(MH_ERR_ARG, "mhs_box: clip=%u outside 1..255", a.clip);
-    if (a.rows < 1 || a.rows > kBoxMaxRows)
-        return m.set(MH_ERR_ARG, "mhs_box: rows=%llu outside 1..%llu", (unsigned long long)a.rows, (unsigned long long)kBoxMaxRows);
-    if (a.cols < 1 || a.cols >= kBoxMaxCols) return m.set(MH_ERR_ARG, "mhs_box: cols=%llu outside 1..2^40-1", (unsigned long long)a.cols);
+    if (int rc = clip_rule(m, "mhs_box", a.clip)) return rc;
+    if (int rc = rows_rule(m, "mhs_box", a.rows, kBoxMaxRows)) return rc;
+    if (int rc = cols_rule(m, "mhs_box", a.cols)) return rc;
     if (!a.hi && a.window * a.clip > 255)
         return m.set(MH_ERR_ARG, "mhs_box: hi is NULL and window * clip = %u is above 255", a.window * a.clip);
     if (a.lo % 16 || a.hi % 16 || a.out_row_stride % 16) return m.set(MH_ERR_ARG, "mhs_box: lo, hi and out_row_stride must be multiples of 16");
     const uint64_t in_row = a.cols + a.window - 1;
-    if (a.rows > 1 && (a.x_row_stride < in_row || a.x_row_stride >= kBoxMaxStride))
+    if (a.rows > 1 && (a.x_row_stride < in_row || a.x_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhs_box: x_row_stride=%llu is below the cols + window - 1 = %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.x_row_stride, (unsigned long long)in_row);
-    if (a.rows > 1 && (a.out_row_stride < a.cols || a.out_row_stride >= kBoxMaxStride))
+    if (a.rows > 1 && (a.out_row_stride < a.cols || a.out_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhs_box: out_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.out_row_stride, (unsigned long long)a.cols);
-    const uint64_t x_end = a.x + (a.rows - 1) * (a.rows > 1 ? a.x_row_stride : 0) + in_row;
-    const uint64_t out_len = (a.rows - 1) * (a.rows > 1 ? a.out_row_stride : 0) + a.cols;
-    if (smooth_overlap(a.lo, a.lo + out_len, a.x, x_end) || (a.hi && smooth_overlap(a.hi, a.hi + out_len, a.x, x_end)))
+    const uint64_t x_end = strided_end(a.x, a.rows, a.x_row_stride, in_row);
+    const uint64_t out_len = strided_end(0, a.rows, a.out_row_stride, a.cols);
+    if (ranges_overlap(a.lo, a.lo + out_len, a.x, x_end) || (a.hi && ranges_overlap(a.hi, a.hi + out_len, a.x, x_end)))
         return m.set(MH_ERR_ARG, "mhs_box: lo or hi overlaps x");
     if (a.hi && planes_overlap(a.lo, a.hi, a.rows, a.out_row_stride, a.cols)) return m.set(MH_ERR_ARG, "mhs_box: lo and hi overlap");
     return MH_OK;
@@ -153,21 +141,21 @@ inline void boxf_layout(uint64_t cols, uint32_t k, BoxfLayout *L)
 inline int boxf_check(Msg &m, const BoxfArgs &a)
 {
     if (!a.in || !a.bias || !a.out) return m.set(MH_ERR_ARG, "mhs_box_f32: NULL pointer");
-    if (a.k < 1 || a.k > kBoxfMaxK) return m.set(MH_ERR_ARG, "mhs_box_f32: k=%u outside 1..%u", a.k, kBoxfMaxK);
-    if (a.cols < 1 || a.cols >= kBoxMaxCols) return m.set(MH_ERR_ARG, "mhs_box_f32: cols=%llu outside 1..2^40-1", (unsigned long long)a.cols);
+    if (int rc = k_rule(m, "mhs_box_f32", a.k, kBoxfMaxK)) return rc;
+    if (int rc = cols_rule(m, "mhs_box_f32", a.cols)) return rc;
     if (a.window < 1 || a.window > kBoxMaxWindow)
         return m.set(MH_ERR_ARG, "mhs_box_f32: window=%u outside 1..%u", a.window, kBoxMaxWindow);
     if (a.in % 4 || a.in_row_stride % 4 || a.out % 4 || a.out_row_stride % 4)
         return m.set(MH_ERR_ARG, "mhs_box_f32: in, out and their row strides must be multiples of 4");
     if (a.bias % 4) return m.set(MH_ERR_ARG, "mhs_box_f32: bias must be a multiple of 4");
     const uint64_t row = 4 * a.cols;
-    if (a.k > 1 && (a.in_row_stride < row || a.out_row_stride < row || a.in_row_stride >= kBoxMaxStride || a.out_row_stride >= kBoxMaxStride))
+    if (a.k > 1 && (a.in_row_stride < row || a.out_row_stride < row || a.in_row_stride >= kMaxStride || a.out_row_stride >= kMaxStride))
         return m.set(MH_ERR_ARG, "mhs_box_f32: in_row_stride=%llu or out_row_stride=%llu is below the %llu bytes of a row, or not below 2^48",
                      (unsigned long long)a.in_row_stride, (unsigned long long)a.out_row_stride, (unsigned long long)row);
-    const uint64_t in_end = a.in + (a.k - 1) * (a.k > 1 ? a.in_row_stride : 0) + row;
-    const uint64_t out_end = a.out + (a.k - 1) * (a.k > 1 ? a.out_row_stride : 0) + row;
-    if (smooth_overlap(a.out, out_end, a.in, in_end)) return m.set(MH_ERR_ARG, "mhs_box_f32: out overlaps in");
-    if (smooth_overlap(a.out, out_end, a.bias, a.bias + 4ull * a.k)) return m.set(MH_ERR_ARG, "mhs_box_f32: out overlaps bias");
+    const uint64_t in_end = strided_end(a.in, a.k, a.in_row_stride, row);
+    const uint64_t out_end = strided_end(a.out, a.k, a.out_row_stride, row);
+    if (ranges_overlap(a.out, out_end, a.in, in_end)) return m.set(MH_ERR_ARG, "mhs_box_f32: out overlaps in");
+    if (ranges_overlap(a.out, out_end, a.bias, a.bias + 4ull * a.k)) return m.set(MH_ERR_ARG, "mhs_box_f32: out overlaps bias");
     return MH_OK;
 }
 

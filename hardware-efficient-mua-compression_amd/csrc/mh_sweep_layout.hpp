@@ -26,15 +26,8 @@
 #include <stdint.h>
 
 #include "mh_gram_layout.hpp"
-#include "mh_msg.hpp"
+#include "mh_rows.hpp"
 #include "mh_wiener_layout.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_SWEEP_HD __host__ __device__
-#else
-#define MH_SWEEP_HD
-#endif
 
 namespace mh {
 
@@ -117,9 +110,8 @@ inline int sweep_check(Msg &m, const char *fn, uint64_t rows, uint64_t cols, uin
                        uint32_t n_ranges, const uint32_t *clips, uint32_t n_clips, uint64_t room)
 {
     if (lags < 1 || lags > kWienerMaxLags) return m.set(MH_ERR_ARG, "%s: lags=%u outside 1..%u", fn, lags, kWienerMaxLags);
-    if (rows < 1 || rows > kWienerMaxRows)
-        return m.set(MH_ERR_ARG, "%s: rows=%llu outside 1..%llu", fn, (unsigned long long)rows, (unsigned long long)kWienerMaxRows);
-    if (cols < 1 || cols >= kWienerMaxCols) return m.set(MH_ERR_ARG, "%s: cols=%llu outside 1..2^40-1", fn, (unsigned long long)cols);
+    if (int rc = rows_rule(m, fn, rows, kWienerMaxRows)) return rc;
+    if (int rc = cols_rule(m, fn, cols)) return rc;
     if (n_ranges < 1 || n_ranges > kSweepMaxRanges)
         return m.set(MH_ERR_ARG, "%s: n_ranges=%u outside 1..%u", fn, n_ranges, kSweepMaxRanges);
     if (n_clips < 1 || n_clips > kSweepMaxClips) return m.set(MH_ERR_ARG, "%s: n_clips=%u outside 1..%u", fn, n_clips, kSweepMaxClips);
@@ -159,7 +151,7 @@ inline uint64_t sweep_pack(const uint64_t *ranges, uint32_t n_ranges, const uint
 }
 
 // the range a run belongs to; run < R.run_first[kSweepMaxRanges]
-MH_SWEEP_HD inline uint32_t sweep_run_range(const SweepRanges &R, uint64_t run)
+MH_HD inline uint32_t sweep_run_range(const SweepRanges &R, uint64_t run)
 {
     uint32_t r = 0;
     while (run >= R.run_first[r + 1]) ++r;  // at most kSweepMaxRanges - 1 steps: run_first[kSweepMaxRanges] is above run
@@ -193,7 +185,7 @@ inline void gram_clips_layout(const GramClipsArgs &a, GramClipsLayout *L)
 }
 
 // item -> its range, clip, lag difference, tile and columns
-MH_SWEEP_HD inline GramClipsItem gram_clips_owner(const SweepRanges &R, uint32_t n_clips, uint32_t nt, uint64_t tiles0, uint64_t tiles1,
+MH_HD inline GramClipsItem gram_clips_owner(const SweepRanges &R, uint32_t n_clips, uint32_t nt, uint64_t tiles0, uint64_t tiles1,
                                                   uint64_t dt, uint64_t item)
 {
     GramClipsItem it;
@@ -246,7 +238,7 @@ inline int xty_clips_scratch_check(Msg &m, uint64_t rows, uint64_t cols, uint32_
 inline int xty_clips_check(Msg &m, const XtyClipsArgs &a)
 {
     if (!a.x || !a.ranges || !a.clips || !a.y || !a.out || !a.scratch) return m.set(MH_ERR_ARG, "mhq_xty_clips: NULL pointer");
-    if (a.k < 1 || a.k > kWienerMaxK) return m.set(MH_ERR_ARG, "mhq_xty_clips: k=%u outside 1..%u", a.k, kWienerMaxK);
+    if (int rc = k_rule(m, "mhq_xty_clips", a.k, kWienerMaxK)) return rc;
     if (a.lead >= a.cols) return m.set(MH_ERR_ARG, "mhq_xty_clips: lead=%u leaves none of the %llu columns", a.lead, (unsigned long long)a.cols);
     if (int rc = sweep_check(m, "mhq_xty_clips", a.rows, a.cols, a.lags, a.ranges, a.n_ranges, a.clips, a.n_clips, a.cols - a.lead))
         return rc;
@@ -278,7 +270,7 @@ inline void xty_clips_layout(const XtyClipsArgs &a, XtyClipsLayout *L)
 }
 
 // item -> its range, clip, channel and the columns of its run, counted from the range's start as mhw_xty counts them
-MH_SWEEP_HD inline XtyClipsItem xty_clips_owner(const SweepRanges &R, uint32_t n_clips, uint32_t rows, uint64_t item)
+MH_HD inline XtyClipsItem xty_clips_owner(const SweepRanges &R, uint32_t n_clips, uint32_t rows, uint64_t item)
 {
     XtyClipsItem it;
     const uint64_t rn = item / rows;

@@ -3,9 +3,7 @@
 // and no grid is worked out here.  A companion of libmuahuff.so, not part of it; there is no CPU fallback here either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
+#include "mh_abi.hpp"
 #include "mh_wiener.hpp"
 #include "mh_wiener_layout.hpp"
 // built with -fvisibility=hidden: the mhw_* functions of the header are ALL the library exports
@@ -14,28 +12,6 @@
 #pragma GCC visibility pop
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// what the host-only header reported
-int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
-
-// how every entry point ends: MH_OK, or what its launches left behind.  `fn` names the entry point.
-int launched(const char *fn)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MH_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return MH_OK;
-}
 
 template <int K>
 void xty_launch(const mh::XtyParams &p, uint32_t grid, hipStream_t st)
@@ -74,16 +50,7 @@ int mhw_xty(const uint8_t *x, uint64_t x_row_stride, uint64_t rows, uint64_t col
     hipStream_t st = (hipStream_t)stream;
     const mh::XtyParams p = {x, x_row_stride, (uint32_t)rows, cols, lags, clip, reinterpret_cast<const uint8_t *>(y), y_row_stride,
                              static_cast<double *>(scratch), L.items};
-    switch (k) {
-    case 1: xty_launch<1>(p, L.grid, st); break;
-    case 2: xty_launch<2>(p, L.grid, st); break;
-    case 3: xty_launch<3>(p, L.grid, st); break;
-    case 4: xty_launch<4>(p, L.grid, st); break;
-    case 5: xty_launch<5>(p, L.grid, st); break;
-    case 6: xty_launch<6>(p, L.grid, st); break;
-    case 7: xty_launch<7>(p, L.grid, st); break;
-    default: xty_launch<8>(p, L.grid, st); break;
-    }
+    dispatch_k(k, [&](auto K) { xty_launch<K>(p, L.grid, st); });
     hipLaunchKernelGGL(mh::k_xty_sum, dim3(L.sum_grid), dim3(mh::kXtySumThreads), 0, st, static_cast<const double *>(scratch),
                        L.runs, (uint32_t)rows, lags, k, L.elements, out, accumulate);
     return launched("mhw_xty");

@@ -21,21 +21,13 @@
 #pragma once
 #include <stdint.h>
 
-#include "mh_msg.hpp"
-#include "muahuff.h"
-
-#if defined(__HIPCC__)
-#define MH_WIENER_HD __host__ __device__
-#else
-#define MH_WIENER_HD
-#endif
+#include "mh_rows.hpp"
 
 namespace mh {
 
 constexpr uint32_t kWienerMaxLags = 32;
 constexpr uint32_t kWienerMaxK = 8;
 constexpr uint64_t kWienerMaxRows = 65536;
-constexpr uint64_t kWienerMaxCols = 1ull << 40;  // cols is below this
 
 constexpr uint32_t kXtyThreads = 256;       // 4 waves
 constexpr uint32_t kXtyRun = 32768;         // columns of a run
@@ -95,11 +87,9 @@ struct FirLayout {
 inline int wiener_shape_check(Msg &m, const char *fn, uint64_t rows, uint64_t cols, uint32_t lags, uint32_t k)
 {
     if (lags < 1 || lags > kWienerMaxLags) return m.set(MH_ERR_ARG, "%s: lags=%u outside 1..%u", fn, lags, kWienerMaxLags);
-    if (k < 1 || k > kWienerMaxK) return m.set(MH_ERR_ARG, "%s: k=%u outside 1..%u", fn, k, kWienerMaxK);
-    if (rows < 1 || rows > kWienerMaxRows)
-        return m.set(MH_ERR_ARG, "%s: rows=%llu outside 1..%llu", fn, (unsigned long long)rows, (unsigned long long)kWienerMaxRows);
-    if (cols < 1 || cols >= kWienerMaxCols) return m.set(MH_ERR_ARG, "%s: cols=%llu outside 1..2^40-1", fn, (unsigned long long)cols);
-    return MH_OK;
+    if (int rc = k_rule(m, fn, k, kWienerMaxK)) return rc;
+    if (int rc = rows_rule(m, fn, rows, kWienerMaxRows)) return rc;
+    return cols_rule(m, fn, cols);
 }
 
 // the whole layout of mhw_xty; the shape has passed wiener_shape_check
@@ -116,7 +106,7 @@ inline void xty_layout(uint64_t rows, uint64_t cols, uint32_t lags, uint32_t k, 
 }
 
 // the columns [c0, c1) of a run
-MH_WIENER_HD inline void xty_run_cols(uint64_t run, uint64_t cols, uint64_t *c0, uint64_t *c1)
+MH_HD inline void xty_run_cols(uint64_t run, uint64_t cols, uint64_t *c0, uint64_t *c1)
 {
     *c0 = run * kXtyRun;
     *c1 = cols - *c0 < kXtyRun ? cols : *c0 + kXtyRun;
@@ -134,7 +124,7 @@ inline int xty_check(Msg &m, const XtyArgs &a)
 {
     if (!a.x || !a.y || !a.out || !a.scratch) return m.set(MH_ERR_ARG, "mhw_xty: NULL pointer");
     if (int rc = wiener_shape_check(m, "mhw_xty", a.rows, a.cols, a.lags, a.k)) return rc;
-    if (a.clip < 1 || a.clip > 255) return m.set(MH_ERR_ARG, "mhw_xty: clip=%u outside 1..255", a.clip);
+    if (int rc = clip_rule(m, "mhw_xty", a.clip)) return rc;
     if (a.accumulate > 1) return m.set(MH_ERR_ARG, "mhw_xty: accumulate=%u (0 or 1)", a.accumulate);
     if (a.out % 8 || a.scratch % 8) return m.set(MH_ERR_ARG, "mhw_xty: out and scratch must be multiples of 8");
     if (a.y % 4 || a.y_row_stride % 4) return m.set(MH_ERR_ARG, "mhw_xty: y and y_row_stride must be multiples of 4");
@@ -152,8 +142,8 @@ inline int xty_check(Msg &m, const XtyArgs &a)
     return MH_OK;
 }
 
-MH_WIENER_HD inline uint32_t fir_tile_outputs(uint32_t lags) { return kFirTileCols - (lags - 1); }
-MH_WIENER_HD inline uint32_t fir_per_mtile(uint32_t lags) { return kFirMRows / lags; }
+MH_HD inline uint32_t fir_tile_outputs(uint32_t lags) { return kFirTileCols - (lags - 1); }
+MH_HD inline uint32_t fir_per_mtile(uint32_t lags) { return kFirMRows / lags; }
 
 // the whole layout of mhw_fir; the shape has passed wiener_shape_check
 inline void fir_layout(uint64_t cols, uint32_t lags, uint32_t k, FirLayout *L)
@@ -170,7 +160,7 @@ inline int fir_check(Msg &m, const FirArgs &a)
 {
     if (!a.x || !a.w || !a.bias || !a.out) return m.set(MH_ERR_ARG, "mhw_fir: NULL pointer");
     if (int rc = wiener_shape_check(m, "mhw_fir", a.rows, a.cols, a.lags, a.k)) return rc;
-    if (a.clip < 1 || a.clip > 255) return m.set(MH_ERR_ARG, "mhw_fir: clip=%u outside 1..255", a.clip);
+    if (int rc = clip_rule(m, "mhw_fir", a.clip)) return rc;
     if (a.w % 4 || a.bias % 4) return m.set(MH_ERR_ARG, "mhw_fir: w and bias must be multiples of 4");
     if (a.out % 4 || a.out_row_stride % 4) return m.set(MH_ERR_ARG, "mhw_fir: out and out_row_stride must be multiples of 4");
     if (a.rows > 1 && a.x_row_stride < a.cols + a.lags - 1)

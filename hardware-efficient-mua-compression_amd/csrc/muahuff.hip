@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "mh_abi.hpp"
 #include "mh_analysis.hpp"
 #include "mh_codec2.hpp"
 #include "mh_launch.hpp"
@@ -34,20 +34,6 @@
 #pragma GCC visibility pop
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// the error a host-only header reported (mh_msg.hpp)
-int fail(int code, const mh::Msg &m) { return fail(code, "%s", m.text); }
 
 #define MH_HIP(call)                                                                         \
     do {                                                                                     \

@@ -10,7 +10,7 @@
 //   layout cols k n_ranges a0 b0 a1 b1 ..             (a shape that passes the checks)
 //     -> proj_tiles proj_grid scan_tiles scan_grid scratch_bytes
 //        after checking what the kernels rely on.  mhk_project: the tiles partition the columns; of the first two and the
-//        last tile, at every alignment of a row's first byte, a thread's dwords lie inside the row where proj_dwords_ok
+//        last tile, at every alignment of a row's first byte, a thread's dwords lie inside the row where dwords_ok
 //        says so and the byte path stays inside it otherwise; the grid is under its cap and the stride loop reaches
 //        every tile once.  mhk_scan: the tiles partition every range's steps from the range's own start and every step's
 //        column lies inside the range; every tile finds its range; every record the three kernels read or write lies
@@ -103,7 +103,7 @@ static int walk_project_tile(ull tile, ull cols, uint32_t sh)
     for (uint32_t tid = 0; tid < mh::kProjThreads; ++tid) {
         const ull t = tile * mh::kProjTileCols + (ull)mh::kProjGroup * tid;
         if (t >= cols) continue;
-        if (mh::proj_dwords_ok(t, sh, cols)) {
+        if (mh::dwords_ok(t, sh, cols)) {
             CHECK(t >= sh);
             const ull a0 = row + t - sh, end = a0 + (sh ? 8 : 4);
             CHECK(a0 % 4 == 0 && a0 >= row && end <= row + cols);       // aligned, inside the row

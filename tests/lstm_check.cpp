@@ -9,7 +9,7 @@
 //     -> in_tiles gtiles in_grid win_tiles blocks per_wave ksteps win_grid p_bytes
 //        after checking what the kernels rely on.  mhl_inproj: the tiles partition the columns and the g-tiles the 4 units
 //        pre-activations; of the first two and the last tile, at every alignment of a row's first byte, a lane's dwords lie
-//        inside the row where lstm_dwords_ok says so and the byte path stays inside it otherwise; every (bin, pre-activation)
+//        inside the row where dwords_ok says so and the byte path stays inside it otherwise; every (bin, pre-activation)
 //        a lane stores lies inside p's inproj_bytes; the grid is under its cap and the stride loop reaches every item once.
 //        mhl_windows: the tiles partition the windows, every row of p a window reads lies inside p; the registers of the
 //        blocks name every (gate, unit) once and as the row of Wh the A operand holds; a wave owns at most per_wave blocks;
@@ -94,7 +94,7 @@ static int walk_inproj_tile(ull tile, ull cols, uint32_t units, uint32_t gt, uin
             const uint32_t col = lane & 31, h = lane >> 5;
             const ull u = t0 + 4 * col;
             if (u < cols) {
-                if (mh::lstm_dwords_ok(u, sh, cols)) {
+                if (mh::dwords_ok(u, sh, cols)) {
                     CHECK(u >= sh);
                     const ull a0 = row + u - sh, end = a0 + (sh ? 8 : 4);
                     CHECK(a0 % 4 == 0 && a0 >= row && end <= row + cols);   // aligned, inside the row
