@@ -47,6 +47,6 @@ def __getattr__(name):  # torch-dependent modules load lazily
     if name in ("bit_rates", "compress", "decompress"):
         return getattr(importlib.import_module(".api", __name__), name)
     if name in ("codec", "container", "container_io", "archive", "synth", "api", "sweep", "stream", "analysis", "functions_1", "drivers", "dist",
-                "events", "_ingest", "windows", "gram", "_wiener", "wiener", "_cascade", "cascade", "_smooth", "smooth", "_sweep", "_kalman", "kalman", "_lstm", "lstm"):
+                "events", "_ingest", "windows", "gram", "_wiener", "wiener", "_cascade", "cascade", "_smooth", "smooth", "_sweep", "_kalman", "kalman", "_lstm", "lstm", "_train", "train"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the eight shared objects have in common: where a library lies, how it is loaded and how a
+"""What the ctypes bindings of the nine shared objects have in common: where a library lies, how it is loaded and how a
 return code becomes an exception.  Fails loudly: there is no CPU path."""
 import ctypes as ct
 import os

@@ -18,6 +18,9 @@ ROOT = os.path.dirname(HERE)
 LIBRARIES = [("muahuff", "csrc/muahuff.hip", "csrc/exports.map", "../include/muahuff.h")] + \
             [("muahuff_" + n, "csrc/mh_%s.hip" % n, "csrc/exports_%s.map" % n, "../include/muahuff_%s.h" % n)
              for n in ("ingest", "wiener", "cascade", "smooth", "sweep", "kalman", "lstm")]
+# the libraries of the training side, built by the same recipe: train (the loss of a minibatch of the LSTM decoder's windows
+# and its gradient with respect to the weights)
+TRAINING = [("muahuff_train", "csrc/mh_train.hip", "csrc/exports_train.map", "../include/muahuff_train.h")]
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 
 
@@ -39,7 +42,7 @@ def reached(source):
 
 
 def _row(name):
-    return next(row for row in LIBRARIES if row[0] == name)
+    return next(row for row in LIBRARIES + TRAINING if row[0] == name)
 
 
 def so_path(name):
@@ -65,6 +68,7 @@ SMOOTH_SO, SMOOTH_SOURCES, SMOOTH_HEADERS = _names("muahuff_smooth")
 SWEEP_SO, SWEEP_SOURCES, SWEEP_HEADERS = _names("muahuff_sweep")
 KALMAN_SO, KALMAN_SOURCES, KALMAN_HEADERS = _names("muahuff_kalman")
 LSTM_SO, LSTM_SOURCES, LSTM_HEADERS = _names("muahuff_lstm")
+TRAIN_SO, TRAIN_SOURCES, TRAIN_HEADERS = _names("muahuff_train")
 
 
 def stale(name="muahuff"):
@@ -127,6 +131,10 @@ def build_lstm(force=False, verbose=False):
     return build_library("muahuff_lstm", force, verbose)
 
 
+def build_train(force=False, verbose=False):
+    return build_library("muahuff_train", force, verbose)
+
+
 def build_example(force=False):
     """examples/abi_roundtrip: a plain-C client of include/muahuff.h (gcc, HIP runtime only)."""
     src = os.path.join(ROOT, "examples", "abi_roundtrip.c")
@@ -150,3 +158,4 @@ if __name__ == "__main__":
     print(build_sweep(force=True, verbose=True))
     print(build_kalman(force=True, verbose=True))
     print(build_lstm(force=True, verbose=True))
+    print(build_train(force=True, verbose=True))

@@ -12,7 +12,9 @@ dropped: its column of the input weights is zero.
 Wx^T u depends on the bin and not on the window: predict() is one mhl_inproj (every bin's input half of the
 pre-activations, with the z-scoring folded into the weights) and one mhl_windows (the recurrence of every window and the
 dense layer) per batch of columns, the batches sized by what the scratch matrix of pre-activations may take.  fit() trains
-with torch autograd -- plumbing, not the hot path -- on windows gathered from the uint8 matrix minibatch by minibatch.
+minibatch by minibatch with torch's optimizers; the loss of a minibatch and its gradient come from torch autograd on windows
+gathered from the uint8 matrix (engine="autograd", the default) or from one mht_loss_grad that reads the counts where they
+lie (engine="device", muahuff_train.h; loss_and_grad() is that call on its own).
 There is no CPU path: host matrices are refused."""
 import contextlib
 
@@ -56,6 +58,50 @@ def own_kernels():
 def _loss(pred, target):
     """the reference's loss: the mean over the rows of the root of the mean over the outputs of err^2; [n, K] both"""
     return torch.sqrt(((pred - target) ** 2).mean(1)).mean()
+
+
+def _zscoring(mean, std, dev):
+    """-> (mean, inv) float32 [C] on dev, as fit() forms them: inv = 1 / std in float64, 0 where std is 0 (the channel is dropped)"""
+    mean = torch.as_tensor(mean, dtype=torch.float64).to(dev)
+    std = torch.as_tensor(std, dtype=torch.float64).to(dev)
+    keep = std > 0
+    inv = torch.where(keep, 1.0 / torch.where(keep, std, torch.ones_like(std)), torch.zeros_like(std)).float()
+    return mean.float().contiguous(), inv.contiguous()
+
+
+def loss_and_grad(x, y, idx, weights, mean, std, lags, lead=0, clip=None, scale=None):
+    """The loss of one minibatch of windows and its gradient, in one mht_loss_grad (muahuff_train.h).  x: uint8 device tensor
+    [C, T]; y: float32 device tensor [K, T]; idx: int64 device tensor [B], window b being design row idx[b] in WienerFilter's
+    numbering (it ends in bin idx[b], its target is y[:, idx[b] + lead]; lags-1 <= idx[b] <= T-1-lead, a repeated row counts
+    twice); weights: (wx [4U, C], bias [4U], wh [4U, U], wd [K, U], bd [K]), float32 device tensors in torch.nn.LSTM's and
+    nn.Linear's layout, gates i, f, g, o; mean, std [C] of the clipped counts: every channel enters as
+    (min(x, clip) - mean) / std, a channel of std 0 is dropped.
+    -> (out float32 [K, B], loss float32 [B]: sqrt(mean over K of err^2) per window, dict(wx, bias, wh, wd, bd): the gradient of
+    scale * loss.sum() with respect to each of the weights; scale defaults to 1 / B, the reference's mean over the rows).
+    A window whose loss is exactly 0 adds nothing to the gradient, where autograd would give NaN."""
+    from . import _train
+    x, rows, cols = _matrix(x, "lstm.loss_and_grad")
+    y, K = wiener._covariates(y, x, cols)
+    dev, L, g, q = x.device, int(lags), int(lead), wiener._clip(clip)
+    if not (isinstance(idx, torch.Tensor) and idx.dtype == torch.int64 and idx.dim() == 1 and idx.device == dev):
+        raise ValueError("idx is an int64 tensor [B] on the device of the counts")
+    B = int(idx.numel())
+    if not 1 <= B <= _train.MAX_BATCH:
+        raise ValueError("%d windows outside 1..%d" % (B, _train.MAX_BATCH))
+    if len(weights) != 5 or not all(isinstance(w, torch.Tensor) and w.device == dev for w in weights):
+        raise ValueError("weights are (wx, bias, wh, wd, bd), tensors on the device of the counts")
+    wx, bias, wh, wd, bd = (w.detach() for w in weights)
+    if wh.dim() != 2 or wd.dim() != 2 or int(wd.shape[0]) != K:
+        raise ValueError("wh is [4 units, units] and wd [%d, units]" % K)
+    U = int(wh.shape[1])
+    mean32, inv = _zscoring(mean, std, dev)
+    out = torch.empty((K, B), dtype=torch.float32, device=dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    grads = {n: torch.empty_like(w) for n, w in zip(("wx", "bias", "wh", "wd", "bd"), (wx, bias, wh, wd, bd))}
+    scratch = torch.empty((_train.scratch_layout(B, L, U)["floats"],), dtype=torch.float32, device=dev)
+    _train.loss_grad(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, cols, q, mean32, inv, idx.contiguous(), L, g, wx, bias, wh, wd, bd,
+                     y, 1.0 / B if scale is None else float(scale), scratch, out, loss, *grads.values())
+    return out, loss, grads
 
 
 class LSTMDecoder:
@@ -240,15 +286,21 @@ class LSTMDecoder:
         return torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res])
 
     # ---- the fit ---------------------------------------------------------------------------------------------------------
-    def fit(self, x, y, ranges=None, valid=None, epochs=5, batch_size=32, optimizer="RMSprop", lrate=1e-3, shuffle=True, seed=0):
+    def fit(self, x, y, ranges=None, valid=None, epochs=5, batch_size=32, optimizer="RMSprop", lrate=1e-3, shuffle=True, seed=0,
+            engine="autograd"):
         """Train on the design rows of `ranges` ([a, b) in WienerFilter's numbering: row t is the window that ends in bin t;
         default all of them) -> the reference's fit_out: dict(loss_train, loss_valid: one value per epoch, num_params).
         x: uint8 device tensor [C, T]; y: float32 device tensor [K, T].  mean and std of the clipped counts over the
         training rows come from wiener.stats at one lag; y is centred on its training mean, which goes into dense_bias.
         The model is nn.LSTM + nn.Linear with Keras's initial weights (Glorot uniform, orthogonal recurrent kernel, forget
         bias 1) and one bias vector, the loss the reference's rmse, the optimizer RMSprop (rho 0.9, eps 1e-7: Keras's),
-        Adam or SGD at lrate.  A minibatch's windows are gathered from x as they are needed.  After every epoch the weights
+        Adam or SGD at lrate.  engine="autograd": a minibatch's windows are gathered from x as they are needed and torch
+        autograd gives the gradient.  engine="device": the same initial weights, generator, order and optimizer, but the
+        loss and the gradient of a minibatch are one mht_loss_grad (muahuff_train.h) on the counts where they lie, written
+        into gradient tensors bound to the parameters once: no gather, no autograd graph.  After every epoch the weights
         are exported and, with valid = [a, b) or a list of such ranges, the loss over them is taken from predict()."""
+        if engine not in ("autograd", "device"):
+            raise ValueError("engine is autograd or device")
         x, rows, cols = _matrix(x, "LSTMDecoder.fit")
         y, K = wiener._covariates(y, x, cols)
         L, g, U, q, dev = self.lags, self.lead, self.units, self.clip, x.device
@@ -307,11 +359,32 @@ class LSTMDecoder:
         offs = torch.arange(-(L - 1), 1, device=dev)
         xt, yc = x.t(), (y.double() - ybar.unsqueeze(1)).float()
         self.module = (lstm, linear)
+        if engine == "device":
+            from . import _train
+            nb = min(batch_size, int(rows_t.numel()))
+            if nb > _train.MAX_BATCH:
+                raise ValueError("a minibatch of %d rows is above the %d of engine=device" % (nb, _train.MAX_BATCH))
+            wts = [w.detach() for w in (lstm.weight_ih_l0, lstm.bias_ih_l0, lstm.weight_hh_l0, linear.weight, linear.bias)]
+            grads = [torch.zeros_like(w) for w in wts]
+            for w, gr in zip((lstm.weight_ih_l0, lstm.bias_ih_l0, lstm.weight_hh_l0, linear.weight, linear.bias), grads):
+                w.grad = gr                                         # bound once: every mht_loss_grad overwrites them
+            scratch = torch.empty((_train.scratch_layout(nb, L, U)["floats"],), dtype=torch.float32, device=dev)
+            # out of one minibatch, and the loss of every window of an epoch (summed once, at its end)
+            obuf = torch.empty((K * nb,), dtype=torch.float32, device=dev)
+            lbuf = torch.empty((int(rows_t.numel()),), dtype=torch.float32, device=dev)
+            step = _train.prepared(x.data_ptr(), x.stride(0) if rows > 1 else cols, rows, cols, q, mean32.contiguous(), inv.contiguous(), L, g,
+                                   *wts, yc, scratch, *grads)      # checked once: a step is the call and opt.step()
         out = dict(loss_train=[], loss_valid=[], num_params=4 * U * (rows + U + 1) + K * (U + 1))
         for _epoch in range(epochs):
             order = rows_t[torch.randperm(rows_t.numel(), generator=gen).to(dev)] if shuffle else rows_t
             total = torch.zeros((), dtype=torch.float64, device=dev)
+            n_rows = int(order.numel())
             for i in range(0, order.numel(), batch_size):
+                if engine == "device":
+                    B = min(batch_size, n_rows - i)
+                    step(order.data_ptr() + 8 * i, B, 1.0 / B, obuf.data_ptr(), lbuf.data_ptr() + 4 * i)
+                    opt.step()
+                    continue
                 t = order[i:i + batch_size]
                 u = (torch.clamp(xt[t.unsqueeze(1) + offs.unsqueeze(0)], max=q).float() - mean32) * inv   # [B, L, C]
                 with own_kernels():
@@ -321,6 +394,8 @@ class LSTMDecoder:
                 loss.backward()
                 opt.step()
                 total += loss.detach().double() * t.numel()
+            if engine == "device":
+                total = lbuf.sum(dtype=torch.float64)
             out["loss_train"].append(float(total) / order.numel())
             self.from_torch(lstm, linear, mean, std)
             self.dense_bias = self.dense_bias + ybar.cpu().numpy()
